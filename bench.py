@@ -7,6 +7,12 @@
 One step = one reference iteration (models.py:191-192): a discriminator update then a generator
 update, each on its own synthetic batch of `--batch` (default 8) examples per GPU, inputs already
 resident in HBM.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the `--steps` iterations and prints the line (`value`, `ms_per_step`, ...).
+`--full` adds everything else after the timed steps: the per-launch conv profile and `roofline`, the whole step against
+its roofs, the launch count, the in-run PMC traffic passes, the spectral legs, the fp32 leg and the CPU baselines.
+`--dump-outputs DIR` writes what the last timed step computed (both losses, a fixed sample of the updated weights) as
+DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import glob
@@ -299,7 +305,7 @@ def measure_traffic(dtype, batch):
     for counter, scale in (("FETCH_SIZE", 2048.0), ("WRITE_SIZE", 1024.0)):
         d = tempfile.mkdtemp(prefix="gs_pmc_", dir="/tmp")
         cmd = ["rocprofv3", "--kernel-trace", "--pmc", counter, "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1",
-               "--batch", str(batch), "--dtype", dtype, "--no-graphs", "--no-cpu-baseline", "--no-spectral", "--no-launch-count"]
+               "--batch", str(batch), "--dtype", dtype, "--full", "--no-graphs", "--no-cpu-baseline", "--no-spectral", "--no-launch-count"]
         try:
             res = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp", GS_BENCH_NO_PMC="1"), capture_output=True, text=True, timeout=300)
         except subprocess.TimeoutExpired:
@@ -323,7 +329,7 @@ def f32_leg(batch):
     path, see PARITY_NOTE) -- timed by this script in a child process right after the headline run: value, ms per step, and the conv family
     against the exact-fp32 MFMA roof (157.3 TFLOP/s).  One GPU only; GS_BENCH_NO_F32_LEG=1 / --no-f32-leg skips it."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--dtype", "f32", "--steps", "10", "--warmup", "3", "--batch", str(batch), "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.abspath(__file__), "--dtype", "f32", "--steps", "10", "--warmup", "3", "--batch", str(batch), "--full", "--no-cpu-baseline",
            "--no-spectral", "--no-launch-count", "--no-pmc", "--no-f32-leg"]
     try:
         res = subprocess.run(cmd, env=dict(os.environ, GS_BENCH_DETAIL=os.path.join("profiles", "last_bench_detail_f32.json")), capture_output=True, text=True,
@@ -677,13 +683,11 @@ def price_whole_step(model, K, args, stages, ms_per_step, prof_steps, trace_iter
                              "(kernel-layer call log of one eager iteration; Adam 28-32 B / parameter; folds and operand refresh from the parameter count)"}
 
 
-def assemble(args, world, distributed, elapsed, prof_steps, family, stages, kernel_launches, d_loss, g_loss, legs, whole_step=(None, None)):
-    """The bench record: (`out`, the ONE compact line the driver parses; `detail`, everything else -- side file + stderr)."""
-    launches, conv_ms, conv_flops, conv_bytes, roof_ms, roof_ms_hbm = family
+def headline(args, world, distributed, elapsed, d_loss, g_loss):
+    """The members of the bench line that the timed steps alone give (all a plain run prints)."""
     global_batch = args.batch * world
     value = global_batch * args.steps / elapsed
-    detail = {"stages": stages, "kernel_launches_per_iteration": kernel_launches, "parity_note": PARITY_NOTE[args.dtype]}
-    out = {
+    return {
         "metric": "G+D step images/sec at 128x1024x2 mel+IF",
         "value": value, "unit": "images/sec", "n_gpus": world, "rccl_ranks": world if distributed else 0, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -692,11 +696,18 @@ def assemble(args, world, distributed, elapsed, prof_steps, family, stages, kern
                                "R1 + mode-seeking), per-GPU batch %d, random-init weights" % args.batch,
                    "global_batch": global_batch, "parallelism": "dp%d" % world,
                    "launch": "eager" if args.no_graphs else (os.environ.get("GS_SINGLE_MODE") or "hipGraph replay")},
-        "roofline": family_roofline(args, launches, conv_ms, conv_flops, conv_bytes, roof_ms, roof_ms_hbm, stages, prof_steps, elapsed, detail),
         "model_flops_utilization": value * FLOPS_PER_IMAGE / 1e12 / PEAK[args.dtype] / world,
-        "kernel_launches_per_iteration": kernel_launches.get("total") if isinstance(kernel_launches, dict) else None,
         "losses": {"discriminator": d_loss, "generator": g_loss},
     }
+
+
+def assemble(args, world, distributed, elapsed, prof_steps, family, stages, kernel_launches, d_loss, g_loss, legs, whole_step=(None, None)):
+    """The `--full` bench record: (`out`, the ONE compact line the driver parses; `detail`, everything else -- side file + stderr)."""
+    launches, conv_ms, conv_flops, conv_bytes, roof_ms, roof_ms_hbm = family
+    detail = {"stages": stages, "kernel_launches_per_iteration": kernel_launches, "parity_note": PARITY_NOTE[args.dtype]}
+    out = headline(args, world, distributed, elapsed, d_loss, g_loss)
+    out["roofline"] = family_roofline(args, launches, conv_ms, conv_flops, conv_bytes, roof_ms, roof_ms_hbm, stages, prof_steps, elapsed, detail)
+    out["kernel_launches_per_iteration"] = kernel_launches.get("total") if isinstance(kernel_launches, dict) else None
     if whole_step[0] is not None:
         # the WHOLE iteration against its roofs: sum over every kernel family of the time its own roof allows / ms_per_step
         out["roofline"]["step_frac"] = whole_step[0].get("step_frac")
@@ -882,6 +893,24 @@ def supervise_single(args, argv):
     return 1
 
 
+DUMP_SAMPLE = 1 << 22   # weights written per network at most (16 MiB of fp32 each): the whole dump stays far below 64 MB
+
+
+def dump_outputs(out_dir, model, d_loss, g_loss):
+    """What the last timed step computed, as out_dir/<name>.npy: the two losses it returns and the weights its two Adam updates left
+    (fp32 masters, all variables of a network concatenated in order; a fixed seeded sample of DUMP_SAMPLE elements when larger)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"d_loss": d_loss, "g_loss": g_loss}
+    for name, params in (("generator_weights", model.g_params), ("discriminator_weights", model.d_params)):
+        arrays[name] = torch.cat([p.data.reshape(-1) for p in params.named.values()])
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy().astype(np.float32).reshape(-1)
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -896,17 +925,24 @@ def main():
     ap.add_argument("--no-f32-leg", action="store_true", default=bool(os.environ.get("GS_BENCH_NO_F32_LEG")),
                     help="skip the fp32 leg (the same iteration with fp32 activations, timed in a child process)")
     ap.add_argument("--spectral-only", action="store_true", help="run only the configs[3] leg and print its object")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beyond the headline: per-launch conv profile and roofline, whole-step "
+                         "pricing, launch count, PMC traffic, spectral legs, fp32 leg, CPU baselines (the --no-* switches drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (losses, a fixed sample of the updated weights) as DIR/<name>.npy")
     ap.add_argument("--pmc", action="store_true", default=None,
                     help="MEASURE roofline.traffic in this run: two extra rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; counters only with "
-                         "--kernel-trace) over one eager iteration of this same script (+1-2 minutes).  Default: on for the plain one-GPU run "
-                         "(the configuration the driver times), off for partial runs (--no-spectral / --no-cpu-baseline / --no-launch-count)")
+                         "--kernel-trace) over one eager iteration of this same script (+1-2 minutes).  Default: on for the --full one-GPU run, "
+                         "off for partial runs (--no-spectral / --no-cpu-baseline / --no-launch-count)")
     ap.add_argument("--no-pmc", dest="pmc", action="store_false", help="quote the committed PMC passes under profiles/ instead")
     ap.add_argument("--worker", action="store_true", help="(internal) the GPU-side rank of an N > 1 run, started by its supervisor (see DP_LADDER)")
     ap.add_argument("--launch-check", action="store_true",
                     help="no device work: the ranks only rendezvous (gloo), prove the launch plumbing and print one JSON line (CPU test of the self-launch)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.pmc is None:   # (nested passes run with --no-launch-count etc.: they never measure again)
-        args.pmc = (args.gpus == 1 and not (args.no_spectral or args.no_cpu_baseline or args.no_launch_count or args.no_graphs or args.spectral_only
+        args.pmc = (args.full and args.gpus == 1 and not (args.no_spectral or args.no_cpu_baseline or args.no_launch_count or args.no_graphs or args.spectral_only
                                             or args.launch_check) and not os.environ.get("GS_BENCH_NO_PMC"))
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -1032,27 +1068,30 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     one_graph = bool((getattr(model, "_merged", None) or {}).get("fused"))   # (the whole iteration ONE hipGraph, optimizer steps inside)
-    # per-kernel roofline: the same iteration launched eagerly with a HIP event pair around every
-    # conv_igemm_kernel launch on its own stream (events cannot bracket kernels inside a replayed hipGraph)
-    prof_steps = min(args.steps, 5)
-    model.use_graphs = False
-    model.train_step()
-    barrier()
-    K.prof_enable(PROF_BURST)
-    for _ in range(prof_steps):
+    if args.dump_outputs and rank == 0:   # (before --full's extra iterations move the weights on)
+        dump_outputs(args.dump_outputs, model, d_loss, g_loss)
+    if args.full:
+        # per-kernel roofline: the same iteration launched eagerly with a HIP event pair around every
+        # conv_igemm_kernel launch on its own stream (events cannot bracket kernels inside a replayed hipGraph)
+        prof_steps = min(args.steps, 5)
+        model.use_graphs = False
         model.train_step()
-    barrier()
-    conv_bytes, roof_ms, roof_ms_hbm = K.prof_roofline(PEAK[args.dtype], HBM_GBPS)
-    records = K.prof_records() if hasattr(K, "prof_records") else []
-    launches, conv_ms, conv_flops = K.prof_collect()
-    K.prof_enable(False)
-    stages = per_stage(records, prof_steps, PEAK[args.dtype], args.dtype)
-    # (one GPU only: an extra iteration on rank 0 alone would leave the other ranks out of its collectives)
-    kernel_launches = count_launches(model) if world == 1 and not distributed and not args.no_launch_count else None
-    whole = (None, None)
-    if world == 1 and not distributed and not args.no_launch_count:
-        model.use_graphs = not args.no_graphs
-        whole = price_whole_step(model, K, args, stages, elapsed / args.steps * 1e3, prof_steps)
+        barrier()
+        K.prof_enable(PROF_BURST)
+        for _ in range(prof_steps):
+            model.train_step()
+        barrier()
+        conv_bytes, roof_ms, roof_ms_hbm = K.prof_roofline(PEAK[args.dtype], HBM_GBPS)
+        records = K.prof_records() if hasattr(K, "prof_records") else []
+        launches, conv_ms, conv_flops = K.prof_collect()
+        K.prof_enable(False)
+        stages = per_stage(records, prof_steps, PEAK[args.dtype], args.dtype)
+        # (one GPU only: an extra iteration on rank 0 alone would leave the other ranks out of its collectives)
+        kernel_launches = count_launches(model) if world == 1 and not distributed and not args.no_launch_count else None
+        whole = (None, None)
+        if world == 1 and not distributed and not args.no_launch_count:
+            model.use_graphs = not args.no_graphs
+            whole = price_whole_step(model, K, args, stages, elapsed / args.steps * 1e3, prof_steps)
     if distributed:
         t = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -1061,18 +1100,21 @@ def main():
         raise SystemExit(f"non-finite losses: {float(d_loss)} {float(g_loss)}")
 
     if rank == 0:
-        legs = {}
-        if world == 1 and not args.no_spectral:
-            legs["spectral"] = spectral_bench(cpu=not args.no_cpu_baseline)
-            legs["spectral_inverse"] = inverse_bench()
-        if world == 1 and args.dtype == "bf16" and not args.no_f32_leg and not args.no_graphs:
-            torch.cuda.synchronize()
-            legs["f32"] = f32_leg(args.batch)
-        if world == 1 and not args.no_cpu_baseline:
-            legs["cpu_baseline"] = cpu_baseline()
-        out, detail = assemble(args, world, distributed, elapsed, prof_steps, (launches, conv_ms, conv_flops, conv_bytes, roof_ms, roof_ms_hbm),
-                               stages, kernel_launches, float(d_loss), float(g_loss), legs, whole_step=whole)
-        out["detail"] = write_detail(detail)
+        if args.full:
+            legs = {}
+            if world == 1 and not args.no_spectral:
+                legs["spectral"] = spectral_bench(cpu=not args.no_cpu_baseline)
+                legs["spectral_inverse"] = inverse_bench()
+            if world == 1 and args.dtype == "bf16" and not args.no_f32_leg and not args.no_graphs:
+                torch.cuda.synchronize()
+                legs["f32"] = f32_leg(args.batch)
+            if world == 1 and not args.no_cpu_baseline:
+                legs["cpu_baseline"] = cpu_baseline()
+            out, detail = assemble(args, world, distributed, elapsed, prof_steps, (launches, conv_ms, conv_flops, conv_bytes, roof_ms, roof_ms_hbm),
+                                   stages, kernel_launches, float(d_loss), float(g_loss), legs, whole_step=whole)
+            out["detail"] = write_detail(detail)
+        else:
+            out = headline(args, world, distributed, elapsed, float(d_loss), float(g_loss))
         out["config"]["forked_branches"] = bool(getattr(model, "fork", False)) and not args.no_graphs
         out["config"]["graphs_per_iteration"] = (1 if one_graph else 2) if not args.no_graphs else 0
         if distributed:

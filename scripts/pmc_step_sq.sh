@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/${1:-step_sq_pmc.txt}
-CMD="python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-graphs --no-spectral --no-launch-count"
+CMD="python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-graphs --no-spectral --no-launch-count"
 P1="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_WAVES"
 P2="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_MFMA SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
 rm -rf /tmp/sq1 /tmp/sq2
