@@ -37,14 +37,8 @@ KNOBS = {
     "GS_OVERLAP_REDUCE": ("schedule", "data parallel: round 4's four-graph iteration, each all-reduce on a forked branch beside part A of the other run "
                                       "(hides both collectives; +0.7 ms at world size 1)"),
     "GS_NO_OVERLAP_REDUCE": ("schedule", "(overrides GS_OVERLAP_REDUCE)"),
-    "GS_FORK_DIST": ("schedule", "compute branches also in the four-graph data-parallel iteration (host-bound: 7.4 ms of replay calls)"),
-    "GS_PIPELINE": ("schedule", "round 2's pipelined iteration with the update on a side stream (cross-stream hops between replays: -6 %)"),
-    "GS_PIPE_SIDE": ("schedule", "0 | 1: the side stream of that form"),
     "GS_DEBUG_DP_BUCKET": ("operational", "print the range the first message of a two-step discriminator all-reduce covers"),
     "GS_DP_BUCKET_D": ("schedule", "data parallel: the discriminator's gradient all-reduced in two steps, ~98 % of it beside the end of its backward (300-us stand-ins: -0.09 ... -0.14 ms fully grown, +0.15 in a fade-in)"),
-    "GS_SUB_RUNS": ("schedule", "the discriminator run as two independent sub-runs: split loss launches, two backward calls (4.91 -> 5.33 ms)"),
-    "GS_FAKE_FIRST": ("schedule", "the discriminator run's fake pass issued before the real pass (+0.04 ms; hides 0.13 ms of a 0.3 ms all-reduce "
-                                  "stand-in in one process, none in another)"),
     "GS_EARLY_FLUSH_DIV": ("schedule", "a layer is 'large' from 1/DIV of the full resolution's pixels (16)"),
     "GS_EARLY_FLUSH_CUS": ("schedule", "CUs the early weight-gradient contraction is sized for (192; 160 / 224 / 256 within noise, round 6)"),
     "GS_D_TAIL_LEVELS": ("schedule", "levels of the discriminator's tail run over [real; fake] as one batch when the runs do not fork (3)"),

@@ -32,8 +32,6 @@ _PAD = 64  # floats; keeps every parameter view 256-byte aligned inside the flat
 _DEFER_REDUCTIONS = not config.flag("GS_NO_DEFERRED_REDUCE")   # A/B switches for measurements
 _FUSED_LOSSES = not config.flag("GS_NO_FUSED_LOSSES")
 _BATCH_D_TAIL = not config.flag("GS_NO_D_TAIL_BATCH")   # A/B switch: real + fake through the discriminator's tail as one batch
-_PIPELINE = config.flag("GS_PIPELINE")   # opt-in, see GANSynth.pipeline
-_PIPE_SIDE = {"0": False, "1": True}.get(config.value("GS_PIPE_SIDE", ""))
 # The all-reduce beside part A of the other run (forked graph branch, four graphs per iteration: round 4's default) is opt-in since round 5:
 # the two-graph form with the collective as the LAST node of each run's graph keeps the compute branches of section 6.5 (a four-graph
 # iteration with branches would be launch-bound) -- 5.16 against 5.68 ms at world size 1, i.e. the overlapped form has to hide more than
@@ -44,8 +42,6 @@ _FORK = not config.flag("GS_NO_FORK")   # A/B switch: independent sub-passes of 
 LEVEL_STREAMS = int(config.value("GS_LEVEL_STREAMS", "128"))   # see GANSynth._leveled_queues
 EARLY_FLUSH_DIVS = [int(d) for d in config.value("GS_EARLY_FLUSH_DIV", "16").split(",")]   # a layer is "large" from 1/DIV of the full resolution's pixels (several: one early contraction each)
 EARLY_FLUSH_CUS = int(config.value("GS_EARLY_FLUSH_CUS", "192"))   # see GANSynth._early_flush
-_SUB_RUNS = config.flag("GS_SUB_RUNS")   # opt-in (measured slower, see _d_sub_runs): the discriminator run as two independent sub-runs
-_FAKE_FIRST = config.flag("GS_FAKE_FIRST")   # opt-in, see _d_fake_first
 _FORK_EAGER = config.flag("GS_FORK_EAGER")   # tests: the same branches with eager launches (a second stream, event hops)
 
 
@@ -289,29 +285,22 @@ class GANSynth(object):
         self._graphs = {}
         self._restore_from, self.restored_from = None, None
         self._graph_key, self._lerp = None, None
-        # Pipelined iteration (opt-in: pipeline=True / GS_PIPELINE=1; train_step with graphs): every run is captured as two
-        # graphs (own-network part A, the rest B) so that the gradient all-reduce of one network can run on a side stream under
-        # part A of the other network's run, which needs none of it.  Off by default: on this ROCm stack a cross-stream event
-        # hop between hipGraph replays costs 0.25-0.75 ms by itself (scripts/cross_stream_cost.py; the one-GPU step loses 6 %
-        # with the side stream on and nothing to hide), about what an 8-GPU all-reduce of these 26 / 34 MiB buffers takes.
-        self.pipeline = _PIPELINE
-        self.pipe_side = None     # None: side stream iff data-parallel (see _train_step_pipelined)
-        self._pipe = None
-        # Data parallel on our own RCCL communicator with graphs: train_step() runs the pipelined iteration with each gradient
-        # all-reduce as a FORKED BRANCH inside the other run's part-A graph (off the critical path; see "pipelined iteration").
+        # Data parallel on our own RCCL communicator with graphs, opt-in (GS_OVERLAP_REDUCE=1): train_step() runs the pipelined iteration with
+        # each gradient all-reduce as a FORKED BRANCH inside the other run's part-A graph (off the critical path; see "pipelined iteration").
         self.overlap_reduce = _OVERLAP_REDUCE
+        self._pipe = None         # the pipelined iteration's two captured pairs and their key
         self._pipe_capture = False
         self._warming_up = False
         # Forked branches inside a run's hipGraph (see _branch): a run is a chain of ~370 kernels of which ~150 are few-block launches of
         # the <= 8x64 levels -- 200 CUs idle while they run -- and it holds sub-passes that do not depend on each other.
-        # (data parallel: off in the PIPELINED iteration unless GS_FORK_DIST=1 -- a graph with parallel branches costs the host 1.8 ms per
-        #  replay instead of 0.06 (scripts/replay_host_time.py), and that iteration replays FOUR graphs: it would be launch-bound; decided
-        #  in _build, when the transport is known.  The two-graph data-parallel forms keep their branches.)
+        # (data parallel: off in the PIPELINED iteration -- a graph with parallel branches costs the host 1.8 ms per replay instead of 0.06
+        #  (scripts/replay_host_time.py), and that iteration replays FOUR graphs: it would be launch-bound; decided in _build, when the
+        #  transport is known.  The two-graph data-parallel forms keep their branches.)
         self.fork = _FORK and _hw_queues_allow_branches()
         self.fork_eager = _FORK_EAGER
         self.fork_marks = not config.flag("GS_NO_FORK_MARKS")   # (debugging: branches start where they are opened)
         self._side = None
-        self._side2 = None        # the stream of a whole sub-run beside another run (_train_step_merged)
+        self._side2 = None        # the stream of the generator run's own-network nodes beside the discriminator run (_capture_merged)
         self.bucket_d_reduce = config.flag("GS_DP_BUCKET_D")   # (data parallel, captured discriminator run, opt-in: _arm_first_bucket)
         self.first_bucket = None  # (the range of the flat gradient the first message of the last captured discriminator run covers)
         self._split_at = None     # (see _arm_first_bucket)
@@ -326,12 +315,6 @@ class GANSynth(object):
         self.fuse_iteration = not config.flag("GS_NO_FUSED_ITERATION")
         self._opt_scalars = None      # functional.DeviceScalars: [lr_t of the discriminator's step, lr_t of the generator's PENDING step | < 0]
         self._before_fake = None      # hook: issued on the fake pass's stream right before the generator's forward of a discriminator run
-        self._in_sub_runs = False
-        self._early_on_side2 = False
-        self._fake_logits_early = None
-        self.fake_first = _FAKE_FIRST   # (see _d_fake_first)
-        self._g_ready = None          # event: the generator's weights (and prepared operands) of this iteration are final on the fake pass's stream
-        self.sub_runs = _SUB_RUNS
         self.split_g_loss = not config.flag("GS_NO_SPLIT_G_LOSS")   # A/B switch, see _g_losses_b
         self.split_final_flush = not config.flag("GS_NO_SPLIT_FINAL_FLUSH")   # A/B switch, see kernels.HipKernels._flush_groups
         self._g_pending = None        # lr_t of a generator step whose gradient is in the flat buffer and whose update has not run yet
@@ -459,23 +442,6 @@ class GANSynth(object):
                     if then is not None:
                         then()
                 return
-            if self._in_sub_runs and not on_branch and self._forking():
-                # Sub-runs (_d_sub_runs): the contraction goes to the THIRD stream, behind part A of the generator run (issued between the
-                # two sub-runs, _part_b), not behind the fake sub-run on the branch: that chain opens with the generator's all-reduce when the
-                # job is data parallel, and whatever is queued behind it inherits the collective's time (the final contraction waits for
-                # this one, _join_branches)
-                main = torch.cuda.current_stream()
-                third = self._second_stream("_side2", [main, self._side])
-                third.wait_stream(main)
-                if self._side is not None:
-                    third.wait_stream(self._side)   # (the fake sub-run's pairs were recorded THERE: issued, not necessarily written yet)
-                self._early_on_side2 = True
-                self.branches_opened += 1
-                with torch.cuda.stream(third):
-                    K.flush_wgrad_reductions(select=select)
-                    if then is not None:
-                        then()
-                return
             with (contextlib.nullcontext() if on_branch else self._branch(join=False)):   # (a node of the branch itself: in place)
                 K.flush_wgrad_reductions(select=select)
                 if then is not None:
@@ -529,7 +495,7 @@ class GANSynth(object):
                 self.bucket_bytes = (64 << 20) if self._comm is not None else (8 << 20)
             self.g_params.make_buckets(self.bucket_bytes // 4, reverse=True)
             self.d_params.make_buckets(self.bucket_bytes // 4, reverse=False)
-            if (self._overlap_in_graph() or self._comm is None) and not config.flag("GS_FORK_DIST"):
+            if self._overlap_in_graph() or self._comm is None:
                 # the pipelined four-graph iteration (see __init__); and torch.distributed's collectives, which run on THEIR stream beside the
                 # launches that follow them: with the passes apart and the early contraction the world-1 step was no longer bit-identical to
                 # the non-distributed one there (5e-7 on the parameters, cause not found) -- that transport keeps round 4's schedule
@@ -564,8 +530,8 @@ class GANSynth(object):
     # Each run splits into a part that touches only the network being updated and a part that needs the other network:
     #   D run:  A = D(real) + the R1 first-order pass          B = G(z) (no grad), D(fake), loss, backward
     #   G run:  A = G(z) + the mode-seeking first-order pass    B = D(G(z)), loss, backward
-    # (`_a` functions return what `_b` needs).  The pipelined step overlaps the optimizer update of one network (all-reduce,
-    # Adam, operand refresh on a side stream) with part A of the other network's run.
+    # (`_a` functions return what `_b` needs).  The pipelined step overlaps the gradient all-reduce of one network (a forked
+    # branch of the part-A graph) with part A of the other network's run.
     # `fused`: the loss algebra on the [N] / [N, C] tensors -- label-logit select, softplus, penalty, mean, and their autograd
     # mirror images, ~50 torch launches per iteration -- as ONE kernel per loss (gs_gan_d_loss / gs_gan_g_loss: value and
     # gradients); `_b` then returns the mean loss itself instead of the per-sample losses.  The public *_losses methods keep
@@ -616,12 +582,6 @@ class GANSynth(object):
             return self._d_losses_b_batched(part_a, latents, labels)
         real_part, penalty = part_a
         fake_weight = hp.get("fake_gradient_penalty_weight", 0.0)
-        if fused and self._sub_runs_ok():
-            return self._d_sub_runs(real_part, penalty, latents, labels)
-        early, self._fake_logits_early = self._fake_logits_early, None
-        if early is not None and fused:   # (the fake pass was issued in front of the real one, _issue_fake_pass_first: only the join is left)
-            torch.cuda.current_stream().wait_stream(self._side)
-            return F.gan_d_loss(real_part, early, labels, penalty, hp.real_gradient_penalty_weight or 1.0)
         with self._branch("d_root"):   # the whole fake pass beside the real one (its backward then runs on the branch as well)
             self._run_before_fake()
             with torch.no_grad():  # var_list is the discriminator's only: no generator backward (models.py:86-89)
@@ -640,52 +600,6 @@ class GANSynth(object):
                 (fake_gradients,) = torch.autograd.grad(fake_logits.sum(), fake_images, create_graph=True)
             losses = losses + F.sumsq_rows(fake_gradients) * fake_weight
         return losses
-
-    # The discriminator run as TWO INDEPENDENT SUB-RUNS (round 6).  L_D = mean(softplus(-r) + penalty) + mean(softplus(f)): the real pass with
-    # its R1 passes and the fake pass share nothing but the parameters (leaves) -- two disjoint autograd graphs, two backward calls, one sum of
-    # gradients.  With ONE loss node (gs_gan_d_loss over r and f) the real side's backward -- R1 double-backward + the real pass's own, the
-    # longest chain of the run -- waits for the fake pass's forward.  Here each sub-run is issued whole: the fake sub-run on the branch from the
-    # run's root (generator step pending from the previous iteration -- data parallel: its all-reduce first --, G(z), D, its loss, its backward),
-    # part A of the generator run on the third stream (models._capture_merged), then the real sub-run's loss and backward on the capturing stream
-    # (its forward and first-order pass were issued in part A of this run), its early contraction behind part A.  The loss VALUE is the sum of
-    # the two partial means (last-bit association differs from the one-launch form; the gradients are the same numbers).
-    # MEASURED, and OPT-IN (GS_SUB_RUNS=1) because of it (timelines taken from INSIDE the graph, scripts/phase_timeline.py): parity and
-    # bit-identity tests green; the first form (real sub-run first, the early contraction on a stream of its own) ran 5.27 -> 5.98 ms -- four chains
-    # on the runtime's four hardware queues, two of them on one; this form (fake sub-run first, part A of the generator run between the sub-runs,
-    # the early contraction behind part A and behind the fake sub-run's stream: three chains from the graph's root) runs 4.91 -> 5.33 ms.  The
-    # discriminator phase is throughput-bound: three chains already run side by side in the one-loss form as well.
-    def _sub_runs_ok(self):
-        # (also WITHOUT branches -- everything on the one stream, same order: a plain and a forked schedule then issue the same launches in the
-        #  same order and stay bit-identical, tests/test_model_gpu.py::test_forked_branches_change_nothing_but_the_schedule)
-        if self._forking() and not self.fork_marks:
-            return False   # (the fake sub-run must start at the run's root, not behind the real sub-run's backward)
-        return (self.sub_runs and self._serial_run and hasattr(F, "gan_d_loss_real") and hasattr(kernels.get(), "lib")
-                and not self.hyper_params.get("fake_gradient_penalty_weight", 0.0))
-
-    def _d_sub_runs(self, real_logits, penalty, latents, labels):
-        hp = self.hyper_params
-        weight = hp.real_gradient_penalty_weight or 1.0
-        root = self._marks.pop("d_root", None)
-
-        def real_sub_run():
-            return F.gan_d_loss_real(real_logits, labels, penalty, weight)
-
-        def fake_sub_run():
-            self._run_before_fake()
-            with torch.no_grad():  # var_list is the discriminator's only: no generator backward (models.py:86-89)
-                fake_images = self.generator(latents, labels)
-            _, fake_logits = self.discriminator(fake_images, labels)
-            return F.gan_d_loss_fake(fake_logits, labels)
-
-        def on_branch():
-            if root is not None:
-                self._marks["d_root"] = root
-            return self._branch("d_root", join=False)   # (joined at the end of the run, _part_b)
-
-        # issue order: the fake sub-run WHOLE (forward, loss, backward on the branch, from the run's root), then the real sub-run's loss and
-        # backward on this stream (its forward and first-order pass were issued in part A) -- the early contraction of the real backward then
-        # goes behind the fake sub-run on the branch, and the graph holds three chains: this stream, the branch, part A of the generator run
-        return [(on_branch, fake_sub_run), (contextlib.nullcontext, real_sub_run)]
 
     def _d_losses_b_batched(self, part_a, latents, labels):
         """models.py:39-54,65 with the two discriminator passes sharing their tail: logits of [real; fake] from one pass, the R1 term
@@ -715,9 +629,6 @@ class GANSynth(object):
         hook, self._before_fake = self._before_fake, None
         if hook is not None:   # (one graph per iteration: the generator's pending update runs HERE, on the fake pass's stream, see _capture_merged)
             hook()
-        if self._forking():
-            self._g_ready = torch.cuda.Event()
-            self._g_ready.record()
 
     def discriminator_losses(self, latents, labels, real_images):
         return self._d_losses_b(self._d_losses_a(labels, real_images), latents, labels)
@@ -794,15 +705,20 @@ class GANSynth(object):
             for i in range(len(params.buckets)):
                 self._launch_reduce(params, i).wait()
 
+    def _adam(self, params, lr_t, beta1, beta2):
+        """One TF-Adam step of the whole flat buffer on its (reduced) gradient."""
+        zero = not self.keep_gradients
+        kernels.get().adam_tf_step(params.flat, params.grad, params.m, params.v, lr_t, beta1, beta2, 1.0e-8, 1.0 / self.world, zero_grad=zero)
+        params.grad_clean = zero
+
     def _apply(self, params, lr, beta1, beta2, reduced=False):
         params.t += 1
-        lr_t = lr * math.sqrt(1.0 - beta2 ** params.t) / (1.0 - beta1 ** params.t)
+        lr_t = self._lr_t(lr, beta1, beta2, params.t)
+        if not self.distributed or reduced:
+            self._adam(params, lr_t, beta1, beta2)
+            return
         K = kernels.get()
         zero = not self.keep_gradients
-        if not self.distributed or reduced:
-            K.adam_tf_step(params.flat, params.grad, params.m, params.v, lr_t, beta1, beta2, 1.0e-8, 1.0 / self.world, zero_grad=zero)
-            params.grad_clean = zero
-            return
         works = {}
         if self._inflight is not None and self._inflight[0] is params:
             works = dict(self._inflight[1])
@@ -836,16 +752,13 @@ class GANSynth(object):
         self._branched = False
         self._origin = torch.cuda.current_stream() if torch.cuda.is_available() else None   # (the stream this run is issued -- or captured -- on)
         losses = self._d_losses_b(part_a, *inputs, fused=fused) if which == "d" else self._g_losses_b(part_a, *inputs, fused=fused)   # (latents, labels) | (labels,)
-        sub_runs = losses if isinstance(losses, list) else None   # [(context factory, forward() -> root)]: see _d_sub_runs
         multi = losses if isinstance(losses, tuple) else None     # several roots of ONE backward call: see _g_losses_b
-        loss = None if (sub_runs is not None or multi is not None) else (losses if losses.dim() == 0 else losses.mean())   # (the fused loss kernels return the mean itself)
+        loss = None if multi is not None else (losses if losses.dim() == 0 else losses.mean())   # (the fused loss kernels return the mean itself)
         hook, self._after_loss = self._after_loss, None
-        if hook is not None and sub_runs is None:
+        if hook is not None:
             # Merged iteration: part A of the other run forks off HERE and is issued here, in front of this run's backward (see _capture_merged).
             # (Measured round 6, profiles/r06_d_hook_after_backward_ab.txt: issued BEHIND the backward from an event recorded here: 5.23 -> 5.29 ms.)
-            hook(None)
-            hook = None
-        self._g_ready = None
+            hook()
         K = kernels.get()
         deferring = _DEFER_REDUCTIONS and hasattr(K, "defer_wgrad_reductions")   # parameter gradients are only read after the whole backward:
         if deferring:                                        # their ~70 slice reductions are folded in one go at the end
@@ -880,29 +793,9 @@ class GANSynth(object):
                 else:
                     root.backward()
 
-        roots = []
-        self._in_sub_runs = sub_runs is not None
         try:
-            if multi is not None:
-                backward(multi)
-                roots = [r.detach() for r in multi]
-            elif sub_runs is None:
-                backward(loss)
-            else:
-                for context, forward in sub_runs:   # each on its own stream, whole: forward (what is left of it), loss, backward
-                    with context():
-                        root = forward()
-                        if hasattr(F, "reset_fusion_state"):
-                            F.reset_fusion_state()
-                        backward(root)
-                        roots.append(root.detach())
-                    if hook is not None and self._g_ready is not None:
-                        # part A of the other run: issued behind the FAKE sub-run (it starts where the generator's weights are final) and in
-                        # front of the real sub-run's backward, whose early contraction queues behind it on the third stream
-                        hook(self._g_ready)
-                        hook = None
+            backward(multi if multi is not None else loss)
         finally:
-            self._in_sub_runs = False
             if hasattr(F, "reset_fusion_state"):
                 F.reset_fusion_state()   # (the hand-off table holds tensors of this pass -- of a graph's pool while capturing: not beyond it)
             if deferring:
@@ -923,15 +816,13 @@ class GANSynth(object):
                     K.flush_wgrad_reductions()
         if launched:
             self._inflight = (params, launched)
-        if hook is not None:   # (sub-runs: part A of the other run is issued last and starts where the generator's weights are final)
-            hook(self._g_ready)
         self._join_branches()   # (a branch opened by the flush itself; a branch left open would fail the capture)
-        if sub_runs is not None or multi is not None:
-            loss = roots[0]
-            for r in roots[1:]:
+        if multi is not None:
+            loss = multi[0].detach()
+            for r in multi[1:]:
                 if r.is_cuda:
-                    r.record_stream(torch.cuda.current_stream())   # (made on its sub-run's stream, read here)
-                loss = loss + r
+                    r.record_stream(torch.cuda.current_stream())   # (made on its branch's stream, read here)
+                loss = loss + r.detach()
         if self.distributed and self._comm is not None and self._graph_allreduce and self._capturing() and not getattr(self, "_pipe_capture", False):
             # Same-stream RCCL is capturable: the all-reduce of this run's flat gradient becomes the LAST NODE of the run's hipGraph, so
             # a replayed run hands over reduced gradients and no eager collective launch sits between the replay and the update.
@@ -1010,8 +901,7 @@ class GANSynth(object):
         if self._branched:
             self._branched = False
             torch.cuda.current_stream().wait_stream(self._side)
-        if (self._nodes_on_side2 or self._early_on_side2) and self._forking():
-            self._early_on_side2 = False
+        if self._nodes_on_side2 and self._forking():
             torch.cuda.current_stream().wait_stream(self._side2)
 
     def _reduce_in_capture(self, params):
@@ -1044,9 +934,7 @@ class GANSynth(object):
         torch.cuda.synchronize()
         self._graphs.clear()
         self._merged = None
-        if self._pipe is not None:
-            self._pipe.pop("d", None), self._pipe.pop("g", None)
-            self._pipe["key"] = None
+        self._pipe = None
         if self.world > 1 and self._comm is not None:
             # Not destroyed: ncclCommDestroy on a communicator an aborted capture left half-enqueued may block.  It is retired --
             # never used again, kept alive until the process ends -- and the eager collectives go through torch.distributed.
@@ -1114,40 +1002,12 @@ class GANSynth(object):
         try:
             if which == "d":
                 latents, labels, real_images = inputs
-                if self._d_fake_first():
-                    self._issue_fake_pass_first(latents, labels)
                 return self._part_b("d", self._part_a("d", labels, real_images), latents, labels)
             latents, labels = inputs
             return self._part_b("g", self._part_a("g", latents, labels), labels)
         finally:
             self._serial_run = False
             self._marks.clear()
-
-    # One graph per iteration, opt-in (GS_FAKE_FIRST=1 / `fake_first`): the discriminator run's FAKE pass is issued before the real pass.  It
-    # starts with the generator's pending step, i.e. data parallel with the all-reduce of the generator's gradient; issued first it is the
-    # capturing stream's own chain and the real pass the branch.  One GPU: 5.17 -> 5.21 ms.  World size 1 with 300-us stand-ins for the two
-    # collectives (scripts/dp_marker_check.py, profiles/r06_g_dp_markers.txt): the stand-ins add 0.43 ms with this order against 0.56 real-first
-    # and 0.61 in the two-graph form in one process, 0.61 against 0.52 inside tests/test_model_gpu.py's process -- the discriminator phase is
-    # throughput-bound and which chains share a hardware queue depends on the stream pool's history: not a gain to build a
-    # default on.
-    def _d_fake_first(self):
-        if not (self._forking() and self._capturing() and self.fork_marks and self._fused_losses()) or self._sub_runs_ok():
-            return False
-        if self.batch_d_tail:   # (tests: real and fake through the tail as one batch -- there is no separate fake pass then)
-            return False
-        want = self.fake_first
-        return bool(want) and not self.hyper_params.get("fake_gradient_penalty_weight", 0.0)
-
-    def _issue_fake_pass_first(self, latents, labels):
-        self.g_params.requires_grad_(False)   # (what _part_a("d") arms: the discriminator's nodes must be recorded for its backward)
-        self.d_params.requires_grad_(True)
-        self._fork_mark("d_root")
-        with self._branch("d_root", join=False):   # (joined where the loss needs it, _d_losses_b)
-            self._run_before_fake()
-            with torch.no_grad():  # var_list is the discriminator's only: no generator backward (models.py:86-89)
-                fake_images = self.generator(latents, labels)
-            _, fake_logits = self.discriminator(fake_images, labels)
-        self._fake_logits_early = fake_logits
 
     def _regime(self):
         """(head depth, fade weight or None) of the networks at the current growing depth; None for foreign network objects."""
@@ -1161,11 +1021,6 @@ class GANSynth(object):
         depth, faded or not -- graphs are re-captured when it changes) and the one per-step scalar, the fade-in weight, is read
         from device memory (functional.DeviceLerp)."""
         return self.use_graphs and torch.cuda.is_available() and self._regime() is not None
-
-    def _fully_grown(self):
-        reg = self._regime()
-        owner = getattr(self.generator, "__self__", None)
-        return reg is not None and reg[1] is None and reg[0] == owner.max_depth
 
     def _run(self, which, *inputs):
         self._join_updates()
@@ -1269,51 +1124,32 @@ class GANSynth(object):
         return self.generator_loss
 
     # ------------------------------------------------------------------ pipelined iteration
-    # Every run as TWO graphs: part A (own network only) and part B (the rest), so that the optimizer update of the OTHER network --
-    # its gradient all-reduce above all -- can sit between them:
+    # Data parallel, opt-in (GS_OVERLAP_REDUCE=1): every run as TWO graphs, part A (own network only) and part B (the rest), so that the
+    # optimizer update of the OTHER network -- its gradient all-reduce above all -- can sit between them:
     #     D.A | update G | D.B | G.A | update D | G.B
-    # Part A needs neither the gradients being reduced nor the parameters about to change.  Two ways to overlap the collective
-    # with part A:
-    #   (i) IN THE GRAPH (data parallel on our own RCCL communicator, the default there): the all-reduce of the other network's flat
-    #       gradient is a forked branch INSIDE graph A -- fork at the graph's root, join at its end -- so the collective node is off
-    #       the critical path of part A's kernels and there is no cross-stream event between replays (an event hop between a replay
-    #       and another stream costs 0.25-0.75 ms on this stack, scripts/cross_stream_cost.py).  Adam and the operand refresh stay
-    #       eager on the main stream behind graph A (lr_t is a by-value scalar; streaming kernels beside the persistent conv blocks
-    #       cost the main stream 5 %, measured).
-    #   (ii) SIDE STREAM (opt-in, GS_PIPELINE=1 with torch.distributed's collectives): the round-2 form.
+    # Part A needs neither the gradients being reduced nor the parameters about to change.  The all-reduce of the other network's flat
+    # gradient is a forked branch INSIDE graph A -- fork at the graph's root, join at its end -- so the collective node is off the critical
+    # path of part A's kernels and there is no cross-stream event between replays (an event hop between a replay and another stream costs
+    # 0.25-0.75 ms on this stack, scripts/cross_stream_cost.py).  Adam and the operand refresh stay eager on the main stream behind graph A
+    # (lr_t is a by-value scalar; streaming kernels beside the persistent conv blocks cost the main stream 5 %, measured).
+    def _apply_g_pending(self):
+        """The generator's pending step (`_g_pending`: its lr_t) on the gradient in its flat buffer, already all-reduced."""
+        lr_t, self._g_pending = self._g_pending, None
+        self._adam(self.g_params, lr_t, self.hyper_params.generator_beta1, self.hyper_params.generator_beta2)
+
     def _join_updates(self):
-        """A pipelined step leaves the generator's update pending: apply it (reducing the gradient first when the all-reduce was
-        going to ride in the next discriminator graph).  Data parallel: with a reduction pending this IS a collective -- every rank
-        must get here at the same point of its launch sequence.  train() therefore joins on EVERY rank before a rank-0 checkpoint
-        and at its end; synchronize(), state_dict / checkpoint.save and generate() called by hand on a distributed model must be
-        called on all ranks (`collective_pending()` tells whether the call would communicate)."""
-        if self._g_pending is not None:   # (one graph per iteration: the generator's update rides at the front of the NEXT graph -- or here)
-            lr_t, self._g_pending = self._g_pending, None
-            hp = self.hyper_params
-            if self.distributed:
-                self._reduce(self.g_params)
-            zero = not self.keep_gradients
-            kernels.get().adam_tf_step(self.g_params.flat, self.g_params.grad, self.g_params.m, self.g_params.v, lr_t, hp.generator_beta1,
-                                       hp.generator_beta2, 1.0e-8, 1.0 / self.world, zero_grad=zero)
-            self.g_params.grad_clean = zero
-        if self._pipe is not None and self._pipe.get("g_pending"):
-            hp = self.hyper_params
-            P = self._pipe
-            P["g_pending"] = False
-            if P.get("g_unreduced"):
-                P["g_unreduced"] = False
-                self._reduce(self.g_params)
-            else:
-                torch.cuda.current_stream().wait_event(P["g_reduced"])
-            self._apply(self.g_params, hp.generator_learning_rate, hp.generator_beta1, hp.generator_beta2, reduced=True)
+        """The one-graph and the pipelined iteration leave the generator's update pending, its gradient not yet all-reduced (the next
+        iteration's graph does both): reduce and apply it here.  Data parallel: this IS a collective -- every rank must get here at the
+        same point of its launch sequence.  train() therefore joins on EVERY rank before a rank-0 checkpoint and at its end;
+        synchronize(), state_dict / checkpoint.save and generate() called by hand on a distributed model must be called on all ranks
+        (`collective_pending()` tells whether the call would communicate)."""
+        if self._g_pending is not None:
+            self._reduce(self.g_params)
+            self._apply_g_pending()
 
     def collective_pending(self):
-        """True when the next _join_updates() / synchronize() / generate() / checkpoint would issue a gradient all-reduce (the
-        pipelined data-parallel step leaves the generator's gradient unreduced until the next discriminator graph)."""
-        if self.distributed and self.world > 1 and self._g_pending is not None:
-            return True
-        return bool(self.distributed and self.world > 1 and self._pipe is not None and self._pipe.get("g_pending")
-                    and self._pipe.get("g_unreduced"))
+        """True when the next _join_updates() / synchronize() / generate() / checkpoint would issue a gradient all-reduce."""
+        return self.distributed and self.world > 1 and self._g_pending is not None
 
     def synchronize(self):
         """Everything a train_step enqueued (including the pending update) has finished.  Collective when `collective_pending()`."""
@@ -1326,7 +1162,7 @@ class GANSynth(object):
         collectives not refused (GS_NO_GRAPH_ALLREDUCE / a failed capture), not switched off (GS_NO_OVERLAP_REDUCE=1)."""
         return self.distributed and self._comm is not None and self._graph_allreduce and self.overlap_reduce
 
-    def _capture_pair(self, which, a_inputs, b_inputs, reduce_params=None):
+    def _capture_pair(self, which, a_inputs, b_inputs, reduce_params):
         """Two graphs for one run: part A (own network) and part B (the rest), sharing one memory pool (replayed A, B, A, B ...).
         `reduce_params`: the OTHER network's parameters, whose flat gradient is all-reduced on a forked branch of graph A."""
         K = kernels.get()
@@ -1344,8 +1180,7 @@ class GANSynth(object):
             try:
                 with torch.cuda.stream(side):  # one eager pass on a side stream (allocator / lazy-init warm-up)
                     self._part_b(which, self._part_a(which, *sa), *sb)
-                    if reduce_params is not None:   # RCCL sets up its channels on the first collective: not capturable (dead values here)
-                        self._reduce(reduce_params)
+                    self._reduce(reduce_params)   # RCCL sets up its channels on the first collective: not capturable (dead values here)
             finally:
                 self._warming_up = False
             torch.cuda.current_stream().wait_stream(side)
@@ -1357,18 +1192,16 @@ class GANSynth(object):
             import warnings
             with warnings.catch_warnings(record=True) as caught:
                 warnings.simplefilter("always")
-                with _quiet_gc(), self._leveled_queues(), self._stream_guard(), torch.cuda.graph(ga, **_capture_mode(reduce_params is not None, self.fork)):
-                    if reduce_params is not None:
-                        main = torch.cuda.current_stream()
-                        fork = torch.cuda.Stream()
-                        while fork.cuda_stream == main.cuda_stream or (self._side is not None and fork.cuda_stream == self._side.cuda_stream):
-                            fork = torch.cuda.Stream()   # (pooled streams come round-robin: never the capturing one, nor the branches')
-                        fork.wait_stream(main)            # fork at the root of the graph ...
-                        with torch.cuda.stream(fork):
-                            self._reduce_in_capture(reduce_params)
+                with _quiet_gc(), self._leveled_queues(), self._stream_guard(), torch.cuda.graph(ga, **_capture_mode(True, self.fork)):
+                    main = torch.cuda.current_stream()
+                    fork = torch.cuda.Stream()
+                    while fork.cuda_stream == main.cuda_stream or (self._side is not None and fork.cuda_stream == self._side.cuda_stream):
+                        fork = torch.cuda.Stream()   # (pooled streams come round-robin: never the capturing one, nor the branches')
+                    fork.wait_stream(main)            # fork at the root of the graph ...
+                    with torch.cuda.stream(fork):
+                        self._reduce_in_capture(reduce_params)
                     part_a = self._part_a(which, *sa)
-                    if reduce_params is not None:
-                        main.wait_stream(fork)            # ... join at its end: the collective runs beside all of part A
+                    main.wait_stream(fork)            # ... join at its end: the collective runs beside all of part A
             # Part A may hold NO kernel: a discriminator whose whole depth runs in the batched tail has no trunk of its own (shallow
             # growing regimes), and on ONE rank RCCL short-cuts the all-reduce to nothing as well.  torch warns about the empty graph;
             # that is the only way it can be empty -- with peers the collective is a node -- and an empty part A is simply not replayed.
@@ -1376,7 +1209,7 @@ class GANSynth(object):
             for w in caught:
                 if "Graph is empty" not in str(w.message):
                     warnings.warn_explicit(w.message, w.category, w.filename, w.lineno)
-            if a_empty and reduce_params is not None and self.world > 1:
+            if a_empty and self.world > 1:
                 raise RuntimeError("part A of the %s run captured no node although it holds a gradient all-reduce over %d ranks" % (which, self.world))
             gb = torch.cuda.CUDAGraph()
             with _quiet_gc(), self._leveled_queues(), self._stream_guard(), torch.cuda.graph(gb, pool=ga.pool()):
@@ -1384,64 +1217,49 @@ class GANSynth(object):
         finally:
             self._pipe_capture = False
             owner.fade_weight = None
-        return {"a": ga, "b": gb, "sa": sa, "sb": sb, "loss": loss, "reduces": reduce_params is not None, "keep": self.keep_gradients, "a_empty": a_empty,
+        return {"a": ga, "b": gb, "sa": sa, "sb": sb, "loss": loss, "reduces": True, "keep": self.keep_gradients, "a_empty": a_empty,
                 "consts": F.constants_snapshot()}   # (cached junction constants the graphs read: alive as long as the graphs)
 
     def _pipelined_ok(self):
-        if not self._graphable():
-            return False
-        if self._overlap_in_graph():
-            return True
-        return self.pipeline and self._fully_grown()
+        return self._graphable() and self._overlap_in_graph()
 
     def _train_step_pipelined(self, d_latents, d_labels, real_images, g_latents, g_labels):
         """D.A | update G | D.B | G.A | update D | G.B (see above)."""
         hp = self.hyper_params
-        main = torch.cuda.current_stream()
-        if self._pipe is None:
-            ev = lambda: torch.cuda.Event()
-            self._pipe = {"side": torch.cuda.Stream(), "d_done": ev(), "g_done": ev(), "d_reduced": ev(), "g_reduced": ev(), "g_pending": False,
-                          "g_unreduced": False, "key": None}
         P = self._pipe
-        in_graph = self._overlap_in_graph()
-        use_side = (not in_graph) and (self.pipe_side if self.pipe_side is not None else (self.distributed if _PIPE_SIDE is None else _PIPE_SIDE))
         head, fade = self._regime()
-        key = (head, fade is None, in_graph, self.keep_gradients)
+        key = (head, fade is None, self.keep_gradients)
         if fade is not None:
             if self._lerp is None:
                 self._lerp = F.DeviceLerp(self.g_params.flat.device)
             self._lerp.set(fade)   # (stream-ordered before the replays below)
 
         def fresh(entry, a_inputs, b_inputs):
-            return entry is None or any(x.shape != y.shape or x.dtype != y.dtype for x, y in zip(entry["sa"] + entry["sb"], list(a_inputs) + list(b_inputs)))
+            return any(x.shape != y.shape or x.dtype != y.dtype for x, y in zip(entry["sa"] + entry["sb"], list(a_inputs) + list(b_inputs)))
 
         d_in = ((d_labels, real_images), (d_latents, d_labels))
         g_in = ((g_latents, g_labels), (g_labels,))
-        if P["key"] != key or fresh(P.get("d"), *d_in) or fresh(P.get("g"), *g_in):
+        if P is None or P["key"] != key or fresh(P["d"], *d_in) or fresh(P["g"], *g_in):
             self._join_updates()
             self._graphs.clear()
-            P.pop("d", None), P.pop("g", None)
-            if P["key"] is not None and P["key"][:2] != key[:2]:
+            self._pipe = None
+            if P is not None and P["key"][:2] != key[:2]:
                 F.drop_constants()   # (a new growing regime: see _run)
             error = None
             try:
-                P["d"] = self._capture_pair("d", *d_in, reduce_params=self.g_params if in_graph else None)
-                P["g"] = self._capture_pair("g", *g_in, reduce_params=self.d_params if in_graph else None)
+                P = {"key": key, "d": self._capture_pair("d", *d_in, self.g_params), "g": self._capture_pair("g", *g_in, self.d_params)}
             except RuntimeError as e:
-                if not in_graph:
-                    raise
                 error = e
-            if in_graph and not self._agree(error is None):
-                # some rank could not capture the collective: EVERY rank drops the in-graph form (agreed, so that the collective
-                # sequences of the ranks stay identical) and captures plain pairs; the reductions then run eagerly between replays
+            if not self._agree(error is None):
+                # some rank could not capture the collective: EVERY rank (agreed, so that the collective sequences of the ranks stay
+                # identical) drops the in-graph form; this iteration and the later ones run as two plain runs with the all-reduce
+                # eagerly behind each replay (_run)
                 self._give_up_graph_collectives("d", error)
                 self._abandon_capture("g")
-                in_graph = False
-                use_side = self.pipe_side if self.pipe_side is not None else False
-                key = (head, fade is None, in_graph, self.keep_gradients)
-                P["d"] = self._capture_pair("d", *d_in)
-                P["g"] = self._capture_pair("g", *g_in)
-            P["key"] = key
+                d_loss = self.discriminator_step(d_latents, d_labels, real_images)
+                g_loss = self.generator_step(g_latents, g_labels)
+                return d_loss, g_loss
+            self._pipe = P
         D, G = P["d"], P["g"]
         _copy_inputs(D["sa"] + D["sb"] + G["sa"] + G["sb"], list(d_in[0]) + list(d_in[1]) + list(g_in[0]) + list(g_in[1]))
 
@@ -1452,55 +1270,23 @@ class GANSynth(object):
                     params.grad.zero_()
                 params.grad_clean = False
 
-        if in_graph:
-            # D run.  Graph A = {D part A  ||  all-reduce of the generator's pending gradient}; then the generator's update (part B runs
-            # the generator), then part B.
-            armed(self.d_params)
-            if not D["a_empty"]:
-                D["a"].replay()
-            if P["g_pending"]:
-                P["g_pending"] = P["g_unreduced"] = False
-                self._apply(self.g_params, hp.generator_learning_rate, hp.generator_beta1, hp.generator_beta2, reduced=True)
-            D["b"].replay()
-            # G run.  Graph A = {G part A  ||  all-reduce of the discriminator's gradient}; the discriminator's update; part B runs it.
-            armed(self.g_params)
-            if not G["a_empty"]:
-                G["a"].replay()
-            self._apply(self.d_params, hp.discriminator_learning_rate, hp.discriminator_beta1, hp.discriminator_beta2, reduced=True)
-            G["b"].replay()
-            P["g_pending"] = P["g_unreduced"] = True   # reduced inside the next D graph (or eagerly by _join_updates)
-            self.global_step += 1  # models.py:84
-            self.discriminator_loss, self.generator_loss = D["loss"], G["loss"]
-            return D["loss"], G["loss"]
-
-        def reduce_async(params, done, reduced):
-            done.record(main)
-            if use_side:
-                with torch.cuda.stream(P["side"]):
-                    P["side"].wait_event(done)
-                    self._reduce(params)
-                    reduced.record(P["side"])
-            else:
-                self._reduce(params)
-                reduced.record(main)
-
-        # D run.  Part A reads the discriminator only: it runs under the all-reduce of the previous generator gradients.
+        # D run.  Graph A = {D part A  ||  all-reduce of the generator's pending gradient}; then the generator's update (part B runs
+        # the generator), then part B.
         armed(self.d_params)
         if not D["a_empty"]:
             D["a"].replay()
-        self._join_updates()                        # the generator's update; part B runs the generator
+        if self._g_pending is not None:
+            self._apply_g_pending()
         D["b"].replay()
-        reduce_async(self.d_params, P["d_done"], P["d_reduced"])
-        # G run.  Part A reads the generator only: it runs under the all-reduce of the discriminator's gradients.
+        # G run.  Graph A = {G part A  ||  all-reduce of the discriminator's gradient}; the discriminator's update; part B runs it.
         armed(self.g_params)
         if not G["a_empty"]:
             G["a"].replay()
-        main.wait_event(P["d_reduced"])
         self._apply(self.d_params, hp.discriminator_learning_rate, hp.discriminator_beta1, hp.discriminator_beta2, reduced=True)
-        G["b"].replay()                             # runs the updated discriminator
-        reduce_async(self.g_params, P["g_done"], P["g_reduced"])
-        P["g_pending"] = True                       # applied before the next part B (or by _join_updates / synchronize)
-        P["g_unreduced"] = False
+        G["b"].replay()
+        # the generator's step is left pending: its gradient is reduced inside the next D graph (or eagerly by _join_updates)
+        self.g_params.t += 1
+        self._g_pending = self._lr_t(hp.generator_learning_rate, hp.generator_beta1, hp.generator_beta2, self.g_params.t)
         self.global_step += 1  # models.py:84
         self.discriminator_loss, self.generator_loss = D["loss"], G["loss"]
         return D["loss"], G["loss"]
@@ -1597,14 +1383,11 @@ class GANSynth(object):
                         self._before_fake = lambda: self._apply_in_graph(self.g_params, 1, hp.generator_beta1, hp.generator_beta2,
                                                                          reduce_first=with_collective)
 
-                    def part_a_of_g(mark=None):
+                    def part_a_of_g():
                         # from the discriminator run's loss on its second half is one stream wide (R1 double-backward, the real pass's backward,
                         # the final contraction): part A of the generator run goes THERE (from the graph's root, beside the two forward passes,
-                        # measured 5.27 -> 5.34 ms in round 5).  `mark`: an event recorded at the loss -- the branch starts there although it is issued later.
-                        if mark is not None:
-                            side2.wait_event(mark)
-                        else:
-                            side2.wait_stream(torch.cuda.current_stream())
+                        # measured 5.27 -> 5.34 ms in round 5)
+                        side2.wait_stream(torch.cuda.current_stream())
                         with torch.cuda.stream(side2):
                             box.append(self._part_a("g", *sg))
                         self.g_params.requires_grad_(False)      # (back to the discriminator run's arming for its backward)

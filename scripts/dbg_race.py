@@ -13,7 +13,7 @@ NB = 3
 batches = [R.synthetic_batch(n, rank=i, image_shape=res) for i in range(NB)]
 hyper = Dict(R.DEFAULT_HYPER); hyper.generator_learning_rate = hyper.discriminator_learning_rate = 0.0
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 30
-modes = os.environ.get("DBG_MODES", "eager,default,pair,sub_runs,nofork").split(",")
+modes = os.environ.get("DBG_MODES", "eager,default,pair,nofork").split(",")
 if any(m.startswith("dist") or m == "overlapped" for m in modes):
     import torch.distributed as dist
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -22,8 +22,7 @@ ref = None
 for mode in modes:
     variables.set_default_store(variables.VariableStore(device="cuda"))
     pg, opg, model = make(float(os.environ.get("DBG_LEVEL", "1.0")), variables.default_store(), full=full, dtype=dtype, hyper=hyper)
-    model.use_graphs, model.keep_gradients = mode not in ("eager", "sub_runs_eager"), not os.environ.get("DBG_NOKEEP")
-    model.sub_runs = mode.startswith("sub_runs")
+    model.use_graphs, model.keep_gradients = mode != "eager", not os.environ.get("DBG_NOKEEP")
     if mode == "overlapped":
         mode_ = "dist_graph"; model.overlap_reduce = True
     if mode.startswith("dist") or mode == "overlapped":   # dist_eager / dist_torch_eager / dist_graph / overlapped
@@ -31,7 +30,6 @@ for mode in modes:
         model.use_graphs = mode in ("dist_graph", "overlapped")
         if "torch" in mode: os.environ["GS_TORCH_COLLECTIVES"] = "1"
         else: os.environ.pop("GS_TORCH_COLLECTIVES", None)
-    if mode == "sub_runs_nofork": model.fork = False
     if mode == "nofork": model.fork = False
     if mode == "pair": model.fuse_iteration = False
     cur = [0]

@@ -1,7 +1,7 @@
 """World size 1 with the library's RCCL communicator: where do the two gradient all-reduces of an iteration sit?  RCCL short-cuts a one-rank
 all-reduce to nothing, so GS_COMM_MARKER_US=<n> puts a one-block kernel that holds its stream for n us in its place; the iteration is timed
 with markers of 0 and n us in every schedule named on the command line ("ENV=1,ENV2=0" per schedule, "-" = defaults).
-usage (GPU box): python scripts/dp_marker_check.py 300 - GS_FAKE_FIRST=0 GS_HOOK_AFTER_BACKWARD=1 ..."""
+usage (GPU box): python scripts/dp_marker_check.py 300 - GS_NO_FUSED_ITERATION=1 GS_OVERLAP_REDUCE=1 ..."""
 import os
 import subprocess
 import sys

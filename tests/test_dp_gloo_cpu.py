@@ -193,9 +193,9 @@ def _pending_worker(rank, world, port, out_dir, model_dir):
             self._ensure_built(d_latents, labels)
             d_loss = self.discriminator_step(d_latents, labels, real_images)   # (_run joins the pending generator update first)
             g_loss = self._run("g", g_latents, g_labels)                        # gradients only: no reduction, no update
-            if self._pipe is None:
-                self._pipe = {"g_pending": False, "g_unreduced": False, "key": None}
-            self._pipe["g_pending"] = self._pipe["g_unreduced"] = True
+            hp = self.hyper_params
+            self.g_params.t += 1                                                # the update is left pending
+            self._g_pending = self._lr_t(hp.generator_learning_rate, hp.generator_beta1, hp.generator_beta2, self.g_params.t)
             self.global_step += 1
             return d_loss, g_loss
 
@@ -217,7 +217,7 @@ def _pending_worker(rank, world, port, out_dir, model_dir):
 
 
 @pytest.mark.timeout(600)
-def test_checkpoint_in_mid_training_does_not_communicate_from_rank_0_alone():
+def test_checkpoint_with_the_generator_update_pending_does_not_communicate_from_rank_0_alone():
     """with the generator's all-reduce pending, checkpoint.save -> state_dict -> synchronize() on rank 0 alone issued
     a collective its peers never matched.  train() now joins the pending update on EVERY rank before a rank-local save and at its end."""
     sys.path.insert(0, ROOT)

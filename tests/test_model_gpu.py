@@ -387,9 +387,9 @@ def _same_up_to_accumulation_order(a, b, what, far_fraction=2e-2):
         # the tensor's scale) may step the OTHER way in one schedule: 2 lr = 1.6e-3 apart after one step, and the forward pass then carries the
         # difference on, so that more elements follow in the next step (0.2-0.3 % of the discriminator's after three iterations, seen).  Everything
         # else must agree to 1e-5, at most two elements in a hundred may be further apart, and none by more than a few steps' worth.  The sharp
-        # statement -- same arithmetic, another order -- is made where nothing amplifies it: test_alternative_issue_orders_of_the_discriminator_run
-        # compares the schedules with both learning rates at zero, and schedules that issue the same launches in the same order are held to
-        # bit-identity (forked vs plain graphs, one graph vs the pair).
+        # statement -- same arithmetic, another order -- is made where nothing amplifies it: test_replayed_iterations_reproduce_the_eager_gradients
+        # compares every replayed schedule with the eager one with both learning rates at zero, and schedules that issue the same launches in
+        # the same order are held to bit-identity (forked vs plain graphs, one graph vs the pair).
         diff, scale = (a - b).abs(), float(a.abs().max())
         far = diff > 1e-5 * scale
         assert float(far.float().mean()) <= far_fraction, (what, float(far.float().mean()), float(diff.max()), scale)
@@ -551,56 +551,6 @@ def test_discriminator_tail_over_real_and_fake_as_one_batch(gpu_store, full, dty
         else:
             assert float(out[True][1][k].abs().max()) == 0, k
     assert compared >= 14
-
-
-def test_pipelined_train_step_equals_sequential(gpu_store):
-    """train_step with graphs runs every run as two graphs and moves the optimizer updates to a side stream (they overlap the
-    other network's own part): same losses and parameters as the sequential eager iteration, step after step (up to the order
-    of fp32 gradient accumulation), and bit-identical with and without the side stream."""
-    from gansynth_amd import variables
-    out = {}
-    for mode in ("eager", "pipelined", "pipelined+side"):
-        variables.set_default_store(variables.VariableStore(device="cuda"))
-        pg, opg, model = make(1.0, variables.default_store(), full=False)
-        model.use_graphs = model.pipeline = mode != "eager"
-        model.pipe_side = mode == "pipelined+side"   # the gradient all-reduce hop through the side stream
-        gp, dp = opg.init_params(seed=0, bias_std=0.1)
-        batches = [R.synthetic_batch(4, rank=i, image_shape=(2, 16, 128)) for i in range(8)]
-        cur = [0]
-
-        def real_input_fn():
-            lat, lab, real = batches[cur[0] % len(batches)]
-            return cuda(real), cuda(lab)
-
-        def fake_input_fn():
-            lat, _, _ = batches[cur[0] % len(batches)]
-            cur[0] += 1
-            return cuda(lat)
-
-        model.real_input_fn, model.fake_input_fn = real_input_fn, fake_input_fn
-        lat, lab, _ = batches[0]
-        model._build(cuda(lat), cuda(lab))
-        variables.default_store().load_state_dict({**gp, **dp})
-        losses = []
-        for step in range(4):
-            d_loss, g_loss = model.train_step()
-            model.synchronize()
-            losses += [float(d_loss), float(g_loss)]
-        out[mode] = (losses, model.d_params.flat.clone(), model.g_params.flat.clone())
-        if mode != "eager":
-            assert model._pipe is not None and {"d", "g"} <= set(model._pipe)
-            # a plain step afterwards joins the side stream first
-            lat, lab, real = batches[1]
-            assert np.isfinite(float(model.discriminator_step(cuda(lat), cuda(lab), cuda(real))))
-    for mode in ("pipelined", "pipelined+side"):
-        for i, (a, b) in enumerate(zip(out["eager"][0], out[mode][0])):
-            _same_up_to_accumulation_order(a, b, f"{mode}: loss {i}")
-        _same_up_to_accumulation_order(out["eager"][1], out[mode][1], f"{mode}: discriminator parameters")
-        _same_up_to_accumulation_order(out["eager"][2], out[mode][2], f"{mode}: generator parameters")
-    # the side stream changes where the update runs, not what it computes: bit-identical to the one-stream pipeline
-    assert out["pipelined"][0] == out["pipelined+side"][0]
-    assert torch.equal(out["pipelined"][1], out["pipelined+side"][1]) and torch.equal(out["pipelined"][2], out["pipelined+side"][2])
-    assert model.global_step == 4
 
 
 def test_training_driver_visits_every_growing_regime_and_resumes(gpu_store, tmp_path):
@@ -1088,71 +1038,14 @@ def test_generator_part_a_inside_the_discriminator_graph(gpu_store, level, full,
     assert out["pair"][0] == out["one graph"][0] and all(same), (same, out["pair"][0], out["one graph"][0])
 
 
-@pytest.mark.parametrize("level,dtype", [(1.0, torch.float32), (0.6, torch.bfloat16)])
-def test_alternative_issue_orders_of_the_discriminator_run(gpu_store, level, dtype):
-    """The two opt-in schedules of round 6 (gansynth_amd/config.py: GS_SUB_RUNS, GS_FAKE_FIRST): the discriminator run as two
-    independent sub-runs -- two loss launches, two backward calls -- and its fake pass issued in front of the real one.  Same arithmetic in
-    another order.  Both learning rates are ZERO here, so that nothing amplifies a reassociated sum (TF-Adam's first steps are sign-like): the
-    parameters never move, the optimizer steps still run inside the graph, and the losses and BOTH networks' gradients of four one-graph
-    iterations on four different batches must agree with the default schedule to fp32 association (bf16: to a bf16 rounding of a downstream
-    activation)."""
-    from gansynth_amd import variables
-    from gansynth_amd.utils import Dict
-    out = {}
-    batches = [R.synthetic_batch(4, rank=i, image_shape=(2, 16, 128)) for i in range(4)]
-    hyper = Dict(R.DEFAULT_HYPER)
-    hyper.generator_learning_rate = hyper.discriminator_learning_rate = 0.0
-    for mode in ("default", "sub_runs", "fake_first"):
-        variables.set_default_store(variables.VariableStore(device="cuda"))
-        pg, opg, model = make(level, variables.default_store(), full=False, dtype=dtype, hyper=hyper)
-        model.use_graphs, model.keep_gradients = True, True
-        model.sub_runs, model.fake_first = mode == "sub_runs", mode == "fake_first"
-        cur = [0]
-
-        def real_input_fn():
-            lat, lab, real = batches[cur[0] % len(batches)]
-            return cuda(real).to(dtype), cuda(lab).to(dtype)
-
-        def fake_input_fn():
-            lat, _, _ = batches[cur[0] % len(batches)]
-            cur[0] += 1
-            return cuda(lat).to(dtype)
-        model.real_input_fn, model.fake_input_fn = real_input_fn, fake_input_fn
-        gp, dp = opg.init_params(seed=0, bias_std=0.1)
-        lat, lab, _ = batches[0]
-        model._build(cuda(lat).to(dtype), cuda(lab).to(dtype))
-        variables.default_store().load_state_dict({**gp, **dp})
-        before = (model.d_params.flat.clone(), model.g_params.flat.clone())
-        rec = []
-        for _ in range(4):
-            d_loss, g_loss = model.train_step()
-            model.synchronize()
-            rec.append((float(d_loss), float(g_loss), model.d_params.grad.clone(), model.g_params.grad.clone()))
-        assert model._merged is not None and model._merged["fused"] and model.global_step == 4
-        assert (model.d_params.t, model.g_params.t) == (4, 4)
-        assert torch.equal(model.d_params.flat, before[0]) and torch.equal(model.g_params.flat, before[1])   # lr = 0: the steps ran and moved nothing
-        assert float(model.d_params.v.abs().max()) > 0 and float(model.g_params.v.abs().max()) > 0            # ... but they ran
-        out[mode] = rec
-        del model
-    tol = 1e-5 if dtype == torch.float32 else 4e-3
-    for mode in ("sub_runs", "fake_first"):
-        for i, (ref, got) in enumerate(zip(out["default"], out[mode])):
-            for k, what in ((0, "discriminator loss"), (1, "generator loss")):
-                assert abs(ref[k] - got[k]) <= max(tol, 2e-5) * max(1.0, abs(ref[k])), (mode, i, what, ref[k], got[k])
-            for k, what in ((2, "discriminator gradient"), (3, "generator gradient")):
-                err = float((ref[k] - got[k]).abs().max()) / float(ref[k].abs().max())
-                assert err <= tol, (mode, i, what, err)
-
-
 @pytest.mark.parametrize("full,dtype,iterations", [(False, torch.float32, 240), (False, torch.bfloat16, 240), (True, torch.bfloat16, 45)])
 def test_replayed_iterations_reproduce_the_eager_gradients(gpu_store, full, dtype, iterations):
     """A missing dependency between two streams of a captured iteration shows as a WRONG NUMBER ONCE IN A WHILE, which comparisons after a few
     optimizer steps cannot tell from TF-Adam's amplification of round-off.  Here both learning rates are zero: the parameters never move, every
     replayed iteration must reproduce the eagerly launched, one-stream gradients of its batch (three batches in rotation), and hundreds of
-    replays are checked one by one -- every schedule (one graph, the pair, no branches, the two opt-in issue orders), reduced size fp32 / bf16
-    and configs[1] itself.  (Round 6: this found the real and the fake pass's `_WeightSlice.backward` adding into one slice of w.grad from two
-    streams unordered -- one contribution lost in ~2 % of the fp32 iterations -- and the sub-run schedule's early contraction reading the fake
-    sub-run's pairs without waiting for its stream.)"""
+    replays are checked one by one -- every schedule (one graph, the pair, no branches), reduced size fp32 / bf16 and configs[1] itself.
+    (Round 6: this found the real and the fake pass's `_WeightSlice.backward` adding into one slice of w.grad from two streams unordered --
+    one contribution lost in ~2 % of the fp32 iterations.)"""
     from gansynth_amd import variables
     from gansynth_amd.utils import Dict
     n, res = (8, (2, 128, 1024)) if full else (4, (2, 16, 128))
@@ -1161,12 +1054,11 @@ def test_replayed_iterations_reproduce_the_eager_gradients(gpu_store, full, dtyp
     hyper.generator_learning_rate = hyper.discriminator_learning_rate = 0.0
     tol = 1e-5 if dtype == torch.float32 else 1e-3   # (same kernels on the same operands: association of fp32 sums only)
     ref = None
-    for mode in ("eager", "one graph", "pair", "no branches", "sub_runs", "fake_first"):
+    for mode in ("eager", "one graph", "pair", "no branches"):
         variables.set_default_store(variables.VariableStore(device="cuda"))
         pg, opg, model = make(1.0, variables.default_store(), full=full, dtype=dtype, hyper=hyper)
         model.use_graphs, model.keep_gradients = mode != "eager", True
         model.fuse_iteration = mode != "pair"
-        model.sub_runs, model.fake_first = mode == "sub_runs", mode == "fake_first"
         if mode == "no branches":
             model.fork = False
         cur = [0]
@@ -1228,7 +1120,7 @@ def _dp_trainer(level, batches, full=False, dtype=torch.float32, distributed=Tru
     return model
 
 
-def test_gradient_all_reduce_rides_beside_part_a_of_the_other_run():
+def test_gradient_all_reduce_rides_in_the_part_a_graph_of_the_other_run():
     """the all-reduce overlapped with compute.  Data parallel with graphs, train_step() runs every run as two
     graphs and the all-reduce of the OTHER network's flat gradient is a forked branch of the part-A graph (models.GANSynth.
     _capture_pair).  On the one rank this box has: (i) parameters after 4 iterations are bit-identical to the serial data-parallel
@@ -1260,13 +1152,13 @@ def test_gradient_all_reduce_rides_beside_part_a_of_the_other_run():
                 assert model._comm is not None
                 if mode == "overlapped":
                     P = model._pipe
-                    assert P is not None and P["d"]["reduces"] and P["g"]["reduces"] and P["g_pending"] and P["g_unreduced"]
+                    assert P is not None and P["d"]["reduces"] and P["g"]["reduces"] and model._g_pending is not None
                 elif mode == "refused":
                     assert not model._graph_allreduce and not model._pipelined_ok()
                 else:
                     assert model._pipe is None
                 model.synchronize()   # (applies the generator's pending update)
-                assert model._pipe is None or not model._pipe["g_pending"]
+                assert model._g_pending is None
                 out[mode] = (float(d_loss), float(g_loss), model.d_params.flat.clone(), model.g_params.flat.clone(), model.global_step)
             for mode in ("overlapped", "refused"):
                 assert out[mode][4] == out["serial"][4] == 4
