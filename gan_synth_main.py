@@ -7,8 +7,11 @@
 Same flags and defaults; `--filenames` takes the reference's tfrecord files (or NSynth `examples.json` indexes) and
 `--synthetic` replaces them by generated notes of the same shapes when no dataset is at hand.  Multi-GPU: launch with
 `python -m torch.distributed.run --nproc-per-node N gan_synth_main.py ...` (one process per GPU, gradients all-reduced over
-RCCL; the learning rates scale with the global batch like :79,82).  `--evaluate` needs the reference's frozen pitch-classifier
-graph (a TensorFlow GraphDef, :111-122) and is not part of this path.
+RCCL; the learning rates scale with the global batch like :79,82).  `--evaluate` prints the Frechet distance between the pitch
+classifier's features of real and generated notes (:111-124); `--classifier` names the reference's frozen classifier graph (a
+TensorFlow GraphDef, read without TensorFlow) or the same weights as a .safetensors file:
+
+    python gan_synth_main.py --evaluate --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
 """
 import argparse
 import glob
@@ -95,8 +98,22 @@ def main(args):
         if rank == 0:
             print(f"stopped at global_step = {model.global_step}")
 
-    if args.evaluate:
-        raise SystemExit("--evaluate needs the reference's TensorFlow pitch-classifier graph (gan_synth_main.py:111-122): not part of this path")
+    if args.evaluate:   # :111-124, one process
+        if world > 1:
+            raise SystemExit("--evaluate runs in one process: launch it without torch.distributed")
+        if args.synthetic and args.num_generate_batches is None:
+            raise SystemExit("--evaluate --synthetic needs --num_generate_batches (synthetic input never ends)")
+        kept = model.real_input_fn   # evaluate runs over an input of its own: --generate after it still has its batches
+        model.real_input_fn = real_input_fn_factory(False)
+        try:
+            print(model.evaluate(
+                model_dir=args.model_dir,
+                config=None,
+                classifier=args.classifier,    # the frozen pitch-classifier GraphDef (.pb), or its weights as .safetensors
+                input_name="images:0",
+                output_names=["features:0", "logits:0"]))
+        finally:
+            model.real_input_fn = kept
 
     if args.generate and rank == 0:
         from scipy.io import wavfile

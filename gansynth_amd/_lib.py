@@ -122,6 +122,14 @@ SIGNATURES = {
     "gs_stft_mel_if_workspace_bytes": (Z, [P, I]),
     "gs_mel_if_to_waveform": (I, [P, P, I, I, I, P, I, P, Z, P]),
     "gs_mel_if_to_waveform_workspace_bytes": (Z, [P, I]),
+    "gs_weight_standardize": (I, [P, P, I, I, F, P]),
+    "gs_resnet_stem_pool": (I, [P, P, P, P, P, I, I, I, I, I, P]),
+    "gs_max_pool2d": (I, [P, P, I, I, I, I, I, P]),
+    "gs_conv1x1_fwd": (I, [P, P, P, I, I, I, I, I, I, I, P]),
+    "gs_group_norm_workspace_bytes": (Z, [I, I, I, I]),
+    "gs_group_norm_stats": (I, [P, P, P, P, I, I, I, I, F, I, P, Z, P]),
+    "gs_group_norm_apply": (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
+    "gs_group_norm_relu_mean": (I, [P, P, P, P, P, I, I, I, I, I, P]),
 }
 
 WGRAD_MAX_SOURCES = 4   # GS_WGRAD_MAX_SOURCES

@@ -1101,6 +1101,93 @@ class HipKernels(object):
         return _StreamGuard(self)
 
     # --------------------------------------------------------------------------- profiling
+    # ------------------------------------------------------------ pitch classifier (networks.ResNet: inference only)
+    def weight_standardize(self, w, eps, out=None):
+        """ops.py:53-66 on an fp32 HWIO / [in, out] weight: per output channel over everything else."""
+        w = _f32c(w)
+        out = torch.empty_like(w) if out is None else out
+        co = w.shape[-1]
+        _lib.check(self.lib.gs_weight_standardize(w.data_ptr(), out.data_ptr(), w.numel() // co, co, float(eps), _stream()), "gs_weight_standardize")
+        return out
+
+    def conv2d_fwd_bias_ws(self, x, w, bias, ksize, stride, ws, prepared):
+        """gs_conv2d_fwd_bias_act with alpha = 1, no activation, and a workspace the CALLER keeps with its weight (`prepared`: it still
+        holds the re-laid operand of this weight)."""
+        x = _act(x)
+        n, ci, h, wd = x.shape
+        co = w.shape[3]
+        y = _empty_like_act((n, co, h // stride, wd // stride), x)
+        bp = None if bias is None else bias.data_ptr()
+        _lib.check(self.lib.gs_conv2d_fwd_bias_act(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), n, h, wd, ci, co, ksize, stride, 1.0, _lib.ACT_NONE,
+                                                   _dt(x), int(prepared), ws.data_ptr(), ws.numel(), _stream()), "gs_conv2d_fwd_bias_act")
+        return y
+
+    def conv2d_fwd_workspace(self, x_shape, co, ksize, stride, dtype):
+        n, ci, h, wd = x_shape
+        return _ws(self.lib.gs_conv2d_workspace_bytes(_lib.CONV_FWD, n, h, wd, ci, co, ksize, stride, dtype), torch.device("cuda"))
+
+    def resnet_stem_pool(self, x, w, bias, want_stem=False, want_pool=True):
+        """(stem, pool): conv 7x7 / 2 + bias (TF SAME) and max pool 3x3 / 2 of it in one kernel; stem is None unless asked for."""
+        x = _act(x)
+        n, c, h, wd = x.shape
+        co = w.shape[3]
+        stem = _empty_like_act((n, co, h // 2, wd // 2), x) if want_stem else None
+        pool = _empty_like_act((n, co, h // 4, wd // 4), x) if want_pool else None
+        _lib.check(self.lib.gs_resnet_stem_pool(x.data_ptr(), _f32c(w).data_ptr(), None if bias is None else _f32c(bias).data_ptr(),
+                                                None if stem is None else stem.data_ptr(), None if pool is None else pool.data_ptr(),
+                                                n, h, wd, co, _dt(x), _stream()), "gs_resnet_stem_pool")
+        return stem, pool
+
+    def max_pool2d(self, x):
+        x = _act(x)
+        n, c, h, wd = x.shape
+        y = _empty_like_act((n, c, h // 2, wd // 2), x)
+        _lib.check(self.lib.gs_max_pool2d(x.data_ptr(), y.data_ptr(), n, h, wd, c, _dt(x), _stream()), "gs_max_pool2d")
+        return y
+
+    def conv1x1_fwd(self, x, w, stride):
+        """x[:, :, ::stride, ::stride] through the 1x1 weight w ([1, 1, ci, co] or [ci, co]), no bias."""
+        x = _act(x)
+        n, ci, h, wd = x.shape
+        co = w.shape[-1]
+        y = _empty_like_act((n, co, h // stride, wd // stride), x)
+        _lib.check(self.lib.gs_conv1x1_fwd(x.data_ptr(), _f32c(w).data_ptr(), y.data_ptr(), n, h, wd, ci, co, int(stride), _dt(x), _stream()),
+                   "gs_conv1x1_fwd")
+        return y
+
+    def group_norm_stats(self, x, groups, eps, addend=None):
+        """(stats [n, groups, 2] = (mean, rstd), s): the statistics of s = x (+ addend, written as it is read)."""
+        x = _act(x)
+        n, c, h, wd = x.shape
+        s = x
+        if addend is not None:
+            addend = _act(addend)
+            assert addend.shape == x.shape and addend.dtype == x.dtype
+            s = _empty_like_act(tuple(x.shape), x)
+        stats = torch.empty((n, groups, 2), dtype=torch.float32, device=x.device)
+        ws = _ws(self.lib.gs_group_norm_workspace_bytes(n, h * wd, c, groups), x.device)
+        _lib.check(self.lib.gs_group_norm_stats(x.data_ptr(), None if addend is None else addend.data_ptr(), None if addend is None else s.data_ptr(),
+                                                stats.data_ptr(), n, h * wd, c, groups, float(eps), _dt(x), ws.data_ptr(), ws.numel(), _stream()),
+                   "gs_group_norm_stats")
+        return stats, s
+
+    def group_norm_apply(self, x, stats, gamma, beta, relu):
+        x = _act(x)
+        n, c, h, wd = x.shape
+        y = _empty_like_act(tuple(x.shape), x)
+        _lib.check(self.lib.gs_group_norm_apply(x.data_ptr(), stats.data_ptr(), _f32c(gamma).data_ptr(), _f32c(beta).data_ptr(), y.data_ptr(),
+                                                n, h * wd, c, stats.shape[1], int(bool(relu)), _dt(x), _stream()), "gs_group_norm_apply")
+        return y
+
+    def group_norm_relu_mean(self, x, stats, gamma, beta):
+        """fp32 [n, c]: mean over H, W of relu(group_norm(x))."""
+        x = _act(x)
+        n, c, h, wd = x.shape
+        out = torch.empty((n, c), dtype=torch.float32, device=x.device)
+        _lib.check(self.lib.gs_group_norm_relu_mean(x.data_ptr(), stats.data_ptr(), _f32c(gamma).data_ptr(), _f32c(beta).data_ptr(), out.data_ptr(),
+                                                    n, h * wd, c, stats.shape[1], _dt(x), _stream()), "gs_group_norm_relu_mean")
+        return out
+
     def account(self):
         """bench.py: `with K.account() as calls:` lists every kernel-layer call made inside as (method, argument dict, bytes read,
         bytes written) -- the algorithmic traffic of SURVEY.md 8(d): every tensor argument read once, every result written once
@@ -1136,7 +1223,7 @@ class HipKernels(object):
 class _Accounting(object):
     SKIP = ("account", "prof_enable", "prof_roofline", "prof_records", "prof_collect", "register_param_buffer", "invalidate_weights", "early_flush_rule",
             "derived_slice", "defer_wgrad_reductions", "wgrad_slice_target_ok", "drop_deferred", "dense_nhwc_ok", "norm_bwd_bias_ok",
-            "fwd_pnbwdbwd_is_fused", "bwd_data_pnbwd_is_fused")
+            "fwd_pnbwdbwd_is_fused", "bwd_data_pnbwd_is_fused", "conv2d_fwd_workspace")
 
     def __init__(self, K):
         self.K, self.calls, self.depth, self.names = K, [], 0, []

@@ -1,0 +1,66 @@
+"""GANSynth's sample-quality metrics on host arrays (float64), with the reference's semantics (metrics.py:6-63):
+softmax, KL divergence, inception score, Frechet distance between two feature sets, the two-proportion z-test and the number of
+statistically different bins (NDB) of a k-means partition of the real features."""
+import numpy as np
+import scipy.linalg
+import scipy.stats
+
+
+def softmax(logits, axis=-1):
+    z = np.asarray(logits, dtype=np.float64)
+    e = np.exp(z - z.max(axis=axis, keepdims=True))
+    return e / e.sum(axis=axis, keepdims=True)
+
+
+def kl_divergence(p, q, axis=-1):
+    """sum p log(p / q), a zero p contributing nothing."""
+    p, q = np.asarray(p, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    zero = p == 0.0
+    return np.sum(np.where(zero, 0.0, p * np.log(np.where(zero, 1.0, p) / np.where(zero, 1.0, q))), axis=axis)
+
+
+def inception_score(logits):
+    """exp(E_x KL(p(y|x) || p(y))), p(y) the mean of the class posteriors over the set."""
+    p = softmax(logits)
+    return float(np.exp(np.mean(kl_divergence(p, p.mean(axis=0, keepdims=True)))))
+
+
+def frechet_inception_distance(real_features, fake_features):
+    """|mu_r - mu_f|^2 + tr(S_r + S_f - 2 (S_r S_f)^(1/2)), sample covariances (N - 1).  A square root whose diagonal keeps an
+    imaginary part beyond 1e-3 is refused, as the reference refuses it."""
+    a, b = np.asarray(real_features, dtype=np.float64), np.asarray(fake_features, dtype=np.float64)
+    mu_a, mu_b = a.mean(axis=0), b.mean(axis=0)
+    cov_a, cov_b = np.cov(a, rowvar=False), np.cov(b, rowvar=False)
+    root = scipy.linalg.sqrtm(cov_a @ cov_b)
+    if np.iscomplexobj(root):
+        if not np.allclose(np.diagonal(root).imag, 0.0, atol=1.0e-3):
+            raise ValueError(f"Imaginary component {np.max(np.abs(root.imag))}")
+        root = root.real
+    return float(np.sum((mu_a - mu_b) ** 2) + np.trace(cov_a + cov_b - 2.0 * root))
+
+
+def binomial_proportion_test(p, m, q, n, significance_level):
+    """Two-proportion z-test per bin with the pooled standard error: True where proportions p (of m draws) and q (of n) differ.
+    As in the reference (metrics.py:33-38) the statistic is (pooled - q) / se, the pooled proportion standing in for p -- not the
+    textbook (p - q) / se, which is (m + n) / m times larger -- so that num_different_bins counts the bins the reference counts."""
+    p, q = np.asarray(p, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    pooled = (p * m + q * n) / (m + n)
+    se = np.sqrt(pooled * (1.0 - pooled) * (1.0 / m + 1.0 / n))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = (pooled - q) / se
+    return scipy.stats.norm.cdf(-np.abs(z)) * 2.0 < significance_level
+
+
+def num_different_bins(real_features, fake_features, num_bins=50, significance_level=0.05, random_state=None):
+    """NDB: k-means (scikit-learn) on the real features, each fake feature to its nearest centre, then the bins whose two proportions
+    differ significantly.  Raises ImportError without scikit-learn."""
+    from sklearn import cluster
+    real, fake = np.asarray(real_features, dtype=np.float64), np.asarray(fake_features, dtype=np.float64)
+    km = cluster.KMeans(n_clusters=num_bins, random_state=random_state, n_init=10).fit(real)
+    real_counts = np.bincount(km.labels_, minlength=num_bins)
+    real_prop = real_counts / real_counts.sum()
+    c = km.cluster_centers_
+    d = (fake ** 2).sum(axis=1, keepdims=True) - 2.0 * fake @ c.T + (c ** 2).sum(axis=1)[None, :]
+    fake_counts = np.bincount(np.argmin(d, axis=1), minlength=num_bins)
+    fake_prop = fake_counts / fake_counts.sum()
+    return int(np.count_nonzero(binomial_proportion_test(real_prop, len(real), fake_prop, len(fake), significance_level)))

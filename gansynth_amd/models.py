@@ -1651,3 +1651,112 @@ class GANSynth(object):
         with torch.no_grad():
             images = self.generator(latents.to(self.dtype), labels.to(self.dtype))
         return spectral_ops.convert_images_to_waveform(images, **self.spectral_params)
+
+    # ------------------------------------------------------------------------------------------- evaluation
+    def evaluate(self, model_dir, config, classifier, input_name="images:0", output_names=("features:0", "logits:0"), batch_size=64,
+                 extra_metrics=False, classifier_dtype=torch.float32, features_out=None):
+        """models.py:196-230: the Frechet distance between the pitch classifier's features of real and generated spectrograms.
+
+        Restores the latest checkpoint of `model_dir` as `generate` does, then for every batch of `real_input_fn()` until it runs dry:
+        real images from its waveforms (the spectral kernels), fake images from `fake_input_fn()` latents with THAT batch's labels
+        (models.py:22-27); both go through the classifier in batches of `batch_size` (independent of the GAN's batch).
+        `classifier`: a networks.ResNet, or its weights (a frozen GraphDef path or bytes, a .safetensors path) for the reference's
+        pitch classifier.  `input_name` / `output_names` must name the reference graph's tensors ("images:0", then "features:0" and
+        "logits:0").  `config` (tf.ConfigProto) is accepted and ignored.  Returns {"frechet_inception_distance": float}; with
+        `extra_metrics` also the inception score of the fake logits, the pitch accuracy of their argmax against the conditioning labels
+        and, when scikit-learn imports, the number of statistically different bins.  `features_out` (a dict): receives the host arrays
+        real_features, fake_features, real_logits, fake_logits, labels.  One process only."""
+        import numpy as np
+        from . import checkpoint, metrics, networks
+        del config
+        if self.world > 1:
+            raise RuntimeError("GANSynth.evaluate runs in one process: launch it without torch.distributed (world size 1)")
+        if input_name != "images:0" or list(output_names) != ["features:0", "logits:0"]:
+            raise ValueError(f"evaluate: the classifier graph's tensors are 'images:0' -> ['features:0', 'logits:0'] "
+                             f"(got {input_name!r} -> {list(output_names)!r})")
+        if isinstance(classifier, networks.ResNet):
+            resnet = classifier
+        else:
+            resnet = networks.ResNet.pitch_classifier().load(classifier)
+        real_f, fake_f, real_l, fake_l, labs = [], [], [], [], []
+        pending = {"real": [], "fake": []}
+
+        def flush(which, force=False):
+            while pending[which] and (force or sum(t.shape[0] for t in pending[which]) >= batch_size):
+                x = torch.cat(pending[which])
+                take, rest = x[:batch_size], x[batch_size:]
+                pending[which] = [rest] if rest.shape[0] else []
+                f, l = resnet(take.to(classifier_dtype).contiguous(memory_format=torch.channels_last))
+                (real_f if which == "real" else fake_f).append(f.cpu().numpy())
+                (real_l if which == "real" else fake_l).append(l.cpu().numpy())
+
+        restored = False
+        while True:
+            try:
+                data, labels = self.real_input_fn()
+            except StopIteration:
+                break
+            latents = self.fake_input_fn()
+            dev = self.store.device if hasattr(self.store, "device") else labels.device
+            data, latents, labels = data.to(dev), latents.to(dev), labels.to(dev)
+            self._ensure_built(latents.to(self.dtype), labels.to(self.dtype))
+            if not restored:
+                restored = True
+                self.restored_from = checkpoint.restore(self, model_dir) if model_dir is not None else None
+            self._join_updates()
+            with torch.no_grad():
+                real = spectral_ops.convert_to_images(data, **self.spectral_params, dtype=self.dtype) if data.dim() == 2 else data
+                fake = self.generator(latents.to(self.dtype), labels.to(self.dtype))
+            pending["real"].append(real)
+            pending["fake"].append(fake)
+            labs.append(labels.float().cpu().numpy())
+            flush("real")
+            flush("fake")
+        flush("real", True)
+        flush("fake", True)
+        if not real_f:
+            raise ValueError("evaluate: real_input_fn() gave no batch")
+        real_f, fake_f = np.concatenate(real_f), np.concatenate(fake_f)
+        real_l, fake_l, labs = np.concatenate(real_l), np.concatenate(fake_l), np.concatenate(labs)
+        if features_out is not None:
+            features_out.update(real_features=real_f, fake_features=fake_f, real_logits=real_l, fake_logits=fake_l, labels=labs)
+        out = dict(frechet_inception_distance=metrics.frechet_inception_distance(real_f, fake_f))
+        if extra_metrics:
+            out["inception_score"] = metrics.inception_score(fake_l)
+            out["pitch_accuracy"] = float(np.mean(np.argmax(fake_l, axis=1) == np.argmax(labs, axis=1)))
+            try:
+                out["num_different_bins"] = metrics.num_different_bins(real_f, fake_f, random_state=0)
+            except ImportError:
+                pass
+        return out
+
+
+class PitchClassifier(object):
+    """models.py:325-408, evaluation only (training the classifier -- backward through group norm, weight standardisation and the
+    pool, Nesterov SGD -- is not part of this project).  `network`: a networks.ResNet; `input_fn()` -> (waveforms [B, L] or images
+    [B, 2, T, F], one-hot labels [B, classes]) until StopIteration."""
+
+    def __init__(self, network, input_fn, spectral_params, hyper_params=None, dtype=torch.float32):
+        self.network, self.input_fn = network, input_fn
+        self.spectral_params, self.hyper_params = spectral_params, hyper_params
+        self.dtype = dtype
+
+    def evaluate(self, model_dir=None, config=None):
+        """models.py:388-408: top-1 accuracy over the whole input.  `model_dir`: classifier weights to load first (a frozen GraphDef or
+        a .safetensors file), or None for the network's current weights.  `config` is accepted and ignored."""
+        del config
+        if model_dir is not None:
+            self.network.load(model_dir)
+        correct, total = 0, 0
+        while True:
+            try:
+                data, labels = self.input_fn()
+            except StopIteration:
+                break
+            data = data.to(self.network.store.device)
+            with torch.no_grad():
+                images = spectral_ops.convert_to_images(data, **self.spectral_params, dtype=self.dtype) if data.dim() == 2 else data
+                _, logits = self.network(images.to(self.dtype).contiguous(memory_format=torch.channels_last))
+            correct += int((logits.argmax(dim=1).cpu() == labels.argmax(dim=1).cpu()).sum())
+            total += labels.shape[0]
+        return dict(accuracy=correct / max(total, 1))

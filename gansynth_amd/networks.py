@@ -257,3 +257,177 @@ class PGGAN(object):
     def discriminator(self, images, labels, name="discriminator", reuse=AUTO_REUSE):
         x, depth, fresh = self.discriminator_trunk(images, labels.shape[1], name=name, reuse=reuse)
         return self.discriminator_tail(x, depth, fresh, labels, name=name, reuse=reuse)
+
+
+# ====================================================================================================== pitch classifier
+GN_EPS = 1.0e-12   # ops.group_normalization / ops.weight_standardization default (ops.py:53,120)
+
+
+class ResNet(object):
+    """The pitch classifier of networks.py:293-413 (GANSynth.evaluate's feature extractor), inference only.
+
+    Same constructor and call surface: `resnet(images, name="resnet", reuse)` -> (features [n, filters of the last stage] fp32,
+    logits [n, classes] fp32); images [n, 2, 128, 1024] (channels-last, fp32 or bf16: the activation dtype of the whole pass).
+    Variables use the reference's scope names and layouts ("resnet/conv/weight" [7, 7, 2, 64], "resnet/residual_block_0_0/
+    group_normalization_1st/gamma" [1, 64, 1, 1], "resnet/logits/weight" [512, 61], ...) and live in the classifier's OWN store, so a
+    GAN's parameters, checkpoints and graphs never see them.  Every conv is weight-standardised (ops.py:53-66): the standardised copy of
+    a weight is computed once per weight value (re-done when the variable changes) and the convs run on it with alpha = 1.
+    Per block (pre-activation, networks.py:306-353): GN -> ReLU (one pass, the statistics already known), [1x1 projection], 3x3 conv
+    + bias, GN statistics, GN -> ReLU, 3x3 conv + bias, then the residual add inside the pass that takes the NEXT normalisation's
+    statistics (the sum is stored once there: it is the next block's input and shortcut).  The stem conv and the max pool are one
+    kernel; the head (GN -> ReLU -> mean over H, W) is one kernel."""
+
+    def __init__(self, conv_param, pool_param, residual_params, groups, classes, store=None):
+        self.conv_param = conv_param
+        self.pool_param = pool_param
+        self.residual_params = residual_params
+        self.groups = groups
+        self.classes = classes
+        if store is None:
+            store = variables.VariableStore(device="cuda" if torch.cuda.is_available() else "cpu", seed=0)
+        self.store = store
+        self._prep = {}   # variable name -> [stamp, standardised weight, {dtype: [conv workspace, prepared]}]
+
+    @staticmethod
+    def pitch_classifier(store=None):
+        """pitch_classifier_main.py:39-50."""
+        from .utils import Dict
+        return ResNet(conv_param=Dict(filters=64, kernel_size=[7, 7], strides=[2, 2]),
+                      pool_param=Dict(kernel_size=[3, 3], strides=[2, 2]),
+                      residual_params=[Dict(filters=64, strides=[1, 1], blocks=3), Dict(filters=128, strides=[2, 2], blocks=4),
+                                       Dict(filters=256, strides=[2, 2], blocks=6), Dict(filters=512, strides=[2, 2], blocks=3)],
+                      groups=32, classes=len(range(24, 85)), store=store)
+
+    # ------------------------------------------------------------------------------------------------- variables
+    def _conv_vars(self, ksize, ci, co, use_bias):
+        """ops.get_weight / get_bias of conv2d(variance_scale=2.0) (ops.py:149-180, 221-229)."""
+        stddev = float(np.sqrt(2.0 / (ksize * ksize * ci)))
+        w = self.store.get_variable("weight", [ksize, ksize, ci, co], variables.truncated_normal(0.0, stddev))
+        b = self.store.get_variable("bias", [co], variables.zeros()) if use_bias else None
+        return w, b
+
+    def _gn_vars(self, c):
+        """ops.py:136-145 (beta first, then gamma)."""
+        beta = self.store.get_variable("beta", [1, c, 1, 1], variables.zeros())
+        gamma = self.store.get_variable("gamma", [1, c, 1, 1], variables.ones())
+        return beta, gamma
+
+    def create_variables(self, in_channels=2, name="resnet"):
+        """Every variable of the network, in the reference's creation order, without running anything."""
+        self._walk(None, in_channels, name)
+        return self.store.variables
+
+    def load_state_dict(self, state, strict=True):
+        """{variable name: array} -> the store; a missing variable or a wrong shape is refused by name."""
+        if not self.store.variables:
+            self.create_variables()
+        for k, v in self.store.variables.items():
+            if k not in state:
+                raise KeyError(f"classifier weights lack the variable {k} {tuple(v.shape)}")
+            if tuple(np.shape(state[k])) != tuple(v.shape):
+                raise ValueError(f"classifier variable {k} has shape {tuple(np.shape(state[k]))}, the network needs {tuple(v.shape)}")
+        if strict:
+            extra = [k for k in state if k not in self.store.variables and k.startswith("resnet/")]
+            if extra:
+                raise KeyError(f"classifier weights hold variables the network does not have: {extra[:4]}")
+        with torch.no_grad():
+            for k, v in self.store.variables.items():
+                v.copy_(torch.as_tensor(np.asarray(state[k], dtype=np.float32)).to(v.device))
+        self._prep.clear()
+
+    def load(self, source):
+        """A frozen GraphDef (.pb path or bytes) or a .safetensors file under the reference's variable names."""
+        from . import classifier_io
+        self.load_state_dict(classifier_io.load_classifier_weights(source, names=list(self.create_variables()) if not self.store.variables
+                                                                   else list(self.store.variables)))
+        return self
+
+    # ---------------------------------------------------------------------------------------------- prepared weights
+    def _standardized(self, w):
+        """The weight-standardised copy of variable w (fp32, same layout), recomputed only when w changes."""
+        key = id(w)
+        stamp = (w.data_ptr(), w._version)
+        ent = self._prep.get(key)
+        if ent is None or ent[0] != stamp:
+            from . import kernels
+            std = kernels.get().weight_standardize(w.detach(), GN_EPS, out=None if ent is None else ent[1])
+            ent = [stamp, std, {}]
+            self._prep[key] = ent
+        return ent
+
+    def _conv3x3(self, x, w, b, stride):
+        from . import kernels
+        K = kernels.get()
+        ent = self._standardized(w)
+        dt = kernels._dt(x)
+        slot = ent[2].get(dt)
+        if slot is None:
+            slot = ent[2][dt] = [K.conv2d_fwd_workspace(tuple(x.shape), w.shape[3], 3, stride, dt), 0]
+        y = K.conv2d_fwd_bias_ws(x, ent[1], b, 3, stride, slot[0], slot[1])
+        slot[1] = 1
+        return y
+
+    # --------------------------------------------------------------------------------------------------- forward
+    def __call__(self, inputs, name="resnet", reuse=AUTO_REUSE):
+        with torch.no_grad():
+            return self._walk(inputs, inputs.shape[1], name)
+
+    def _walk(self, x, in_channels, name):
+        """The forward of networks.py:355-413 (x None: create the variables only)."""
+        from . import kernels
+        K = kernels.get() if x is not None else None
+        scope = self.store.variable_scope
+        cp, pp, G = self.conv_param, self.pool_param, self.groups
+        if not (cp and list(cp.kernel_size) == [7, 7] and list(cp.strides) == [2, 2] and pp and list(pp.kernel_size) == [3, 3]
+                and list(pp.strides) == [2, 2] and cp.filters == 64 and in_channels == 2):
+            raise ValueError("ResNet: the stem is the pitch classifier's (conv 7x7 / 2, 2 -> 64 channels, max pool 3x3 / 2: "
+                             "pitch_classifier_main.py:39-41)")
+        with scope(name):
+            with scope("conv"):
+                w, b = self._conv_vars(7, in_channels, cp.filters, True)
+            stats = None
+            if x is not None:
+                _, x = K.resnet_stem_pool(x, self._standardized(w)[1], b)
+                stats, _ = K.group_norm_stats(x, G, GN_EPS)
+            c = cp.filters
+            for i, rp in enumerate(self.residual_params):
+                for j in range(rp.blocks):
+                    stride = int(rp.strides[0]) if j == 0 else 1
+                    if list(rp.strides) not in ([1, 1], [2, 2]):
+                        raise ValueError(f"ResNet: residual strides {rp.strides}")
+                    with scope(f"residual_block_{i}_{j}"):
+                        with scope("group_normalization_1st"):
+                            beta, gamma = self._gn_vars(c)
+                        shortcut = x
+                        if x is not None:
+                            x = K.group_norm_apply(x, stats, gamma, beta, relu=True)
+                        if j == 0:   # projection_shortcut=True for the first block of every stage (networks.py:370-378)
+                            with scope("projection_shortcut"):
+                                wp, _ = self._conv_vars(1, c, rp.filters, False)
+                            if x is not None:
+                                shortcut = K.conv1x1_fwd(x, self._standardized(wp)[1], stride)
+                        with scope("conv_1st"):
+                            w1, b1 = self._conv_vars(3, c, rp.filters, True)
+                        with scope("group_normalization_2nd"):
+                            beta2, gamma2 = self._gn_vars(rp.filters)
+                        with scope("conv_2nd"):
+                            w2, b2 = self._conv_vars(3, rp.filters, rp.filters, True)
+                        if x is not None:
+                            t = self._conv3x3(x, w1, b1, stride)
+                            st2, _ = K.group_norm_stats(t, G, GN_EPS)
+                            t = K.group_norm_apply(t, st2, gamma2, beta2, relu=True)
+                            t = self._conv3x3(t, w2, b2, 1)
+                            stats, x = K.group_norm_stats(t, G, GN_EPS, addend=shortcut)   # inputs += shortcut, stored once
+                    c = rp.filters
+            with scope("group_normalization"):
+                beta, gamma = self._gn_vars(c)
+            features = K.group_norm_relu_mean(x, stats, gamma, beta) if x is not None else None
+            with scope("logits"):   # dense(variance_scale=1.0), no weight standardisation (networks.py:404-411)
+                wl = self.store.get_variable("weight", [c, self.classes], variables.truncated_normal(0.0, float(np.sqrt(1.0 / c))))
+                bl = self.store.get_variable("bias", [self.classes], variables.zeros())
+            if x is None:
+                return None
+            from ._lib import ACT_NONE
+            # (the small-batch dense kernel: 64 rows per launch)
+            logits = torch.cat([K.dense_fwd_bias_act(features[r:r + 64], wl, bl, 1.0, ACT_NONE) for r in range(0, features.shape[0], 64)])
+            return features, logits

@@ -183,3 +183,37 @@ def lerp(a, b, t):
         ca, cb = t.weights()
         return F.axpby(a, b, ca, cb)
     return F.axpby(a, b, float(t), 1.0 - float(t))
+
+
+# ------------------------------------------------------------------------------------------------ pitch classifier operators
+# (networks.ResNet: inference only, no autograd.  The classifier's standardised convs do not go through the
+#  apply_weight_standardization flag above, which stays refused: they are networks.ResNet's own layers.)
+def weight_standardization(weight, epsilon=1.0e-12):
+    """ops.py:53-66: per output channel (last axis), (w - mean) / sqrt(var + epsilon) over all other axes, population variance."""
+    from . import kernels
+    return kernels.get().weight_standardize(weight.detach(), epsilon)
+
+
+def group_normalization(inputs, groups, epsilon=1.0e-12, activation=None):
+    """ops.py:120-146 (variables beta, gamma [1, C, 1, 1] in the current scope).  `activation="relu"`: the tf.nn.relu the classifier
+    applies right after it (networks.py:320,342,400), fused into the same pass."""
+    from . import kernels
+    if activation not in (None, "relu"):
+        raise ValueError(f"group_normalization: activation {activation!r} (None or 'relu')")
+    c = inputs.shape[1]
+    store = variables.default_store()
+    beta = store.get_variable("beta", [1, c, 1, 1], variables.zeros())
+    gamma = store.get_variable("gamma", [1, c, 1, 1], variables.ones())
+    K = kernels.get()
+    with torch.no_grad():
+        stats, _ = K.group_norm_stats(inputs, groups, epsilon)
+        return K.group_norm_apply(inputs, stats, gamma, beta, relu=activation == "relu")
+
+
+def max_pooling2d(inputs, kernel_size, strides):
+    """ops.py:308-316 (SAME); the classifier's 3x3 / stride 2 on an even input."""
+    from . import kernels
+    if list(kernel_size) != [3, 3] or list(strides) != [2, 2]:
+        raise ValueError("max_pooling2d: kernel 3x3, strides 2x2 (the pitch classifier's, networks.py:364-368)")
+    with torch.no_grad():
+        return kernels.get().max_pool2d(inputs)

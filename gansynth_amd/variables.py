@@ -86,6 +86,12 @@ def zeros():
     return init
 
 
+def ones():
+    def init(shape, gen):
+        return torch.ones(shape, dtype=torch.float32)
+    return init
+
+
 _default = None
 
 

@@ -448,6 +448,38 @@ int gs_mel_if_to_waveform(const gs_spectral_plan* plan, const void* images, int 
                           float* wave, int dtype, void* ws, size_t ws_bytes, void* stream);
 size_t gs_mel_if_to_waveform_workspace_bytes(const gs_spectral_plan* plan, int batch);
 
+/* ------------------------------------------------------------------- pitch classifier (GANSynth.evaluate, inference only)
+ * The ResNet of networks.py:293-413 (pitch_classifier_main.py:39-50: 7x7 stem, 3x3 max pool, four stages of pre-activation residual
+ * blocks with group normalisation and weight-standardised convs, global mean, dense logits).  Its 3x3 convs are gs_conv2d_fwd_bias_act
+ * with alpha = 1 on standardised weights, its logits gs_dense_fwd_bias_act; the entry points below are the rest.  Deterministic:
+ * fixed-order reductions, no float atomics.
+ *   weight_standardize  ops.py:53-66 on an HWIO weight viewed as [fan_in][co]: per output channel (w - mean) / sqrt(var + eps),
+ *                       population variance; fp32 in, fp32 out (run once per loaded weight set, not per batch)
+ *   resnet_stem_pool    conv 7x7 stride 2, 2 -> co = 64 channels, + bias, TF SAME on h, w multiples of 4 (2 before / 3 after), then
+ *                       max pool 3x3 stride 2 SAME (0 before / 1 after): x [n][h][w][2] -> y_pool [n][h/4][w/4][64] in one kernel,
+ *                       the stem output never leaves the CU; y_stem [n][h/2][w/2][64] (optional) receives it anyway (tests)
+ *   max_pool2d          ops.py:308-316 with kernel 3x3, stride 2, SAME on even h, w: x [n][h][w][c] -> y [n][h/2][w/2][c]
+ *   conv1x1_fwd         the projection shortcut (networks.py:320-330): y = x[:, ::stride, ::stride, :] @ w [ci][co], no bias;
+ *                       stride 1 or 2, ci % 32 == 0, co % 64 == 0
+ *   group_norm_stats    ops.py:120-146, statistics only: stats [n][groups][2] = (mean, 1 / sqrt(var + eps)) per (image, group) over
+ *                       hw * c / groups values (Welford within a thread, Chan merges in a fixed order).  addend (optional): the
+ *                       statistics are of x + addend, which is written to `sum` in the same pass (the residual add of a block)
+ *   group_norm_apply    y = (x - mean) * rstd * gamma[c] + beta[c], then relu when `relu` != 0 (networks.py:316-320,338-342)
+ *   group_norm_relu_mean  the head (networks.py:396-402): features [n][c] fp32 = mean over hw of relu(group_norm(x)); c % 64 == 0
+ * x / y / sum: [n][hw][c] channels-last in `dtype`; gamma, beta: [c] fp32. */
+int gs_weight_standardize(const float* w, float* out, int fan_in, int co, float eps, void* stream);
+int gs_resnet_stem_pool(const void* x, const float* w_hwio, const float* bias, void* y_stem, void* y_pool, int n, int h, int w, int co,
+                        int dtype, void* stream);
+int gs_max_pool2d(const void* x, void* y, int n, int h, int w, int c, int dtype, void* stream);
+int gs_conv1x1_fwd(const void* x, const float* w_io, void* y, int n, int h, int w, int ci, int co, int stride, int dtype, void* stream);
+size_t gs_group_norm_workspace_bytes(int n, int hw, int c, int groups);
+int gs_group_norm_stats(const void* x, const void* addend, void* sum, float* stats, int n, int hw, int c, int groups, float eps, int dtype,
+                        void* ws, size_t ws_bytes, void* stream);
+int gs_group_norm_apply(const void* x, const float* stats, const float* gamma, const float* beta, void* y, int n, int hw, int c, int groups,
+                        int relu, int dtype, void* stream);
+int gs_group_norm_relu_mean(const void* x, const float* stats, const float* gamma, const float* beta, float* features, int n, int hw, int c,
+                            int groups, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
