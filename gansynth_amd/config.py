@@ -18,10 +18,10 @@ KNOBS = {
     "GS_TORCH_COLLECTIVES": ("operational", "gradient all-reduce through torch.distributed's communicator instead of the library's own (gs_comm_*)"),
     "GS_NO_GRAPH_ALLREDUCE": ("operational", "no RCCL collective inside captured graphs: eager all-reduce behind each replay (bench.DP_LADDER's tamer modes)"),
     "GS_FORK_PROBE": ("operational", "auto | always | never: probe a forked hipGraph replay in a child process before the first forked capture "
-                                     "(auto: only on HIP builds the workaround was not debugged on, models._forked_replay_ok)"),
+                                     "(auto: only on HIP builds the workaround was not debugged on, fork_probe._forked_replay_ok)"),
     "GS_FORK_PROBED": ("operational", "(set by the probe for child processes: ok | died)"),
     "GS_FORK_PROBE_TIMEOUT_S": ("operational", "budget of that probe, seconds (600)"),
-    "GS_LEVEL_STREAMS": ("operational", "throw-away streams alive while a graph is instantiated (128; models.GANSynth._leveled_queues)"),
+    "GS_LEVEL_STREAMS": ("operational", "throw-away streams alive while a graph is instantiated (128; capture.Capture._leveled_queues)"),
     "GS_COMM_MARKER_US": ("operational", "tests / profiles at world size 1: the one-rank all-reduce becomes a kernel that holds its stream this long "
                                          "(read once per communicator, comm.RcclComm; gs_comm_set_marker_us)"),
     "GS_CAPTURE_MODE": ("operational", "debugging: force torch.cuda.graph's capture_error_mode"),

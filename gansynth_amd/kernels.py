@@ -721,7 +721,7 @@ class HipKernels(object):
         return gx
 
     def drop_deferred(self):
-        """Forget every deferred job (a backward pass that raised in the middle of a capture: models.GANSynth._abandon_capture)."""
+        """Forget every deferred job (a backward pass that raised in the middle of a capture: capture.Capture._abandon_capture)."""
         self._pending, self._folds = None, None
         self._seen, self._complete = None, None
 

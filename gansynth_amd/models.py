@@ -12,10 +12,13 @@ Parameters, gradients and Adam slots of each network live in one flat fp32 buffe
 Adam launch, one all-reduce payload).  Data parallelism (new -- the reference is single GPU):
 one process per GPU, gradients summed with torch.distributed all_reduce (backend "nccl" = RCCL
 over xGMI) and averaged inside the Adam kernel.
+
+This module keeps the reference's surface (GANSynth, PitchClassifier) and is the import path for everything outside the package.  GANSynth's
+mix-ins hold the rest: iteration.py (the three iteration forms under hipGraph replay), capture.py (how a run is captured and replayed),
+data_parallel.py (all-reduce, agreement between ranks); flat_params.py is the flat parameter buffer, fork_probe.py the check of the runtime.
 """
 import contextlib
 import math
-from collections import OrderedDict
 
 import torch
 import torch.nn.functional as TF
@@ -25,233 +28,27 @@ from . import functional as F
 from . import kernels
 from . import spectral_ops
 from . import variables
-
-_PAD = 64  # floats; keeps every parameter view 256-byte aligned inside the flat buffer
-
+from .capture import Capture
+from .data_parallel import DataParallel
+from .flat_params import _FlatParams
+from .fork_probe import _hw_queues_allow_branches
+from .iteration import Iterations
 
 _DEFER_REDUCTIONS = not config.flag("GS_NO_DEFERRED_REDUCE")   # A/B switches for measurements
 _FUSED_LOSSES = not config.flag("GS_NO_FUSED_LOSSES")
 _BATCH_D_TAIL = not config.flag("GS_NO_D_TAIL_BATCH")   # A/B switch: real + fake through the discriminator's tail as one batch
-# The all-reduce beside part A of the other run (forked graph branch, four graphs per iteration: round 4's default) is opt-in since round 5:
-# the two-graph form with the collective as the LAST node of each run's graph keeps the compute branches of section 6.5 (a four-graph
+# The all-reduce beside part A of the other run (forked graph branch, four graphs per iteration) is opt-in: the two-graph form with the collective as the LAST node of each run's graph keeps the compute branches of section 6.5 (a four-graph
 # iteration with branches would be launch-bound) -- 5.16 against 5.68 ms at world size 1, i.e. the overlapped form has to hide more than
 # half a millisecond of all-reduce to break even.
 _OVERLAP_REDUCE = config.flag("GS_OVERLAP_REDUCE") and not config.flag("GS_NO_OVERLAP_REDUCE")
 _GRAPH_ALLREDUCE = not config.flag("GS_NO_GRAPH_ALLREDUCE")   # A/B switch: the gradient all-reduce as a node of the captured graph
 _FORK = not config.flag("GS_NO_FORK")   # A/B switch: independent sub-passes of a run on a forked branch of its hipGraph (GANSynth._branch)
-LEVEL_STREAMS = int(config.value("GS_LEVEL_STREAMS", "128"))   # see GANSynth._leveled_queues
 EARLY_FLUSH_DIVS = [int(d) for d in config.value("GS_EARLY_FLUSH_DIV", "16").split(",")]   # a layer is "large" from 1/DIV of the full resolution's pixels (several: one early contraction each)
 EARLY_FLUSH_CUS = int(config.value("GS_EARLY_FLUSH_CUS", "192"))   # see GANSynth._early_flush
 _FORK_EAGER = config.flag("GS_FORK_EAGER")   # tests: the same branches with eager launches (a second stream, event hops)
 
 
-def _capture_mode(with_collective, forked=False):
-    """Keyword arguments of torch.cuda.graph for a capture that contains an RCCL collective: the communicator's helper threads may call
-    the HIP runtime while this thread captures (proxy progress, registration), which the default "global" capture mode turns into a capture
-    error on THEIR call -- captures with a collective inside run "thread_local" (only this thread's calls are checked), as captured NCCL
-    work is run elsewhere.  With forked branches in the same capture (GANSynth._branch: autograd's device thread then records and waits on
-    events between two captured streams) a thread_local capture replayed into a segmentation fault on this stack (ROCm 7.0.2, RCCL 2.26.6,
-    one rank; "global" and "relaxed" captures of the same run replay fine): those captures are "relaxed" (no thread's calls are checked).
-    Everything else keeps the strict default."""
-    forced = config.value("GS_CAPTURE_MODE")   # (debugging)
-    if forced:
-        return {"capture_error_mode": forced}
-    if not with_collective:
-        return {}
-    return {"capture_error_mode": "relaxed" if forked else "thread_local"}
-
-
-def _hw_queues_allow_branches():
-    """Graphs with parallel branches need the HIP runtime's default of four hardware queues (GPU_MAX_HW_QUEUES): with two, the streams an
-    executable graph makes for its branches cannot all miss the launch stream's queue and hip::Graph::UpdateStreams walks off its list
-    (see GANSynth._leveled_queues; measured: GPU_MAX_HW_QUEUES=2 crashes at the first replay, =8 runs at 7.8 ms instead of 5.2)."""
-    n = __import__("os").environ.get("GPU_MAX_HW_QUEUES")
-    if n is None:
-        return True
-    try:
-        ok = int(n) == 4
-    except ValueError:
-        ok = False
-    if not ok:
-        import sys
-        print("gansynth_amd.models: GPU_MAX_HW_QUEUES=%s: the runs' graphs are captured without parallel branches (they need the default, 4)" % n,
-              file=sys.stderr, flush=True)
-    return ok
-
-
-# The forked schedule was debugged on ONE build of the HIP runtime (ROCm 7.0.2: the stream-list defect of hipGraphLaunch and the workaround
-# for it, GANSynth._leveled_queues).  On that build the branches are used as they are; on any other the first trainer of a process that is about
-# to capture a forked graph runs a reduced forked iteration in a CHILD process first -- a defect of this kind is a segmentation fault inside
-# the runtime, which no exception handler of this process would see -- and a child that dies switches the branches off for the process (and
-# for its children: GS_FORK_PROBED), with a line on stderr.  GS_FORK_PROBE=always / never overrides.
-_VALIDATED_HIP = ("7.0.51831",)
-_FORK_PROBE_RESULT = []
-_FORK_PROBE = r"""
-import sys, torch
-sys.path.insert(0, %r)
-from gansynth_amd import variables
-from gansynth_amd.models import GANSynth
-from gansynth_amd.networks import PGGAN
-from gansynth_amd.utils import Dict
-variables.set_default_store(variables.VariableStore(device="cuda"))
-pg = PGGAN(min_resolution=[2, 16], max_resolution=[16, 128], min_channels=32, max_channels=64, growing_level=1.0)
-hp = Dict(generator_learning_rate=8e-4, generator_beta1=0.0, generator_beta2=0.99, discriminator_learning_rate=8e-4, discriminator_beta1=0.0,
-          discriminator_beta2=0.99, mode_seeking_loss_weight=0.1, real_gradient_penalty_weight=5.0, fake_gradient_penalty_weight=0.0)
-dt = torch.bfloat16
-lab = torch.nn.functional.one_hot(torch.arange(4) %% 61, 61).to("cuda", dt)
-real = lambda: (torch.randn(4, 2, 16, 128, device="cuda").clamp(-1, 1).contiguous(memory_format=torch.channels_last).to(dt), lab)
-model = GANSynth(pg.generator, pg.discriminator, real, lambda: torch.randn(4, 256, device="cuda", dtype=dt), None, hp, dtype=dt, use_graphs=True)
-assert model.fork
-for _ in range(4):
-    model.train_step()
-model.synchronize()
-assert model.branches_opened > 0 and bool(torch.isfinite(model.g_params.flat).all())
-print("forked replay ok")
-"""
-
-
-def _forked_replay_ok():
-    if _FORK_PROBE_RESULT:
-        return _FORK_PROBE_RESULT[0]
-    import os
-    import sys
-    mode = config.value("GS_FORK_PROBE", "auto")
-    hip = getattr(torch.version, "hip", None) or ""
-    ok = True
-    if config.value("GS_FORK_PROBED") in ("ok", "died"):
-        ok = os.environ["GS_FORK_PROBED"] == "ok"
-    elif mode == "never" or (mode != "always" and any(hip.startswith(v) for v in _VALIDATED_HIP)):
-        ok = True
-    else:
-        import subprocess
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        try:
-            res = subprocess.run([sys.executable, "-c", _FORK_PROBE % root], env=dict(os.environ, GS_FORK_PROBE="never"), capture_output=True, text=True,
-                                 timeout=float(config.value("GS_FORK_PROBE_TIMEOUT_S", "600")))
-            ok = res.returncode == 0 and "forked replay ok" in res.stdout
-            why = "rc %s: %s" % (res.returncode, (res.stderr or res.stdout).strip().splitlines()[-1:] or "")
-        except subprocess.TimeoutExpired:
-            ok, why = False, "no result in time"
-        os.environ["GS_FORK_PROBED"] = "ok" if ok else "died"
-        if not ok:
-            print("gansynth_amd.models: a forked hipGraph replay did not survive its probe on HIP %s (%s): the runs' graphs are captured without "
-                  "parallel branches in this process" % (hip or "?", why), file=sys.stderr, flush=True)
-    _FORK_PROBE_RESULT.append(ok)
-    return ok
-
-
-def _copy_inputs(dsts, srcs):
-    """A run's inputs into the static buffers its graph reads: ONE multi-tensor launch where the tensors allow it (same device, dtype and
-    strides pairwise) instead of a ~5 us copy kernel per input in front of every replay."""
-    dsts, srcs = list(dsts), list(srcs)
-    pairs = [(d, s) for d, s in zip(dsts, srcs) if d.data_ptr() != s.data_ptr()]
-    if not pairs:
-        return
-    # (only the SMALL inputs share a launch: the multi-tensor kernel moves a 4 MB image batch on 34 blocks -- 21 us against 5 for its own copy)
-    small = [(d, s) for d, s in pairs if d.numel() * d.element_size() <= (256 << 10)]
-    if len(small) > 1 and all(d.is_cuda and s.is_cuda and d.dtype == s.dtype == small[0][0].dtype and d.stride() == s.stride() for d, s in small):
-        torch._foreach_copy_([d for d, _ in small], [s for _, s in small])
-        pairs = [(d, s) for d, s in pairs if d.numel() * d.element_size() > (256 << 10)]
-    for d, s in pairs:
-        d.copy_(s)
-
-
-class _quiet_gc(object):
-    """Collect garbage NOW and keep the cyclic collector off while a hipGraph is being captured: a collection in the middle of a
-    capture may destroy an old CUDAGraph / event of an earlier trainer (a destructor that is illegal during capture: the process
-    aborts).  torch.cuda.graph no longer collects on entry by itself."""
-
-    def __enter__(self):
-        import gc
-        self._gc = gc
-        gc.collect()
-        self._was = gc.isenabled()
-        gc.disable()
-
-    def __exit__(self, *exc):
-        if self._was:
-            self._gc.enable()
-        return False
-
-
-class _FlatParams(object):
-    """All trainable variables of one scope re-homed into one flat fp32 buffer (+grad, m, v)."""
-
-    def __init__(self, named_params):
-        self.named = OrderedDict(named_params)
-        sizes = [p.numel() for p in self.named.values()]
-        offs, total = [], 0
-        for n in sizes:
-            offs.append(total)
-            total += (n + _PAD - 1) // _PAD * _PAD
-        dev = next(iter(self.named.values())).device
-        self.flat = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.grad = torch.zeros_like(self.flat)
-        self.m = torch.zeros_like(self.flat)
-        self.v = torch.zeros_like(self.flat)
-        self.numel = sum(sizes)
-        for (name, p), off, n in zip(self.named.items(), offs, sizes):
-            self.flat[off:off + n].copy_(p.data.reshape(-1))
-            p.data = self.flat[off:off + n].view(p.shape)
-            p.grad = self.grad[off:off + n].view(p.shape)
-        self.t = 0
-        self.grad_clean = True   # the flat gradient is all zeros (fresh buffer / cleared by the optimizer step)
-        self.buckets = [(0, total)]
-        self._offsets = list(zip(offs, sizes, self.named.keys()))
-
-    def make_buckets(self, max_floats, reverse=False):
-        """Split the flat buffer into contiguous ranges of whole tensors, each <= max_floats unless a single tensor is larger
-        (the generator's 4.2 M-element dense weight gets a bucket of its own), ordered as the backward pass completes them:
-        `reverse` for the generator (its backward ends at the first variables), natural order for the discriminator."""
-        total = self.flat.numel()
-        starts = [o for o, _, _ in self._offsets] + [total]
-        buckets, a = [], 0
-        for i in range(len(self._offsets)):
-            nxt = starts[i + 1]
-            if nxt - a > max_floats and starts[i] > a:      # closing before this tensor keeps the bucket under the limit
-                buckets.append((a, starts[i]))
-                a = starts[i]
-            if nxt - a >= max_floats:
-                buckets.append((a, nxt))
-                a = nxt
-        if a < total:
-            buckets.append((a, total))
-        self.buckets = buckets[::-1] if reverse else buckets
-        return self.buckets
-
-    def bucket_of(self, ptr):
-        """Index (in completion order) of the bucket holding the gradient element at device address `ptr`, or None."""
-        off = (ptr - self.grad.data_ptr()) // 4
-        if 0 <= off < self.grad.numel():
-            for i, (a, b) in enumerate(self.buckets):
-                if a <= off < b:
-                    return i
-        return None
-
-    def requires_grad_(self, flag):
-        for p in self.named.values():
-            p.requires_grad_(flag)
-
-    def zero_grad(self):
-        self.grad.zero_()
-        self.grad_clean = False   # (about to be accumulated into)
-        for p in self.named.values():
-            if p.grad is None:
-                raise RuntimeError("parameter lost its flat gradient view")
-
-    def begin_run(self):
-        """Gradients of a run are accumulated in place from zero.  The previous optimizer step may have left the buffer cleared
-        (gs_adam_tf_step_zero_grad, `grad_clean`): then there is no fill pass."""
-        if self.grad_clean:
-            self.grad_clean = False
-            for p in self.named.values():
-                if p.grad is None:
-                    raise RuntimeError("parameter lost its flat gradient view")
-        else:
-            self.zero_grad()
-
-
-class GANSynth(object):
+class GANSynth(Iterations, DataParallel, Capture):
 
     def __init__(self, generator, discriminator, real_input_fn, fake_input_fn, spectral_params, hyper_params,
                  dtype=torch.float32, store=None, distributed=False, use_graphs=False, bucket_bytes=None, keep_gradients=False):
@@ -278,16 +75,12 @@ class GANSynth(object):
         self.d_params = None
         self.generator_loss = None
         self.discriminator_loss = None
-        # hipGraph replay of the forward+backward of each run (launch-bound otherwise: ~600 kernels per run).
-        # Only valid while the network structure and every by-value kernel scalar are step-invariant, i.e. in the
-        # fully grown regime (no fade coefficient); the optimizer update and the all-reduce stay outside the graph.
+        # hipGraph replay of the iteration (launch-bound otherwise: ~600 kernels per run); which form runs when: iteration.py
         self.use_graphs = bool(use_graphs)
         self._graphs = {}
-        self._restore_from, self.restored_from = None, None
+        self.restored_from = None
         self._graph_key, self._lerp = None, None
-        # Data parallel on our own RCCL communicator with graphs, opt-in (GS_OVERLAP_REDUCE=1): train_step() runs the pipelined iteration with
-        # each gradient all-reduce as a FORKED BRANCH inside the other run's part-A graph (off the critical path; see "pipelined iteration").
-        self.overlap_reduce = _OVERLAP_REDUCE
+        self.overlap_reduce = _OVERLAP_REDUCE   # data parallel, opt-in: the pipelined iteration (iteration.py)
         self._pipe = None         # the pipelined iteration's two captured pairs and their key
         self._pipe_capture = False
         self._warming_up = False
@@ -326,7 +119,6 @@ class GANSynth(object):
         self.batch_d_tail = None   # None: the discriminator's tail over [real; fake] as one batch unless the runs fork (see _batched_tail)
         self.early_flush_always = False   # (tests: the same flush points without branches -- in place, on the one stream)
         self.early_flushes = 0
-        self._early_in_run = 0
 
     # ------------------------------------------------------------------------ forked branches
     # A run holds sub-passes that do not depend on each other:
@@ -343,33 +135,6 @@ class GANSynth(object):
     # Memory: torch's caching allocator hands a freed block back to the stream that allocated it, so a tensor read on the other stream must
     # not be recycled under that read: kernels.HipKernels.stream_guard() marks every tensor argument of every kernel-layer call with the
     # stream it is used on (record_stream; inside a capture such a block is simply not reused before the capture ends).
-    @contextlib.contextmanager
-    def _leveled_queues(self):
-        """Around a capture whose graph may hold parallel branches: LEVEL_STREAMS throw-away streams exist while the graph is instantiated
-        (torch does that when the capture ends), so that the streams the HIP runtime makes for the branches land on different hardware
-        queues -- see gs_streams_create in include/gansynth_hip.h for the runtime defect this keeps hipGraphLaunch away from."""
-        # (also without branches of our own: the data-parallel graphs fork for their all-reduce)
-        K = kernels.get() if ((self.fork or self.distributed) and torch.cuda.is_available()) else None
-        if K is None or not hasattr(K, "lib") or LEVEL_STREAMS <= 0:
-            yield
-            return
-        import ctypes
-        from . import _lib
-        handles = (ctypes.c_void_p * LEVEL_STREAMS)()
-        ptr = ctypes.cast(handles, ctypes.POINTER(ctypes.c_void_p))
-        t0 = __import__("time").perf_counter()
-        try:
-            _lib.check(K.lib.gs_streams_create(LEVEL_STREAMS, ptr), "gs_streams_create")   # (on failure the ones made so far are in `handles`)
-            self.level_seconds = getattr(self, "level_seconds", 0.0) + __import__("time").perf_counter() - t0
-            yield
-        finally:
-            _lib.check(K.lib.gs_streams_destroy(LEVEL_STREAMS, ptr), "gs_streams_destroy")
-
-    def _check_fork_runtime(self):
-        """Before the first capture that may hold parallel branches (see _forked_replay_ok)."""
-        if self.fork and torch.cuda.is_available() and not _forked_replay_ok():
-            self.fork = False
-
     def _forking(self):
         if not self.fork or not torch.cuda.is_available() or not hasattr(kernels.get(), "stream_guard"):
             return False
@@ -383,21 +148,6 @@ class GANSynth(object):
             ev = torch.cuda.Event()
             ev.record()
             self._marks[tag] = ev
-
-    def _second_stream(self, which, avoid):
-        """A pooled stream for a branch that is none of `avoid` (torch.cuda.Stream() hands out 32 pooled streams round-robin: after enough
-        captures -- every one takes a warm-up stream -- the next one IS the stream being captured: a branch that waits for itself)."""
-        cur = getattr(self, which)
-        taken = {a.cuda_stream for a in avoid if a is not None}
-        if cur is None or cur.device != avoid[0].device or cur.cuda_stream in taken:
-            for _ in range(64):
-                cur = torch.cuda.Stream(device=avoid[0].device)
-                if cur.cuda_stream not in taken:
-                    break
-            else:
-                raise RuntimeError("no further stream for the forked branches of a captured run")
-            setattr(self, which, cur)
-        return cur
 
     @contextlib.contextmanager
     def _branch(self, tag=None, join=True):
@@ -456,12 +206,6 @@ class GANSynth(object):
             return None
         full = int(owner.resolution(owner.max_depth).prod())
         return [max(1, full // d) for d in EARLY_FLUSH_DIVS]   # (16: the three levels at the top of the pyramid)
-
-    def _stream_guard(self):
-        K = kernels.get()
-        if self.fork and hasattr(K, "stream_guard") and torch.cuda.is_available():
-            return K.stream_guard()
-        return contextlib.nullcontext()
 
     # ----------------------------------------------------------------------------- build
     def _build(self, latents, labels):
@@ -618,7 +362,7 @@ class GANSynth(object):
         penalty = None
         if hp.real_gradient_penalty_weight:
             n = labels.shape[0]
-            seed = self._zero_padded_rows(raw)   # (rows n..2n stay zero for the life of the buffer)
+            seed = self._constant_like(raw, 0)   # (rows n..2n stay zero for the life of the buffer)
             seed[:n].copy_(labels)   # d sum_i real_logit_i / d logits: the one-hot labels on the real rows
             with F.data_grads_only():   # tf.gradients(real_logits, [real_images]) (models.py:47): no parameter gradients on this pass
                 (real_gradients,) = torch.autograd.grad(raw, real_images, grad_outputs=seed, create_graph=True)
@@ -640,7 +384,7 @@ class GANSynth(object):
         self._fork_mark("g_images")   # (the discriminator's pass over these images in part B does not wait for the first-order pass below)
         mode_seeking = None
         if hp.mode_seeking_loss_weight:
-            ones = self._ones_like(fake_images)  # tf.gradients(ys) sums ys
+            ones = self._constant_like(fake_images, 1)  # tf.gradients(ys) sums ys
             with F.data_grads_only():   # tf.gradients(fake_images, [latents]) (models.py:60)
                 (latent_gradients,) = torch.autograd.grad(fake_images, latents, grad_outputs=ones, create_graph=True)
             if fused:
@@ -682,57 +426,11 @@ class GANSynth(object):
         return self._g_losses_b(self._g_losses_a(latents, labels), labels)
 
     # ------------------------------------------------------------------------- updates
-    # Data parallelism (the reference is single-GPU): the flat gradient of a network is all-reduced in BUCKETS of
-    # whole tensors (<= bucket_bytes; the generator's 16.8 MB dense weight alone), in the order the backward pass completes them,
-    # and the TF-Adam update runs bucket by bucket behind its all-reduce; in eager mode the first buckets are launched from inside
-    # the backward's tail (the per-layer weight-gradient contraction, kernels.flush_wgrad_reductions) as soon as their last
-    # gradient is written.  The 1/world averaging is folded into the Adam kernel.
-    # Two transports.  (i) Default on HIP: libgansynth_hip.so's own RCCL communicator (comm.py, gs_comm_*), every collective on
-    # the backward's stream.  Nothing overlaps then -- and nothing needs an event: measured on one MI355X (RCCL, world 1, graphs):
-    # 7.31 ms per iteration against 7.28 without any collective, whereas two all-reduces through torch.distributed's
-    # communicator stream cost 0.43-0.49 ms of cross-stream hops (7.71-7.82 ms) before a single byte moves.  One bucket per network
-    # by default (fewest launches).  (ii) torch.distributed's collectives (CPU / gloo tests, GS_TORCH_COLLECTIVES=1): asynchronous
-    # on the communicator's stream, bucket k+1 on the wire under the update of bucket k.
-    def _launch_reduce(self, params, bucket):
-        a, b = params.buckets[bucket]
-        if self._comm is not None:   # same stream as the backward: ordered by the stream itself, no event hop
-            return self._comm.all_reduce_(params.grad[a:b])
-        return torch.distributed.all_reduce(params.grad[a:b], async_op=True)
-
-    def _reduce(self, params):
-        """Blocking form (pipelined step): every bucket reduced, in order, on the current stream's timeline."""
-        if self.distributed:
-            for i in range(len(params.buckets)):
-                self._launch_reduce(params, i).wait()
-
     def _adam(self, params, lr_t, beta1, beta2):
         """One TF-Adam step of the whole flat buffer on its (reduced) gradient."""
         zero = not self.keep_gradients
         kernels.get().adam_tf_step(params.flat, params.grad, params.m, params.v, lr_t, beta1, beta2, 1.0e-8, 1.0 / self.world, zero_grad=zero)
         params.grad_clean = zero
-
-    def _apply(self, params, lr, beta1, beta2, reduced=False):
-        params.t += 1
-        lr_t = self._lr_t(lr, beta1, beta2, params.t)
-        if not self.distributed or reduced:
-            self._adam(params, lr_t, beta1, beta2)
-            return
-        K = kernels.get()
-        zero = not self.keep_gradients
-        works = {}
-        if self._inflight is not None and self._inflight[0] is params:
-            works = dict(self._inflight[1])
-        self._inflight = None
-        for i in range(len(params.buckets)):
-            if i not in works:
-                works[i] = self._launch_reduce(params, i)
-        for i, (a, b) in enumerate(params.buckets):
-            works[i].wait()   # (stream-side wait: the host does not block)
-            K.adam_tf_step(params.flat[a:b], params.grad[a:b], params.m[a:b], params.v[a:b], lr_t, beta1, beta2, 1.0e-8,
-                           1.0 / self.world, refresh=False, zero_grad=zero)
-        params.grad_clean = zero   # (the buckets cover the whole buffer)
-        K.invalidate_weights(params.flat)
-        K.refresh_weights(params.flat)
 
     def _part_a(self, which, *inputs):
         """Own-network part of a run (see _d_losses_a / _g_losses_a); also arms the run: requires_grad flags, zeroed gradients."""
@@ -774,7 +472,6 @@ class GANSynth(object):
             #  data-parallel eager path, whose buckets go on the wire from the flush at the end of the pass, behind every early launch)
             big = self._large_layer_pixels()
             if big is not None:
-                self._early_in_run = 0
                 K.early_flush_rule(big, self._early_flush)
         if deferring and which == "d":
             self._arm_first_bucket(K, params)
@@ -839,61 +536,6 @@ class GANSynth(object):
             self._captured_reduce = True
         return loss.detach()
 
-    def _arm_first_bucket(self, K, params):
-        """Data parallel, captured discriminator run, OPT-IN (`bucket_d_reduce`, GS_DP_BUCKET_D=1): the all-reduce of the gradient in two steps.
-        (Opt-in because of what it measured, DESIGN.md 7: with 300-us stand-ins for the collectives -0.09 ... -0.14 ms fully grown, +0.15 ms in a
-        fade-in regime, +0.03 with 150-us ones.)
-        The layers with >= 128 input channels (and the one-channel slice of the last block's conv) hold ~90 % of the bytes and sit at the BOTTOM of
-        the pyramid: every pass of the backward is done with them long before it ends.  kernels.complete_rule tells when the last of their pairs
-        is recorded; their contraction then runs on the branch (as the early contraction of the large layers does), and behind it, on the branch
-        as well, the all-reduce of the largest range of the flat buffer that holds none of the OTHER layers' gradients -- beside the rest of the
-        backward and the final contraction.  What is left on either side of that range follows where the one message went."""
-        self._split_at, self._first_bucket_stream = None, None
-        if not (self.bucket_d_reduce and self.distributed and self._comm is not None and self._graph_allreduce and self._capturing()
-                and not self._pipe_capture and hasattr(K, "complete_rule")):
-            return
-        pred = lambda key: int(key[5][0]) >= 128 or int(key[5][0]) == 1   # (key: kernels._defer_wgrad; [5] = the conv input's (channels, h, w))
-        named = list(params.named.items())
-        sibling = {}   # weight gradient -> its bias gradient (a layer's bias follows its weight; it is complete when the layer is)
-        for (name, p), (name2, p2) in zip(named, named[1:]):
-            if name.endswith("/weight") and name2 == name[:-len("weight")] + "bias":
-                sibling[p.grad.data_ptr()] = p2.grad
-        base, size, total = params.grad.data_ptr(), params.grad.element_size(), params.grad.numel()
-
-        def on_complete(select, others):
-            def then():
-                K.flush_bias_folds()
-                spans = []
-                for out, bias in others:
-                    for t in (out, bias, sibling.get(out.data_ptr())):
-                        if t is not None:
-                            a, b = K._span(t)
-                            spans.append(((a - base) // size, (b - base + size - 1) // size))
-                if any(not (0 <= a < b <= total) for a, b in spans):
-                    return   # (a gradient outside the flat buffer: the one message at the end)
-                edges, at = [], 0
-                for a, b in sorted(spans):
-                    edges.append((at, max(at, a)))
-                    at = max(at, b)
-                edges.append((at, total))
-                first = max(edges, key=lambda e: e[1] - e[0])
-                if first[1] - first[0] > 0:
-                    self._split_at = self.first_bucket = first
-                    if config.flag("GS_DEBUG_DP_BUCKET"):
-                        print("first bucket", first, "of", total, "behind", sum(1 for _ in others), "other layers", flush=True)
-                    # on a stream of its own, behind the contraction just issued: the branch goes on to the final contraction's thin layers, and
-                    # nothing of this run waits for the message before the messages at the end do (_part_b)
-                    done = torch.cuda.Event()
-                    done.record()
-                    cur = torch.cuda.current_stream()
-                    third = self._second_stream("_side3", [cur, self._origin, self._side, self._side2])
-                    third.wait_event(done)
-                    with torch.cuda.stream(third):
-                        self._comm.all_reduce_(params.grad[first[0]:first[1]], marker_share=(first[1] - first[0]) / total)
-                    self._first_bucket_stream = third
-            self._early_flush(select, then=then)
-        K.complete_rule(pred, on_complete)
-
     def _join_branches(self):
         """The current stream waits for every branch this run opened: the side stream (every branch was joined where it closed, except the
         early contraction's, and autograd joins the streams it used) and, in the merged iteration, the stream this run's own-network nodes
@@ -904,86 +546,18 @@ class GANSynth(object):
         if self._nodes_on_side2 and self._forking():
             torch.cuda.current_stream().wait_stream(self._side2)
 
-    def _reduce_in_capture(self, params):
-        """The gradient all-reduce issued while the current stream is being captured into a hipGraph (a method of its own so that a
-        test can make it raise and watch every rank fall back together)."""
-        self._reduce(params)
-
-    def _agree(self, ok):
-        """Data parallel: did EVERY rank succeed?  A rank-local failure (allocator, capture) must not leave one rank on a different
-        launch sequence than its peers -- their collectives would no longer pair up and the job would hang -- so the outcome of
-        anything that may fail locally is agreed on with an eager MIN all-reduce over the launcher's process group, outside any
-        capture, and every rank takes the same branch."""
-        if not self.distributed or self.world <= 1:
-            return bool(ok)
-        dev = self.g_params.flat.device
-        flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=dev)
-        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN)
-        return bool(flag.item())
-
-    def _give_up_graph_collectives(self, which, error):
-        """Every rank lands here together (see _agree): no collective inside captured graphs any more.  A capture that aborted with an
-        ncclAllReduce inside may have left our communicator unusable, so the eager collectives move to torch.distributed's own."""
-        import sys
-        print("gansynth_amd.models: capturing the gradient all-reduce inside the %s run's graph failed on some rank (here: %s); "
-              "it will run eagerly after each replay" % (which, "ok" if error is None else str(error).splitlines()[0]), file=sys.stderr, flush=True)
-        self._graph_allreduce = False
-        self._captured_reduce = False
-        # Every graph captured so far may replay an ncclAllReduce on the communicator given up here (the OTHER run's graph of the
-        # serial path, the pairs of the pipelined step): all of them go, so that every run is captured again without a collective.
-        torch.cuda.synchronize()
-        self._graphs.clear()
-        self._merged = None
-        self._pipe = None
-        if self.world > 1 and self._comm is not None:
-            # Not destroyed: ncclCommDestroy on a communicator an aborted capture left half-enqueued may block.  It is retired --
-            # never used again, kept alive until the process ends -- and the eager collectives go through torch.distributed.
-            self._retired_comm = self._comm
-            self._comm = None
-        self._abandon_capture(which)
-
-    def _abandon_capture(self, which):
-        """State left behind by a _forward_backward that raised in the middle of a stream capture: deferred kernel-layer jobs, half-built
-        fusion hand-offs and the gradients the partial backward wrote."""
-        torch.cuda.synchronize()
-        K = kernels.get()
-        if hasattr(K, "drop_deferred"):
-            K.drop_deferred()
-        F.reset_fusion_state()
-        self._inflight = None
-        self._after_loss = None
-        self._marks.clear()
-        params = self.d_params if which == "d" else self.g_params
-        if not self.keep_gradients:   # (as before the first capture: a graph without a fill must find the buffer the way every replay will)
-            params.grad.zero_()
-            params.grad_clean = True
-
-    @staticmethod
-    def _capturing():
-        return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-
-    def _ones_like(self, t):
-        """A constant all-ones tensor of t's shape, layout and dtype, filled once (never written afterwards; a fill created inside a
-        stream capture would belong to that graph's pool, so there the plain ones_like runs)."""
-        cache = self.__dict__.setdefault("_ones_cache", {})
-        key = (tuple(t.shape), tuple(t.stride()), t.dtype, str(t.device))
-        ones = cache.get(key)
-        if ones is None:
-            ones = torch.ones_like(t)
+    def _constant_like(self, t, value):
+        """A constant tensor of t's shape, layout and dtype, all ones or all zeros, filled once and never written afterwards (of the zeros
+        the caller overwrites the same rows every time).  A fill created inside a stream capture would belong to that graph's pool, so
+        there the plain fill runs."""
+        cache = self.__dict__.setdefault("_constants", {})
+        key = (value, tuple(t.shape), tuple(t.stride()), t.dtype, str(t.device))
+        c = cache.get(key)
+        if c is None:
+            c = torch.ones_like(t) if value else torch.zeros_like(t)
             if not self._capturing():
-                cache[key] = ones
-        return ones
-
-    def _zero_padded_rows(self, t):
-        """A tensor of t's shape whose rows the caller overwrites only in the upper half; zeroed once (same rule as _ones_like)."""
-        cache = self.__dict__.setdefault("_zero_cache", {})
-        key = (tuple(t.shape), t.dtype, str(t.device))
-        z = cache.get(key)
-        if z is None:
-            z = torch.zeros_like(t)
-            if not self._capturing():
-                cache[key] = z
-        return z
+                cache[key] = c
+        return c
 
     def _capturing_fresh_seed(self, device):
         """True when the constant seed of this device would have to be CREATED inside a stream capture (its memory would belong
@@ -1016,96 +590,6 @@ class GANSynth(object):
             return None
         return owner._head_depth(owner.growing_depth)
 
-    def _graphable(self):
-        """hipGraph replay needs a step-invariant launch sequence: the network structure is fixed within a growing regime (head
-        depth, faded or not -- graphs are re-captured when it changes) and the one per-step scalar, the fade-in weight, is read
-        from device memory (functional.DeviceLerp)."""
-        return self.use_graphs and torch.cuda.is_available() and self._regime() is not None
-
-    def _run(self, which, *inputs):
-        self._join_updates()
-        owner = getattr(self.generator, "__self__", None)
-        self._run_reduced = False
-        if not self._graphable():
-            self._graphs.clear()
-            with self._stream_guard() if self.fork_eager else contextlib.nullcontext():
-                return self._forward_backward(which, *inputs)
-        head, fade = self._regime()
-        key = (head, fade is None)
-        if self._graph_key != key:   # a new growing regime: different launch sequence
-            self._graphs.clear()
-            self._graph_key = key
-            F.drop_constants()   # (junction constants of the old regime's shapes; live graphs hold their own references)
-        if fade is not None:
-            if self._lerp is None:
-                self._lerp = F.DeviceLerp(self.g_params.flat.device)
-            self._lerp.set(fade)   # (stream-ordered before the replay below)
-        entry = self._graphs.get(which)
-        if entry is not None and entry[4] != self.keep_gradients:
-            entry = None   # (a graph captured without a gradient fill relies on the zeroing optimizer step behind every replay)
-        if entry is None or any(a.shape != b.shape or a.dtype != b.dtype for a, b in zip(entry[1], inputs)):
-            self._check_fork_runtime()
-            static = [t.detach().clone() for t in inputs]
-            K = kernels.get()
-            owner.fade_weight = self._lerp if fade is not None else None   # the networks read the weight from the device table
-            try:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                self._warming_up = True
-                try:
-                    with torch.cuda.stream(side):  # one eager pass on a side stream (allocator / lazy-init warm-up)
-                        self._forward_backward(which, *static)
-                        if self.distributed and self._comm is not None and self._graph_allreduce:
-                            # RCCL sets up its channels on the first collective of a kind: not capturable, so one eager all-reduce
-                            # of the buffers the graph will reduce (every rank does the same; the gradients are dead values here)
-                            self._reduce(self.d_params if which == "d" else self.g_params)
-                finally:
-                    self._warming_up = False
-                torch.cuda.current_stream().wait_stream(side)
-                # the warm-up pass left its gradients in the flat buffer and no optimizer step clears them: a graph that relies on the
-                # step's clearing (keep_gradients = False: no fill inside) must find the buffer as every later replay will
-                params_ = self.d_params if which == "d" else self.g_params
-                if not self.keep_gradients:
-                    params_.grad.zero_()
-                    params_.grad_clean = True
-                # the prepared weight operands live in persistent workspaces that the optimizer step refreshes eagerly
-                # (kernels.adam_tf_step): bring them up to date now so that the captured graph holds no re-layout launches
-                K.refresh_weights()
-                graph = torch.cuda.CUDAGraph()
-                self._captured_reduce = False
-                with_collective = self.distributed and self._comm is not None and self._graph_allreduce
-                error = None
-                try:
-                    with _quiet_gc(), self._leveled_queues(), self._stream_guard(), torch.cuda.graph(graph, **_capture_mode(with_collective, self.fork)):
-                        loss = self._forward_backward(which, *static)
-                except RuntimeError as e:
-                    if not with_collective:
-                        raise
-                    error = e
-                if with_collective and not self._agree(error is None):
-                    # The collective would not go into the graph on SOME rank: every rank (agreed above, so that no rank keeps a graph
-                    # with the collective inside while a peer reduces eagerly) captures the run again without it -- the all-reduce
-                    # then follows each replay eagerly, as in round 2.
-                    self._give_up_graph_collectives(which, error)
-                    graph = torch.cuda.CUDAGraph()
-                    with _quiet_gc(), self._leveled_queues(), self._stream_guard(), torch.cuda.graph(graph):
-                        loss = self._forward_backward(which, *static)
-            finally:
-                owner.fade_weight = None   # (only captured launches use the table; eager callers keep passing the number)
-            entry = (graph, static, loss, self._captured_reduce, self.keep_gradients, F.constants_snapshot())
-            self._graphs[which] = entry
-        graph, static, loss, reduced = entry[:4]
-        if not self.keep_gradients:
-            params_ = self.d_params if which == "d" else self.g_params
-            if not params_.grad_clean:   # (a replay not preceded by the zeroing update: e.g. a run repeated without its optimizer step)
-                params_.grad.zero_()
-                params_.grad_clean = True
-            params_.grad_clean = False   # (what begin_run did at capture time: the replay accumulates into the buffer)
-        _copy_inputs(static, inputs)
-        graph.replay()
-        self._run_reduced = reduced   # (the replay already summed the gradients over the ranks: _apply goes straight to the update)
-        return loss
-
     def discriminator_step(self, latents, labels, real_images):
         self._ensure_built(latents, labels)
         hp = self.hyper_params
@@ -1123,398 +607,9 @@ class GANSynth(object):
         self.generator_loss = loss
         return self.generator_loss
 
-    # ------------------------------------------------------------------ pipelined iteration
-    # Data parallel, opt-in (GS_OVERLAP_REDUCE=1): every run as TWO graphs, part A (own network only) and part B (the rest), so that the
-    # optimizer update of the OTHER network -- its gradient all-reduce above all -- can sit between them:
-    #     D.A | update G | D.B | G.A | update D | G.B
-    # Part A needs neither the gradients being reduced nor the parameters about to change.  The all-reduce of the other network's flat
-    # gradient is a forked branch INSIDE graph A -- fork at the graph's root, join at its end -- so the collective node is off the critical
-    # path of part A's kernels and there is no cross-stream event between replays (an event hop between a replay and another stream costs
-    # 0.25-0.75 ms on this stack, scripts/cross_stream_cost.py).  Adam and the operand refresh stay eager on the main stream behind graph A
-    # (lr_t is a by-value scalar; streaming kernels beside the persistent conv blocks cost the main stream 5 %, measured).
-    def _apply_g_pending(self):
-        """The generator's pending step (`_g_pending`: its lr_t) on the gradient in its flat buffer, already all-reduced."""
-        lr_t, self._g_pending = self._g_pending, None
-        self._adam(self.g_params, lr_t, self.hyper_params.generator_beta1, self.hyper_params.generator_beta2)
-
-    def _join_updates(self):
-        """The one-graph and the pipelined iteration leave the generator's update pending, its gradient not yet all-reduced (the next
-        iteration's graph does both): reduce and apply it here.  Data parallel: this IS a collective -- every rank must get here at the
-        same point of its launch sequence.  train() therefore joins on EVERY rank before a rank-0 checkpoint and at its end;
-        synchronize(), state_dict / checkpoint.save and generate() called by hand on a distributed model must be called on all ranks
-        (`collective_pending()` tells whether the call would communicate)."""
-        if self._g_pending is not None:
-            self._reduce(self.g_params)
-            self._apply_g_pending()
-
-    def collective_pending(self):
-        """True when the next _join_updates() / synchronize() / generate() / checkpoint would issue a gradient all-reduce."""
-        return self.distributed and self.world > 1 and self._g_pending is not None
-
-    def synchronize(self):
-        """Everything a train_step enqueued (including the pending update) has finished.  Collective when `collective_pending()`."""
-        self._join_updates()
-        if torch.cuda.is_available():
-            torch.cuda.synchronize()
-
-    def _overlap_in_graph(self):
-        """The gradient all-reduce as a forked branch of the other run's part-A graph: data parallel, own RCCL communicator, in-graph
-        collectives not refused (GS_NO_GRAPH_ALLREDUCE / a failed capture), not switched off (GS_NO_OVERLAP_REDUCE=1)."""
-        return self.distributed and self._comm is not None and self._graph_allreduce and self.overlap_reduce
-
-    def _capture_pair(self, which, a_inputs, b_inputs, reduce_params):
-        """Two graphs for one run: part A (own network) and part B (the rest), sharing one memory pool (replayed A, B, A, B ...).
-        `reduce_params`: the OTHER network's parameters, whose flat gradient is all-reduced on a forked branch of graph A."""
-        K = kernels.get()
-        owner = getattr(self.generator, "__self__", None)
-        _, fade = self._regime()
-        sa = [t.detach().clone() for t in a_inputs]
-        sb = [t.detach().clone() for t in b_inputs]
-        params = self.d_params if which == "d" else self.g_params
-        owner.fade_weight = self._lerp if fade is not None else None   # the networks read the fade weight from the device table
-        self._pipe_capture = True   # (the pipelined step places its reductions itself: none at the end of part B)
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            self._warming_up = True
-            try:
-                with torch.cuda.stream(side):  # one eager pass on a side stream (allocator / lazy-init warm-up)
-                    self._part_b(which, self._part_a(which, *sa), *sb)
-                    self._reduce(reduce_params)   # RCCL sets up its channels on the first collective: not capturable (dead values here)
-            finally:
-                self._warming_up = False
-            torch.cuda.current_stream().wait_stream(side)
-            if not self.keep_gradients:   # the graphs hold no fill: they rely on the zeroing optimizer step behind every part B (see _run)
-                params.grad.zero_()
-                params.grad_clean = True
-            K.refresh_weights()   # (see _run: the captured graphs hold no re-layout launches)
-            ga = torch.cuda.CUDAGraph()
-            import warnings
-            with warnings.catch_warnings(record=True) as caught:
-                warnings.simplefilter("always")
-                with _quiet_gc(), self._leveled_queues(), self._stream_guard(), torch.cuda.graph(ga, **_capture_mode(True, self.fork)):
-                    main = torch.cuda.current_stream()
-                    fork = torch.cuda.Stream()
-                    while fork.cuda_stream == main.cuda_stream or (self._side is not None and fork.cuda_stream == self._side.cuda_stream):
-                        fork = torch.cuda.Stream()   # (pooled streams come round-robin: never the capturing one, nor the branches')
-                    fork.wait_stream(main)            # fork at the root of the graph ...
-                    with torch.cuda.stream(fork):
-                        self._reduce_in_capture(reduce_params)
-                    part_a = self._part_a(which, *sa)
-                    main.wait_stream(fork)            # ... join at its end: the collective runs beside all of part A
-            # Part A may hold NO kernel: a discriminator whose whole depth runs in the batched tail has no trunk of its own (shallow
-            # growing regimes), and on ONE rank RCCL short-cuts the all-reduce to nothing as well.  torch warns about the empty graph;
-            # that is the only way it can be empty -- with peers the collective is a node -- and an empty part A is simply not replayed.
-            a_empty = any("Graph is empty" in str(w.message) for w in caught)
-            for w in caught:
-                if "Graph is empty" not in str(w.message):
-                    warnings.warn_explicit(w.message, w.category, w.filename, w.lineno)
-            if a_empty and self.world > 1:
-                raise RuntimeError("part A of the %s run captured no node although it holds a gradient all-reduce over %d ranks" % (which, self.world))
-            gb = torch.cuda.CUDAGraph()
-            with _quiet_gc(), self._leveled_queues(), self._stream_guard(), torch.cuda.graph(gb, pool=ga.pool()):
-                loss = self._part_b(which, part_a, *sb)
-        finally:
-            self._pipe_capture = False
-            owner.fade_weight = None
-        return {"a": ga, "b": gb, "sa": sa, "sb": sb, "loss": loss, "reduces": True, "keep": self.keep_gradients, "a_empty": a_empty,
-                "consts": F.constants_snapshot()}   # (cached junction constants the graphs read: alive as long as the graphs)
-
-    def _pipelined_ok(self):
-        return self._graphable() and self._overlap_in_graph()
-
-    def _train_step_pipelined(self, d_latents, d_labels, real_images, g_latents, g_labels):
-        """D.A | update G | D.B | G.A | update D | G.B (see above)."""
-        hp = self.hyper_params
-        P = self._pipe
-        head, fade = self._regime()
-        key = (head, fade is None, self.keep_gradients)
-        if fade is not None:
-            if self._lerp is None:
-                self._lerp = F.DeviceLerp(self.g_params.flat.device)
-            self._lerp.set(fade)   # (stream-ordered before the replays below)
-
-        def fresh(entry, a_inputs, b_inputs):
-            return any(x.shape != y.shape or x.dtype != y.dtype for x, y in zip(entry["sa"] + entry["sb"], list(a_inputs) + list(b_inputs)))
-
-        d_in = ((d_labels, real_images), (d_latents, d_labels))
-        g_in = ((g_latents, g_labels), (g_labels,))
-        if P is None or P["key"] != key or fresh(P["d"], *d_in) or fresh(P["g"], *g_in):
-            self._join_updates()
-            self._graphs.clear()
-            self._pipe = None
-            if P is not None and P["key"][:2] != key[:2]:
-                F.drop_constants()   # (a new growing regime: see _run)
-            error = None
-            try:
-                P = {"key": key, "d": self._capture_pair("d", *d_in, self.g_params), "g": self._capture_pair("g", *g_in, self.d_params)}
-            except RuntimeError as e:
-                error = e
-            if not self._agree(error is None):
-                # some rank could not capture the collective: EVERY rank (agreed, so that the collective sequences of the ranks stay
-                # identical) drops the in-graph form; this iteration and the later ones run as two plain runs with the all-reduce
-                # eagerly behind each replay (_run)
-                self._give_up_graph_collectives("d", error)
-                self._abandon_capture("g")
-                d_loss = self.discriminator_step(d_latents, d_labels, real_images)
-                g_loss = self.generator_step(g_latents, g_labels)
-                return d_loss, g_loss
-            self._pipe = P
-        D, G = P["d"], P["g"]
-        _copy_inputs(D["sa"] + D["sb"] + G["sa"] + G["sb"], list(d_in[0]) + list(d_in[1]) + list(g_in[0]) + list(g_in[1]))
-
-        def armed(params):
-            """A no-fill graph is about to accumulate into this buffer: it must be clean (the zeroing update behind the last part B)."""
-            if not self.keep_gradients:
-                if not params.grad_clean:
-                    params.grad.zero_()
-                params.grad_clean = False
-
-        # D run.  Graph A = {D part A  ||  all-reduce of the generator's pending gradient}; then the generator's update (part B runs
-        # the generator), then part B.
-        armed(self.d_params)
-        if not D["a_empty"]:
-            D["a"].replay()
-        if self._g_pending is not None:
-            self._apply_g_pending()
-        D["b"].replay()
-        # G run.  Graph A = {G part A  ||  all-reduce of the discriminator's gradient}; the discriminator's update; part B runs it.
-        armed(self.g_params)
-        if not G["a_empty"]:
-            G["a"].replay()
-        self._apply(self.d_params, hp.discriminator_learning_rate, hp.discriminator_beta1, hp.discriminator_beta2, reduced=True)
-        G["b"].replay()
-        # the generator's step is left pending: its gradient is reduced inside the next D graph (or eagerly by _join_updates)
-        self.g_params.t += 1
-        self._g_pending = self._lr_t(hp.generator_learning_rate, hp.generator_beta1, hp.generator_beta2, self.g_params.t)
-        self.global_step += 1  # models.py:84
-        self.discriminator_loss, self.generator_loss = D["loss"], G["loss"]
-        return D["loss"], G["loss"]
-
-    # ------------------------------------------------------------------- merged iteration
-    # One GPU, graphs with branches: part A of the GENERATOR run (G(z) and the mode-seeking first-order pass: its own network only, whose
-    # parameters the discriminator run does not touch) is captured INSIDE the discriminator run's graph, on a stream of its own from the
-    # graph's root -- the discriminator run's second half is one stream wide (the fake pass and the early weight gradients are done, the R1
-    # double-backward, the real pass's backward and the final contraction remain), and the generator's few-block levels fill from it and
-    # into it.  Two graphs per iteration as before:   X = { D run  ||  G.A }   update D   Y = { G.B }   update G.
-    # 5.13 / 5.07 -> 4.99 / 4.93 ms on one box (first measured neutral, 5.19-5.23 against 5.22-5.24: the two passes of the discriminator
-    # run were still waiting on each other at every accumulate target, kernels._adds_into).
-    # The generator's own-network nodes were created on that stream, so autograd runs their backward there in Y as well (joined at the
-    # end of the run, _part_b).
-    def _merged_ok(self):
-        # (data parallel: with the gradient all-reduce as the last node of each of the two graphs -- own communicator, in-graph collectives
-        #  not refused, not the four-graph overlapped form)
-        dp_ok = not self.distributed or (self._comm is not None and self._graph_allreduce and not self._overlap_in_graph())
-        return (self.merge_runs and self.fork and self._graphable() and dp_ok and self._fused_losses() and hasattr(kernels.get(), "lib"))
-
-    # One graph per iteration (round 6; `fuse_iteration`, GS_NO_FUSED_ITERATION=1 returns to the pair above).  The two optimizer steps were the
-    # only eager launches left between the graphs -- lr_t is a by-value scalar -- and with them outside, (i) every iteration pays two graph
-    # boundaries, (ii) nothing can run beside an update, and (iii) data parallel, an all-reduce can only be the LAST node of a graph: exposed.
-    # gs_adam_tf_step_dev reads lr_t from device memory, so the whole iteration is ONE graph Z:
-    #     Z_k = { D real pass + R1 first-order pass        ||  [all-reduce G_{k-1}] -> Adam G_{k-1} -> refresh G -> D run's fake pass }
-    #           -> D loss -> { D backward, contraction [all-reduce D_k] -> Adam D_k -> refresh D   ||  G.A_k }  ->  G.B_k
-    # The GENERATOR's update of iteration k - 1 rides at the front of Z_k on the fake pass's branch: the discriminator's real pass and its R1
-    # passes need nothing of the generator, and the fake pass (G fwd + D fwd + D bwd = 4 network passes against ~7 on the real side) has the
-    # slack.  Data parallel this is where the generator's all-reduce hides by construction.  The discriminator's update sits where it always
-    # did -- behind its backward -- but part A of the generator run is still in flight beside it.  After Z_k the generator's gradient is
-    # PENDING (`_g_pending` holds its lr_t): the next replay applies it (lr slot >= 0), anything else that needs the weights -- generate(),
-    # a checkpoint, a run outside this path, a new growing regime -- goes through _join_updates() first.  A freshly captured Z finds no
-    # pending step: its lr slot is negative and the kernel leaves every buffer untouched.
-    def _fused_ok(self):
-        return self.fuse_iteration and hasattr(kernels.get(), "adam_tf_step_dev")
-
     @staticmethod
     def _lr_t(lr, beta1, beta2, t):
         return lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
-
-    def _apply_in_graph(self, params, slot, beta1, beta2, reduce_first=False):
-        """The optimizer step as nodes of the graph being captured: [all-reduce] -> Adam with lr_t from the device table -> operand refresh."""
-        if reduce_first:
-            self._reduce_in_capture(params)
-        kernels.get().adam_tf_step_dev(params.flat, params.grad, params.m, params.v, self._opt_scalars.ptr(slot), beta1, beta2, 1.0e-8,
-                                       1.0 / self.world, zero_grad=not self.keep_gradients)
-
-    def _capture_merged(self, d_inputs, g_inputs, fused=False):
-        K = kernels.get()
-        owner = getattr(self.generator, "__self__", None)
-        _, fade = self._regime()
-        sd = [t.detach().clone() for t in d_inputs]
-        sg = [t.detach().clone() for t in g_inputs]
-        owner.fade_weight = self._lerp if fade is not None else None   # the networks read the fade weight from the device table
-        with_collective = self.distributed and self._comm is not None and self._graph_allreduce
-        error, reduced = None, [False, False]
-        try:
-            warm = torch.cuda.Stream()
-            warm.wait_stream(torch.cuda.current_stream())
-            self._warming_up = True
-            try:
-                with torch.cuda.stream(warm):  # one eager pass on a side stream (allocator / lazy-init warm-up)
-                    self._forward_backward("d", *sd)
-                    self._forward_backward("g", *sg)
-                    if with_collective:   # RCCL sets up its channels on the first collective of a kind: not capturable (dead values here)
-                        self._reduce(self.d_params)
-                        self._reduce(self.g_params)
-            finally:
-                self._warming_up = False
-            torch.cuda.current_stream().wait_stream(warm)
-            if not self.keep_gradients:   # the graphs hold no fill: they rely on the zeroing optimizer steps (see _run)
-                for params in (self.d_params, self.g_params):
-                    params.grad.zero_()
-                    params.grad_clean = True
-            K.refresh_weights()   # (see _run: the captured graphs hold no re-layout launches)
-            hp = self.hyper_params
-            if fused:
-                if self._opt_scalars is None:
-                    self._opt_scalars = F.DeviceScalars(self.g_params.flat.device, 2)
-                # the per-network refresh launches read descriptor tables that are built (host -> device) on first use: not inside a capture
-                for params in (self.d_params, self.g_params):
-                    K.invalidate_weights(params.flat)
-                    K.refresh_weights(params.flat)
-            try:
-                gx = torch.cuda.CUDAGraph()
-                self._captured_reduce = False
-                with _quiet_gc(), self._leveled_queues(), self._stream_guard(), torch.cuda.graph(gx, **_capture_mode(with_collective, self.fork)):
-                    main = torch.cuda.current_stream()
-                    side2 = self._second_stream("_side2", [main, self._side])
-                    box = []
-                    if fused:
-                        # the generator's PENDING step at the front of the fake pass's branch (no stream of its own: the branch is its only
-                        # consumer until the join, and a graph one branch wider would need one more of the runtime's four hardware queues)
-                        self._before_fake = lambda: self._apply_in_graph(self.g_params, 1, hp.generator_beta1, hp.generator_beta2,
-                                                                         reduce_first=with_collective)
-
-                    def part_a_of_g():
-                        # from the discriminator run's loss on its second half is one stream wide (R1 double-backward, the real pass's backward,
-                        # the final contraction): part A of the generator run goes THERE (from the graph's root, beside the two forward passes,
-                        # measured 5.27 -> 5.34 ms in round 5)
-                        side2.wait_stream(torch.cuda.current_stream())
-                        with torch.cuda.stream(side2):
-                            box.append(self._part_a("g", *sg))
-                        self.g_params.requires_grad_(False)      # (back to the discriminator run's arming for its backward)
-                        self.d_params.requires_grad_(True)
-                    self._after_loss = part_a_of_g
-                    d_loss = self._forward_backward("d", *sd)    # (data parallel: ends with the all-reduce of the discriminator's gradient, _part_b)
-                    g_part_a = box[0]
-                    if fused:
-                        if self._before_fake is not None:
-                            raise RuntimeError("the discriminator run never reached its fake pass: the generator's pending step has no place in the graph")
-                        # the discriminator's step, behind its (all-reduced) gradient; part A of the generator run is still in flight beside it
-                        self._apply_in_graph(self.d_params, 0, hp.discriminator_beta1, hp.discriminator_beta2)
-                    main.wait_stream(side2)                      # ... join at its end
-                    if fused:   # part B of the generator run in the same graph (reads the discriminator just updated)
-                        reduced[0] = self._captured_reduce
-                        self.g_params.requires_grad_(True)
-                        self.d_params.requires_grad_(False)
-                        self._side2.wait_stream(main)            # (as in the pair's second graph: the generator's nodes run on their stream again)
-                        self._nodes_on_side2 = True
-                        self._pipe_capture = True                # (no all-reduce at the end of THIS run: it opens the next graph, beside the real pass)
-                        try:
-                            g_loss = self._part_b("g", g_part_a, sg[1])
-                        finally:
-                            self._nodes_on_side2 = False
-                            self._pipe_capture = False
-                        reduced[1] = reduced[0]
-                if not fused:
-                    reduced[0] = self._captured_reduce
-                gy = None if fused else torch.cuda.CUDAGraph()
-                self._captured_reduce = False
-                with (contextlib.nullcontext() if fused else contextlib.ExitStack()) as stack:
-                    if not fused:
-                        for cm in (_quiet_gc(), self._leveled_queues(), self._stream_guard(),
-                                   torch.cuda.graph(gy, pool=gx.pool(), **_capture_mode(with_collective, self.fork))):
-                            stack.enter_context(cm)
-                        self.g_params.requires_grad_(True)           # (the discriminator run in between armed the other network)
-                        self.d_params.requires_grad_(False)
-                        # the generator's nodes will run on their stream again (autograd): it joins THIS capture here, from the root, as a child of
-                        # the capturing stream -- joining later through an event of the other branch (the discriminator's gradient arrives from
-                        # there) made the two branches each other's parent and hip::Stream::EndCapture recursed until the stack ran out
-                        self._side2.wait_stream(torch.cuda.current_stream())
-                        self._nodes_on_side2 = True
-                        try:
-                            g_loss = self._part_b("g", g_part_a, sg[1])
-                        finally:
-                            self._nodes_on_side2 = False
-                if not fused:
-                    reduced[1] = self._captured_reduce
-            except RuntimeError as e:
-                if not with_collective:
-                    raise
-                error = e
-            if with_collective and not self._agree(error is None):
-                # the collective would not go into a graph on SOME rank: every rank (agreed) drops the in-graph form; the iteration then runs as
-                # two plain runs with the all-reduce eagerly behind each replay (_run)
-                self._give_up_graph_collectives("d", error)
-                self._abandon_capture("g")
-                return None
-        finally:
-            owner.fade_weight = None
-            self._after_loss = None   # (a capture that raised before the discriminator run's loss must not leave the hook armed for an unrelated run)
-            self._before_fake = None
-            self._nodes_on_side2 = False
-            self._pipe_capture = False
-        return {"fused": fused, "x": gx, "y": gy, "sd": sd, "sg": sg, "d_loss": d_loss, "g_loss": g_loss, "keep": self.keep_gradients, "reduced": reduced,
-                "consts": F.constants_snapshot()}
-
-    def _train_step_merged(self, d_latents, d_labels, real_images, g_latents, g_labels):
-        hp = self.hyper_params
-        head, fade = self._regime()
-        fused = self._fused_ok()
-        key = (head, fade is None, self.keep_gradients, fused)
-        if not (fused and self._merged is not None and self._merged["key"] == key):
-            self._join_updates()   # (the one-graph iteration applies a pending generator step itself, at the front of the replay)
-        if fade is not None:
-            if self._lerp is None:
-                self._lerp = F.DeviceLerp(self.g_params.flat.device)
-            self._lerp.set(fade)   # (stream-ordered before the replays below)
-        d_in, g_in = (d_latents, d_labels, real_images), (g_latents, g_labels)
-        M = self._merged
-        if (M is None or M["key"] != key
-                or any(a.shape != b.shape or a.dtype != b.dtype for a, b in zip(M["sd"] + M["sg"], d_in + g_in))):
-            self._join_updates()   # (a pending generator step belongs to the graph being dropped)
-            if M is not None and M["key"][:2] != key[:2]:
-                F.drop_constants()   # (a new growing regime: see _run)
-            self._graphs.clear()
-            self._merged = None
-            M = self._capture_merged(d_in, g_in, fused=fused)
-            if M is None:   # (data parallel: the collectives were refused by the capture on some rank)
-                d_loss = self.discriminator_step(d_latents, d_labels, real_images)
-                g_loss = self.generator_step(g_latents, g_labels)
-                return d_loss, g_loss
-            M["key"] = key
-            self._merged = M
-        _copy_inputs(M["sd"] + M["sg"], list(d_in) + list(g_in))
-
-        def armed(params):   # a no-fill graph is about to accumulate into this buffer: it must be clean (see _run)
-            if not self.keep_gradients:
-                if not params.grad_clean:
-                    params.grad.zero_()
-                params.grad_clean = False
-        if M["fused"]:
-            zero = not self.keep_gradients
-            self.d_params.t += 1
-            self.g_params.t += 1
-            lr_d = self._lr_t(hp.discriminator_learning_rate, hp.discriminator_beta1, hp.discriminator_beta2, self.d_params.t)
-            self._opt_scalars.set([lr_d, -1.0 if self._g_pending is None else self._g_pending])   # (stream-ordered before the replay)
-            armed(self.d_params)
-            if self._g_pending is None:
-                armed(self.g_params)      # (no step at the front of this replay: the buffer must already be clean)
-            self._g_pending = None
-            M["x"].replay()
-            self.d_params.grad_clean = zero
-            self.g_params.grad_clean = False   # (holds the gradient of the step that is now pending)
-            self._g_pending = self._lr_t(hp.generator_learning_rate, hp.generator_beta1, hp.generator_beta2, self.g_params.t)
-            self.global_step += 1  # models.py:84
-            self.discriminator_loss, self.generator_loss = M["d_loss"], M["g_loss"]
-            return M["d_loss"], M["g_loss"]
-        armed(self.d_params)
-        M["x"].replay()
-        self._apply(self.d_params, hp.discriminator_learning_rate, hp.discriminator_beta1, hp.discriminator_beta2, reduced=M["reduced"][0])
-        armed(self.g_params)
-        M["y"].replay()
-        self._apply(self.g_params, hp.generator_learning_rate, hp.generator_beta1, hp.generator_beta2, reduced=M["reduced"][1])
-        self.global_step += 1  # models.py:84
-        self.discriminator_loss, self.generator_loss = M["d_loss"], M["g_loss"]
-        return M["d_loss"], M["g_loss"]
 
     def _next_inputs(self):
         """One iteration's inputs (models.py:191-192: a fresh batch for each of the two runs).  StopIteration = the input ran dry."""
@@ -1537,21 +632,7 @@ class GANSynth(object):
             return self._train_step_pipelined(d_latents, labels, real_images, g_latents, g_labels)
         if self._merged_ok():
             return self._train_step_merged(d_latents, labels, real_images, g_latents, g_labels)
-        d_loss = self.discriminator_step(d_latents, labels, real_images)
-        g_loss = self.generator_step(g_latents, g_labels)
-        return d_loss, g_loss
-
-    def _all_ranks_have_input(self, have):
-        """Data parallel: the input shards are rank-local (files[rank::world], per-record filters), so they run dry at different
-        steps; a rank that stopped alone would leave the others blocked in the next all-reduce.  Every rank votes before each
-        iteration and all stop together at the first "no" (the reference's single process stops at its OutOfRangeError,
-        models.py:193).  Inputs that cannot run dry (`real_input_fn.finite == False`) skip the vote and its host sync."""
-        if not self.distributed or not getattr(self.real_input_fn, "finite", True):
-            return have
-        dev = self.g_params.flat.device if self.g_params is not None else (torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu"))
-        flag = torch.tensor([1 if have else 0], dtype=torch.int32, device=dev)
-        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN)
-        return bool(flag.item())
+        return self._plain_iteration(d_latents, labels, real_images, g_latents, g_labels)
 
     def train(self, model_dir=None, config=None, total_steps=None, save_checkpoint_steps=1000, save_summary_steps=None, log_tensor_steps=100,
               log=print, save=None):

@@ -48,7 +48,7 @@ def timed(fn, n=20):
     return (time.perf_counter() - t0) / n * 1e3
 
 
-gd, gg = model._graphs["d"][0], model._graphs["g"][0]
+gd, gg = model._graphs["d"]["graph"], model._graphs["g"]["graph"]
 hp = model.hyper_params
 print(f"train_step              {timed(model.train_step):7.3f} ms")
 print(f"D graph + G graph       {timed(lambda: (gd.replay(), gg.replay())):7.3f} ms")
