@@ -10,7 +10,8 @@ namespace gs {
 
 // from conv_igemm.hip
 bool igemm_supported(int ic, int oc, int dtype);
-bool igemm_normbwd_fused(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int form = 1);
+bool igemm_norm_fused(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int want);
+int igemm_config(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int want, int* out);
 extern "C" int gs_pixel_norm_bwd_bwd_fused(const void* gg, const void* g, const void* x, void* out, void* out_g, int64_t p, int c, float eps, int pre_act,
                                            int dtype, void* stream);
 bool wgrad_mfma_supported(int ic, int oc, int dtype);
@@ -1325,8 +1326,8 @@ extern "C" int gs_conv2d_transpose_s2_fwd_pnbwdbwd(const void* x, const float* w
 // 1 when that call runs as one launch for the shape (n, h, w: the conv's input side)
 extern "C" int gs_conv2d_fwd_pnbwdbwd_is_fused(int n, int h, int w, int ci, int co, int ksize, int stride, int transposed, int dtype) {
     if (ksize != 3 || !igemm_supported(ci, co, dtype)) return 0;
-    if (transposed) return stride == 2 && igemm_normbwd_fused(MODE_T2, n, h, w, ci, co, dtype, 2) ? 1 : 0;
-    return stride == 1 && igemm_normbwd_fused(MODE_S1, n, h, w, ci, co, dtype, 2) ? 1 : 0;
+    if (transposed) return stride == 2 && igemm_norm_fused(MODE_T2, n, h, w, ci, co, dtype, IGEMM_NORM_BWD2) ? 1 : 0;
+    return stride == 1 && igemm_norm_fused(MODE_S1, n, h, w, ci, co, dtype, IGEMM_NORM_BWD2) ? 1 : 0;
 }
 
 // Data gradient of a conv whose INPUT was y = pixel_norm(z), z = act(...) the previous block's activation (networks.py:41-93: every
@@ -1358,8 +1359,14 @@ extern "C" int gs_conv2d_bwd_data_pnbwd(const void* gy, const float* w_hwio, con
 extern "C" int gs_conv2d_bwd_data_pnbwd_is_fused(int n, int h, int w, int ci, int co, int ksize, int stride, int transposed, int dtype) {
     if (ksize == 1) return !transposed && stride == 1 && thin_expand_pnbwd_ok(1, co, ci, dtype) ? 1 : 0;
     if (ksize != 3) return 0;
-    if (transposed) return stride == 2 && igemm_supported(co, ci, dtype) && igemm_normbwd_fused(MODE_S2, n, h, w, co, ci, dtype) ? 1 : 0;
-    return stride == 1 && igemm_supported(co, ci, dtype) && igemm_normbwd_fused(MODE_S1, n, h, w, co, ci, dtype) ? 1 : 0;
+    if (transposed) return stride == 2 && igemm_norm_fused(MODE_S2, n, h, w, co, ci, dtype, IGEMM_NORM_BWD) ? 1 : 0;
+    return stride == 1 && igemm_norm_fused(MODE_S1, n, h, w, co, ci, dtype, IGEMM_NORM_BWD) ? 1 : 0;
+}
+// Which implicit-GEMM configuration a 3x3 layer runs with (kernel-role shape: hb x wb the base grid, ic -> oc the kernel's channels; mode 0 stride
+// 1, 1 stride 2, 2 transposed; want: the epilogue asked for, 0 none, 1 pixel norm, 2 / 3 its first- / second-order backward).  Host arithmetic
+// only -- no launch, no device needed.  out_cfg[10]: A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC, then 1 if that configuration is compiled.
+extern "C" int gs_conv_igemm_config(int mode, int n, int hb, int wb, int ic, int oc, int dtype, int want, int* out_cfg) {
+    return igemm_config(mode, n, hb, wb, ic, oc, dtype, want, out_cfg);
 }
 extern "C" int gs_conv2d_transpose_s2_bwd_data_pnbwd(const void* gy, const float* w_hwio, const void* z, const void* addend, int act, float eps, void* gx, int n,
                                                      int h, int w, int ci, int co, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream) {

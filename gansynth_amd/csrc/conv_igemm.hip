@@ -2155,178 +2155,174 @@ static int launch_igemm(ConvP p, hipStream_t st) {
     return 0;
 }
 
-// choose the tile configuration from (OC, Wb, problem size)
-// Which configuration families run wave-specialised (bit 0 few-block, 1 S1, 2 S2 / T2; GS_SPEC overrides for measurements).  Measured
-// per iteration of configs[1] (scripts/run_spec.sh): few-block layers 1086 -> 1068 us; the larger S1 / S2 / T2 tiles LOSE 60-190 us
-// (their stages are bound by the fragment reads and the barrier, not by the DMA issue) -- so only bit 0 is on.
-static int spec_mask() {
-    static const int m = getenv("GS_SPEC") ? atoi(getenv("GS_SPEC")) : 1;
-    return m;
+// ---- which configuration: one value, one chooser, one table of instantiations
+// The template arguments of conv_igemm_kernel a launch runs with, bar T and MODE (the caller's) and BITS (launch_igemm reads it off ConvP).
+struct IgemmCfg {
+    int A, B, TW, TG;                         // 32 A channels x 128 B pixels per tile, TW pixels wide; TG taps per stage
+    bool RESIDENT = false;                    // the layer's whole weight slab stays in LDS
+    int D = 2, NORM = IGEMM_PLAIN, RB = 64;   // stages in flight; the epilogue (IGEMM_*); bytes per operand row
+    bool SPEC = false;                        // wave-specialised 8-wave block
+    bool operator==(const IgemmCfg& o) const {
+        return A == o.A && B == o.B && TW == o.TW && TG == o.TG && RESIDENT == o.RESIDENT && D == o.D && NORM == o.NORM && RB == o.RB && SPEC == o.SPEC;
+    }
+};
+// Measurement knobs of the chooser, read from the environment once.  GS_SPEC: 1 (default) runs the few-block bf16 layers wave-specialised,
+// 0 does not -- per iteration of configs[1] (scripts/run_spec.sh) those layers go 1086 -> 1068 us.  (Its former bits 1 and 2, the same for the
+// larger S1 / S2 / T2 tiles, lost 60-190 us -- stages bound by the fragment reads and the barrier, not by the DMA issue -- and are retired:
+// DESIGN.md, "Measured and rejected in round 3".)
+struct IgemmKnobs { bool no_small_tiles, no_rb128, spec; };
+static IgemmKnobs igemm_knobs() {
+    static const IgemmKnobs k = {getenv("GS_NO_SMALL_TILES") != nullptr, getenv("GS_NO_RB128") != nullptr,
+                                 getenv("GS_SPEC") ? (atoi(getenv("GS_SPEC")) & 1) != 0 : true};
+    return k;
+}
+
+// The configuration a layer runs with: (mode, dtype, kernel-role shape, wanted epilogue) -> IgemmCfg.  Pure host arithmetic -- `cus` and the
+// knobs arrive as arguments.  Where the wanted fused norm form has no epilogue for the shape the answer is the plain configuration (NORM ==
+// IGEMM_PLAIN) and the caller runs the norm as its own pass: the forms exist only where a tile owns every channel of a pixel (OC = 32 A) and
+// that the generator's 32- / 64-channel blocks actually use.
+static IgemmCfg choose_igemm(int mode, int dtype, int N, int Hb, int Wb, int IC, int OC, int want, long cus, IgemmKnobs knobs) {
+    constexpr int FWD = 1 << IGEMM_NORM_FWD, BWD = 1 << IGEMM_NORM_BWD, BWD2 = 1 << IGEMM_NORM_BWD2;
+    auto epi = [&](int forms) { return (forms >> want) & 1 ? want : IGEMM_PLAIN; };   // `want` if the configuration has that epilogue
+    const int nch = IC / (dtype == GS_F32 ? 16 : 32);   // 64-byte channel chunks
+    const bool a2 = OC % 64 == 0;
+    const int tw = Wb >= 32 ? 32 : 16;
+    // blocks the layer gives with 128*B-pixel x 64-channel tiles (TW = 32)
+    auto items64 = [&](int B_) { return (long)N * cdiv(Hb, 4 * B_) * cdiv(Wb, 32) * (OC / 64); };
+    // Measured on the layers of the fully grown networks (scripts/probe/run_variants.sh): two resident blocks per CU (<= 80 KiB
+    // of LDS each, i.e. a one-stage-deep ring) beat one block with a deeper ring or a larger tile wherever the layer has at
+    // least two blocks per CU to give -- the epilogue and DMA waits of one block run under the MFMAs of the other.
+    const bool small = !knobs.no_small_tiles && items64(1) <= cus;   // no more blocks than CUs: a serial chain of stages per block
+    // 128-byte operand rows (whole cache lines per DMA row, half the stages), bf16 only
+    const bool rb128 = dtype == GS_BF16 && !knobs.no_rb128 && IC % 64 == 0;
+    if (mode == MODE_S2) {
+        if (small) return {1, 1, tw, 9, false, 1};
+        if (!a2) return {1, 1, 32, 3};
+        // stride 2: the patch is 4.6x the output tile, so a 128-channel tile (the patch staged once for all of them) is worth
+        // more than a second pixel tile as long as every CU still gets a block
+        if (OC == 64 && nch == 1 && Wb >= 32 && items64(1) >= cus) return {2, 1, 32, 9, true, 1, epi(BWD)};   // 36 KiB of weights: resident
+        if (OC % 128 == 0 && Wb >= 32 && (long)N * cdiv(Hb, 4) * cdiv(Wb, 32) * (OC / 128) >= cus) return {4, 1, 32, 3};
+        return {2, 1, tw, 3};
+    }
+    const bool s1 = mode == MODE_S1;   // (else MODE_T2: four output pixels per base pixel, so half the base pixels per tile)
+    if (OC == 32 && nch <= 2 && Wb >= 64) return {1, s1 ? 2 : 1, 64, 9, true, 1, epi(s1 ? FWD | BWD | BWD2 : FWD | BWD2)};
+    // few blocks, each a serial chain of stages: 32-channel tiles double the number of busy CUs, 9-tap stages cut the
+    // barriers and DMA round trips of the chain to a third
+    if (small) {
+        // 128-byte rows: the few-block layers are bound by the L2 -> LDS rate of a CU, not by its MFMAs
+        if (rb128) return {1, 1, tw, 9, false, 1, IGEMM_PLAIN, 128, knobs.spec};
+        return {1, 1, tw, 9, false, GS_SMALL_D};
+    }
+    if (!a2) return {1, 1, s1 ? 32 : tw, 3};
+    if (!s1) return {2, 1, tw, 3, false, 2, Wb >= 32 && OC == 64 ? epi(FWD | BWD2) : IGEMM_PLAIN};
+    if (Wb >= 32 && items64(2) >= 2 * cus) return {2, 2, 32, 3, false, 1, OC == 64 ? epi(FWD | BWD | BWD2) : IGEMM_PLAIN};
+    if (OC == 64 && nch <= 2 && Wb >= 32 && items64(2) >= cus / 2) return {2, 2, 32, 9, true};   // 9 taps x 64 x (<= 64 channels) <= 72 KiB stay in LDS
+    // every block re-streams its 64 x IC x 9 weight slab from L2: the more pixels a block owns the smaller that
+    // stream is per MFMA -- take the largest pixel tile that still gives every CU a block
+    if (Wb >= 32 && items64(2) >= cus) {
+        // one block per CU: 128-byte rows halve the stages of the chain (22.0 -> 20.1 us on 256 -> 256 @ 16x128 x8, scripts/run_abl.sh)
+        if (rb128) return {2, 2, 32, 3, false, 1, IGEMM_PLAIN, 128};
+        return {2, 2, 32, 3};
+    }
+    return {2, 1, tw, 3};
+}
+
+// Every (MODE, configuration) that is compiled, once: X(MODE, BF16_ONLY, A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC).  A configuration the
+// chooser can return has a row here (tests/test_igemm_config_cpu.py sweeps it); BF16_ONLY rows are the ones only bf16 reaches.
+#define GS_APPLY(X, ...) X(__VA_ARGS__)
+#ifdef GS_FORCE_CFG   // probes only: -DGS_FORCE_MODE=0 -DGS_FORCE_CFG=2,2,32,3,false,1,0,64,false -- all nine fields of one IgemmCfg, which every
+                      // bf16 launch of that mode then runs with (scripts/probe/build_variants.sh)
+#define GS_IGEMM_FORCED(X) GS_APPLY(X, GS_FORCE_MODE, true, GS_FORCE_CFG)
+#else
+#define GS_IGEMM_FORCED(X)
+#endif
+#define GS_IGEMM_CONFIGS(X)                                                     \
+    X(MODE_S1, false, 1, 2, 64, 9, true, 1, IGEMM_PLAIN, 64, false)             \
+    X(MODE_S1, false, 1, 2, 64, 9, true, 1, IGEMM_NORM_FWD, 64, false)          \
+    X(MODE_S1, false, 1, 2, 64, 9, true, 1, IGEMM_NORM_BWD, 64, false)          \
+    X(MODE_S1, false, 1, 2, 64, 9, true, 1, IGEMM_NORM_BWD2, 64, false)         \
+    X(MODE_S1, true, 1, 1, 32, 9, false, 1, IGEMM_PLAIN, 128, true)             \
+    X(MODE_S1, true, 1, 1, 16, 9, false, 1, IGEMM_PLAIN, 128, true)             \
+    X(MODE_S1, true, 1, 1, 32, 9, false, 1, IGEMM_PLAIN, 128, false)            \
+    X(MODE_S1, true, 1, 1, 16, 9, false, 1, IGEMM_PLAIN, 128, false)            \
+    X(MODE_S1, false, 1, 1, 32, 9, false, GS_SMALL_D, IGEMM_PLAIN, 64, false)   \
+    X(MODE_S1, false, 1, 1, 16, 9, false, GS_SMALL_D, IGEMM_PLAIN, 64, false)   \
+    X(MODE_S1, false, 1, 1, 32, 3, false, 2, IGEMM_PLAIN, 64, false)            \
+    X(MODE_S1, false, 2, 2, 32, 3, false, 1, IGEMM_PLAIN, 64, false)            \
+    X(MODE_S1, false, 2, 2, 32, 3, false, 1, IGEMM_NORM_FWD, 64, false)         \
+    X(MODE_S1, false, 2, 2, 32, 3, false, 1, IGEMM_NORM_BWD, 64, false)         \
+    X(MODE_S1, false, 2, 2, 32, 3, false, 1, IGEMM_NORM_BWD2, 64, false)        \
+    X(MODE_S1, false, 2, 2, 32, 9, true, 2, IGEMM_PLAIN, 64, false)             \
+    X(MODE_S1, true, 2, 2, 32, 3, false, 1, IGEMM_PLAIN, 128, false)            \
+    X(MODE_S1, false, 2, 2, 32, 3, false, 2, IGEMM_PLAIN, 64, false)            \
+    X(MODE_S1, false, 2, 1, 32, 3, false, 2, IGEMM_PLAIN, 64, false)            \
+    X(MODE_S1, false, 2, 1, 16, 3, false, 2, IGEMM_PLAIN, 64, false)            \
+    X(MODE_S2, false, 1, 1, 32, 9, false, 1, IGEMM_PLAIN, 64, false)            \
+    X(MODE_S2, false, 1, 1, 16, 9, false, 1, IGEMM_PLAIN, 64, false)            \
+    X(MODE_S2, false, 1, 1, 32, 3, false, 2, IGEMM_PLAIN, 64, false)            \
+    X(MODE_S2, false, 2, 1, 32, 9, true, 1, IGEMM_PLAIN, 64, false)             \
+    X(MODE_S2, false, 2, 1, 32, 9, true, 1, IGEMM_NORM_BWD, 64, false)          \
+    X(MODE_S2, false, 4, 1, 32, 3, false, 2, IGEMM_PLAIN, 64, false)            \
+    X(MODE_S2, false, 2, 1, 32, 3, false, 2, IGEMM_PLAIN, 64, false)            \
+    X(MODE_S2, false, 2, 1, 16, 3, false, 2, IGEMM_PLAIN, 64, false)            \
+    X(MODE_T2, false, 1, 1, 64, 9, true, 1, IGEMM_PLAIN, 64, false)             \
+    X(MODE_T2, false, 1, 1, 64, 9, true, 1, IGEMM_NORM_FWD, 64, false)          \
+    X(MODE_T2, false, 1, 1, 64, 9, true, 1, IGEMM_NORM_BWD2, 64, false)         \
+    X(MODE_T2, true, 1, 1, 32, 9, false, 1, IGEMM_PLAIN, 128, true)             \
+    X(MODE_T2, true, 1, 1, 16, 9, false, 1, IGEMM_PLAIN, 128, true)             \
+    X(MODE_T2, true, 1, 1, 32, 9, false, 1, IGEMM_PLAIN, 128, false)            \
+    X(MODE_T2, true, 1, 1, 16, 9, false, 1, IGEMM_PLAIN, 128, false)            \
+    X(MODE_T2, false, 1, 1, 32, 9, false, GS_SMALL_D, IGEMM_PLAIN, 64, false)   \
+    X(MODE_T2, false, 1, 1, 16, 9, false, GS_SMALL_D, IGEMM_PLAIN, 64, false)   \
+    X(MODE_T2, false, 1, 1, 32, 3, false, 2, IGEMM_PLAIN, 64, false)            \
+    X(MODE_T2, false, 1, 1, 16, 3, false, 2, IGEMM_PLAIN, 64, false)            \
+    X(MODE_T2, false, 2, 1, 32, 3, false, 2, IGEMM_PLAIN, 64, false)            \
+    X(MODE_T2, false, 2, 1, 32, 3, false, 2, IGEMM_NORM_FWD, 64, false)         \
+    X(MODE_T2, false, 2, 1, 32, 3, false, 2, IGEMM_NORM_BWD2, 64, false)        \
+    X(MODE_T2, false, 2, 1, 16, 3, false, 2, IGEMM_PLAIN, 64, false)            \
+    GS_IGEMM_FORCED(X)
+
+static bool igemm_instantiated(int mode, int dtype, const IgemmCfg& c) {
+#define GS_ROW(M, BF16_ONLY, ...) if (mode == M && (dtype == GS_BF16 || !BF16_ONLY) && c == IgemmCfg{__VA_ARGS__}) return true;
+    GS_IGEMM_CONFIGS(GS_ROW)
+#undef GS_ROW
+    return false;
 }
 
 template <typename T, int MODE>
 static int dispatch_igemm(ConvP p, hipStream_t st) {
-    constexpr int BK = 64 / (int)sizeof(T);
-    const int OC = p.OC, Wb = p.Wb;
-    const int nch = p.IC / BK;
-    const bool resident_ok = OC == 32 && nch <= 2;
-    const bool resident64_ok = OC == 64 && nch <= 2;   // 9 taps x 64 x (<= 64 channels) <= 72 KiB stay in LDS
-    const int a2 = OC % 64 == 0;
-    // blocks the layer gives with 128*B-pixel x 64-channel tiles (TW = 32)
-    auto items64 = [&](int B_) { return (long)p.N * cdiv(p.Hb, 4 * B_) * cdiv(Wb, 32) * (OC / 64); };
-#ifdef GS_FORCE_CFG   // probes only: -DGS_FORCE_MODE=0 -DGS_FORCE_CFG=2,2,32,3,false,1
-    if constexpr (MODE == GS_FORCE_MODE && sizeof(T) == 2) return launch_igemm<T, MODE, GS_FORCE_CFG>(p, st);
+    constexpr int dtype = sizeof(T) == 4 ? GS_F32 : GS_BF16;
+    const int want = p.normbwd ? 1 + p.normbwd : (p.y2 ? IGEMM_NORM_FWD : IGEMM_PLAIN);   // the epilogue asked for, as ConvP carries it
+    IgemmCfg c = choose_igemm(MODE, dtype, p.N, p.Hb, p.Wb, p.IC, p.OC, want, num_cus(), igemm_knobs());
+#ifdef GS_FORCE_CFG
+    if (MODE == GS_FORCE_MODE && dtype == GS_BF16) c = IgemmCfg{GS_FORCE_CFG};
 #endif
-    // Measured on the layers of the fully grown networks (scripts/probe/run_variants.sh): two resident blocks per CU (<= 80 KiB
-    // of LDS each, i.e. a one-stage-deep ring) beat one block with a deeper ring or a larger tile wherever the layer has at
-    // least two blocks per CU to give -- the epilogue and DMA waits of one block run under the MFMAs of the other.
-    const long cus = num_cus();
-    static const bool no_small = getenv("GS_NO_SMALL_TILES") != nullptr;   // measurement knob
-    const bool small = !no_small && items64(1) <= cus;   // no more blocks than CUs: a serial chain of stages per block
-    // Fused pixel norm (p.y2): only the configurations whose tile owns every channel of a pixel (OC = 32 A) and that the generator's
-    // 32- / 64-channel blocks actually use; everything else runs the plain kernel and the caller's separate norm pass (p.y2 = NULL
-    // on return tells it so -- see run_igemm_t).
-    const bool norm = p.y2 != nullptr && p.normbwd == 0;
-    const bool nbwd = p.normbwd == 1;   // (the three data-gradient shapes of the generator's 32- / 64-channel blocks below; anything else falls back)
-    const bool nbb = p.normbwd == 2;    // (second-order form: the forward-role shapes that have the NORM == 1 epilogue)
-    if constexpr (MODE == MODE_T2) {
-        if (resident_ok && Wb >= 64) {
-            if (norm) return launch_igemm<T, MODE, 1, 1, 64, 9, true, 1, true>(p, st);
-            if (nbb) return launch_igemm<T, MODE, 1, 1, 64, 9, true, 1, 3>(p, st);
-            return launch_igemm<T, MODE, 1, 1, 64, 9, true, 1>(p, st);
-        }
-        // few blocks, each a serial chain of stages: 32-channel tiles double the number of busy CUs, 9-tap stages cut the
-        // barriers and DMA round trips of the chain to a third
-        if (small) {
-            // 128-byte operand rows (whole cache lines per DMA row, half the stages): the few-block layers are bound by the L2 -> LDS
-            // rate of a CU, not by its MFMAs
-            if constexpr (sizeof(T) == 2) {
-                static const bool rb128 = getenv("GS_NO_RB128") == nullptr;
-                if (rb128 && p.IC % 64 == 0) {
-                    if (spec_mask() & 1) {
-                        if (Wb >= 32) return launch_igemm<T, MODE, 1, 1, 32, 9, false, 1, false, 128, true>(p, st);
-                        return launch_igemm<T, MODE, 1, 1, 16, 9, false, 1, false, 128, true>(p, st);
-                    }
-                    if (Wb >= 32) return launch_igemm<T, MODE, 1, 1, 32, 9, false, 1, false, 128>(p, st);
-                    return launch_igemm<T, MODE, 1, 1, 16, 9, false, 1, false, 128>(p, st);
-                }
-            }
-            if (Wb >= 32) return launch_igemm<T, MODE, 1, 1, 32, 9, false, GS_SMALL_D>(p, st);
-            return launch_igemm<T, MODE, 1, 1, 16, 9, false, GS_SMALL_D>(p, st);
-        }
-        if (!a2) { if (Wb >= 32) return launch_igemm<T, MODE, 1, 1, 32, 3>(p, st); return launch_igemm<T, MODE, 1, 1, 16, 3>(p, st); }
-        if (Wb >= 32) {
-            if (norm && OC == 64) return launch_igemm<T, MODE, 2, 1, 32, 3, false, 2, true>(p, st);
-            if (nbb && OC == 64) return launch_igemm<T, MODE, 2, 1, 32, 3, false, 2, 3>(p, st);
-            if (spec_mask() & 4) return launch_igemm<T, MODE, 2, 1, 32, 3, false, 2, false, 64, true>(p, st);
-            return launch_igemm<T, MODE, 2, 1, 32, 3>(p, st);
-        }
-        return launch_igemm<T, MODE, 2, 1, 16, 3>(p, st);
-    } else if constexpr (MODE == MODE_S2) {
-        if (small) { if (Wb >= 32) return launch_igemm<T, MODE, 1, 1, 32, 9, false, 1>(p, st); return launch_igemm<T, MODE, 1, 1, 16, 9, false, 1>(p, st); }
-        if (!a2) return launch_igemm<T, MODE, 1, 1, 32, 3>(p, st);
-        // stride 2: the patch is 4.6x the output tile, so a 128-channel tile (the patch staged once for all of them) is worth
-        // more than a second pixel tile as long as every CU still gets a block
-        if (OC == 64 && nch == 1 && Wb >= 32 && items64(1) >= cus) {   // 36 KiB of weights: resident
-            if (nbwd) return launch_igemm<T, MODE, 2, 1, 32, 9, true, 1, 2>(p, st);
-            return launch_igemm<T, MODE, 2, 1, 32, 9, true, 1>(p, st);
-        }
-        if (OC % 128 == 0 && Wb >= 32 && (long)p.N * cdiv(p.Hb, 4) * cdiv(Wb, 32) * (OC / 128) >= cus) {
-            if (spec_mask() & 4) return launch_igemm<T, MODE, 4, 1, 32, 3, false, 2, false, 64, true>(p, st);
-            return launch_igemm<T, MODE, 4, 1, 32, 3>(p, st);
-        }
-        if (Wb >= 32) {
-            if (spec_mask() & 4) return launch_igemm<T, MODE, 2, 1, 32, 3, false, 2, false, 64, true>(p, st);
-            return launch_igemm<T, MODE, 2, 1, 32, 3>(p, st);
-        }
-        return launch_igemm<T, MODE, 2, 1, 16, 3>(p, st);
-    } else {
-        if (resident_ok && Wb >= 64) {
-            if (norm) return launch_igemm<T, MODE, 1, 2, 64, 9, true, 1, true>(p, st);
-            if (nbwd) return launch_igemm<T, MODE, 1, 2, 64, 9, true, 1, 2>(p, st);
-            if (nbb) return launch_igemm<T, MODE, 1, 2, 64, 9, true, 1, 3>(p, st);
-            return launch_igemm<T, MODE, 1, 2, 64, 9, true, 1>(p, st);
-        }
-        if (small) {
-            // 128-byte operand rows (whole cache lines per DMA row, half the stages): the few-block layers are bound by the L2 -> LDS
-            // rate of a CU, not by its MFMAs
-            if constexpr (sizeof(T) == 2) {
-                static const bool rb128 = getenv("GS_NO_RB128") == nullptr;
-                if (rb128 && p.IC % 64 == 0) {
-                    if (spec_mask() & 1) {
-                        if (Wb >= 32) return launch_igemm<T, MODE, 1, 1, 32, 9, false, 1, false, 128, true>(p, st);
-                        return launch_igemm<T, MODE, 1, 1, 16, 9, false, 1, false, 128, true>(p, st);
-                    }
-                    if (Wb >= 32) return launch_igemm<T, MODE, 1, 1, 32, 9, false, 1, false, 128>(p, st);
-                    return launch_igemm<T, MODE, 1, 1, 16, 9, false, 1, false, 128>(p, st);
-                }
-            }
-            if (Wb >= 32) return launch_igemm<T, MODE, 1, 1, 32, 9, false, GS_SMALL_D>(p, st);
-            return launch_igemm<T, MODE, 1, 1, 16, 9, false, GS_SMALL_D>(p, st);
-        }
-        if (!a2) return launch_igemm<T, MODE, 1, 1, 32, 3>(p, st);
-        if (Wb >= 32 && items64(2) >= 2 * cus) {
-            if (norm && OC == 64) return launch_igemm<T, MODE, 2, 2, 32, 3, false, 1, true>(p, st);
-            if (nbwd && OC == 64) return launch_igemm<T, MODE, 2, 2, 32, 3, false, 1, 2>(p, st);
-            if (nbb && OC == 64) return launch_igemm<T, MODE, 2, 2, 32, 3, false, 1, 3>(p, st);
-            if (spec_mask() & 2) return launch_igemm<T, MODE, 2, 2, 32, 3, false, 2, false, 64, true>(p, st);
-            return launch_igemm<T, MODE, 2, 2, 32, 3, false, 1>(p, st);
-        }
-        if (resident64_ok && Wb >= 32 && items64(2) >= cus / 2) return launch_igemm<T, MODE, 2, 2, 32, 9, true>(p, st);
-        // every block re-streams its 64 x IC x 9 weight slab from L2: the more pixels a block owns the smaller that
-        // stream is per MFMA -- take the largest pixel tile that still gives every CU a block
-        if (Wb >= 32 && items64(2) >= cus) {
-            if (spec_mask() & 2) return launch_igemm<T, MODE, 2, 2, 32, 3, false, 2, false, 64, true>(p, st);
-            // one block per CU: 128-byte rows halve the stages of the chain (22.0 -> 20.1 us on 256 -> 256 @ 16x128 x8, scripts/run_abl.sh)
-            if constexpr (sizeof(T) == 2) {
-                static const bool rb128 = getenv("GS_NO_RB128") == nullptr;
-                if (rb128 && p.IC % 64 == 0) return launch_igemm<T, MODE, 2, 2, 32, 3, false, 1, false, 128>(p, st);
-            }
-            return launch_igemm<T, MODE, 2, 2, 32, 3>(p, st);
-        }
-        if (Wb >= 32) {
-            if (spec_mask() & 2) return launch_igemm<T, MODE, 2, 1, 32, 3, false, 2, false, 64, true>(p, st);
-            return launch_igemm<T, MODE, 2, 1, 32, 3>(p, st);
-        }
-        return launch_igemm<T, MODE, 2, 1, 16, 3>(p, st);
-    }
-}
-
-// does dispatch_igemm have the NORM == 2 (pixel-norm backward) epilogue for this data-gradient shape?  (mirrors its three branches)
-// form 1: NORM == 2 (first order, data-gradient roles); form 2: NORM == 3 (second order, forward roles)
-bool igemm_normbwd_fused(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int form) {
-    const int bk = dtype == GS_F32 ? 16 : 32;
-    if (IC % bk != 0 || OC % 32 != 0) return false;
-    const int nch = IC / bk;
-    const long cus = num_cus();
-    auto items64 = [&](int B_) { return (long)N * cdiv(Hb, 4 * B_) * cdiv(Wb, 32) * (OC / 64); };
-    if (form == 2) {   // mirrors the NORM == 1 branches of dispatch_igemm
-        const bool small = items64(1) <= cus;
-        if (mode == MODE_T2) {
-            if (OC == 32 && nch <= 2 && Wb >= 64) return true;
-            return !small && OC == 64 && Wb >= 32;
-        }
-        if (mode == MODE_S1) {
-            if (OC == 32 && nch <= 2 && Wb >= 64) return true;
-            return !small && OC == 64 && Wb >= 32 && items64(2) >= 2 * cus;
-        }
-        return false;
-    }
-    if (mode == MODE_S1) {
-        if (OC == 32 && nch <= 2 && Wb >= 64) return true;
-        const bool small = items64(1) <= cus;
-        return !small && OC == 64 && Wb >= 32 && items64(2) >= 2 * cus;
-    }
-    if (mode == MODE_S2) {
-        const bool small = items64(1) <= cus;
-        return !small && OC == 64 && nch == 1 && Wb >= 32 && items64(1) >= cus;
-    }
-    return false;
+#define GS_ROW(M, BF16_ONLY, A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC)                                \
+    if constexpr (MODE == M && (dtype == GS_BF16 || !BF16_ONLY))                                       \
+        if (c == IgemmCfg{A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC}) return launch_igemm<T, MODE, A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC>(p, st);
+    GS_IGEMM_CONFIGS(GS_ROW)
+#undef GS_ROW
+    return fail(GS_ERR_UNSUPPORTED, "conv igemm: no instantiation of mode %d dtype %d A=%d B=%d TW=%d TG=%d RESIDENT=%d D=%d NORM=%d RB=%d SPEC=%d", MODE, dtype,
+                c.A, c.B, c.TW, c.TG, (int)c.RESIDENT, c.D, c.NORM, c.RB, (int)c.SPEC);
 }
 
 bool igemm_supported(int ic, int oc, int dtype) {
     const int bk = dtype == GS_F32 ? 16 : 32;
     return ic % bk == 0 && oc % 32 == 0;
+}
+// does the layer get the epilogue `want` (IGEMM_NORM_*), i.e. run as one launch?
+bool igemm_norm_fused(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int want) {
+    return igemm_supported(IC, OC, dtype) && choose_igemm(mode, dtype, N, Hb, Wb, IC, OC, want, num_cus(), igemm_knobs()).NORM == want;
+}
+// gs_conv_igemm_config: the chosen fields in IgemmCfg's order, then whether that (mode, dtype, configuration) is compiled
+int igemm_config(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int want, int* out) {
+    if (mode < MODE_S1 || mode > MODE_T2 || (dtype != GS_F32 && dtype != GS_BF16) || want < IGEMM_PLAIN || want > IGEMM_NORM_BWD2 || N < 1 || Hb < 1 || Wb < 1 || !out)
+        return fail(GS_ERR_ARG, "conv igemm config: bad mode %d / dtype %d / epilogue %d / shape %d x %d x %d", mode, dtype, want, N, Hb, Wb);
+    if (!igemm_supported(IC, OC, dtype)) return fail(GS_ERR_UNSUPPORTED, "conv igemm config: %d -> %d channels do not run on the implicit GEMM", IC, OC);
+    const IgemmCfg c = choose_igemm(mode, dtype, N, Hb, Wb, IC, OC, want, num_cus(), igemm_knobs());
+    const int v[10] = {c.A, c.B, c.TW, c.TG, c.RESIDENT, c.D, c.NORM, c.RB, c.SPEC, igemm_instantiated(mode, dtype, c)};
+    memcpy(out, v, sizeof(v));
+    return 0;
 }
 bool wgrad_mfma_supported(int ic, int oc, int dtype) { return (dtype == GS_F32 || dtype == GS_BF16) && ic % 32 == 0 && oc % 32 == 0; }
 

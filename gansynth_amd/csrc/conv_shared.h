@@ -5,6 +5,8 @@
 namespace gs {
 
 enum { MODE_S1 = 0, MODE_S2 = 1, MODE_T2 = 2 };
+// the epilogue of an implicit-GEMM launch (conv_igemm_kernel's NORM): none, pixel norm, its first-order backward, its second-order backward
+enum { IGEMM_PLAIN = 0, IGEMM_NORM_FWD = 1, IGEMM_NORM_BWD = 2, IGEMM_NORM_BWD2 = 3 };
 #define GS_WGRAD_MAX_SRC 4   // (x, gy) pairs one weight-gradient launch contracts (gs_conv2d_bwd_weight_bias_multi)
 
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }

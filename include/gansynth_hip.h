@@ -188,6 +188,12 @@ int gs_conv2d_bwd_data_pnbwd(const void* gy, const float* w_hwio, const void* z,
 /* 1 when that call is one launch for the shape (n, h, w: the conv's INPUT side, i.e. gx / z; transposed: the s2 transposed conv), 0 when it
  * runs as the plain data gradient followed by gs_pixel_norm_bwd_fused in place */
 int gs_conv2d_bwd_data_pnbwd_is_fused(int n, int h, int w, int ci, int co, int ksize, int stride, int transposed, int dtype);
+/* Which implicit-GEMM tile configuration a 3x3 layer runs with, asked without running it: host arithmetic only, works without a device (the CU
+ * count then defaults to the MI355X's 256).  Kernel-role arguments: mode 0 stride 1 / 1 stride 2 / 2 transposed, hb x wb the base grid (the smaller
+ * side of a strided map), ic -> oc the channels the kernel contracts / produces; want: the epilogue asked for, 0 none, 1 pixel norm, 2 / 3 its
+ * first- / second-order backward.  out_cfg[10] = A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC (conv_igemm.hip: IgemmCfg) and 1 if that
+ * configuration is compiled for the dtype; NORM == want says the epilogue is fused, 0 that the norm runs as its own pass. */
+int gs_conv_igemm_config(int mode, int n, int hb, int wb, int ic, int oc, int dtype, int want, int* out_cfg);
 int gs_conv2d_transpose_s2_bwd_data_pnbwd(const void* gy, const float* w_hwio, const void* z, const void* addend, int act, float eps, void* gx, int n,
                                           int h, int w, int ci, int co, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream);
 int gs_conv2d_transpose_s2_bwd_weight(const void* x, const void* gy, float* gw_hwio, int n, int h, int w, int ci, int co,

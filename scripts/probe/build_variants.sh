@@ -1,6 +1,7 @@
 #!/bin/bash
 # builds igemm_trace_<tag> probes with forced tile configurations / ablations (see conv_igemm.hip GS_FORCE_CFG, GS_ABL_*)
 # usage: build_variants.sh  "tag|mode|cfg|extra flags" ...
+#   cfg: the nine fields of one IgemmCfg, A,B,TW,TG,RESIDENT,D,NORM,RB,SPEC -- e.g. "m0_d2|0|2,2,32,3,false,2,0,64,false" (empty: the chooser's own pick)
 cd "$(dirname "$0")"
 pids=()
 for v in "$@"; do
