@@ -131,6 +131,20 @@ SIGNATURES = {
     "gs_group_norm_stats": (I, [P, P, P, P, I, I, I, I, F, I, P, Z, P]),
     "gs_group_norm_apply": (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
     "gs_group_norm_relu_mean": (I, [P, P, P, P, P, I, I, I, I, I, P]),
+    "gs_group_norm_bwd_workspace_bytes": (Z, [I, I, I, I]),
+    "gs_group_norm_relu_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, Z, P]),
+    "gs_group_norm_relu_mean_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, Z, P]),
+    "gs_weight_standardize_batch": (I, [P, I, I, F, P]),
+    "gs_weight_standardize_bwd_batch": (I, [P, I, I, P]),
+    "gs_max_pool2d_bwd": (I, [P, P, P, I, I, I, I, I, P]),
+    "gs_resnet_stem_bwd_weight_workspace_bytes": (Z, [I, I, I]),
+    "gs_resnet_stem_bwd_weight": (I, [P, P, P, P, I, I, I, I, I, I, P, Z, P]),
+    "gs_conv1x1_bwd_data": (I, [P, P, P, I, I, I, I, I, I, I, I, P]),
+    "gs_conv1x1_bwd_weight_workspace_bytes": (Z, [I, I, I, I, I, I]),
+    "gs_conv1x1_bwd_weight": (I, [P, P, P, I, I, I, I, I, I, I, I, P, Z, P]),
+    "gs_softmax_xent": (I, [P, P, P, P, P, I, I, P]),
+    "gs_momentum_workspace_bytes": (Z, [L]),
+    "gs_momentum_tf_step": (I, [P, P, P, L, L, L, F, F, F, I, I, P, P, Z, P]),
 }
 
 WGRAD_MAX_SOURCES = 4   # GS_WGRAD_MAX_SOURCES
@@ -160,6 +174,12 @@ class GsWgradJob(ctypes.Structure):
                 ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("ci", ctypes.c_int32), ("co", ctypes.c_int32), ("ksize", ctypes.c_int32),
                 ("stride", ctypes.c_int32), ("transposed", ctypes.c_int32), ("alpha", c_float), ("accumulate", ctypes.c_int32),
                 ("dtype", ctypes.c_int32), ("gw_ci_stride", ctypes.c_int32)]
+
+
+class GsWsDesc(ctypes.Structure):
+    """include/gansynth_hip.h: one weight of gs_weight_standardize_batch / _bwd_batch (the table lives in device memory)."""
+    _fields_ = [("w", c_void_p), ("out", c_void_p), ("rstd", c_void_p), ("gout", c_void_p), ("gw", c_void_p),
+                ("fan_in", ctypes.c_int32), ("co", ctypes.c_int32)]
 
 
 _lib = None

@@ -107,6 +107,9 @@ def read_safetensors(path):
         raw = data[base + lo:base + hi]
         if info["dtype"] == "BF16":
             arr = (np.frombuffer(raw, dtype="<u2").astype(np.uint32) << 16).view(np.float32)
+        elif info["dtype"] == "I64":   # counters (a checkpoint's global_step): kept as integers
+            out[name] = np.frombuffer(raw, dtype="<i8").reshape(info["shape"]).copy()
+            continue
         elif info["dtype"] in _ST_DTYPES:
             arr = np.frombuffer(raw, dtype=_ST_DTYPES[info["dtype"]])
         else:
@@ -116,11 +119,12 @@ def read_safetensors(path):
 
 
 def write_safetensors(path, tensors):
-    """{name: array} -> a .safetensors file of fp32 tensors."""
+    """{name: array} -> a .safetensors file of fp32 tensors; integer arrays (counters) are stored as I64."""
     header, blobs, off = {}, [], 0
     for name, t in tensors.items():
-        arr = np.ascontiguousarray(np.asarray(t, dtype="<f4"))
-        header[name] = {"dtype": "F32", "shape": list(arr.shape), "data_offsets": [off, off + arr.nbytes]}
+        integer = np.issubdtype(np.asarray(t).dtype, np.integer)
+        arr = np.ascontiguousarray(np.asarray(t, dtype="<i8" if integer else "<f4"))
+        header[name] = {"dtype": "I64" if integer else "F32", "shape": list(arr.shape), "data_offsets": [off, off + arr.nbytes]}
         blobs.append(arr.tobytes())
         off += arr.nbytes
     h = json.dumps(header).encode()

@@ -1188,6 +1188,149 @@ class HipKernels(object):
                                                     n, h * wd, c, stats.shape[1], _dt(x), _stream()), "gs_group_norm_relu_mean")
         return out
 
+    # ------------------------------------------------------------ pitch classifier, training (networks.ResNet.forward_backward)
+    def _gn_bwd_outputs(self, x, dgamma, dbeta):
+        c = x.shape[1]
+        if dgamma is None:
+            dgamma = torch.empty((c,), dtype=torch.float32, device=x.device)
+        if dbeta is None:
+            dbeta = torch.empty((c,), dtype=torch.float32, device=x.device)
+        for t in (dgamma, dbeta):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == c
+        return dgamma, dbeta
+
+    def group_norm_relu_bwd(self, x, stats, gamma, beta, gy, addend=None, dgamma=None, dbeta=None):
+        """(dx [+ addend], dgamma, dbeta) of y = relu(group_norm(x)) from the upstream gradient gy; `dgamma` / `dbeta` (fp32, c
+        elements): written in place."""
+        x, gy = _act(x), _act(gy)
+        n, c, h, wd = x.shape
+        assert gy.shape == x.shape and gy.dtype == x.dtype
+        if addend is not None:
+            addend = _act(addend)
+            assert addend.shape == x.shape and addend.dtype == x.dtype
+        dgamma, dbeta = self._gn_bwd_outputs(x, dgamma, dbeta)
+        dx = _empty_like_act(tuple(x.shape), x)
+        groups = stats.shape[1]
+        ws = _ws(self.lib.gs_group_norm_bwd_workspace_bytes(n, h * wd, c, groups), x.device)
+        _lib.check(self.lib.gs_group_norm_relu_bwd(x.data_ptr(), stats.data_ptr(), _f32c(gamma).data_ptr(), _f32c(beta).data_ptr(), gy.data_ptr(),
+                                                   None if addend is None else addend.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                                   n, h * wd, c, groups, 0, _dt(x), ws.data_ptr(), ws.numel(), _stream()), "gs_group_norm_relu_bwd")
+        return dx, dgamma, dbeta
+
+    def group_norm_relu_mean_bwd(self, x, stats, gamma, beta, gfeatures, dgamma=None, dbeta=None):
+        """The backward of group_norm_relu_mean from d features [n, c] (fp32)."""
+        x, gfeatures = _act(x), _f32c(gfeatures)
+        n, c, h, wd = x.shape
+        assert tuple(gfeatures.shape) == (n, c)
+        dgamma, dbeta = self._gn_bwd_outputs(x, dgamma, dbeta)
+        dx = _empty_like_act(tuple(x.shape), x)
+        groups = stats.shape[1]
+        ws = _ws(self.lib.gs_group_norm_bwd_workspace_bytes(n, h * wd, c, groups), x.device)
+        _lib.check(self.lib.gs_group_norm_relu_mean_bwd(x.data_ptr(), stats.data_ptr(), _f32c(gamma).data_ptr(), _f32c(beta).data_ptr(),
+                                                        gfeatures.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), n, h * wd, c, groups, 0,
+                                                        _dt(x), ws.data_ptr(), ws.numel(), _stream()), "gs_group_norm_relu_mean_bwd")
+        return dx, dgamma, dbeta
+
+    def weight_standardize_table(self, rows):
+        """Device table for weight_standardize_batch / _bwd_batch.  rows: (w, out, rstd, gout, gw) fp32 contiguous tensors per weight
+        ([..., co]; rstd [co]; gout / gw may be None for a forward-only table).  The table keeps its tensors alive."""
+        arr = (_lib.GsWsDesc * len(rows))()
+        max_co = 0
+        for d, (w, out, rstd, gout, gw) in zip(arr, rows):
+            co = w.shape[-1]
+            for t in (w, out, rstd, gout, gw):
+                assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+            assert out.shape == w.shape and rstd.numel() == co and (gout is None or gout.shape == w.shape) and (gw is None or gw.shape == w.shape)
+            d.w, d.out, d.rstd = w.data_ptr(), out.data_ptr(), rstd.data_ptr()
+            d.gout, d.gw = (None if gout is None else gout.data_ptr()), (None if gw is None else gw.data_ptr())
+            d.fan_in, d.co = w.numel() // co, co
+            max_co = max(max_co, co)
+        host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
+        return dict(table=host.to(rows[0][0].device), n=len(rows), max_co=max_co, rows=rows, backward=all(r[3] is not None and r[4] is not None for r in rows))
+
+    def weight_standardize_batch(self, table, eps):
+        _lib.check(self.lib.gs_weight_standardize_batch(table["table"].data_ptr(), table["n"], table["max_co"], float(eps), _stream()),
+                   "gs_weight_standardize_batch")
+
+    def weight_standardize_bwd_batch(self, table):
+        """gw = the gradient through the standardisation of every weight of the table, from gout (cleared behind the read)."""
+        assert table["backward"], "the table was built without gradient buffers"
+        _lib.check(self.lib.gs_weight_standardize_bwd_batch(table["table"].data_ptr(), table["n"], table["max_co"], _stream()),
+                   "gs_weight_standardize_bwd_batch")
+
+    def max_pool2d_bwd(self, x, gy):
+        """Gradient of the 3x3 / 2 SAME max pool of x (any h, w): a window's gradient goes to its first maximum."""
+        x, gy = _act(x), _act(gy)
+        n, c, h, wd = x.shape
+        assert tuple(gy.shape) == (n, c, (h + 1) // 2, (wd + 1) // 2) and gy.dtype == x.dtype
+        gx = _empty_like_act(tuple(x.shape), x)
+        _lib.check(self.lib.gs_max_pool2d_bwd(x.data_ptr(), gy.data_ptr(), gx.data_ptr(), n, h, wd, c, _dt(x), _stream()), "gs_max_pool2d_bwd")
+        return gx
+
+    def resnet_stem_bwd_weight(self, x, gstem, out=None, bias_out=None):
+        """(gw [7, 7, 2, 64], gb [64]) of the stem conv from its input and the gradient of its output; `out` / `bias_out`: added into."""
+        x, gstem = _act(x), _act(gstem)
+        n, c, h, wd = x.shape
+        co = gstem.shape[1]
+        assert c == 2 and tuple(gstem.shape) == (n, co, h // 2, wd // 2) and gstem.dtype == x.dtype and (out is None) == (bias_out is None)
+        gw = torch.empty((7, 7, 2, co), dtype=torch.float32, device=x.device) if out is None else out
+        gb = torch.empty((co,), dtype=torch.float32, device=x.device) if bias_out is None else bias_out
+        assert gw.is_contiguous() and gb.is_contiguous() and gw.dtype == gb.dtype == torch.float32
+        ws = _ws(self.lib.gs_resnet_stem_bwd_weight_workspace_bytes(n, h, wd), x.device)
+        _lib.check(self.lib.gs_resnet_stem_bwd_weight(x.data_ptr(), gstem.data_ptr(), gw.data_ptr(), gb.data_ptr(), n, h, wd, co, 0 if out is None else 1,
+                                                      _dt(x), ws.data_ptr(), ws.numel(), _stream()), "gs_resnet_stem_bwd_weight")
+        return gw, gb
+
+    def conv1x1_bwd_data(self, gy, w, x_shape, stride, out=None):
+        """gx [n, ci, h, w] of conv1x1_fwd; `out`: the gradient is ADDED into it at the sampled pixels (the other consumer's gradient
+        is already there)."""
+        gy = _act(gy)
+        n, ci, h, wd = x_shape
+        co = w.shape[-1]
+        assert tuple(gy.shape) == (n, co, h // stride, wd // stride)
+        gx = _empty_like_act((n, ci, h, wd), gy) if out is None else out
+        assert gx.dtype == gy.dtype and tuple(gx.shape) == (n, ci, h, wd) and gx.is_contiguous(memory_format=CL)
+        _lib.check(self.lib.gs_conv1x1_bwd_data(gy.data_ptr(), _f32c(w).data_ptr(), gx.data_ptr(), n, h, wd, ci, co, int(stride), 0 if out is None else 1,
+                                                _dt(gy), _stream()), "gs_conv1x1_bwd_data")
+        return gx
+
+    def conv1x1_bwd_weight(self, x, gy, stride, out=None):
+        """gw [1, 1, ci, co] of conv1x1_fwd; `out`: added into."""
+        x, gy = _act(x), _act(gy)
+        n, ci, h, wd = x.shape
+        co = gy.shape[1]
+        assert tuple(gy.shape) == (n, co, h // stride, wd // stride) and gy.dtype == x.dtype
+        gw = torch.empty((1, 1, ci, co), dtype=torch.float32, device=x.device) if out is None else out
+        assert gw.is_contiguous() and gw.dtype == torch.float32 and gw.numel() == ci * co
+        ws = _ws(self.lib.gs_conv1x1_bwd_weight_workspace_bytes(n, h, wd, ci, co, int(stride)), x.device)
+        _lib.check(self.lib.gs_conv1x1_bwd_weight(x.data_ptr(), gy.data_ptr(), gw.data_ptr(), n, h, wd, ci, co, int(stride), 0 if out is None else 1,
+                                                  _dt(x), ws.data_ptr(), ws.numel(), _stream()), "gs_conv1x1_bwd_weight")
+        return gw
+
+    def softmax_xent(self, logits, labels, want_grad=True):
+        """(loss [1] fp32 = mean softmax cross-entropy, dlogits or None, correct [1] int32 = rows whose argmax matches the labels')."""
+        logits, labels = _f32c(logits), _f32c(labels)
+        n, c = logits.shape
+        assert labels.shape == logits.shape
+        loss = torch.empty((1,), dtype=torch.float32, device=logits.device)
+        correct = torch.empty((1,), dtype=torch.int32, device=logits.device)
+        dlogits = torch.empty_like(logits) if want_grad else None
+        _lib.check(self.lib.gs_softmax_xent(logits.data_ptr(), labels.data_ptr(), loss.data_ptr(), None if dlogits is None else dlogits.data_ptr(),
+                                            correct.data_ptr(), n, c, _stream()), "gs_softmax_xent")
+        return loss, dlogits, correct
+
+    def momentum_tf_step(self, p, g, accum, lr, momentum, use_nesterov, weight_decay=0.0, decay_range=(0, 0), zero_grad=True, want_l2=True):
+        """tf.train.MomentumOptimizer over a flat buffer, the L2 term's gradient (weight_decay * p on decay_range) folded in; returns
+        sum p^2 / 2 of that range at the pre-update values ([1] fp32) or None."""
+        for t in (p, g, accum):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()
+        l2 = torch.empty((1,), dtype=torch.float32, device=p.device) if want_l2 else None
+        ws = _ws(self.lib.gs_momentum_workspace_bytes(p.numel()), p.device)
+        _lib.check(self.lib.gs_momentum_tf_step(p.data_ptr(), g.data_ptr(), accum.data_ptr(), p.numel(), int(decay_range[0]), int(decay_range[1]),
+                                                float(weight_decay), float(lr), float(momentum), 1 if use_nesterov else 0, 1 if zero_grad else 0,
+                                                None if l2 is None else l2.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_momentum_tf_step")
+        return l2
+
     def account(self):
         """bench.py: `with K.account() as calls:` lists every kernel-layer call made inside as (method, argument dict, bytes read,
         bytes written) -- the algorithmic traffic of SURVEY.md 8(d): every tensor argument read once, every result written once

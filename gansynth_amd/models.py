@@ -19,6 +19,7 @@ data_parallel.py (all-reduce, agreement between ranks); flat_params.py is the fl
 """
 import contextlib
 import math
+import os
 
 import torch
 import torch.nn.functional as TF
@@ -812,21 +813,151 @@ class GANSynth(Iterations, DataParallel, Capture):
         return out
 
 
+def exponential_decay(learning_rate, global_step, decay_steps, decay_rate):
+    """tf.train.exponential_decay, staircase=False: learning_rate * decay_rate ** (global_step / decay_steps)."""
+    return float(learning_rate) * float(decay_rate) ** (float(global_step) / float(decay_steps))
+
+
 class PitchClassifier(object):
-    """models.py:325-408, evaluation only (training the classifier -- backward through group norm, weight standardisation and the
-    pool, Nesterov SGD -- is not part of this project).  `network`: a networks.ResNet; `input_fn()` -> (waveforms [B, L] or images
-    [B, 2, T, F], one-hot labels [B, classes]) until StopIteration."""
+    """models.py:253-408: the pitch classifier's training and evaluation.  `network`: a networks.ResNet; `input_fn()` -> (waveforms
+    [B, L] or images [B, 2, T, F], one-hot labels [B, classes]) until StopIteration; `hyper_params`: weight_decay, learning_rate (a
+    float or a callable of the global step), momentum, use_nesterov (pitch_classifier_main.py:71-81).
+
+    Training (fp32 activations) is softmax cross-entropy + weight_decay * sum(v^2) / 2 over every variable whose name does not contain
+    "normalization", minimised by tf.train.MomentumOptimizer: networks.ResNet.forward_backward and .momentum_step, all on HIP kernels.
+    Checkpoints are .safetensors files (classifier_io.write_safetensors) named like checkpoint.py's: the variables under their reference
+    names, the momentum accumulators under "momentum/<variable>" and "global_step" -- nothing but the variables starts with "resnet/",
+    so a checkpoint is itself a classifier weight file (GANSynth.evaluate's `classifier`, gan_synth_main.py --classifier)."""
+
+    SLOT_PREFIX = "momentum/"
+    MAX_TO_KEEP = 10   # tf.train.Saver(max_to_keep=10), models.py:322-325
 
     def __init__(self, network, input_fn, spectral_params, hyper_params=None, dtype=torch.float32):
         self.network, self.input_fn = network, input_fn
         self.spectral_params, self.hyper_params = spectral_params, hyper_params
         self.dtype = dtype
+        self.global_step = 0
+        self.restored_from = None
+
+    def _images(self, data, dtype):
+        data = data.to(self.network.store.device)
+        with torch.no_grad():
+            images = spectral_ops.convert_to_images(data, **self.spectral_params, dtype=dtype) if data.dim() == 2 else data
+        return images.to(dtype).contiguous(memory_format=torch.channels_last)
+
+    # ------------------------------------------------------------------------------------------------ checkpoints
+    @classmethod
+    def slot_name(cls, variable):
+        """Checkpoint key of a variable's momentum accumulator."""
+        return cls.SLOT_PREFIX + variable
+
+    @classmethod
+    def split_state(cls, state):
+        """A checkpoint's entries -> ({variable: array}, {variable: its accumulator}, global_step or None)."""
+        import numpy as np
+        slots = {k[len(cls.SLOT_PREFIX):]: v for k, v in state.items() if k.startswith(cls.SLOT_PREFIX)}
+        weights = {k: v for k, v in state.items() if not k.startswith(cls.SLOT_PREFIX) and k != "global_step"}
+        return weights, slots, (int(np.asarray(state["global_step"]).reshape(-1)[0]) if "global_step" in state else None)
+
+    def state_dict(self):
+        """{name: host array}: variables, "momentum/<variable>" accumulators, "global_step"."""
+        st = self.network.train_state()
+        torch.cuda.synchronize()
+        out = {}
+        for name, p in st.flat.named.items():
+            out[name] = p.data.detach().cpu().numpy().copy()
+        for name, p in st.flat.named.items():
+            off = (p.data.data_ptr() - st.flat.flat.data_ptr()) // 4
+            out[self.slot_name(name)] = st.flat.m[off:off + p.numel()].view(p.shape).cpu().numpy().copy()
+        import numpy as np
+        out["global_step"] = np.asarray(self.global_step, dtype=np.int64)
+        return out
+
+    def save(self, model_dir):
+        import glob
+        import re
+        from . import classifier_io
+        os.makedirs(model_dir, exist_ok=True)
+        path = os.path.join(model_dir, f"model.ckpt-{self.global_step}.safetensors")
+        classifier_io.write_safetensors(path, self.state_dict())
+        with open(os.path.join(model_dir, "checkpoint"), "w") as f:
+            f.write(f'model_checkpoint_path: "{os.path.basename(path)}"\n')
+        old = sorted(glob.glob(os.path.join(model_dir, "model.ckpt-*.safetensors")), key=lambda q: int(re.findall(r"ckpt-(\d+)", q)[-1]))
+        for q in old[:-self.MAX_TO_KEEP]:
+            os.remove(q)
+        return path
+
+    def restore(self, model_dir_or_file):
+        """Variables, accumulators and global_step from a checkpoint file or the latest one of a directory; returns its path, or None
+        when the directory has none (a fresh run)."""
+        from . import checkpoint, classifier_io
+        path = model_dir_or_file if os.path.isfile(model_dir_or_file) else checkpoint.latest(model_dir_or_file)
+        if path is None:
+            return None
+        state = classifier_io.read_safetensors(path)
+        st = self.network.train_state()
+        weights, slots, step = self.split_state(state)
+        self.network.load_state_dict(weights, strict=True)
+        with torch.no_grad():
+            st.flat.m.zero_()   # (a plain weight file: fresh accumulators)
+            for name, p in st.flat.named.items():
+                if name in slots:
+                    if tuple(slots[name].shape) != tuple(p.shape):
+                        raise ValueError(f"checkpoint: {self.slot_name(name)} has shape {tuple(slots[name].shape)}, the variable has {tuple(p.shape)}")
+                    off = (p.data.data_ptr() - st.flat.flat.data_ptr()) // 4
+                    st.flat.m[off:off + p.numel()].view(p.shape).copy_(torch.from_numpy(slots[name].copy()))
+        self.global_step = step or 0
+        return path
+
+    # --------------------------------------------------------------------------------------------------- training
+    def train(self, model_dir, config, total_steps, save_checkpoint_steps, save_summary_steps, log_tensor_steps, log=print):
+        """models.py:306-386 with the reference's signature and argument order.  `config` (tf.ConfigProto) and `save_summary_steps` (the
+        TensorBoard hooks) are accepted and ignored, as GANSynth.train does.  Resumes from the latest checkpoint of `model_dir`, steps
+        until global_step reaches `total_steps` or the input runs dry, logs global_step, loss (cross-entropy + L2 term, at the
+        pre-update weights) and accuracy (tf.metrics.accuracy: cumulative correct / total since this call began) every
+        `log_tensor_steps`, saves every `save_checkpoint_steps` and at the end."""
+        del config, save_summary_steps
+        hp, net = self.hyper_params, self.network
+        if self.dtype != torch.float32:
+            raise TypeError("PitchClassifier.train: training runs in fp32 (bf16 training is not implemented)")
+        net.train_state()
+        if model_dir is not None:
+            self.restored_from = self.restore(model_dir)
+        correct, total, last_saved = None, 0, None
+        while self.global_step < total_steps:
+            try:
+                data, labels = self.input_fn()
+            except StopIteration:
+                break
+            images = self._images(data, torch.float32)
+            lr = hp.learning_rate(self.global_step) if callable(hp.learning_rate) else hp.learning_rate
+            loss, hits, _, _ = net.forward_backward(images, labels)
+            l2 = net.momentum_step(float(lr), hp.momentum, hp.use_nesterov, hp.weight_decay)
+            self.global_step += 1
+            correct = hits.to(torch.int64) if correct is None else correct + hits
+            total += int(labels.shape[0])
+            if log is not None and log_tensor_steps and self.global_step % log_tensor_steps == 0:
+                log(f"global_step = {self.global_step}, loss = {float(loss) + float(hp.weight_decay) * float(l2):.6f}, "
+                    f"accuracy = {int(correct) / max(total, 1):.6f}")
+            if model_dir is not None and save_checkpoint_steps and self.global_step % save_checkpoint_steps == 0:
+                last_saved = self.global_step
+                self.save(model_dir)
+        if model_dir is not None and last_saved != self.global_step:
+            self.save(model_dir)
+        return dict(global_step=self.global_step, accuracy=(int(correct) / max(total, 1)) if total else None)
 
     def evaluate(self, model_dir=None, config=None):
-        """models.py:388-408: top-1 accuracy over the whole input.  `model_dir`: classifier weights to load first (a frozen GraphDef or
-        a .safetensors file), or None for the network's current weights.  `config` is accepted and ignored."""
+        """models.py:388-408: top-1 accuracy over the whole input.  `model_dir`: a training directory (its latest checkpoint is loaded),
+        or classifier weights as a file (a frozen GraphDef or a .safetensors file), or None for the network's current weights.
+        `config` is accepted and ignored."""
         del config
         if model_dir is not None:
+            if os.path.isdir(model_dir):
+                from . import checkpoint
+                path = checkpoint.latest(model_dir)
+                if path is None:
+                    raise FileNotFoundError(f"PitchClassifier.evaluate: no checkpoint in {model_dir}")
+                model_dir = path
             self.network.load(model_dir)
         correct, total = 0, 0
         while True:
@@ -834,10 +965,9 @@ class PitchClassifier(object):
                 data, labels = self.input_fn()
             except StopIteration:
                 break
-            data = data.to(self.network.store.device)
+            images = self._images(data, self.dtype)
             with torch.no_grad():
-                images = spectral_ops.convert_to_images(data, **self.spectral_params, dtype=self.dtype) if data.dim() == 2 else data
-                _, logits = self.network(images.to(self.dtype).contiguous(memory_format=torch.channels_last))
+                _, logits = self.network(images)
             correct += int((logits.argmax(dim=1).cpu() == labels.argmax(dim=1).cpu()).sum())
             total += labels.shape[0]
         return dict(accuracy=correct / max(total, 1))

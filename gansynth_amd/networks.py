@@ -264,7 +264,8 @@ GN_EPS = 1.0e-12   # ops.group_normalization / ops.weight_standardization defaul
 
 
 class ResNet(object):
-    """The pitch classifier of networks.py:293-413 (GANSynth.evaluate's feature extractor), inference only.
+    """The pitch classifier of networks.py:293-413: GANSynth.evaluate's feature extractor (`__call__`, inference) and its training pass
+    (`forward_backward` / `momentum_step`, fp32).
 
     Same constructor and call surface: `resnet(images, name="resnet", reuse)` -> (features [n, filters of the last stage] fp32,
     logits [n, classes] fp32); images [n, 2, 128, 1024] (channels-last, fp32 or bf16: the activation dtype of the whole pass).
@@ -287,6 +288,7 @@ class ResNet(object):
             store = variables.VariableStore(device="cuda" if torch.cuda.is_available() else "cpu", seed=0)
         self.store = store
         self._prep = {}   # variable name -> [stamp, standardised weight, {dtype: [conv workspace, prepared]}]
+        self._train = None   # train_state()
 
     @staticmethod
     def pitch_classifier(store=None):
@@ -366,6 +368,149 @@ class ResNet(object):
         y = K.conv2d_fwd_bias_ws(x, ent[1], b, 3, stride, slot[0], slot[1])
         slot[1] = 1
         return y
+
+    # --------------------------------------------------------------------------------------------------- training
+    # A hand-scheduled reverse walk instead of autograd Functions: the step is one fixed sequence of launches (nothing to trace, no
+    # graph of Python objects per step), every saved tensor is named here, the gradients land in the flat buffer's views directly,
+    # and the fusions the backward wants (the shortcut gradient as the norm backward's addend, the projection's data gradient added
+    # into the conv's) cross what would be node boundaries.
+    @staticmethod
+    def is_decayed(name):
+        """models.py:268-272: the L2 term covers every trainable variable whose name does not contain "normalization"."""
+        return "normalization" not in name
+
+    def train_state(self, name="resnet"):
+        """The training-side storage, built on first use: every variable re-homed into one flat fp32 buffer (flat_params._FlatParams:
+        .flat, .grad, .m = the momentum accumulators) with the decayed variables first -- one contiguous decayed range --, the
+        standardised copies of the conv weights and their gradients in flat buffers of their own, and the descriptor table of the
+        batched standardisation."""
+        if getattr(self, "_train", None) is not None:
+            return self._train
+        from . import kernels
+        from .flat_params import _FlatParams
+        from .utils import Dict
+        if not self.store.variables:
+            self.create_variables(name=name)
+        V = self.store.variables
+        order = [k for k in V if self.is_decayed(k)] + [k for k in V if not self.is_decayed(k)]
+        flat = _FlatParams([(k, V[k]) for k in order])
+        flat.v = None   # (Adam's second slot: momentum has one)
+        decay_hi = next((off for off, _, k in flat._offsets if not self.is_decayed(k)), flat.flat.numel())
+        convs = [k for k in order if k.endswith("/weight") and V[k].dim() == 4]
+        pad = lambda n: (n + 63) // 64 * 64
+        total, chans = sum(pad(V[k].numel()) for k in convs), sum(pad(V[k].shape[3]) for k in convs)
+        dev = flat.flat.device
+        std, gstd, rstd = (torch.zeros(n, dtype=torch.float32, device=dev) for n in (total, total, chans))
+        views, rows, o, oc = {}, [], 0, 0
+        for k in convs:
+            w = V[k]
+            n, co = w.numel(), w.shape[3]
+            views[k] = (std[o:o + n].view(w.shape), gstd[o:o + n].view(w.shape))
+            rows.append((w.data, views[k][0], rstd[oc:oc + co], views[k][1], w.grad))
+            o, oc = o + pad(n), oc + pad(co)
+        # gstd_clean: the standardised weights' gradient buffer is all zeros (fresh, or cleared by the last pass's final launch)
+        self._train = Dict(flat=flat, decay_range=(0, decay_hi), std=views, gstd=gstd, gstd_clean=True, table=kernels.get().weight_standardize_table(rows), ws={}, name=name)
+        self._prep.clear()   # (the variables moved)
+        return self._train
+
+    def parameters_changed(self):
+        """The variables were updated in place by a kernel (no torch version bump): the inference path's standardised copies are stale."""
+        for ent in self._prep.values():
+            ent[0] = None
+
+    def _conv3x3_train(self, K, st, x, key, stride):
+        V = self.store.variables
+        w = st.std[key + "/weight"][0]
+        from . import kernels
+        wk = (key, tuple(x.shape))
+        if wk not in st.ws:
+            st.ws[wk] = K.conv2d_fwd_workspace(tuple(x.shape), w.shape[3], 3, stride, kernels._dt(x))
+        return K.conv2d_fwd_bias_ws(x, w, V[key + "/bias"].data, 3, stride, st.ws[wk], 0)
+
+    def forward_backward(self, images, onehot_labels, name="resnet"):
+        """One training pass: -> (loss_xent [1] fp32 = the mean softmax cross-entropy WITHOUT the L2 term, correct [1] int32 = rows whose
+        argmax is the label's, features, logits), and the gradient of that loss w.r.t. every variable in the flat gradient buffer
+        (train_state().flat.grad; each variable's .grad is its view).  The L2 term's gradient, weight_decay * v, is added by the
+        optimizer step (kernels.momentum_tf_step).  fp32 activations; the images receive no gradient."""
+        from . import kernels
+        from ._lib import ACT_NONE
+        if images.dtype != torch.float32:
+            raise TypeError(f"ResNet.forward_backward: activations are {images.dtype}; training runs in fp32 (bf16 training is not implemented)")
+        K = kernels.get()
+        st = self.train_state(name)
+        if st.name != name:
+            raise ValueError(f"ResNet.forward_backward: the training state was built under the scope {st.name!r}")
+        V, G = self.store.variables, self.groups
+        S = lambda key: st.std[key + "/weight"]          # (standardised weight, its gradient buffer)
+        gn = lambda key: (V[key + "/gamma"].data.view(-1), V[key + "/beta"].data.view(-1))
+        gn_grads = lambda key: dict(dgamma=V[key + "/gamma"].grad.view(-1), dbeta=V[key + "/beta"].grad.view(-1))
+        with torch.no_grad():
+            st.flat.begin_run()
+            if not st.gstd_clean:   # the previous pass raised before its last launch: its partial sums must not be added onto
+                st.gstd.zero_()
+            st.gstd_clean = False
+            K.weight_standardize_batch(st.table, GN_EPS)
+            images = images.contiguous(memory_format=torch.channels_last)
+            labels = onehot_labels.to(device=images.device, dtype=torch.float32)
+            # ---- forward, keeping what the backward reads
+            stem, x = K.resnet_stem_pool(images, S(name + "/conv")[0], V[name + "/conv/bias"].data, want_stem=True)
+            stats, _ = K.group_norm_stats(x, G, GN_EPS)
+            tape = []
+            for i, rp in enumerate(self.residual_params):
+                for j in range(rp.blocks):
+                    stride = int(rp.strides[0]) if j == 0 else 1
+                    b = f"{name}/residual_block_{i}_{j}"
+                    x_in, st1 = x, stats
+                    a = K.group_norm_apply(x, stats, *gn(b + "/group_normalization_1st"), relu=True)
+                    shortcut = K.conv1x1_fwd(a, S(b + "/projection_shortcut")[0], stride) if j == 0 else x
+                    t1 = self._conv3x3_train(K, st, a, b + "/conv_1st", stride)
+                    st2, _ = K.group_norm_stats(t1, G, GN_EPS)
+                    a2 = K.group_norm_apply(t1, st2, *gn(b + "/group_normalization_2nd"), relu=True)
+                    t2 = self._conv3x3_train(K, st, a2, b + "/conv_2nd", 1)
+                    stats, x = K.group_norm_stats(t2, G, GN_EPS, addend=shortcut)
+                    tape.append((b, j == 0, stride, x_in, st1, a, t1, st2, a2))
+            features = K.group_norm_relu_mean(x, stats, *gn(name + "/group_normalization"))
+            wl, bl = V[name + "/logits/weight"], V[name + "/logits/bias"]
+            logits = torch.cat([K.dense_fwd_bias_act(features[r:r + 64], wl.data, bl.data, 1.0, ACT_NONE) for r in range(0, features.shape[0], 64)])
+            loss, dlogits, correct = K.softmax_xent(logits, labels)
+            # ---- backward
+            K.dense_bwd_weight(features, dlogits, 1.0, out=wl.grad)
+            K.channel_sum(dlogits, out=bl.grad)
+            dfeat = K.dense_bwd_data(dlogits, wl.data, 1.0)
+            dx, _, _ = K.group_norm_relu_mean_bwd(x, stats, *gn(name + "/group_normalization"), dfeat, **gn_grads(name + "/group_normalization"))
+            for b, projected, stride, x_in, st1, a, t1, st2, a2 in reversed(tape):
+                w2, gw2 = S(b + "/conv_2nd")
+                K.conv2d_bwd_weight(a2, dx, 3, 1, 1.0, out=gw2, bias_out=V[b + "/conv_2nd/bias"].grad)
+                da2 = K.conv2d_bwd_data(dx, w2, tuple(a2.shape), 3, 1, 1.0)
+                dt1, _, _ = K.group_norm_relu_bwd(t1, st2, *gn(b + "/group_normalization_2nd"), da2, **gn_grads(b + "/group_normalization_2nd"))
+                w1, gw1 = S(b + "/conv_1st")
+                K.conv2d_bwd_weight(a, dt1, 3, stride, 1.0, out=gw1, bias_out=V[b + "/conv_1st/bias"].grad)
+                da = K.conv2d_bwd_data(dt1, w1, tuple(a.shape), 3, stride, 1.0)
+                addend = dx   # the identity shortcut's gradient joins inside the norm's backward
+                if projected:
+                    wp, gwp = S(b + "/projection_shortcut")
+                    K.conv1x1_bwd_weight(a, dx, stride, out=gwp)
+                    K.conv1x1_bwd_data(dx, wp, tuple(a.shape), stride, out=da)
+                    addend = None
+                dx, _, _ = K.group_norm_relu_bwd(x_in, st1, *gn(b + "/group_normalization_1st"), da, addend=addend,
+                                                 **gn_grads(b + "/group_normalization_1st"))
+            dstem = K.max_pool2d_bwd(stem, dx)
+            K.resnet_stem_bwd_weight(images, dstem, out=S(name + "/conv")[1], bias_out=V[name + "/conv/bias"].grad)
+            K.weight_standardize_bwd_batch(st.table)   # d standardised weights -> the variables' gradients (and cleared for the next pass)
+            st.gstd_clean = True
+        return loss, correct, features, logits
+
+    def momentum_step(self, lr, momentum, use_nesterov, weight_decay):
+        """tf.train.MomentumOptimizer.apply_gradients on the flat buffer, the L2 term's gradient folded in (one launch; the gradient
+        buffer is cleared behind it).  Returns sum v^2 / 2 over the decayed variables at the pre-update values ([1] fp32)."""
+        from . import kernels
+        st = self.train_state()
+        l2 = kernels.get().momentum_tf_step(st.flat.flat, st.flat.grad, st.flat.m, lr, momentum, use_nesterov, weight_decay=weight_decay,
+                                            decay_range=st.decay_range, zero_grad=True, want_l2=True)
+        st.flat.grad_clean = True
+        st.flat.t += 1
+        self.parameters_changed()
+        return l2
 
     # --------------------------------------------------------------------------------------------------- forward
     def __call__(self, inputs, name="resnet", reuse=AUTO_REUSE):

@@ -454,7 +454,7 @@ int gs_mel_if_to_waveform(const gs_spectral_plan* plan, const void* images, int 
                           float* wave, int dtype, void* ws, size_t ws_bytes, void* stream);
 size_t gs_mel_if_to_waveform_workspace_bytes(const gs_spectral_plan* plan, int batch);
 
-/* ------------------------------------------------------------------- pitch classifier (GANSynth.evaluate, inference only)
+/* ------------------------------------------------------------------- pitch classifier, forward (GANSynth.evaluate)
  * The ResNet of networks.py:293-413 (pitch_classifier_main.py:39-50: 7x7 stem, 3x3 max pool, four stages of pre-activation residual
  * blocks with group normalisation and weight-standardised convs, global mean, dense logits).  Its 3x3 convs are gs_conv2d_fwd_bias_act
  * with alpha = 1 on standardised weights, its logits gs_dense_fwd_bias_act; the entry points below are the rest.  Deterministic:
@@ -485,6 +485,59 @@ int gs_group_norm_apply(const void* x, const float* stats, const float* gamma, c
                         int relu, int dtype, void* stream);
 int gs_group_norm_relu_mean(const void* x, const float* stats, const float* gamma, const float* beta, float* features, int n, int hw, int c,
                             int groups, int dtype, void* stream);
+
+/* ------------------------------------------------------------------- pitch classifier, training (models.py:253-299)
+ * The backward of the entry points above, softmax cross-entropy and tf.train.MomentumOptimizer.  The 3x3 convs and the logits layer
+ * reuse gs_conv2d_bwd_data, gs_conv2d_bwd_weight_bias and gs_dense_bwd_* on the standardised weights with alpha = 1.  Deterministic:
+ * fixed-order reductions, no float atomics.  `accumulate` != 0: the result is added into its target.
+ *   group_norm_relu_bwd       y = relu(group_norm(x)): from x, its stats, gamma, beta and gy -> dx (+ addend, the identity-shortcut
+ *                             gradient of a pre-activation block), dgamma [c], dbeta [c] (folded over the images in order).  The ReLU
+ *                             mask is recomputed with gs_group_norm_apply's expression.  c / groups <= 64
+ *   group_norm_relu_mean_bwd  the head: the same from d features [n][c] fp32 (every pixel receives d features / hw)
+ *   weight_standardize_batch  every row of a descriptor table (DEVICE memory) in one launch: out = standardised w (bit-identical to
+ *                             gs_weight_standardize), rstd [co] = 1 / sqrt(var + eps).  max_co: the widest weight of the table
+ *   weight_standardize_bwd_batch  gw = (gout - mean(gout) - out mean(gout out)) rstd per output channel; gout is cleared behind it
+ *   max_pool2d_bwd            3x3 stride 2 SAME on any h, w (odd sizes pad 1 / 1): a window's gradient goes to its first maximum in
+ *                             row-major order; x [n][h][w][c], gy [n][ceil(h/2)][ceil(w/2)][c] -> gx
+ *   resnet_stem_bwd_weight    the 7x7 / 2 stem: x [n][h][w][2], d stem [n][h/2][w/2][64] -> gw [7][7][2][64], gb [64] (fp32 FMA, K split
+ *                             over blocks, folded in order)
+ *   conv1x1_bwd_data / _weight  the projection shortcut, stride 1 or 2, ci and co multiples of 64: gx [n][h][w][ci] (pixels the stride
+ *                             skips are zero, or untouched when accumulating); gw [ci][co]
+ *   softmax_xent              loss[0] = mean_n xent(logits_n, labels_n), dlogits (optional) its gradient, correct[0] = rows whose
+ *                             argmax equals the labels' argmax; logits, labels [n][c] fp32
+ *   momentum_tf_step          over a flat fp32 buffer of n (multiple of 4) elements: g += weight_decay p on [decay_lo, decay_hi),
+ *                             accum = momentum accum + g, p -= lr g + lr momentum accum (nesterov) or lr accum; g cleared when
+ *                             zero_grad; l2 (optional) receives sum p^2 / 2 over the decayed range at the pre-update values */
+typedef struct GsWsDesc {
+    const float* w;   /* [fan_in][co] */
+    float* out;       /* standardised copy */
+    float* rstd;      /* [co] */
+    float* gout;      /* gradient w.r.t. out (backward: read, then cleared) */
+    float* gw;        /* gradient w.r.t. w (backward: written) */
+    int32_t fan_in, co;
+} GsWsDesc;
+size_t gs_group_norm_bwd_workspace_bytes(int n, int hw, int c, int groups);
+int gs_group_norm_relu_bwd(const void* x, const float* stats, const float* gamma, const float* beta, const void* gy, const void* addend, void* dx,
+                           float* dgamma, float* dbeta, int n, int hw, int c, int groups, int accumulate, int dtype, void* ws, size_t ws_bytes,
+                           void* stream);
+int gs_group_norm_relu_mean_bwd(const void* x, const float* stats, const float* gamma, const float* beta, const float* gfeatures, void* dx,
+                                float* dgamma, float* dbeta, int n, int hw, int c, int groups, int accumulate, int dtype, void* ws, size_t ws_bytes,
+                                void* stream);
+int gs_weight_standardize_batch(const GsWsDesc* descs, int n, int max_co, float eps, void* stream);
+int gs_weight_standardize_bwd_batch(const GsWsDesc* descs, int n, int max_co, void* stream);
+int gs_max_pool2d_bwd(const void* x, const void* gy, void* gx, int n, int h, int w, int c, int dtype, void* stream);
+size_t gs_resnet_stem_bwd_weight_workspace_bytes(int n, int h, int w);
+int gs_resnet_stem_bwd_weight(const void* x, const void* gstem, float* gw, float* gb, int n, int h, int w, int co, int accumulate, int dtype,
+                              void* ws, size_t ws_bytes, void* stream);
+int gs_conv1x1_bwd_data(const void* gy, const float* w_io, void* gx, int n, int h, int w, int ci, int co, int stride, int accumulate, int dtype,
+                        void* stream);
+size_t gs_conv1x1_bwd_weight_workspace_bytes(int n, int h, int w, int ci, int co, int stride);
+int gs_conv1x1_bwd_weight(const void* x, const void* gy, float* gw, int n, int h, int w, int ci, int co, int stride, int accumulate, int dtype,
+                          void* ws, size_t ws_bytes, void* stream);
+int gs_softmax_xent(const float* logits, const float* labels, float* loss, float* dlogits, int* correct, int n, int c, void* stream);
+size_t gs_momentum_workspace_bytes(int64_t n);
+int gs_momentum_tf_step(float* p, float* g, float* accum, int64_t n, int64_t decay_lo, int64_t decay_hi, float weight_decay, float lr,
+                        float momentum, int nesterov, int zero_grad, float* l2, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
