@@ -62,6 +62,7 @@ SIGNATURES = {
     "gs_conv2d_bwd_data_pnbwd_is_fused": (I, [I, I, I, I, I, I, I, I, I]),
     "gs_conv2d_fwd_pnbwdbwd_is_fused": (I, [I, I, I, I, I, I, I, I, I]),
     "gs_conv_igemm_config": (I, [I, I, I, I, I, I, I, I, POINTER(c_int)]),
+    "gs_conv_igemm_table": (I, [I, POINTER(c_int)]),
     "gs_units_bias_act_to_nhwc": (I, [P, P, P, P, I, I, I, I, I, P]),
     "gs_nhwc_act_bwd_to_units": (I, [P, P, P, I, I, I, I, I, P]),
     "gs_conv2d_fwd_pnbwdbwd": (I, [P, P, P, P, I, F, P, P, I, I, I, I, I, I, I, F, I, I, P, Z, P]),

@@ -12,6 +12,7 @@ namespace gs {
 bool igemm_supported(int ic, int oc, int dtype);
 bool igemm_norm_fused(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int want);
 int igemm_config(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int want, int* out);
+int igemm_table(int index, int* out);
 extern "C" int gs_pixel_norm_bwd_bwd_fused(const void* gg, const void* g, const void* x, void* out, void* out_g, int64_t p, int c, float eps, int pre_act,
                                            int dtype, void* stream);
 bool wgrad_mfma_supported(int ic, int oc, int dtype);
@@ -1368,6 +1369,9 @@ extern "C" int gs_conv2d_bwd_data_pnbwd_is_fused(int n, int h, int w, int ci, in
 extern "C" int gs_conv_igemm_config(int mode, int n, int hb, int wb, int ic, int oc, int dtype, int want, int* out_cfg) {
     return igemm_config(mode, n, hb, wb, ic, oc, dtype, want, out_cfg);
 }
+// Row `index` of the table of compiled implicit-GEMM kernels (conv_igemm.hip: GS_IGEMM_CONFIGS), for tests that want one case per kernel.  Host
+// only.  out11: mode, bf16_only, A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC; GS_ERR_ARG past the last row.
+extern "C" int gs_conv_igemm_table(int index, int* out11) { return igemm_table(index, out11); }
 extern "C" int gs_conv2d_transpose_s2_bwd_data_pnbwd(const void* gy, const float* w_hwio, const void* z, const void* addend, int act, float eps, void* gx, int n,
                                                      int h, int w, int ci, int co, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream) {
     if (int e = check_conv_args(n, 2 * h, 2 * w, co, ci, 3, 2, dtype)) return e;

@@ -2324,6 +2324,23 @@ int igemm_config(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int
     memcpy(out, v, sizeof(v));
     return 0;
 }
+// gs_conv_igemm_table: row `index` of GS_IGEMM_CONFIGS as the table spells it -- mode, BF16_ONLY, then IgemmCfg's fields -- expanded from the
+// table itself.  The probes' forced row (last, GS_FORCE_CFG builds only) is not a row of the table.
+int igemm_table(int index, int* out) {
+    static const int rows[][11] = {
+#define GS_ROW(M, BF16_ONLY, A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC) {M, BF16_ONLY, A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC},
+        GS_IGEMM_CONFIGS(GS_ROW)
+#undef GS_ROW
+    };
+#ifdef GS_FORCE_CFG
+    constexpr int n = (int)(sizeof(rows) / sizeof(rows[0])) - 1;
+#else
+    constexpr int n = (int)(sizeof(rows) / sizeof(rows[0]));
+#endif
+    if (index < 0 || index >= n || !out) return fail(GS_ERR_ARG, "conv igemm table: row %d of %d", index, n);
+    memcpy(out, rows[index], sizeof(rows[0]));
+    return 0;
+}
 bool wgrad_mfma_supported(int ic, int oc, int dtype) { return (dtype == GS_F32 || dtype == GS_BF16) && ic % 32 == 0 && oc % 32 == 0; }
 
 size_t igemm_prep_bytes(int ic, int oc, int dtype) {

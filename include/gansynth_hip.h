@@ -194,6 +194,10 @@ int gs_conv2d_bwd_data_pnbwd_is_fused(int n, int h, int w, int ci, int co, int k
  * first- / second-order backward.  out_cfg[10] = A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC (conv_igemm.hip: IgemmCfg) and 1 if that
  * configuration is compiled for the dtype; NORM == want says the epilogue is fused, 0 that the norm runs as its own pass. */
 int gs_conv_igemm_config(int mode, int n, int hb, int wb, int ic, int oc, int dtype, int want, int* out_cfg);
+/* The table of compiled implicit-GEMM kernels, row by row (conv_igemm.hip: GS_IGEMM_CONFIGS): out11 = mode, bf16_only (1: compiled for bf16 alone,
+ * 0: for fp32 and bf16), then A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC as above.  0 for 0 <= index < number of rows, GS_ERR_ARG past the end.  Host
+ * only: no launch, no device.  tests/test_igemm_cover_*.py run one case per row and dtype. */
+int gs_conv_igemm_table(int index, int* out11);
 int gs_conv2d_transpose_s2_bwd_data_pnbwd(const void* gy, const float* w_hwio, const void* z, const void* addend, int act, float eps, void* gx, int n,
                                           int h, int w, int ci, int co, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream);
 int gs_conv2d_transpose_s2_bwd_weight(const void* x, const void* gy, float* gw_hwio, int n, int h, int w, int ci, int co,

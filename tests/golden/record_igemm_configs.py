@@ -21,6 +21,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from gansynth_amd import _lib  # noqa: E402  (prototypes only: the library loaded is the patched tree's)
+from tests.igemm_cover import api_call, layer_args  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 S1, S2, T2 = 0, 1, 2
@@ -50,34 +51,17 @@ FUSED_MODES = {0: (S1, S2), 1: (S1, T2)}   # the igemm mode behind each entry po
 
 
 def drive(lib, mode, dtype, n, hb, wb, ic, oc, want):
-    """Calls the entry point that reaches the dispatch with this kernel-role shape and epilogue; False where the ABI has none."""
+    """Calls the entry point that reaches the dispatch with this kernel-role shape and epilogue (tests/igemm_cover.py: api_call names it and
+    layer_args turns the shape into its arguments); False where the ABI has none."""
+    call = api_call(mode, want)
+    if call is None:
+        return False   # (no data gradient runs as the transposed kernel with a norm behind it)
     P = ctypes.c_void_p(0x10000)   # never dereferenced
-    ws, wsb = P, 1 << 30
-    s = 2 if mode == S2 else 1
-    h, w = hb * s, wb * s
     act, eps = _lib.ACT_LRELU, 1e-8
-    if want == PLAIN:
-        if mode == T2:
-            lib.gs_conv2d_transpose_s2_fwd(P, P, P, n, h, w, ic, oc, 1.0, dtype, 1, ws, wsb, None)
-        else:
-            lib.gs_conv2d_fwd(P, P, P, n, h, w, ic, oc, 3, s, 1.0, dtype, 1, ws, wsb, None)
-    elif want == NORM_FWD:
-        if mode == T2:
-            lib.gs_conv2d_transpose_s2_fwd_bias_act_norm(P, P, None, P, P, n, h, w, ic, oc, 1.0, act, eps, dtype, 1, ws, wsb, None)
-        else:
-            lib.gs_conv2d_fwd_bias_act_norm(P, P, None, P, P, n, h, w, ic, oc, 3, s, 1.0, act, eps, dtype, 1, ws, wsb, None)
-    elif want == NORM_BWD:   # data gradients: the layer's (ci, co) are the kernel's (oc, ic)
-        if mode == S1:
-            lib.gs_conv2d_bwd_data_pnbwd(P, P, P, None, act, eps, P, n, hb, wb, oc, ic, 3, 1, 1.0, dtype, 1, ws, wsb, None)
-        elif mode == S2:
-            lib.gs_conv2d_transpose_s2_bwd_data_pnbwd(P, P, P, None, act, eps, P, n, hb, wb, oc, ic, 1.0, dtype, 1, ws, wsb, None)
-        else:
-            return False   # (no data gradient runs as the transposed kernel with a norm behind it)
-    else:
-        if mode == T2:
-            lib.gs_conv2d_transpose_s2_fwd_pnbwdbwd(P, P, P, P, act, eps, P, P, n, h, w, ic, oc, 1.0, dtype, 1, ws, wsb, None)
-        else:
-            lib.gs_conv2d_fwd_pnbwdbwd(P, P, P, P, act, eps, P, P, n, h, w, ic, oc, 3, s, 1.0, dtype, 1, ws, wsb, None)
+    tensors = {PLAIN: (P, P, P), NORM_FWD: (P, P, None, P, P), NORM_BWD: (P, P, P, None, act, eps, P), NORM_BWD2: (P, P, P, P, act, eps, P, P)}[want]
+    shape = layer_args(call, n, hb, wb, ic, oc) + (() if call.transposed else (3, call.stride))
+    scalars = (1.0, act, eps) if want == NORM_FWD else (1.0,)
+    getattr(lib, call.name)(*tensors, *shape, *scalars, dtype, 1, P, 1 << 30, None)
     return True
 
 

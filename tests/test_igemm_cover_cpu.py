@@ -1,0 +1,112 @@
+"""CPU: the cases of tests/test_igemm_cover_gpu.py exist and mean something (no GPU: the chooser answers for the MI355X's 256 CUs).
+
+Reachability: every (mode, dtype, configuration) of the table of compiled implicit-GEMM kernels (gs_conv_igemm_table) is what the chooser
+(gs_conv_igemm_config) answers for some shape of tests/igemm_cover.py's grid, under the default knobs or, failing that, under one of the
+chooser's measurement knobs.  A kernel nothing reaches is dead code or a gap of the grid.  Every chosen case stays under igemm_cover.MAX_MACS
+for its float64 reference.  (The grid holds one output-channel count beyond the layers' own, 352 = 5 * 64 + 32: the two transposed kernels with
+A = 1, TG = 3 run only layers whose channel count is no multiple of 64 and that have more blocks than the chip has CUs, counted in whole
+64-channel tiles -- with 96 channels that takes 64 images of 32 rows, 2.5e9 to 5.4e9 multiply-adds in bf16.)
+
+Sensitivity: the GPU test's tolerance is not vacuous -- a result that lost ONE (tap, 32-channel chunk) stage of the K loop differs from the
+reference by at least ten times that tolerance, at every plain case small enough to evaluate twice here."""
+import pytest
+import torch
+
+from tests import igemm_cover as C
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from gansynth_amd import _lib
+    assert (C.F32, C.BF16) == (_lib.GS_F32, _lib.GS_BF16)
+    return _lib.load()
+
+
+@pytest.fixture(scope="module")
+def plan():
+    return C.assignment()
+
+
+def test_table_is_the_compiled_rows(lib):
+    import ctypes
+    rows, out = C.rows(lib), (ctypes.c_int * 11)()
+    assert len(rows) == 43 and len(C.table(lib)) == 77 == len(set(C.table(lib)))
+    assert sum(1 for k in C.table(lib) if k.dtype == C.BF16 and k.cfg[6] == C.PLAIN) == 32   # the rows that also have a sign-bit form: 109 symbols
+    assert lib.gs_conv_igemm_table(len(rows), out) == -1 and lib.gs_conv_igemm_table(-1, out) == -1 and lib.gs_conv_igemm_table(0, None) == -1
+    for r in rows:
+        assert r[0] in (C.S1, C.S2, C.T2) and r[1] in (0, 1) and r[6] in (0, 1) and r[8] in range(4) and r[10] in (0, 1), r
+    cfg_out = (ctypes.c_int * 10)()   # the chooser's answer for the top-of-pyramid layer is a row of the table, spelled the same way
+    assert lib.gs_conv_igemm_config(C.S1, 8, 128, 1024, 32, 32, C.BF16, C.NORM_FWD, cfg_out) == 0 and cfg_out[9] == 1
+    assert C.Kernel(C.S1, C.BF16, tuple(cfg_out[:9])) in C.table(lib)
+
+
+def test_every_compiled_kernel_is_reached_by_a_case_under_the_cap(lib, plan):
+    reached = {}
+    for knobs, found in plan:
+        for k, shapes in found.items():
+            assert k not in reached
+            reached[k] = (knobs, shapes)
+    missing = [C.kernel_id(k) for k in C.table(lib) if k not in reached]
+    assert not missing, f"compiled, but no shape of the grid runs them under any knob setting: {missing}"
+    assert set(reached) == set(C.table(lib)), [C.kernel_id(k) for k in reached if k not in C.table(lib)]
+    total = 0
+    for k, (knobs, shapes) in reached.items():
+        assert 1 <= len(shapes) <= 2
+        for s in shapes:
+            assert s.want == k.cfg[6] and C.api_call(k.mode, s.want) is not None
+            assert C.macs(k.mode, s) <= C.MAX_MACS, (C.kernel_id(k), s, C.macs(k.mode, s))
+            total += C.macs(k.mode, s) * (2 if s.want == C.PLAIN else 1)
+        assert C.raggedness(k, shapes[-1]) >= 1, (C.kernel_id(k), shapes)   # every kernel has a case with a partial tile
+    print(f"{len(reached)} kernels, {sum(len(v[1]) for v in reached.values())} shapes, {total:.3g} reference multiply-adds; "
+          f"by knob setting: {[(knobs, len(found)) for knobs, found in plan]}")
+
+
+def test_default_process_finds_what_its_child_found(lib, plan):
+    """find_shapes is a function of the knobs alone: this process (default knobs) and the default child agree, shape for shape."""
+    import os
+    assert not any(k in os.environ for k in C.KNOBS), "the cases are searched under the default knobs"
+    assert C.find_shapes(lib) == {k: v for k, v in plan[0][1].items()}
+
+
+@pytest.mark.parametrize("mode,second", [(m, s) for m in (C.S1, C.S2, C.T2) for s in (False, True)])
+def test_reference_agrees_with_the_cpu_emulation(mode, second):
+    """conv_ref64 (torch's own conv / conv_transpose in float64) against tests/cpu_kernels.py (autograd of the oracle's convs, fp32): the three
+    maps and their data gradients at one small ragged shape each."""
+    from tests.cpu_kernels import CpuEmuKernels
+    E = CpuEmuKernels()
+    call = C.api_call(mode, C.PLAIN, second)
+    s = C.Shape(2, 3, 5, 32, 64, C.PLAIN)
+    a, wt, alpha = C.plain_inputs(call, s, seed=1)
+    n, h, w, ci, co = C.layer_args(call, *s[:5])
+    emu = {"gs_conv2d_fwd": lambda: E.conv2d_fwd(a, wt, 3, call.stride, alpha),
+           "gs_conv2d_bwd_data": lambda: E.conv2d_bwd_data(a, wt, (n, ci, h, w), 3, call.stride, alpha),
+           "gs_conv2d_transpose_s2_fwd": lambda: E.conv2d_transpose_fwd(a, wt, alpha),
+           "gs_conv2d_transpose_s2_bwd_data": lambda: E.conv2d_transpose_bwd_data(a, wt, alpha)}[call.name]()
+    ref = C.conv_ref64(call, a, wt, alpha)
+    assert tuple(ref.shape) == tuple(emu.shape) and ref.dtype == torch.float64
+    assert C.ratio(emu, ref) <= 1e-5   # fp32 accumulation of 9 * 32 resp. 9 * 64 terms
+    rounded = C.conv_ref64(call, a, wt, alpha, bf16=True)   # the bf16 reference is the same map on rounded operands: within 2 * 2^-9 per product
+    assert 1e-5 < C.ratio(rounded, ref) < 2e-2
+
+
+def test_a_dropped_stage_is_ten_tolerances_away(plan):
+    """One (tap, 32-channel chunk) of the weight zeroed in the reference moves the result by >= 10 x the GPU test's tolerance for the shape and
+    dtype (same measure: max error over max |ref|), for both entry points of every plain case of at most 5e7 multiply-adds."""
+    checked, worst = 0, {}
+    for knobs, found in plan:
+        for k, shapes in found.items():
+            for s in shapes:
+                if s.want != C.PLAIN or C.macs(k.mode, s) > 5e7:
+                    continue
+                for second in (False, True):
+                    call = C.api_call(k.mode, C.PLAIN, second)
+                    a, wt, alpha = C.plain_inputs(call, s, seed=3)
+                    bf16 = k.dtype == C.BF16
+                    ref = C.conv_ref64(call, a, wt, alpha, bf16=bf16)
+                    for drop in ((0, (s.ic - 1) // 32), (4, 0)):   # a corner tap's last chunk, the centre tap's first
+                        moved = C.ratio(C.conv_ref64(call, a, wt, alpha, bf16=bf16, drop=drop), ref)
+                        worst[k.dtype] = min(worst.get(k.dtype, moved), moved)
+                        assert moved >= 10 * C.TOLERANCE[k.dtype], (C.kernel_id(k), s, call.name, drop, moved)
+                        checked += 1
+    print(f"{checked} dropped stages, the least visible per dtype (fp32, bf16): {worst}")
+    assert checked >= 100 and set(worst) == {C.F32, C.BF16}

@@ -42,20 +42,23 @@ def close(got, ref, rel=1e-3, name=""):
     assert err <= rel, f"{name}: max err / max|ref| = {err:.3e} > {rel:.1e}"
 
 
-# (n, ci, co, h, w, ksize, stride) -- covers every MFMA tile configuration + the direct kernels
+# (n, ci, co, h, w, ksize, stride): the layer shapes of the small networks -- all three maps of a layer, the direct kernels included.  Every one
+# of these 3x3 cases is a few-block layer, so between them they launch only the few-block ("small", TG = 9) implicit-GEMM kernels and the
+# resident A = 1 one; which compiled kernel a shape runs is the chooser's answer (gs_conv_igemm_config), and tests/test_igemm_cover_gpu.py
+# holds EVERY compiled kernel to a float64 reference at shapes it finds through that chooser.
 CONV_CASES = [
-    (2, 32, 32, 8, 128, 3, 1),    # S1 A1 B2 TW64 TG9 (top-level shape class)
-    (2, 32, 32, 4, 32, 3, 1),     # S1 A1 B1 TW32
-    (1, 64, 64, 8, 64, 3, 1),     # S1 A2 B2 TW64
-    (2, 64, 64, 4, 32, 3, 1),     # S1 A2 B1 TW32
-    (4, 64, 64, 2, 16, 3, 1),     # S1 A2 B1 TW16 (tile taller than the image)
-    (1, 128, 128, 8, 32, 3, 1),   # S1 A4 B1 TW32
-    (4, 256, 256, 2, 16, 3, 1),   # S1 A4 B1 TW16, two oc tiles (the 2x16 stage)
+    (2, 32, 32, 8, 128, 3, 1),    # 32 -> 32 at width >= 64: the resident 32-channel tile (top-level shape class)
+    (2, 32, 32, 4, 32, 3, 1),
+    (1, 64, 64, 8, 64, 3, 1),
+    (2, 64, 64, 4, 32, 3, 1),
+    (4, 64, 64, 2, 16, 3, 1),     # 16-wide tile, taller than the image
+    (1, 128, 128, 8, 32, 3, 1),
+    (4, 256, 256, 2, 16, 3, 1),   # eight 32-channel tiles (the 2x16 stage)
     (2, 64, 32, 6, 40, 3, 1),     # ragged spatial tile edges, ci != co
-    (2, 32, 64, 8, 128, 3, 2),    # S2 A2 B1 TW32  (D downscale 32->64)
-    (2, 64, 128, 8, 64, 3, 2),    # S2 A4 B1 TW32
-    (4, 256, 256, 4, 32, 3, 2),   # S2 A4 TW16 (4x32 -> 2x16)
-    (2, 64, 32, 8, 64, 3, 2),     # S2 A1 (oc 32); its bwd-data is T2 with 64 outputs
+    (2, 32, 64, 8, 128, 3, 2),    # stride 2 (D downscale 32->64)
+    (2, 64, 128, 8, 64, 3, 2),
+    (4, 256, 256, 4, 32, 3, 2),   # 4x32 -> 2x16
+    (2, 64, 32, 8, 64, 3, 2),     # its bwd-data is the transposed kernel with 64 outputs
     (2, 32, 32, 12, 72, 3, 2),    # ragged stride-2
     (2, 32, 2, 8, 64, 1, 1),      # G colour block 32->2 (direct)
     (2, 2, 32, 8, 64, 1, 1),      # D colour block 2->32 (direct)
@@ -77,11 +80,12 @@ def test_conv2d_three_maps(K, E, case):
     close(K.conv2d_bwd_weight(dev(x), dev(gy), ks, st, alpha), E.conv2d_bwd_weight(x, gy, ks, st, alpha), name="bwd_weight")
 
 
+# (n, ci, co, h, w) -- see CONV_CASES: layer shapes, not a list of kernels (tests/test_igemm_cover_gpu.py has one case per compiled kernel)
 CONVT_CASES = [
-    (2, 64, 32, 8, 64),    # T2 A1 B2 TW64 (top level 64->32)
-    (2, 64, 32, 4, 32),    # T2 A1 B1 TW32
-    (1, 128, 64, 8, 32),   # T2 A2 B1 TW32
-    (4, 256, 256, 2, 16),  # T2 A2 B1 TW16, 4 oc tiles (2x16 -> 4x32)
+    (2, 64, 32, 8, 64),    # 64 -> 32 at width >= 64: the resident 32-channel tile (top level)
+    (2, 64, 32, 4, 32),
+    (1, 128, 64, 8, 32),
+    (4, 256, 256, 2, 16),  # 16-wide tile, eight 32-channel tiles (2x16 -> 4x32)
     (2, 32, 64, 5, 24),    # ragged, ci < co
 ]
 
@@ -844,6 +848,11 @@ def test_throwaway_streams(K):
 def test_conv_bias_act_norm_in_one_call(K, E, case, dtype):
     """gs_conv2d[_transpose_s2]_fwd_bias_act_norm: (z, y) = (act(conv + b), pixel_norm(z)) -- fused into the conv epilogue for the
     32- / 64-channel tiles (first, second, fifth and sixth case), conv + separate norm pass otherwise; with and without z."""
+    check_conv_bias_act_norm(K, E, case, dtype)
+
+
+def check_conv_bias_act_norm(K, E, case, dtype):
+    """The assertions of test_conv_bias_act_norm_in_one_call for one case (also run per fused-norm kernel by tests/test_igemm_cover_gpu.py)."""
     kind, n, ci, co, h, w = case
     x = rnd(n, ci, h, w, seed=1).to(dtype).float()
     wt = rnd(3, 3, ci, co, seed=2)
@@ -936,6 +945,12 @@ def test_data_gradient_continued_through_the_previous_pixel_norm(K, E, case, dty
     backward applied to the ORACLE-side data gradient (tests/cpu_kernels.py: torch-CPU autograd of oracle.torch_ref's conv on the same
     inputs -- nothing of the HIP path feeds the reference); second, the two separate HIP kernels.  In bf16 the separate path rounds the
     intermediate gradient to bf16, the fused one does not: compared at bf16 resolution of the tensor's scale; fp32 at 1e-5."""
+    check_data_gradient_through_pixel_norm(K, E, case, dtype, with_addend)
+
+
+def check_data_gradient_through_pixel_norm(K, E, case, dtype, with_addend):
+    """The assertions of test_data_gradient_continued_through_the_previous_pixel_norm for one case (also run per kernel with that epilogue by
+    tests/test_igemm_cover_gpu.py)."""
     kind, n, ci, co, h, w = case   # ci: channels of z / gx (the conv's input side), co: of gy
     gen = torch.Generator(device="cuda").manual_seed(11)
     CL = torch.channels_last
@@ -970,7 +985,6 @@ def test_data_gradient_continued_through_the_previous_pixel_norm(K, E, case, dty
         assert float((got.double() - want).pow(2).mean()) <= 1.05 * float((ref.double() - want).pow(2).mean()) + 1e-12
 
 
-
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("case", [("conv", 8, 32, 32, 128, 1024), ("conv", 8, 64, 64, 64, 512), ("convT", 8, 64, 32, 64, 512),   # fused at full size
                                   ("convT", 8, 128, 64, 32, 256), ("conv", 2, 32, 32, 8, 128), ("conv", 2, 8, 64, 8, 64), ("convT", 2, 16, 32, 8, 64),
@@ -980,6 +994,12 @@ def test_second_order_norm_gradients_in_the_forward_conv(K, E, case, dtype):
     node (w.r.t. g and w.r.t. z) from the conv's epilogue, against a float64 autograd evaluation of the definition on the ORACLE-side fp32
     conv output (tests/cpu_kernels.py: oracle.torch_ref's conv on the same inputs -- nothing of the HIP path feeds the reference) and against
     the two-kernel path (conv, then gs_pixel_norm_bwd_bwd_fused).  bf16: compared at bf16 resolution of each tensor's scale."""
+    check_second_order_norm_gradients(K, E, case, dtype)
+
+
+def check_second_order_norm_gradients(K, E, case, dtype):
+    """The assertions of test_second_order_norm_gradients_in_the_forward_conv for one case (also run per kernel with that epilogue by
+    tests/test_igemm_cover_gpu.py)."""
     kind, n, ci, co, h, w = case
     gen = torch.Generator(device="cuda").manual_seed(5)
     CL = torch.channels_last
@@ -1072,6 +1092,14 @@ def test_one_bit_leaky_relu_masks(K, case):
     """GS_ACT_WRITE_BITS / GS_ACT_LRELU_BITS: a bf16 leaky-relu conv result carries its sign bits behind it (written by the MFMA epilogue, or by
     gs_pack_act_bits after the direct kernels), and the masked launches that read them give bit-identical results to the ones that read the
     values.  An activation without the bits (a clone) takes the values path."""
+    check_one_bit_leaky_relu_masks(K, case)
+
+
+def check_one_bit_leaky_relu_masks(K, case, reader_channels=None, readers=("bwd_data", "bwd_data_s2", "fwd_mask")):
+    """The assertions of test_one_bit_leaky_relu_masks for one case.  reader_channels: the other channel count of the masked launches (default:
+    the case's own co, and 64); readers: which masked launches read z -- the three of that test, and "fwd_mask_s2", behind a stride-2 case the
+    stride-2 forward-on-cotangents conv whose output has z's shape (tests/test_igemm_cover_gpu.py: each bf16 kernel's sign-bit form, written and
+    read at that kernel's own shapes)."""
     from gansynth_amd import kernels
     n, ci, co, h, w, ks, st = case
     gen = torch.Generator(device="cuda").manual_seed(11)
@@ -1087,22 +1115,30 @@ def test_one_bit_leaky_relu_masks(K, case):
     zc = z.clone(memory_format=CL)
     assert not kernels._has_bits(zc)
     # z as the mask of a data gradient (the conv whose INPUT z was) and of a forward-on-cotangents conv (whose output has z's shape)
-    for c2 in (co, 64):
+    for c2 in reader_channels or (co, 64):
         w2 = torch.randn(3, 3, co, c2, device="cuda", generator=gen)
         gy = torch.randn(n, c2, z.shape[2], z.shape[3], device="cuda", generator=gen).bfloat16().contiguous(memory_format=CL)
-        a = K.conv2d_bwd_data(gy, w2, tuple(z.shape), 3, 1, 0.07, mask=z, mask_act=1)
-        b = K.conv2d_bwd_data(gy, w2, tuple(z.shape), 3, 1, 0.07, mask=zc, mask_act=1)
-        assert torch.equal(a, b), f"bwd_data mask, {c2} channels"
-        if z.shape[2] % 2 == 0:   # behind a stride-2 conv: the transposed-conv-shaped data gradient
+        if "bwd_data" in readers:
+            a = K.conv2d_bwd_data(gy, w2, tuple(z.shape), 3, 1, 0.07, mask=z, mask_act=1)
+            b = K.conv2d_bwd_data(gy, w2, tuple(z.shape), 3, 1, 0.07, mask=zc, mask_act=1)
+            assert torch.equal(a, b), f"bwd_data mask, {c2} channels"
+        if "bwd_data_s2" in readers and z.shape[2] % 2 == 0:   # behind a stride-2 conv: the transposed-conv-shaped data gradient
             gy2 = torch.randn(n, c2, z.shape[2] // 2, z.shape[3] // 2, device="cuda", generator=gen).bfloat16().contiguous(memory_format=CL)
             a = K.conv2d_bwd_data(gy2, w2, tuple(z.shape), 3, 2, 0.07, mask=z, mask_act=1)
             b = K.conv2d_bwd_data(gy2, w2, tuple(z.shape), 3, 2, 0.07, mask=zc, mask_act=1)
             assert torch.equal(a, b), f"stride-2 bwd_data mask, {c2} channels"
         w3 = torch.randn(3, 3, c2, co, device="cuda", generator=gen)
         xx = torch.randn(n, c2, z.shape[2], z.shape[3], device="cuda", generator=gen).bfloat16().contiguous(memory_format=CL)
-        a = K.conv2d_fwd_mask(xx, w3, 3, 1, 0.07, z, 1)
-        b = K.conv2d_fwd_mask(xx, w3, 3, 1, 0.07, zc, 1)
-        assert torch.equal(a, b), f"fwd mask, {c2} channels"
+        if "fwd_mask" in readers:
+            a = K.conv2d_fwd_mask(xx, w3, 3, 1, 0.07, z, 1)
+            b = K.conv2d_fwd_mask(xx, w3, 3, 1, 0.07, zc, 1)
+            assert torch.equal(a, b), f"fwd mask, {c2} channels"
+        if "fwd_mask_s2" in readers:
+            assert st == 2
+            xx = torch.randn(n, c2, h, w, device="cuda", generator=gen).bfloat16().contiguous(memory_format=CL)
+            a = K.conv2d_fwd_mask(xx, w3, 3, 2, 0.07, z, 1)
+            b = K.conv2d_fwd_mask(xx, w3, 3, 2, 0.07, zc, 1)
+            assert torch.equal(a, b), f"stride-2 fwd mask, {c2} channels"
 
 
 _CHUNK_CHILD = r"""
