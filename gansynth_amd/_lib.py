@@ -146,6 +146,9 @@ SIGNATURES = {
     "gs_softmax_xent": (I, [P, P, P, P, P, I, I, P]),
     "gs_momentum_workspace_bytes": (Z, [L]),
     "gs_momentum_tf_step": (I, [P, P, P, L, L, L, F, F, F, I, I, P, P, Z, P]),
+    "gs_summary_image_u8_workspace_bytes": (Z, [I, L, I]),
+    "gs_summary_image_u8": (I, [P, P, I, L, I, I, P, Z, P]),
+    "gs_summary_audio_s16": (I, [P, P, I, L, L, I, P]),
 }
 
 WGRAD_MAX_SOURCES = 4   # GS_WGRAD_MAX_SOURCES

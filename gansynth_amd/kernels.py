@@ -1331,6 +1331,33 @@ class HipKernels(object):
                                                 None if l2 is None else l2.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_momentum_tf_step")
         return l2
 
+    def summary_image_u8(self, x, count=4):
+        """tf.summary.image's 8-bit rule (include/gansynth_hip.h) on the first min(B, count) images of x: [B, H, W], or [B, 2, H, W]
+        channels-last (both planes from one pass).  Returns uint8 [n, C, H, W], contiguous."""
+        n = min(int(x.shape[0]), int(count))
+        x = _act(x[:n])
+        if x.dim() == 4:
+            _, c, h, w = x.shape
+        else:
+            (_, h, w), c = x.shape, 1
+        out = torch.empty((n, c, h, w), dtype=torch.uint8, device=x.device)
+        ws = _ws(self.lib.gs_summary_image_u8_workspace_bytes(n, h * w, c), x.device)
+        _lib.check(self.lib.gs_summary_image_u8(x.data_ptr(), out.data_ptr(), n, h * w, c, _dt(x), ws.data_ptr(), ws.numel(), _stream()),
+                   "gs_summary_image_u8")
+        return out
+
+    def summary_audio_s16(self, x, count=4):
+        """TF's FloatToInt16Sample on the first min(B, count) rows of x [B, L] (any row stride): int16 [n, L]."""
+        n = min(int(x.shape[0]), int(count))
+        x = x[:n]
+        length = int(x.shape[1])
+        if x.stride(1) != 1 or (n > 1 and x.stride(0) < length):
+            x = x.contiguous()
+        out = torch.empty((n, length), dtype=torch.int16, device=x.device)
+        _lib.check(self.lib.gs_summary_audio_s16(x.data_ptr(), out.data_ptr(), n, length, int(x.stride(0)) if n > 1 else length, _dt(x), _stream()),
+                   "gs_summary_audio_s16")
+        return out
+
     def account(self):
         """bench.py: `with K.account() as calls:` lists every kernel-layer call made inside as (method, argument dict, bytes read,
         bytes written) -- the algorithmic traffic of SURVEY.md 8(d): every tensor argument read once, every result written once

@@ -68,6 +68,8 @@ class GANSynth(Iterations, DataParallel, Capture):
         self._inflight = None                   # (params, [(bucket, work)]) all-reduces launched during the eager backward's tail
         self._comm = None                       # comm.RcclComm: the gradient all-reduce on the backward's own stream (HIP + nccl only)
         self._peeked = None                     # a batch fetched ahead of the first step (train: eager build / restore)
+        self._keep_waveforms = False            # train() with summaries on: _real_batch keeps the waveforms of the batch it converted
+        self._real_waveforms = None
         self._run_reduced = False               # the last _run replayed a graph that contains its own gradient all-reduce
         self._captured_reduce = False
         self._graph_allreduce = _GRAPH_ALLREDUCE   # cleared for the life of the model if a capture with the collective inside fails
@@ -263,6 +265,8 @@ class GANSynth(Iterations, DataParallel, Capture):
             images = spectral_ops.convert_to_images(data, **self.spectral_params, dtype=self.dtype)
         else:
             images = data
+        if self._keep_waveforms:   # (the audio summary of the real side: models.py:141)
+            self._real_waveforms = data if data.dim() == 2 else None
         return images.to(self.dtype), labels.to(self.dtype)
 
     # --------------------------------------------------------------------------- losses
@@ -640,21 +644,46 @@ class GANSynth(Iterations, DataParallel, Capture):
         """models.py:110 -- `train(model_dir, config, total_steps, save_checkpoint_steps, save_summary_steps, log_tensor_steps)`, the
         reference's own signature and argument order, so that gan_synth_main.py:102-109 calls it unchanged.  `config` is the reference's
         tf.ConfigProto (session / GPU-allocator options, gan_synth_main.py:91-98): nothing of it applies to this runtime, it is accepted
-        and ignored.  `save_summary_steps` drives the reference's SummarySaverHook (TensorBoard images / audio, models.py:131-136): out of
-        this path's scope, accepted and ignored.  `log`, `save` are additions (keyword only in practice).
-        models.py:110-194 without the TF summary hooks: resume from the latest checkpoint of `model_dir` (CheckpointSaverHook /
-        MonitoredSession semantics), alternate D and G runs until global_step reaches total_steps (StopAtStepHook) or the input
-        runs dry (OutOfRangeError, :193), log the two losses every `log_tensor_steps` (LoggingTensorHook), checkpoint every
-        `save_checkpoint_steps` and at the end.  Data parallel: EVERY rank passes `model_dir` and restores from the same file
-        (weights, Adam slots, optimizer steps, global_step -- so that all ranks resume in the same growing regime); only rank 0
-        writes (`save` defaults to rank == 0)."""
-        from . import checkpoint
+        and ignored.  `log`, `save` are additions (keyword only in practice).
+        models.py:110-194: resume from the latest checkpoint of `model_dir` (CheckpointSaverHook / MonitoredSession semantics),
+        alternate D and G runs until global_step reaches total_steps (StopAtStepHook) or the input runs dry (OutOfRangeError, :193),
+        log the two losses every `log_tensor_steps` (LoggingTensorHook), checkpoint every `save_checkpoint_steps` and at the end.
+        `save_summary_steps` (honoured when truthy and `model_dir` is given; the default None keeps summaries off): the three
+        SummarySaverHooks of models.py:131-174 -- whenever global_step % save_summary_steps == 0 after a step, one Event record each
+        for audio (real_waveforms, fake_waveforms), images (real / fake magnitude_spectrograms and instantaneous_frequencies, four
+        items each) and scalars (generator_loss, discriminator_loss), in that order, into the events file of `model_dir`
+        (summary.SummaryWriter; a record that would hold no value is not written).  The real side is the batch the discriminator run
+        just used; real_waveforms only when the input gave waveforms, fake_waveforms only with `spectral_params`.  Two differences from
+        the reference: TF's hook also fires on the first run of a session, this one follows the modulus rule of the logs and the
+        checkpoints alone; and the reference fetches the fake side inside the training run, while this tree summarises AFTER the update
+        -- a no-grad generator pass over that iteration's generator-run latents and labels, eagerly between two replays of the captured
+        iteration, drawing no random number and leaving the training trajectory bit for bit as it is without summaries.  The file is
+        flushed at every checkpoint and at the end.
+        Data parallel: EVERY rank passes `model_dir` and restores from the same file (weights, Adam slots, optimizer steps, global_step
+        -- so that all ranks resume in the same growing regime); only rank 0 saves (`save` defaults to rank == 0) and summarises, and
+        every rank joins the pending update at a summary step as at a checkpoint."""
         if isinstance(model_dir, (int, float)) and not isinstance(model_dir, bool) and total_steps is None:
             model_dir, total_steps = None, model_dir   # (rounds 1-5 of this tree: train(total_steps, ...) with the count first)
         if total_steps is None:
             raise TypeError("train(): total_steps is required (models.py:110)")
-        del config, save_summary_steps
+        del config
         save = (self.rank == 0) if save is None else bool(save)
+        summarize = bool(save_summary_steps) and model_dir is not None
+        self._keep_waveforms, self._real_waveforms = summarize, None
+        writer = None
+        if summarize and self.rank == 0:
+            from . import summary
+            writer = summary.SummaryWriter(model_dir)
+        try:
+            self._train_loop(model_dir, total_steps, save_checkpoint_steps, save_summary_steps if summarize else None, log_tensor_steps,
+                             log, save, writer)
+        finally:
+            self._keep_waveforms, self._real_waveforms = False, None
+            if writer is not None:
+                writer.close()
+
+    def _train_loop(self, model_dir, total_steps, save_checkpoint_steps, save_summary_steps, log_tensor_steps, log, save, writer):
+        from . import checkpoint
         have = True
         if model_dir is not None and self.g_params is None:
             # the variables exist from step 0 in the reference's graph: build them from the first batch's shapes and restore BEFORE the
@@ -684,6 +713,10 @@ class GANSynth(Iterations, DataParallel, Capture):
             if log is not None and self.global_step % log_tensor_steps == 0:
                 log(f"global_step = {self.global_step}, generator_loss = {float(g_loss):.6f}, "
                     f"discriminator_loss = {float(d_loss):.6f}")
+            if save_summary_steps and self.global_step % save_summary_steps == 0:
+                self._join_updates()   # (every rank, as for the checkpoint below: it may be a collective)
+                if writer is not None:
+                    self._summarize(writer, inputs, d_loss, g_loss)
             if model_dir is not None and save_checkpoint_steps and self.global_step % save_checkpoint_steps == 0:
                 # (global_step is the same on every rank.)  The pending generator update may still need its all-reduce: EVERY rank
                 # joins here, so that the rank-local save below finds nothing left to communicate -- a collective issued by rank 0
@@ -692,10 +725,31 @@ class GANSynth(Iterations, DataParallel, Capture):
                 if save:
                     last_saved = self.global_step
                     checkpoint.save(self, model_dir)
+                if writer is not None:
+                    writer.flush()
         if self.g_params is not None:
             self._join_updates()   # (every rank: the last generator update, and the final save must not communicate either)
         if model_dir is not None and save and self.g_params is not None and last_saved != self.global_step:
             checkpoint.save(self, model_dir)
+        if writer is not None:
+            writer.flush()
+
+    def _summarize(self, writer, inputs, d_loss, g_loss):
+        """One summary step (see train): the updates are joined; `inputs` are the iteration's own (_next_inputs)."""
+        real_images, _, _, g_latents, g_labels = inputs
+        step = self.global_step
+        with torch.no_grad():
+            fake_images = self.generator(g_latents, g_labels)
+        audio = {}
+        if self._real_waveforms is not None:
+            audio["real_waveforms"] = self._real_waveforms
+        if self.spectral_params is not None:
+            audio["fake_waveforms"] = spectral_ops.convert_images_to_waveform(fake_images, **self.spectral_params)
+        if audio:
+            writer.audio(step, audio, self.spectral_params["sample_rate"] if self.spectral_params is not None else 16000)
+        writer.images(step, {("real_magnitude_spectrograms", "real_instantaneous_frequencies"): real_images,
+                             ("fake_magnitude_spectrograms", "fake_instantaneous_frequencies"): fake_images})
+        writer.scalars(step, dict(generator_loss=float(g_loss), discriminator_loss=float(d_loss)))
 
     def generate(self, *args, **kwargs):
         """Two forms.
@@ -911,18 +965,34 @@ class PitchClassifier(object):
 
     # --------------------------------------------------------------------------------------------------- training
     def train(self, model_dir, config, total_steps, save_checkpoint_steps, save_summary_steps, log_tensor_steps, log=print):
-        """models.py:306-386 with the reference's signature and argument order.  `config` (tf.ConfigProto) and `save_summary_steps` (the
-        TensorBoard hooks) are accepted and ignored, as GANSynth.train does.  Resumes from the latest checkpoint of `model_dir`, steps
-        until global_step reaches `total_steps` or the input runs dry, logs global_step, loss (cross-entropy + L2 term, at the
-        pre-update weights) and accuracy (tf.metrics.accuracy: cumulative correct / total since this call began) every
-        `log_tensor_steps`, saves every `save_checkpoint_steps` and at the end."""
-        del config, save_summary_steps
-        hp, net = self.hyper_params, self.network
+        """models.py:306-386 with the reference's signature and argument order.  `config` (tf.ConfigProto) is accepted and ignored, as
+        GANSynth.train does.  Resumes from the latest checkpoint of `model_dir`, steps until global_step reaches `total_steps` or the
+        input runs dry, logs global_step, loss (cross-entropy + L2 term, at the pre-update weights) and accuracy (tf.metrics.accuracy:
+        cumulative correct / total since this call began) every `log_tensor_steps`, saves every `save_checkpoint_steps` and at the end.
+        `save_summary_steps` (when truthy and `model_dir` is given): the SummarySaverHooks of models.py:327-367 -- whenever
+        global_step % save_summary_steps == 0 after a step, audio `waveforms` (when the input gave waveforms), images
+        `magnitude_spectrograms` and `instantaneous_frequencies` and scalars `loss` and `accuracy` (the log line's values) of the step's
+        own batch, into the events file of `model_dir`; by the modulus rule alone (TF's hook also fires on the first run of a session),
+        flushed at every checkpoint and at the end."""
+        del config
+        net = self.network
         if self.dtype != torch.float32:
             raise TypeError("PitchClassifier.train: training runs in fp32 (bf16 training is not implemented)")
         net.train_state()
         if model_dir is not None:
             self.restored_from = self.restore(model_dir)
+        writer = None
+        if save_summary_steps and model_dir is not None:
+            from . import summary
+            writer = summary.SummaryWriter(model_dir)
+        try:
+            return self._train_loop(model_dir, total_steps, save_checkpoint_steps, save_summary_steps, log_tensor_steps, log, writer)
+        finally:
+            if writer is not None:
+                writer.close()
+
+    def _train_loop(self, model_dir, total_steps, save_checkpoint_steps, save_summary_steps, log_tensor_steps, log, writer):
+        hp, net = self.hyper_params, self.network
         correct, total, last_saved = None, 0, None
         while self.global_step < total_steps:
             try:
@@ -939,11 +1009,21 @@ class PitchClassifier(object):
             if log is not None and log_tensor_steps and self.global_step % log_tensor_steps == 0:
                 log(f"global_step = {self.global_step}, loss = {float(loss) + float(hp.weight_decay) * float(l2):.6f}, "
                     f"accuracy = {int(correct) / max(total, 1):.6f}")
+            if writer is not None and self.global_step % save_summary_steps == 0:
+                step = self.global_step
+                if data.dim() == 2:
+                    writer.audio(step, dict(waveforms=data), self.spectral_params["sample_rate"])
+                writer.images(step, {("magnitude_spectrograms", "instantaneous_frequencies"): images})
+                writer.scalars(step, dict(loss=float(loss) + float(hp.weight_decay) * float(l2), accuracy=int(correct) / max(total, 1)))
             if model_dir is not None and save_checkpoint_steps and self.global_step % save_checkpoint_steps == 0:
                 last_saved = self.global_step
                 self.save(model_dir)
+                if writer is not None:
+                    writer.flush()
         if model_dir is not None and last_saved != self.global_step:
             self.save(model_dir)
+        if writer is not None:
+            writer.flush()
         return dict(global_step=self.global_step, accuracy=(int(correct) / max(total, 1)) if total else None)
 
     def evaluate(self, model_dir=None, config=None):

@@ -543,6 +543,23 @@ size_t gs_momentum_workspace_bytes(int64_t n);
 int gs_momentum_tf_step(float* p, float* g, float* accum, int64_t n, int64_t decay_lo, int64_t decay_hi, float weight_decay, float lr,
                         float momentum, int nesterov, int zero_grad, float* l2, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- TensorBoard summaries (models.py:131-161, :327-354: tf.summary.image / tf.summary.audio with max_outputs = 4) -------------------
+ * What a summary step sends to the host is quantised on the device: 8-bit image planes and 16-bit PCM, not activations.
+ *
+ * summary_image_u8: tf.summary.image's rule for float input, per image and per channel plane.  x: [n][p][c] (p = h*w pixels, c = 1 or 2
+ * interleaved channels -- the channels-last [B,2,T,F] images give both planes in one pass), out: [n][c][p] uint8.  Of a plane, lo / hi
+ * are the min / max over its FINITE values; lo < 0: m = max(|lo|, |hi|), scale = m < 1e-6 ? 0 : 127 / m, offset = 128; else
+ * scale = hi < 1e-6 ? 0 : 255 / hi, offset = 0.  A finite v becomes (uint8) trunc(fl(fl(v * scale) + offset)), a non-finite v 255.
+ * fp32 throughout, the divide correctly rounded, the multiply and the add rounded separately (no FMA); bf16 widens exactly.
+ * Two launches, no atomics (ws: per-slab (min, max) pairs, sized by the query; 0 for a shape the entry point refuses).
+ *
+ * summary_audio_s16: TF's FloatToInt16Sample.  x: [n] rows of l samples, `row_stride` elements apart; out: [n][l] int16,
+ * s = clamp(roundf(x * 32768), -32768, 32767), roundf rounding halves away from zero; NaN -> 0 (TF leaves it undefined).
+ * GS_ERR_ARG without a launch: c outside {1, 2}, n <= 0, a workspace that is too small. */
+size_t gs_summary_image_u8_workspace_bytes(int n, int64_t p, int c);
+int gs_summary_image_u8(const void* x, uint8_t* out, int n, int64_t p, int c, int dtype, void* ws, size_t ws_bytes, void* stream);
+int gs_summary_audio_s16(const void* x, int16_t* out, int n, int64_t l, int64_t row_stride, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@ parser.add_argument("--synthetic", action="store_true", help="generated notes in
 parser.add_argument("--dtype", choices=["f32", "bf16"], default="f32", help="activation storage of --evaluate (training is fp32)")
 parser.add_argument("--save_checkpoint_steps", type=int, default=1000)
 parser.add_argument("--log_tensor_steps", type=int, default=100)
+parser.add_argument("--save_summary_steps", type=int, default=100, help="TensorBoard summaries into --model_dir every this many steps (0: off)")
 parser.add_argument("--num_evaluate_batches", type=int, default=None, help="stop --evaluate --synthetic after this many batches (synthetic input never ends)")
 
 
@@ -70,7 +71,7 @@ def main(args):
             config=None,                               # (the reference's tf.ConfigProto: nothing of it applies here)
             total_steps=args.total_steps,
             save_checkpoint_steps=args.save_checkpoint_steps,
-            save_summary_steps=100,
+            save_summary_steps=args.save_summary_steps,
             log_tensor_steps=args.log_tensor_steps)
         print(f"stopped at global_step = {classifier.global_step}")
 
