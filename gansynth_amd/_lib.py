@@ -18,6 +18,16 @@ CONV_FWD, CONV_BWD_DATA, CONV_BWD_WEIGHT = 0, 1, 2
 
 P, I, F, L, Z = c_void_p, c_int, c_float, c_int64, c_size_t
 
+
+class GsConv(ctypes.Structure):
+    """include/gansynth_hip.h: one conv / transposed-conv LAYER in its own forward labelling, whichever of its maps is asked for."""
+    _fields_ = [("n", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("ci", ctypes.c_int32), ("co", ctypes.c_int32),
+                ("ksize", ctypes.c_int32), ("stride", ctypes.c_int32), ("transposed", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("w_prepared", ctypes.c_int32), ("alpha", c_float), ("ws", c_void_p), ("ws_bytes", c_size_t)]
+
+
+C = POINTER(GsConv)
+
 # name -> (restype, argtypes); every symbol include/gansynth_hip.h declares
 SIGNATURES = {
     "gs_last_error": (c_char_p, []),
@@ -37,39 +47,23 @@ SIGNATURES = {
     "gs_allreduce_sum_f32": (I, [P, P, ctypes.c_int64, P]),
     "gs_comm_set_marker_us": (I, [P, ctypes.c_double]),
     "gs_broadcast_f32": (I, [P, P, ctypes.c_int64, I, P]),
-    "gs_conv2d_workspace_bytes": (Z, [I, I, I, I, I, I, I, I, I]),
-    "gs_conv2d_fwd": (I, [P, P, P, I, I, I, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_conv2d_fwd_bias_act": (I, [P, P, P, P, I, I, I, I, I, I, I, F, I, I, I, P, Z, P]),
-    "gs_conv2d_bwd_data": (I, [P, P, P, I, I, I, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_conv2d_fwd_bias_act_norm": (I, [P, P, P, P, P, I, I, I, I, I, I, I, F, I, F, I, I, P, Z, P]),
-    "gs_conv2d_transpose_s2_fwd_bias_act_norm": (I, [P, P, P, P, P, I, I, I, I, I, F, I, F, I, I, P, Z, P]),
-    "gs_conv2d_fwd_mask": (I, [P, P, P, I, P, I, I, I, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_conv2d_bwd_data_mask": (I, [P, P, P, I, P, I, I, I, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_conv2d_bwd_weight": (I, [P, P, P, I, I, I, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_conv2d_bwd_weight_bias": (I, [P, P, P, P, I, I, I, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_conv2d_bwd_weight_bias_partial": (I, [P, P, P, P, I, I, I, I, I, I, I, F, I, I, P, Z, P, P]),
-    "gs_conv2d_transpose_s2_bwd_weight_partial": (I, [P, P, P, I, I, I, I, I, F, I, I, P, Z, P, P]),
-    "gs_wgrad_reduce_batch": (I, [P, I, P]),
-    "gs_conv2d_bwd_weight_bias_multi": (I, [P, P, P, I, ctypes.c_uint, P, P, I, I, I, I, I, I, I, F, I, I, P, Z, P, P]),
-    "gs_conv2d_transpose_s2_bwd_weight_multi": (I, [P, P, P, I, P, I, I, I, I, I, F, I, I, P, Z, P, P]),
+    # conv entry points: C = POINTER(GsConv), the layer (include/gansynth_hip.h)
+    "gs_conv_workspace_bytes": (Z, [C, I]),
+    "gs_conv_fwd": (I, [C, P, P, P, I, P, P, F, P]),
+    "gs_conv_fwd_mask": (I, [C, P, P, P, I, P, P]),
+    "gs_conv_bwd_data": (I, [C, P, P, P, I, P, P]),
+    "gs_conv_bwd_data_pnbwd": (I, [C, P, P, P, P, I, F, P, P]),
+    "gs_conv_bwd_data_pnbwd_is_fused": (I, [C]),
+    "gs_conv_fwd_pnbwdbwd": (I, [C, P, P, P, P, I, F, P, P, P]),
+    "gs_conv_fwd_pnbwdbwd_is_fused": (I, [C]),
+    "gs_conv_bwd_weight": (I, [C, P, P, P, P, I, P]),
     "gs_conv_wgrad_jobs_workspace_bytes": (Z, [P, I]),
     "gs_conv_wgrad_jobs": (I, [P, I, P, Z, P]),
     "gs_wgrad_cu_cap": (I, [I]),
-    "gs_conv2d_transpose_s2_workspace_bytes": (Z, [I, I, I, I, I, I, I]),
-    "gs_conv2d_transpose_s2_fwd": (I, [P, P, P, I, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_conv2d_transpose_s2_fwd_bias_act": (I, [P, P, P, P, I, I, I, I, I, F, I, I, I, P, Z, P]),
-    "gs_conv2d_transpose_s2_bwd_data": (I, [P, P, P, I, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_conv2d_bwd_data_pnbwd_is_fused": (I, [I, I, I, I, I, I, I, I, I]),
-    "gs_conv2d_fwd_pnbwdbwd_is_fused": (I, [I, I, I, I, I, I, I, I, I]),
     "gs_conv_igemm_config": (I, [I, I, I, I, I, I, I, I, POINTER(c_int)]),
     "gs_conv_igemm_table": (I, [I, POINTER(c_int)]),
     "gs_units_bias_act_to_nhwc": (I, [P, P, P, P, I, I, I, I, I, P]),
     "gs_nhwc_act_bwd_to_units": (I, [P, P, P, I, I, I, I, I, P]),
-    "gs_conv2d_fwd_pnbwdbwd": (I, [P, P, P, P, I, F, P, P, I, I, I, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_conv2d_transpose_s2_fwd_pnbwdbwd": (I, [P, P, P, P, I, F, P, P, I, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_conv2d_bwd_data_pnbwd": (I, [P, P, P, P, I, F, P, I, I, I, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_conv2d_transpose_s2_bwd_data_pnbwd": (I, [P, P, P, P, I, F, P, I, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_conv2d_transpose_s2_bwd_weight": (I, [P, P, P, I, I, I, I, I, F, I, I, P, Z, P]),
     "gs_dense_fwd_workspace_bytes": (Z, [I, I, I]),
     "gs_dense_fwd": (I, [P, P, P, I, I, I, F, I, P, Z, P]),
     "gs_dense_fwd_bias_act": (I, [P, P, P, P, I, I, I, F, I, I, P, Z, P]),
@@ -92,12 +86,10 @@ SIGNATURES = {
     "gs_channel_fold_batch_workspace_bytes": (Z, [P, I]),
     "gs_channel_fold_batch": (I, [P, I, P, Z, P]),
     "gs_pixel_norm_fwd": (I, [P, P, L, I, F, I, P]),
-    "gs_pixel_norm_bwd": (I, [P, P, P, L, I, F, I, P]),
     "gs_pixel_norm_bwd_fused": (I, [P, P, P, P, L, I, F, I, I, I, P]),
     "gs_pixel_norm_bwd_bias_workspace_bytes": (Z, [L, I, I]),
     "gs_pixel_norm_bwd_fused_bias": (I, [P, P, P, P, P, L, I, F, I, I, I, I, P, Z, P]),
     "gs_pixel_norm_bwd_bwd_fused": (I, [P, P, P, P, P, L, I, F, I, I, P]),
-    "gs_pixel_norm_bwd_bwd": (I, [P, P, P, P, L, I, F, I, P]),
     "gs_upscale2d": (I, [P, P, I, I, I, I, I, I, F, I, P]),
     "gs_blocksum2d": (I, [P, P, I, I, I, I, I, I, F, I, P]),
     "gs_batch_stddev_fwd": (I, [P, P, I, I, I, F, I, P]),
@@ -152,13 +144,6 @@ SIGNATURES = {
 }
 
 WGRAD_MAX_SOURCES = 4   # GS_WGRAD_MAX_SOURCES
-
-
-class GsWgradReduce(ctypes.Structure):
-    """include/gansynth_hip.h: one pending slice reduction of a weight gradient."""
-    _fields_ = [("partials", c_void_p), ("gw", c_void_p), ("gb", c_void_p), ("nslices", ctypes.c_int32), ("taps", ctypes.c_int32),
-                ("ic", ctypes.c_int32), ("oc", ctypes.c_int32), ("alpha", c_float), ("transpose", ctypes.c_int32),
-                ("accumulate", ctypes.c_int32), ("ic_ld", ctypes.c_int32)]
 
 
 SUM_PARTIALS = 2   # GS_SUM_PARTIALS

@@ -1,5 +1,5 @@
 // Training the pitch classifier (reference models.py:253-299): the backward of the operators of classifier.hip, softmax cross-entropy
-// and TF's momentum update.  The 3x3 convs and the logits layer go through gs_conv2d_bwd_data / gs_conv2d_bwd_weight_bias /
+// and TF's momentum update.  The 3x3 convs and the logits layer go through gs_conv_bwd_data / gs_conv_bwd_weight /
 // gs_dense_bwd_* on the standardised weights with alpha = 1.  Every reduction runs in a fixed order with no float atomics: two runs
 // on the same input are bit-identical, as the forward is.
 #include <math.h>

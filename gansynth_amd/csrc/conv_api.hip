@@ -137,7 +137,7 @@ template <int ACT> __device__ inline float thin_act(float v) {
 // A thread keeps its Wide::N output channels (weights + bias in registers) and strides over pixels.
 template <typename T, int IC, int ACT, bool MASKED>
 // `mask` (MASKED, y's shape): y *= mask_act'(.) through that activation output -- the second-order pass of the R1 penalty runs the colour
-// block forward on a cotangent and the next node's first step is that multiplication (gs_conv2d_fwd_mask)
+// block forward on a cotangent and the next node's first step is that multiplication (gs_conv_fwd_mask)
 __global__ __launch_bounds__(256) void thin_expand_kernel(const T* __restrict__ x, const float* __restrict__ wp, const float* __restrict__ bias,
                                                           T* __restrict__ y, long P, int OC, float alpha,
                                                           const T* __restrict__ mask = nullptr, int mask_act = 0, unsigned* __restrict__ bits = nullptr) {
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256) void thin_expand_kernel(const T* __restrict__ 
 }
 
 // The same map as a DATA GRADIENT continued through the pixel norm and activation of the block that produced the conv's input
-// (gs_conv2d_bwd_data_pnbwd for the colour block, networks.py:98-104): g[p][oc] = alpha * sum_ic x[p][ic] wp[oc][ic] is the gradient
+// (gs_conv_bwd_data_pnbwd for the colour block, networks.py:98-104): g[p][oc] = alpha * sum_ic x[p][ic] wp[oc][ic] is the gradient
 // w.r.t. pixel_norm(z); out = (r (g - z r^2 mean_c(z g)) + addend) * act'(z), r = rsqrt(mean_c z^2 + eps).  The OC / Wide::N lanes of
 // a pixel are neighbours in the wave: two xor-shuffle folds give the pixel's sums.  One pass instead of thin_expand + a 4-tensor norm pass.
 template <typename T, int IC>
@@ -847,156 +847,161 @@ static int run_wgrad_direct(int mode, int ks, const void* x, const void* gy, flo
     return 0;
 }
 
-static int check_conv_args(int n, int h, int w, int ci, int co, int ksize, int stride, int dtype) {
-    GS_CHECK_ARG(n > 0 && h > 0 && w > 0 && ci > 0 && co > 0, "conv2d: non-positive dim");
-    GS_CHECK_ARG(ksize == 1 || ksize == 3, "conv2d: ksize %d not in {1,3}", ksize);
-    GS_CHECK_ARG(stride == 1 || (stride == 2 && ksize == 3), "conv2d: stride %d unsupported with ksize %d", stride, ksize);
-    GS_CHECK_ARG(stride == 1 || (h % 2 == 0 && w % 2 == 0), "conv2d: stride 2 needs even h,w (got %d,%d)", h, w);
-    GS_CHECK_ARG(dtype == GS_F32 || dtype == GS_BF16, "conv2d: bad dtype %d", dtype);
+static int check_conv(const GsConv* c) {
+    GS_CHECK_ARG(c != nullptr, "conv: no layer descriptor");
+    GS_CHECK_ARG(c->n > 0 && c->h > 0 && c->w > 0 && c->ci > 0 && c->co > 0, "conv: non-positive dim");
+    GS_CHECK_ARG(!c->transposed || (c->ksize == 3 && c->stride == 2), "conv: a transposed layer is 3x3 stride 2 (got %dx%d stride %d)", c->ksize, c->ksize, c->stride);
+    GS_CHECK_ARG(c->ksize == 1 || c->ksize == 3, "conv: ksize %d not in {1,3}", c->ksize);
+    GS_CHECK_ARG(c->stride == 1 || (c->stride == 2 && c->ksize == 3), "conv: stride %d unsupported with ksize %d", c->stride, c->ksize);
+    GS_CHECK_ARG(c->stride == 1 || c->transposed || (c->h % 2 == 0 && c->w % 2 == 0), "conv: stride 2 needs even h,w (got %d,%d)", c->h, c->w);
+    GS_CHECK_ARG(c->dtype == GS_F32 || c->dtype == GS_BF16, "conv: bad dtype %d", c->dtype);
     return 0;
+}
+
+// ---- THE relabelling: a layer and one of its three maps -> the roles the kernels know.  A transposed conv is the stride-2 conv with its two
+// sides swapped, so every map of either kind is one of MODE_S1 / MODE_S2 / MODE_T2 over (ICk -> OCk) channels, reading Hi x Wi and walking
+// the base grid Hb x Wb (the smaller side of a strided map).  Every entry point below, plan_jobs and the *_is_fused queries take their
+// geometry from here and nowhere else (a valid layer is assumed: check_conv first).
+struct ConvRole {
+    int mode;         // MODE_*
+    int variant;      // weight_prep_kernel's (fwd / bwd_data)
+    int ICk, OCk;     // channels the kernel contracts / produces; bwd_weight: its input side / gradient side
+    int Hi, Wi;       // what the kernel reads (bwd_weight: its input side)
+    int Hb, Wb;       // base grid
+    int Ho, Wo;       // what the kernel writes: the base grid, twice it in MODE_T2
+    int swapped;      // bwd_weight of a transposed layer: x and gy change places and gw is stored transposed
+};
+static ConvRole conv_role(const GsConv& c, int map) {
+    const int s = c.stride;
+    ConvRole r;
+    memset(&r, 0, sizeof(r));
+    const bool up = c.transposed != 0;
+    if (map == GS_CONV_BWD_DATA) {
+        r.ICk = c.co; r.OCk = c.ci;
+        if (up) { r.mode = MODE_S2; r.variant = 2; r.Hi = 2 * c.h; r.Wi = 2 * c.w; r.Hb = c.h; r.Wb = c.w; }
+        else if (s == 2) { r.mode = MODE_T2; r.variant = 2; r.Hi = r.Hb = c.h / 2; r.Wi = r.Wb = c.w / 2; }
+        else { r.mode = MODE_S1; r.variant = 1; r.Hi = r.Hb = c.h; r.Wi = r.Wb = c.w; }
+    } else if (map == GS_CONV_BWD_WEIGHT && up) {   // the stride-2 conv from the big side to the small one
+        r.mode = MODE_S2; r.swapped = 1;
+        r.ICk = c.co; r.OCk = c.ci; r.Hi = 2 * c.h; r.Wi = 2 * c.w; r.Hb = c.h; r.Wb = c.w;
+    } else {                                         // fwd, and the plain conv's bwd_weight
+        r.mode = up ? MODE_T2 : (s == 2 ? MODE_S2 : MODE_S1);
+        r.ICk = c.ci; r.OCk = c.co; r.Hi = c.h; r.Wi = c.w;
+        r.Hb = up ? c.h : c.h / s; r.Wb = up ? c.w : c.w / s;
+    }
+    const int f = r.mode == MODE_T2 ? 2 : 1;
+    r.Ho = f * r.Hb; r.Wo = f * r.Wb;
+    return r;
 }
 
 }  // namespace gs
 
 using namespace gs;
 
-extern "C" size_t gs_conv2d_workspace_bytes(int which, int n, int h, int w, int ci, int co, int ksize, int stride, int dtype) {
-    const int hb = h / stride, wb = w / stride;
-    if (which == GS_CONV_BWD_WEIGHT) {
-        const size_t cs = align256(gs_channel_sum_workspace_bytes((int64_t)n * hb * wb, co));  // bias-gradient fallback of gs_conv2d_bwd_weight_bias
-        size_t wg;
-        if (ksize == 3 && wgrad_mfma_supported(ci, co, dtype)) wg = wgrad_mfma_bytes(stride == 2 ? MODE_S2 : MODE_S1, dtype, n, hb, wb, ci, co);
-        else wg = wgrad_direct_bytes(ksize, n, hb, wb, ci, co);
-        return wg > cs ? wg : cs;
-    }
-    return align256((size_t)ksize * ksize * ci * co * 4);
+extern "C" size_t gs_channel_sum_workspace_bytes(int64_t p, int c);
+extern "C" int gs_channel_sum(const void* g, float* out, int64_t p, int c, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream);
+extern "C" int gs_bias_act_fwd(const void* x, const float* bias, void* y, int64_t p, int c, int act, int dtype, void* stream);   // the epilogue of the shapes without the MFMA kernel
+extern "C" int gs_act_bwd(const void* g, const void* y, void* gx, int64_t numel, int act, int dtype, void* stream);
+
+extern "C" size_t gs_conv_workspace_bytes(const GsConv* c, int which) {
+    if (check_conv(c)) return 0;
+    if (which != GS_CONV_BWD_WEIGHT) return align256((size_t)c->ksize * c->ksize * c->ci * c->co * 4);   // the re-laid weight
+    const ConvRole r = conv_role(*c, GS_CONV_BWD_WEIGHT);
+    const size_t wg = c->ksize == 3 && wgrad_mfma_supported(r.ICk, r.OCk, c->dtype) ? wgrad_mfma_bytes(r.mode, c->dtype, c->n, r.Hb, r.Wb, r.ICk, r.OCk)
+                                                                                      : wgrad_direct_bytes(c->ksize, c->n, r.Hb, r.Wb, r.ICk, r.OCk);
+    if (c->transposed) return wg;   // (no bias)
+    const size_t cs = align256(gs_channel_sum_workspace_bytes((int64_t)c->n * r.Hb * r.Wb, c->co));   // bias-gradient fallback of gs_conv_bwd_weight
+    return wg > cs ? wg : cs;
 }
 
-// the bias/activation epilogue for the shapes that do not go through the MFMA kernel
-extern "C" int gs_bias_act_fwd(const void* x, const float* bias, void* y, int64_t p, int c, int act, int dtype, void* stream);
-
-// y2 (optional): y2 = pixel_norm(act(conv + bias)) as well -- fused into the conv epilogue where the tile owns all channels of a
-// pixel, a separate pass otherwise; y (the activation itself) may then be NULL
 static int mask_fuse_min_channels() {
     static const int v = [] { const char* e = getenv("GS_MASK_FUSE_MIN_CI"); return e ? atoi(e) : 32; }();   // (env: measurement knob)
     return v;
 }
+static bool mask_act_ok(int a) { return a == GS_ACT_LRELU || a == GS_ACT_TANH || a == GS_ACT_LRELU_BITS; }
 
-static int conv2d_fwd_impl(const void* x, const float* w_hwio, const float* bias, int act, void* y, int n, int h, int w, int ci, int co, int ksize,
-                           int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream, void* y2 = nullptr,
-                           float pn_eps = 0.f) {
-    if (int e = check_conv_args(n, h, w, ci, co, ksize, stride, dtype)) return e;
+// y_norm (optional): y_norm = pixel_norm(act(conv + bias)) as well -- fused into the conv epilogue where the tile owns all channels of a
+// pixel, a separate pass otherwise; y (the activation itself) may then be NULL
+extern "C" int gs_conv_fwd(const GsConv* c, const void* x, const float* w_hwio, const float* bias, int act, void* y, void* y_norm, float eps, void* stream) {
+    if (int e = check_conv(c)) return e;
     const bool want_bits = (act & GS_ACT_WRITE_BITS) != 0;   // (the caller's y has room for the sign bits behind it: include/gansynth_hip.h)
     act &= ~GS_ACT_WRITE_BITS;
-    GS_CHECK_ARG(act == GS_ACT_NONE || act == GS_ACT_LRELU || act == GS_ACT_TANH, "conv2d: bad activation %d", act);
-    GS_CHECK_ARG(!want_bits || (act == GS_ACT_LRELU && dtype == GS_BF16 && co % 32 == 0 && y), "conv2d: sign bits go with a bf16 leaky-relu result of 32 k channels");
-    GS_CHECK_ARG(y || y2, "conv2d: no output");
+    GS_CHECK_ARG(act == GS_ACT_NONE || act == GS_ACT_LRELU || act == GS_ACT_TANH, "conv_fwd: bad activation %d", act);
+    GS_CHECK_ARG(!want_bits || (act == GS_ACT_LRELU && c->dtype == GS_BF16 && c->co % 32 == 0 && y && !c->transposed),
+                 "conv_fwd: sign bits go with a plain conv's bf16 leaky-relu result of 32 k channels");
+    GS_CHECK_ARG(y || y_norm, "conv_fwd: no output");
     hipStream_t st = as_stream(stream);
-    const int hb = h / stride, wb = w / stride;
-    const int mode = stride == 2 ? MODE_S2 : MODE_S1;
-    if (ksize == 3 && igemm_supported(ci, co, dtype) && act != GS_ACT_TANH)
-        return run_igemm(mode, 0, x, w_hwio, y, n, h, w, ci, co, ci, co, hb, wb, alpha, bias, act | (want_bits ? GS_ACT_WRITE_BITS : 0), dtype, w_prepared, ws,
-                         ws_bytes, st, nullptr, 0, y2, pn_eps);
-    void* z = y ? y : y2;
+    const ConvRole r = conv_role(*c, GS_CONV_FWD);
+    if (c->ksize == 3 && igemm_supported(r.ICk, r.OCk, c->dtype) && act != GS_ACT_TANH)
+        return run_igemm(r.mode, r.variant, x, w_hwio, y, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Hb, r.Wb, c->alpha, bias, act | (want_bits ? GS_ACT_WRITE_BITS : 0),
+                         c->dtype, c->w_prepared, c->ws, c->ws_bytes, st, nullptr, 0, y_norm, eps);
+    void* z = y ? y : y_norm;
+    const int64_t P = (int64_t)c->n * r.Ho * r.Wo;
     bool fused = false;
     bool bits_done = false;
-    unsigned* bits_out = (want_bits && !y2) ? reinterpret_cast<unsigned*>(reinterpret_cast<unsigned short*>(y) + (size_t)n * hb * wb * co) : nullptr;
-    if (int e = run_direct(mode, ksize, 0, x, w_hwio, z, n, h, w, ci, co, ci, co, hb, wb, alpha, dtype, w_prepared, ws, ws_bytes, st, bias, act, &fused, nullptr, 0, nullptr,
-                           bits_out, &bits_done))
+    unsigned* bits_out = (want_bits && !y_norm) ? reinterpret_cast<unsigned*>(reinterpret_cast<unsigned short*>(y) + (size_t)P * c->co) : nullptr;
+    if (int e = run_direct(r.mode, c->ksize, r.variant, x, w_hwio, z, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Ho, r.Wo, c->alpha, c->dtype, c->w_prepared, c->ws,
+                           c->ws_bytes, st, bias, act, &fused, nullptr, 0, nullptr, bits_out, &bits_done))
         return e;
     if (!fused && (bias || act != GS_ACT_NONE))
-        if (int e = gs_bias_act_fwd(z, bias, z, (int64_t)n * hb * wb, co, act, dtype, stream)) return e;
-    if (y2)
-        if (int e = gs_pixel_norm_fwd(z, y2, (int64_t)n * hb * wb, co, pn_eps, dtype, stream)) return e;
-    if (want_bits && !bits_done) return gs_pack_act_bits(y, (int64_t)n * hb * wb, co, dtype, stream);   // (direct kernels other than the colour block's)
+        if (int e = gs_bias_act_fwd(z, bias, z, P, c->co, act, c->dtype, stream)) return e;
+    if (y_norm)
+        if (int e = gs_pixel_norm_fwd(z, y_norm, P, c->co, eps, c->dtype, stream)) return e;
+    if (want_bits && !bits_done) return gs_pack_act_bits(y, P, c->co, c->dtype, stream);   // (direct kernels other than the colour block's)
     return 0;
 }
 
-extern "C" int gs_conv2d_fwd(const void* x, const float* w_hwio, void* y, int n, int h, int w, int ci, int co, int ksize,
-                             int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream) {
-    return conv2d_fwd_impl(x, w_hwio, nullptr, GS_ACT_NONE, y, n, h, w, ci, co, ksize, stride, alpha, dtype, w_prepared, ws, ws_bytes, stream);
-}
-
-extern "C" int gs_conv2d_fwd_bias_act(const void* x, const float* w_hwio, const float* bias, void* y, int n, int h, int w, int ci, int co,
-                                      int ksize, int stride, float alpha, int act, int dtype, int w_prepared, void* ws, size_t ws_bytes,
-                                      void* stream) {
-    return conv2d_fwd_impl(x, w_hwio, bias, act, y, n, h, w, ci, co, ksize, stride, alpha, dtype, w_prepared, ws, ws_bytes, stream);
-}
-
-extern "C" int gs_act_bwd(const void* g, const void* y, void* gx, int64_t numel, int act, int dtype, void* stream);
-
-// y = conv2d(x, w) * mask_act'(.) through `mask` (an activation OUTPUT of y's shape): the second-order pass of the R1 penalty runs
+// y = conv(x, w) * mask_act'(.) through `mask` (an activation OUTPUT of y's shape): the second-order pass of the R1 penalty runs
 // the discriminator's convs forward on cotangents and multiplies each result by the derivative of the activation that follows
-// the conv; in the epilogue on the MFMA path (see gs_conv2d_bwd_data_mask), in place after the conv otherwise
-extern "C" int gs_conv2d_fwd_mask(const void* x, const float* w_hwio, const void* mask, int mask_act, void* y, int n, int h, int w, int ci, int co,
-                                  int ksize, int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream) {
-    if (int e = check_conv_args(n, h, w, ci, co, ksize, stride, dtype)) return e;
-    GS_CHECK_ARG(mask == nullptr || mask_act == GS_ACT_LRELU || mask_act == GS_ACT_TANH || mask_act == GS_ACT_LRELU_BITS, "conv2d_fwd_mask: bad activation %d", mask_act);
+// the conv; in the epilogue on the MFMA path (see gs_conv_bwd_data), in place after the conv otherwise
+extern "C" int gs_conv_fwd_mask(const GsConv* c, const void* x, const float* w_hwio, const void* mask, int mask_act, void* y, void* stream) {
+    if (int e = check_conv(c)) return e;
+    if (c->transposed) return fail(GS_ERR_UNSUPPORTED, "conv_fwd_mask: no masked forward of a transposed layer");
+    GS_CHECK_ARG(mask == nullptr || mask_act_ok(mask_act), "conv_fwd_mask: bad activation %d", mask_act);
     hipStream_t st = as_stream(stream);
-    const int hb = h / stride, wb = w / stride;
-    const int mode = stride == 2 ? MODE_S2 : MODE_S1;
-    const bool fused = mask != nullptr && co >= mask_fuse_min_channels() && ksize == 3 && igemm_supported(ci, co, dtype);
+    const ConvRole r = conv_role(*c, GS_CONV_FWD);
+    const bool mfma = c->ksize == 3 && igemm_supported(r.ICk, r.OCk, c->dtype);
+    const bool fused = mask != nullptr && c->co >= mask_fuse_min_channels() && mfma;
     int rc;
     const int bits_act = mask_act;   // (only the MFMA epilogue reads the sign bits; every other path reads the values they stand behind)
     if (mask_act == GS_ACT_LRELU_BITS) mask_act = GS_ACT_LRELU;
-    if (ksize == 3 && igemm_supported(ci, co, dtype))
-        rc = run_igemm(mode, 0, x, w_hwio, y, n, h, w, ci, co, ci, co, hb, wb, alpha, nullptr, GS_ACT_NONE, dtype, w_prepared, ws, ws_bytes, st, fused ? mask : nullptr, bits_act);
+    if (mfma)
+        rc = run_igemm(r.mode, r.variant, x, w_hwio, y, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Hb, r.Wb, c->alpha, nullptr, GS_ACT_NONE, c->dtype, c->w_prepared, c->ws,
+                       c->ws_bytes, st, fused ? mask : nullptr, bits_act);
     else {   // (the colour block's streaming kernel applies the mask itself; the other direct kernels leave it to the pass below)
         bool epi = false, mdone = false;
-        rc = run_direct(mode, ksize, 0, x, w_hwio, y, n, h, w, ci, co, ci, co, hb, wb, alpha, dtype, w_prepared, ws, ws_bytes, st, nullptr, GS_ACT_NONE, &epi, mask, mask_act, &mdone);
+        rc = run_direct(r.mode, c->ksize, r.variant, x, w_hwio, y, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Ho, r.Wo, c->alpha, c->dtype, c->w_prepared, c->ws, c->ws_bytes,
+                        st, nullptr, GS_ACT_NONE, &epi, mask, mask_act, &mdone);
         if (rc || !mask || mdone) return rc;
     }
     if (rc || !mask || fused) return rc;
-    return gs_act_bwd(y, mask, y, (int64_t)n * hb * wb * co, mask_act, dtype, stream);
+    return gs_act_bwd(y, mask, y, (int64_t)c->n * r.Ho * r.Wo * c->co, mask_act, c->dtype, stream);
 }
 
-extern "C" int gs_conv2d_fwd_bias_act_norm(const void* x, const float* w_hwio, const float* bias, void* z, void* y, int n, int h, int w, int ci, int co,
-                                           int ksize, int stride, float alpha, int act, float eps, int dtype, int w_prepared, void* ws,
-                                           size_t ws_bytes, void* stream) {
-    GS_CHECK_ARG(y != nullptr, "conv2d_fwd_bias_act_norm: y is required (z is optional)");
-    return conv2d_fwd_impl(x, w_hwio, bias, act, z, n, h, w, ci, co, ksize, stride, alpha, dtype, w_prepared, ws, ws_bytes, stream, y, eps);
-}
-
-extern "C" int gs_act_bwd(const void* g, const void* y, void* gx, int64_t numel, int act, int dtype, void* stream);
-
-// gx = conv2d_bwd_data(gy, w) * mask_act'(.) through `mask` (the activation OUTPUT that was the conv's input; NULL: plain)
-extern "C" int gs_conv2d_bwd_data_mask(const void* gy, const float* w_hwio, const void* mask, int mask_act, void* gx, int n, int h, int w, int ci, int co,
-                                       int ksize, int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream) {
-    if (int e = check_conv_args(n, h, w, ci, co, ksize, stride, dtype)) return e;
-    GS_CHECK_ARG(mask == nullptr || mask_act == GS_ACT_LRELU || mask_act == GS_ACT_TANH || mask_act == GS_ACT_LRELU_BITS, "conv2d_bwd_data_mask: bad activation %d", mask_act);
-    const int bits_act = mask_act;   // (see gs_conv2d_fwd_mask)
+// gx = bwd_data(gy, w) * mask_act'(.) through `mask` (the activation OUTPUT that was the layer's input; NULL: plain)
+extern "C" int gs_conv_bwd_data(const GsConv* c, const void* gy, const float* w_hwio, const void* mask, int mask_act, void* gx, void* stream) {
+    if (int e = check_conv(c)) return e;
+    if (c->transposed && mask) return fail(GS_ERR_UNSUPPORTED, "conv_bwd_data: no masked data gradient of a transposed layer");
+    GS_CHECK_ARG(mask == nullptr || mask_act_ok(mask_act), "conv_bwd_data: bad activation %d", mask_act);
+    const int bits_act = mask_act;   // (see gs_conv_fwd_mask)
     if (mask_act == GS_ACT_LRELU_BITS) mask_act = GS_ACT_LRELU;
-    const float* bias = nullptr;
-    const int act = GS_ACT_NONE;
     hipStream_t st = as_stream(stream);
-    const int hb = h / stride, wb = w / stride;
+    const ConvRole r = conv_role(*c, GS_CONV_BWD_DATA);
     int rc;
     // In the epilogue the mask costs one more read of gx's size; with the mask vectors fetched ahead of the epilogue arithmetic
     // (conv_igemm.hip) that beats the separate in-place pass on every MFMA-path layer, the HBM-bound 32-channel top included
     // (+1.6 % on the step against fusing from 64 channels up).
-    bool fused = mask != nullptr && ci >= mask_fuse_min_channels();
-    const void* km = fused ? mask : nullptr;
-    if (stride == 1) {  // flipped taps, roles of ci/co swapped
-        if (ksize == 3 && igemm_supported(co, ci, dtype))
-            rc = run_igemm(MODE_S1, 1, gy, w_hwio, gx, n, h, w, co, ci, ci, co, h, w, alpha, bias, act, dtype, w_prepared, ws, ws_bytes, st, km, bits_act);
-        else { rc = run_direct(MODE_S1, ksize, 1, gy, w_hwio, gx, n, h, w, co, ci, ci, co, h, w, alpha, dtype, w_prepared, ws, ws_bytes, st); fused = false; }
-    } else if (igemm_supported(co, ci, dtype)) {
-        rc = run_igemm(MODE_T2, 2, gy, w_hwio, gx, n, hb, wb, co, ci, ci, co, hb, wb, alpha, bias, act, dtype, w_prepared, ws, ws_bytes, st, km, bits_act);
-    } else {
-        rc = run_direct(MODE_T2, 3, 2, gy, w_hwio, gx, n, hb, wb, co, ci, ci, co, h, w, alpha, dtype, w_prepared, ws, ws_bytes, st);
+    bool fused = mask != nullptr && c->ci >= mask_fuse_min_channels();
+    if (c->ksize == 3 && igemm_supported(r.ICk, r.OCk, c->dtype))
+        rc = run_igemm(r.mode, r.variant, gy, w_hwio, gx, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Hb, r.Wb, c->alpha, nullptr, GS_ACT_NONE, c->dtype, c->w_prepared, c->ws,
+                       c->ws_bytes, st, fused ? mask : nullptr, bits_act);
+    else {
+        rc = run_direct(r.mode, c->ksize, r.variant, gy, w_hwio, gx, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Ho, r.Wo, c->alpha, c->dtype, c->w_prepared, c->ws, c->ws_bytes, st);
         fused = false;
     }
     if (rc || !mask || fused) return rc;
-    return gs_act_bwd(gx, mask, gx, (int64_t)n * h * w * ci, mask_act, dtype, stream);   // shapes without the MFMA kernel: in place
+    return gs_act_bwd(gx, mask, gx, (int64_t)c->n * r.Ho * r.Wo * c->ci, mask_act, c->dtype, stream);   // shapes without the MFMA kernel: in place
 }
-
-extern "C" int gs_conv2d_bwd_data(const void* gy, const float* w_hwio, void* gx, int n, int h, int w, int ci, int co,
-                                  int ksize, int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream) {
-    return gs_conv2d_bwd_data_mask(gy, w_hwio, nullptr, 0, gx, n, h, w, ci, co, ksize, stride, alpha, dtype, w_prepared, ws, ws_bytes, stream);
-}
-
-extern "C" size_t gs_channel_sum_workspace_bytes(int64_t p, int c);
-extern "C" int gs_channel_sum(const void* g, float* out, int64_t p, int c, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream);
 
 // the (x, gy) pairs of one launch, as the kernels want them; for the transposed conv the roles of the two sides swap
 static WgradSrcs make_srcs(const void* const* xs, const void* const* gys, int nsrc, int n_per, const int* ns, unsigned bias_mask, bool swap, int* total) {
@@ -1016,58 +1021,58 @@ static WgradSrcs make_srcs(const void* const* xs, const void* const* gys, int ns
     return s;
 }
 
-extern "C" int gs_conv2d_bwd_weight_bias_multi(const void* const* xs, const void* const* gys, const int* ns, int nsrc, unsigned bias_mask, float* gw_hwio,
-                                               float* gb, int n, int h, int w, int ci, int co, int ksize, int stride, float alpha, int accumulate,
-                                               int dtype, void* ws, size_t ws_bytes, GsWgradReduce* pending, void* stream) {
-    if (int e = check_conv_args(n, h, w, ci, co, ksize, stride, dtype)) return e;
-    GS_CHECK_ARG(xs && gys && nsrc >= 1 && nsrc <= GS_WGRAD_MAX_SRC, "conv2d_bwd_weight_bias_multi: %d sources (1..%d)", nsrc, GS_WGRAD_MAX_SRC);
-    for (int i = 0; i < nsrc; ++i) GS_CHECK_ARG(xs[i] && gys[i], "conv2d_bwd_weight_bias_multi: null source %d", i);
+// One layer's weight gradient from several (x, gy) pairs in one launch: gw (+)= sum_s bwd_weight(xs[s], gys[s]); pair s has ns[s] images
+// (ns NULL: c.n each) and bit s of bias_mask says whether it contributes to gb (ignored when gb is NULL).  The layer then costs one set of
+// block partials and one slice reduction instead of one per pair.  `pending` (NULL = reduce at once): see GsWgradReduce.  c.ws is sized by
+// gs_conv_workspace_bytes(GS_CONV_BWD_WEIGHT) for the total image count.
+static int wgrad_layer(const GsConv& c, const void* const* xs, const void* const* gys, const int* ns, int nsrc, unsigned bias_mask, float* gw_hwio, float* gb,
+                       int accumulate, GsWgradReduce* pending, void* stream) {
+    if (int e = check_conv(&c)) return e;
+    GS_CHECK_ARG(!(c.transposed && gb), "conv_bwd_weight: a transposed layer has no bias gradient");
+    GS_CHECK_ARG(xs && gys && nsrc >= 1 && nsrc <= GS_WGRAD_MAX_SRC, "conv_bwd_weight: %d sources (1..%d)", nsrc, GS_WGRAD_MAX_SRC);
+    for (int i = 0; i < nsrc; ++i) GS_CHECK_ARG(xs[i] && gys[i], "conv_bwd_weight: null source %d", i);
     hipStream_t st = as_stream(stream);
-    const int hb = h / stride, wb = w / stride;
-    const int mode = stride == 2 ? MODE_S2 : MODE_S1;
-    const bool mfma = ksize == 3 && wgrad_mfma_supported(ci, co, dtype);
+    const ConvRole r = conv_role(c, GS_CONV_BWD_WEIGHT);
+    const bool mfma = c.ksize == 3 && wgrad_mfma_supported(r.ICk, r.OCk, c.dtype);
     if (pending) memset(pending, 0, sizeof(*pending));
     if (!gb) bias_mask = 0;
-    if (nsrc > 1 && !(mfma && (!gb || wgrad_mfma_has_bias(dtype)))) {
+    if (nsrc > 1 && !(mfma && (!gb || wgrad_mfma_has_bias(c.dtype)))) {
         // shapes without the multi-source kernels: one call per source (the first applies `accumulate`, the rest add)
         for (int i = 0; i < nsrc; ++i) {
-            const int rc = gs_conv2d_bwd_weight_bias_multi(xs + i, gys + i, nullptr, 1, 1u, gw_hwio, ((bias_mask >> i) & 1u) ? gb : nullptr, ns ? ns[i] : n, h, w, ci, co,
-                                                           ksize, stride, alpha, i == 0 ? accumulate : 1, dtype, ws, ws_bytes, nullptr, stream);
+            GsConv one = c;
+            if (ns) one.n = ns[i];
+            const int rc = wgrad_layer(one, xs + i, gys + i, nullptr, 1, 1u, gw_hwio, ((bias_mask >> i) & 1u) ? gb : nullptr, i == 0 ? accumulate : 1, nullptr, stream);
             if (rc) return rc;
         }
         return 0;
     }
-    const bool fused_bias = bias_mask && mfma && wgrad_mfma_has_bias(dtype);
+    const bool fused_bias = bias_mask && mfma && wgrad_mfma_has_bias(c.dtype);
     // the channel-sum fallback of the bias gradient reuses ws: such calls cannot leave their partials pending
     GsWgradReduce* defer = (bias_mask && !fused_bias) ? nullptr : pending;
     int rc;
-    const int n0 = ns ? ns[0] : n;   // (the single-source paths below)
+    const int n0 = ns ? ns[0] : c.n;   // (the single-source paths below)
     if (mfma) {
         int total = 0;
-        const WgradSrcs srcs = make_srcs(xs, gys, nsrc, n, ns, bias_mask, false, &total);
-        rc = run_wgrad_mfma(mode, srcs, nsrc, gw_hwio, fused_bias ? gb : nullptr, total, h, w, ci, co, hb, wb, alpha, 0, accumulate, dtype, ws, ws_bytes, st, defer);
+        const WgradSrcs srcs = make_srcs(xs, gys, nsrc, c.n, ns, bias_mask, r.swapped != 0, &total);
+        rc = run_wgrad_mfma(r.mode, srcs, nsrc, gw_hwio, fused_bias ? gb : nullptr, total, r.Hi, r.Wi, r.ICk, r.OCk, r.Hb, r.Wb, c.alpha, r.swapped, accumulate, c.dtype, c.ws,
+                            c.ws_bytes, st, defer);
     } else {
-        rc = run_wgrad_direct(mode, ksize, xs[0], gys[0], gw_hwio, n0, h, w, ci, co, hb, wb, alpha, 0, accumulate, dtype, ws, ws_bytes, st, defer);
+        rc = run_wgrad_direct(r.mode, c.ksize, r.swapped ? gys[0] : xs[0], r.swapped ? xs[0] : gys[0], gw_hwio, n0, r.Hi, r.Wi, r.ICk, r.OCk, r.Hb, r.Wb, c.alpha, r.swapped,
+                              accumulate, c.dtype, c.ws, c.ws_bytes, st, defer);
     }
     if (rc || !bias_mask || fused_bias) return rc;
     // shapes without the fused path: the plain channel sum (stream-ordered after the kernels above, same workspace)
-    return gs_channel_sum(gys[0], gb, (int64_t)n0 * hb * wb, co, accumulate, dtype, ws, ws_bytes, stream);
+    return gs_channel_sum(gys[0], gb, (int64_t)n0 * r.Hb * r.Wb, c.co, accumulate, c.dtype, c.ws, c.ws_bytes, stream);
 }
 
-extern "C" int gs_conv2d_bwd_weight_bias_partial(const void* x, const void* gy, float* gw_hwio, float* gb, int n, int h, int w, int ci, int co,
-                                                 int ksize, int stride, float alpha, int accumulate, int dtype, void* ws, size_t ws_bytes,
-                                                 GsWgradReduce* pending, void* stream) {
-    return gs_conv2d_bwd_weight_bias_multi(&x, &gy, nullptr, 1, 1u, gw_hwio, gb, n, h, w, ci, co, ksize, stride, alpha, accumulate, dtype, ws, ws_bytes, pending, stream);
-}
-
-extern "C" int gs_conv2d_bwd_weight_bias(const void* x, const void* gy, float* gw_hwio, float* gb, int n, int h, int w, int ci, int co,
-                                         int ksize, int stride, float alpha, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream) {
-    return gs_conv2d_bwd_weight_bias_partial(x, gy, gw_hwio, gb, n, h, w, ci, co, ksize, stride, alpha, accumulate, dtype, ws, ws_bytes, nullptr, stream);
+extern "C" int gs_conv_bwd_weight(const GsConv* c, const void* x, const void* gy, float* gw_hwio, float* gb, int accumulate, void* stream) {
+    if (int e = check_conv(c)) return e;
+    return wgrad_layer(*c, &x, &gy, nullptr, 1, 1u, gw_hwio, gb, accumulate, nullptr, stream);
 }
 
 // many pending slice reductions in a handful of launches: up to GS_REDUCE_BATCH entries per launch, a new launch whenever an
-// entry adds into a gradient that the current launch already touches (list order = summation order)
-extern "C" int gs_wgrad_reduce_batch(const GsWgradReduce* pending, int n, void* stream) {
+// entry adds into a gradient that the current launch already touches (list order = summation order).  `pending`: host array
+static int wgrad_reduce_batch(const GsWgradReduce* pending, int n, void* stream) {
     GS_CHECK_ARG(n >= 0 && (n == 0 || pending), "wgrad_reduce_batch: bad args");
     hipStream_t st = as_stream(stream);
     ReduceBatch b;
@@ -1100,7 +1105,7 @@ extern "C" int gs_wgrad_reduce_batch(const GsWgradReduce* pending, int n, void* 
 
 // ---- all weight gradients of a backward pass in one call (gs_conv_wgrad_jobs): the layers the 64 x 64-tile bf16 kernel takes are
 // grouped by its instantiation (conv mode, tile width) and each group runs as ONE stream-K launch + one fold (conv_shared.h); every
-// other layer goes through the per-layer entry points above, its slice reduction left pending, and one gs_wgrad_reduce_batch folds
+// other layer goes through wgrad_layer above, its slice reduction left pending, and one wgrad_reduce_batch folds
 // those at the end.  Workspace: the largest group (groups run one after the other on the stream) + the sum of the per-layer needs.
 namespace gs {
 struct JobPlan {
@@ -1109,13 +1114,20 @@ struct JobPlan {
     std::vector<size_t> single_off;               // their workspace offsets
     size_t group_bytes = 0, total_bytes = 0;
 };
+static GsConv job_conv(const GsWgradJob& jb, int n) {   // the job's layer, with n images
+    GsConv c;
+    memset(&c, 0, sizeof(c));
+    c.n = n; c.h = jb.h; c.w = jb.w; c.ci = jb.ci; c.co = jb.co; c.ksize = jb.ksize; c.stride = jb.stride; c.transposed = jb.transposed;
+    c.dtype = jb.dtype; c.alpha = jb.alpha;
+    return c;
+}
 static int job_check(const GsWgradJob& jb, int idx) {
     GS_CHECK_ARG(jb.nsrc >= 1 && jb.nsrc <= GS_WGRAD_MAX_SRC && jb.gw, "conv_wgrad_jobs: job %d has %d sources (1..%d) / no output", idx, jb.nsrc, GS_WGRAD_MAX_SRC);
     for (int i = 0; i < jb.nsrc; ++i) GS_CHECK_ARG(jb.x[i] && jb.gy[i] && jb.n[i] > 0, "conv_wgrad_jobs: job %d, null or empty source %d", idx, i);
     GS_CHECK_ARG(!jb.transposed || (jb.ksize == 3 && jb.stride == 2 && !jb.gb), "conv_wgrad_jobs: job %d: the transposed conv is 3x3 stride 2 without bias", idx);
     GS_CHECK_ARG(jb.gw_ci_stride == 0 || (jb.gw_ci_stride >= jb.ci && !jb.transposed), "conv_wgrad_jobs: job %d: bad gw_ci_stride %d", idx, jb.gw_ci_stride);
-    if (jb.transposed) return check_conv_args(jb.n[0], 2 * jb.h, 2 * jb.w, jb.co, jb.ci, 3, 2, jb.dtype);
-    return check_conv_args(jb.n[0], jb.h, jb.w, jb.ci, jb.co, jb.ksize, jb.stride, jb.dtype);
+    const GsConv c = job_conv(jb, jb.n[0]);
+    return check_conv(&c);
 }
 static int job_total_images(const GsWgradJob& jb) {
     int t = 0;
@@ -1128,15 +1140,11 @@ static int plan_jobs(const GsWgradJob* jobs, int njobs, JobPlan& plan) {
     for (int i = 0; i < njobs; ++i) {
         const GsWgradJob& jb = jobs[i];
         if (int e = job_check(jb, i)) return e;
-        // kernel-role geometry: a transposed conv's gradient is the stride-2 one with the two sides swapped, stored transposed
-        const int mode = jb.transposed ? MODE_S2 : (jb.stride == 2 ? MODE_S2 : MODE_S1);
-        const int IC = jb.transposed ? jb.co : jb.ci, OC = jb.transposed ? jb.ci : jb.co;
-        const int Hi = jb.transposed ? 2 * jb.h : jb.h, Wi = jb.transposed ? 2 * jb.w : jb.w;
-        const int Hb = jb.transposed ? jb.h : jb.h / jb.stride, Wb = jb.transposed ? jb.w : jb.w / jb.stride;
         const int total = job_total_images(jb);
-        if (!no_sk && jb.ksize == 3 && wgrad_sk_supported(mode, jb.dtype, IC, OC)) {
-            const int tw = wgrad_sk_tile_width(Wb);
-            const int key = mode * 64 + tw;
+        const ConvRole r = conv_role(job_conv(jb, total), GS_CONV_BWD_WEIGHT);
+        if (!no_sk && jb.ksize == 3 && wgrad_sk_supported(r.mode, jb.dtype, r.ICk, r.OCk)) {
+            const int tw = wgrad_sk_tile_width(r.Wb);
+            const int key = r.mode * 64 + tw;
             int gi = open_idx[key];
             if (gi >= 0) {   // a full group, or one that already adds into this gradient, is closed (launch order = summation order)
                 const SkGroup& og = plan.groups[gi].second;
@@ -1154,15 +1162,15 @@ static int plan_jobs(const GsWgradJob* jobs, int njobs, JobPlan& plan) {
             SkGroup& g = plan.groups[gi].second;
             SkJob& q = g.job[g.njobs++];
             int tot = 0;
-            q.srcs = make_srcs(jb.x, jb.gy, jb.nsrc, 0, jb.n, jb.gb ? jb.bias_mask : 0u, jb.transposed != 0, &tot);
-            q.gw = jb.gw; q.gb = jb.gb; q.alpha = jb.alpha; q.transpose = jb.transposed ? 1 : 0; q.accumulate = jb.accumulate;
-            q.Hi = Hi; q.Wi = Wi; q.IC = IC; q.OC = OC; q.Hb = Hb; q.Wb = Wb;
-            q.ICld = jb.gw_ci_stride > 0 ? jb.gw_ci_stride : IC;
-            wgrad_sk_job_geometry(mode, tw, total, q);
+            q.srcs = make_srcs(jb.x, jb.gy, jb.nsrc, 0, jb.n, jb.gb ? jb.bias_mask : 0u, r.swapped != 0, &tot);
+            q.gw = jb.gw; q.gb = jb.gb; q.alpha = jb.alpha; q.transpose = r.swapped; q.accumulate = jb.accumulate;
+            q.Hi = r.Hi; q.Wi = r.Wi; q.IC = r.ICk; q.OC = r.OCk; q.Hb = r.Hb; q.Wb = r.Wb;
+            q.ICld = jb.gw_ci_stride > 0 ? jb.gw_ci_stride : r.ICk;
+            wgrad_sk_job_geometry(r.mode, tw, total, q);
         } else {
             // layers without a multi-source kernel (direct / thin kernels, fp32 bias sums): one single-source job per pair, each with its own
             // partials so that every slice reduction can stay pending
-            const bool mfma = jb.ksize == 3 && (jb.transposed ? wgrad_mfma_supported(jb.co, jb.ci, jb.dtype) : wgrad_mfma_supported(jb.ci, jb.co, jb.dtype));
+            const bool mfma = jb.ksize == 3 && wgrad_mfma_supported(r.ICk, r.OCk, jb.dtype);
             const bool multi = mfma && (!jb.gb || wgrad_mfma_has_bias(jb.dtype));
             if (jb.nsrc == 1 || multi) {
                 plan.single.push_back(jb);
@@ -1186,10 +1194,9 @@ static int plan_jobs(const GsWgradJob* jobs, int njobs, JobPlan& plan) {
     }
     size_t off = plan.group_bytes;
     for (const GsWgradJob& jb : plan.single) {
-        const int total = job_total_images(jb);
+        const GsConv c = job_conv(jb, job_total_images(jb));
         plan.single_off.push_back(off);
-        off += jb.transposed ? gs_conv2d_transpose_s2_workspace_bytes(GS_CONV_BWD_WEIGHT, total, jb.h, jb.w, jb.ci, jb.co, jb.dtype)
-                             : gs_conv2d_workspace_bytes(GS_CONV_BWD_WEIGHT, total, jb.h, jb.w, jb.ci, jb.co, jb.ksize, jb.stride, jb.dtype);
+        off += gs_conv_workspace_bytes(&c, GS_CONV_BWD_WEIGHT);
     }
     plan.total_bytes = off;
     return 0;
@@ -1215,86 +1222,20 @@ extern "C" int gs_conv_wgrad_jobs(const GsWgradJob* jobs, int njobs, void* ws, s
     std::vector<GsWgradReduce> pend;
     for (size_t k = 0; k < plan.single.size(); ++k) {
         const GsWgradJob& jb = plan.single[k];
-        unsigned char* jws = reinterpret_cast<unsigned char*>(ws) + plan.single_off[k];
-        const size_t jbytes = (k + 1 < plan.single.size() ? plan.single_off[k + 1] : plan.total_bytes) - plan.single_off[k];
+        GsConv c = job_conv(jb, jb.n[0]);
+        c.ws = reinterpret_cast<unsigned char*>(ws) + plan.single_off[k];
+        c.ws_bytes = (k + 1 < plan.single.size() ? plan.single_off[k + 1] : plan.total_bytes) - plan.single_off[k];
         GsWgradReduce d;
         memset(&d, 0, sizeof(d));
-        int rc;
-        if (jb.transposed)
-            rc = gs_conv2d_transpose_s2_bwd_weight_multi(jb.x, jb.gy, jb.n, jb.nsrc, jb.gw, jb.n[0], jb.h, jb.w, jb.ci, jb.co, jb.alpha, jb.accumulate, jb.dtype, jws, jbytes, &d, stream);
-        else
-            rc = gs_conv2d_bwd_weight_bias_multi(jb.x, jb.gy, jb.n, jb.nsrc, jb.bias_mask, jb.gw, jb.gb, jb.n[0], jb.h, jb.w, jb.ci, jb.co, jb.ksize, jb.stride, jb.alpha,
-                                                 jb.accumulate, jb.dtype, jws, jbytes, &d, stream);
-        if (rc) return rc;
+        if (int rc = wgrad_layer(c, jb.x, jb.gy, jb.n, jb.nsrc, jb.bias_mask, jb.gw, jb.gb, jb.accumulate, &d, stream)) return rc;
         if (jb.gw_ci_stride > jb.ci) {   // a channel-slice target: only the pending (batched) fold knows the row stride
             if (d.nslices <= 0 || d.transpose) return fail(GS_ERR_UNSUPPORTED, "conv_wgrad_jobs: a %d -> %d layer cannot add into a channel slice", jb.ci, jb.co);
             d.ic_ld = jb.gw_ci_stride;
         }
         if (d.nslices > 0) pend.push_back(d);
     }
-    if (!pend.empty()) return gs_wgrad_reduce_batch(pend.data(), (int)pend.size(), stream);
+    if (!pend.empty()) return wgrad_reduce_batch(pend.data(), (int)pend.size(), stream);
     return 0;
-}
-
-extern "C" int gs_conv2d_bwd_weight(const void* x, const void* gy, float* gw_hwio, int n, int h, int w, int ci, int co,
-                                    int ksize, int stride, float alpha, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream) {
-    return gs_conv2d_bwd_weight_bias(x, gy, gw_hwio, nullptr, n, h, w, ci, co, ksize, stride, alpha, accumulate, dtype, ws, ws_bytes, stream);
-}
-
-// ---- conv2d_transpose 3x3 stride 2: re-labelings of the stride-2 maps (see include/gansynth_hip.h)
-extern "C" size_t gs_conv2d_transpose_s2_workspace_bytes(int which, int n, int h, int w, int ci, int co, int dtype) {
-    if (which == GS_CONV_BWD_WEIGHT) {
-        if (wgrad_mfma_supported(co, ci, dtype)) return wgrad_mfma_bytes(MODE_S2, dtype, n, h, w, co, ci);
-        return wgrad_direct_bytes(3, n, h, w, co, ci);
-    }
-    return align256((size_t)9 * ci * co * 4);
-}
-
-static int conv2d_transpose_fwd_impl(const void* x, const float* w_hwio, const float* bias, int act, void* y, int n, int h, int w, int ci,
-                                     int co, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream, void* y2 = nullptr,
-                                     float pn_eps = 0.f) {
-    if (int e = check_conv_args(n, 2 * h, 2 * w, co, ci, 3, 2, dtype)) return e;
-    GS_CHECK_ARG(y || y2, "conv2d_transpose: no output");
-    hipStream_t st = as_stream(stream);
-    // out[2i+k][co] += x[i][ci] * w[k][ci][co]: kernel roles ICk = ci, OCk = co, Wp[t][co][ci] (variant 0)
-    if (igemm_supported(ci, co, dtype) && act != GS_ACT_TANH)
-        return run_igemm(MODE_T2, 0, x, w_hwio, y, n, h, w, ci, co, ci, co, h, w, alpha, bias, act, dtype, w_prepared, ws, ws_bytes, st, nullptr, 0, y2, pn_eps);
-    void* z = y ? y : y2;
-    if (int e = run_direct(MODE_T2, 3, 0, x, w_hwio, z, n, h, w, ci, co, ci, co, 2 * h, 2 * w, alpha, dtype, w_prepared, ws, ws_bytes, st)) return e;
-    if (bias || act != GS_ACT_NONE)
-        if (int e = gs_bias_act_fwd(z, bias, z, (int64_t)n * 4 * h * w, co, act, dtype, stream)) return e;
-    if (y2) return gs_pixel_norm_fwd(z, y2, (int64_t)n * 4 * h * w, co, pn_eps, dtype, stream);
-    return 0;
-}
-
-extern "C" int gs_conv2d_transpose_s2_fwd(const void* x, const float* w_hwio, void* y, int n, int h, int w, int ci, int co,
-                                          float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream) {
-    return conv2d_transpose_fwd_impl(x, w_hwio, nullptr, GS_ACT_NONE, y, n, h, w, ci, co, alpha, dtype, w_prepared, ws, ws_bytes, stream);
-}
-
-extern "C" int gs_conv2d_transpose_s2_fwd_bias_act_norm(const void* x, const float* w_hwio, const float* bias, void* z, void* y, int n, int h, int w,
-                                                        int ci, int co, float alpha, int act, float eps, int dtype, int w_prepared, void* ws,
-                                                        size_t ws_bytes, void* stream) {
-    GS_CHECK_ARG(y != nullptr, "conv2d_transpose_s2_fwd_bias_act_norm: y is required (z is optional)");
-    return conv2d_transpose_fwd_impl(x, w_hwio, bias, act, z, n, h, w, ci, co, alpha, dtype, w_prepared, ws, ws_bytes, stream, y, eps);
-}
-
-extern "C" int gs_conv2d_transpose_s2_fwd_bias_act(const void* x, const float* w_hwio, const float* bias, void* y, int n, int h, int w, int ci,
-                                                   int co, float alpha, int act, int dtype, int w_prepared, void* ws, size_t ws_bytes,
-                                                   void* stream) {
-    return conv2d_transpose_fwd_impl(x, w_hwio, bias, act, y, n, h, w, ci, co, alpha, dtype, w_prepared, ws, ws_bytes, stream);
-}
-
-extern "C" int gs_conv2d_transpose_s2_bwd_data(const void* gy, const float* w_hwio, void* gx, int n, int h, int w, int ci,
-                                               int co, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream) {
-    if (int e = check_conv_args(n, 2 * h, 2 * w, co, ci, 3, 2, dtype)) return e;
-    const float* bias = nullptr;
-    const int act = GS_ACT_NONE;
-    hipStream_t st = as_stream(stream);
-    // gx[i][ci] = sum gy[2i+k][co] * w[k][ci][co]: stride-2 conv, roles ICk = co, OCk = ci, Wp[t][ci][co] (variant 2)
-    if (igemm_supported(co, ci, dtype))
-        return run_igemm(MODE_S2, 2, gy, w_hwio, gx, n, 2 * h, 2 * w, co, ci, ci, co, h, w, alpha, bias, act, dtype, w_prepared, ws, ws_bytes, st);
-    return run_direct(MODE_S2, 3, 2, gy, w_hwio, gx, n, 2 * h, 2 * w, co, ci, ci, co, h, w, alpha, dtype, w_prepared, ws, ws_bytes, st);
 }
 
 // Second-order pass (the mode-seeking term differentiates the generator's backward, models.py:60): the forward conv applied to a cotangent gives
@@ -1302,33 +1243,22 @@ extern "C" int gs_conv2d_transpose_s2_bwd_data(const void* gy, const float* w_hw
 // are given.  Both gradients of that node in the conv's epilogue (h = t act'(z)):
 //   out_g = pixel_norm_bwd(h, z)                 (w.r.t. g)          out_z = d<h, pixel_norm_bwd(g, z)>/dz      (w.r.t. z)
 // where a tile owns all channels of a pixel; otherwise the conv into out_g and gs_pixel_norm_bwd_bwd_fused (out_g in place).
-extern "C" int gs_conv2d_fwd_pnbwdbwd(const void* x, const float* w_hwio, const void* g, const void* z, int act, float eps, void* out_g, void* out_z, int n, int h,
-                                      int w, int ci, int co, int ksize, int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream) {
-    if (int e = check_conv_args(n, h, w, ci, co, ksize, stride, dtype)) return e;
-    GS_CHECK_ARG(g && z && out_g && out_z && (act == GS_ACT_NONE || act == GS_ACT_LRELU), "conv2d_fwd_pnbwdbwd: g, z and both outputs are required, activation none or leaky relu (got %d)", act);
-    hipStream_t st = as_stream(stream);
-    const int hb = h / stride, wb = w / stride;
-    if (ksize == 3 && igemm_supported(ci, co, dtype))
-        return run_igemm(stride == 2 ? MODE_S2 : MODE_S1, 0, x, w_hwio, out_g, n, h, w, ci, co, ci, co, hb, wb, alpha, nullptr, GS_ACT_NONE, dtype, w_prepared, ws, ws_bytes, st,
-                         z, act, out_z, eps, g, 2);
-    if (int e = gs_conv2d_fwd(x, w_hwio, out_g, n, h, w, ci, co, ksize, stride, alpha, dtype, w_prepared, ws, ws_bytes, stream)) return e;
-    return gs_pixel_norm_bwd_bwd_fused(out_g, g, z, out_z, out_g, (int64_t)n * hb * wb, co, eps, act, dtype, stream);
+extern "C" int gs_conv_fwd_pnbwdbwd(const GsConv* c, const void* x, const float* w_hwio, const void* g, const void* z, int act, float eps, void* out_g, void* out_z,
+                                    void* stream) {
+    if (int e = check_conv(c)) return e;
+    GS_CHECK_ARG(g && z && out_g && out_z && (act == GS_ACT_NONE || act == GS_ACT_LRELU), "conv_fwd_pnbwdbwd: g, z and both outputs are required, activation none or leaky relu (got %d)", act);
+    const ConvRole r = conv_role(*c, GS_CONV_FWD);
+    if (c->ksize == 3 && igemm_supported(r.ICk, r.OCk, c->dtype))
+        return run_igemm(r.mode, r.variant, x, w_hwio, out_g, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Hb, r.Wb, c->alpha, nullptr, GS_ACT_NONE, c->dtype, c->w_prepared, c->ws,
+                         c->ws_bytes, as_stream(stream), z, act, out_z, eps, g, 2);
+    if (int e = gs_conv_fwd(c, x, w_hwio, nullptr, GS_ACT_NONE, out_g, nullptr, 0.f, stream)) return e;
+    return gs_pixel_norm_bwd_bwd_fused(out_g, g, z, out_z, out_g, (int64_t)c->n * r.Ho * r.Wo, c->co, eps, act, c->dtype, stream);
 }
-extern "C" int gs_conv2d_transpose_s2_fwd_pnbwdbwd(const void* x, const float* w_hwio, const void* g, const void* z, int act, float eps, void* out_g, void* out_z, int n,
-                                                   int h, int w, int ci, int co, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream) {
-    if (int e = check_conv_args(n, 2 * h, 2 * w, co, ci, 3, 2, dtype)) return e;
-    GS_CHECK_ARG(g && z && out_g && out_z && (act == GS_ACT_NONE || act == GS_ACT_LRELU), "conv2d_transpose_s2_fwd_pnbwdbwd: g, z and both outputs are required, activation none or leaky relu (got %d)", act);
-    hipStream_t st = as_stream(stream);
-    if (igemm_supported(ci, co, dtype))
-        return run_igemm(MODE_T2, 0, x, w_hwio, out_g, n, h, w, ci, co, ci, co, h, w, alpha, nullptr, GS_ACT_NONE, dtype, w_prepared, ws, ws_bytes, st, z, act, out_z, eps, g, 2);
-    if (int e = gs_conv2d_transpose_s2_fwd(x, w_hwio, out_g, n, h, w, ci, co, alpha, dtype, w_prepared, ws, ws_bytes, stream)) return e;
-    return gs_pixel_norm_bwd_bwd_fused(out_g, g, z, out_z, out_g, (int64_t)n * 4 * h * w, co, eps, act, dtype, stream);
-}
-// 1 when that call runs as one launch for the shape (n, h, w: the conv's input side)
-extern "C" int gs_conv2d_fwd_pnbwdbwd_is_fused(int n, int h, int w, int ci, int co, int ksize, int stride, int transposed, int dtype) {
-    if (ksize != 3 || !igemm_supported(ci, co, dtype)) return 0;
-    if (transposed) return stride == 2 && igemm_norm_fused(MODE_T2, n, h, w, ci, co, dtype, IGEMM_NORM_BWD2) ? 1 : 0;
-    return stride == 1 && igemm_norm_fused(MODE_S1, n, h, w, ci, co, dtype, IGEMM_NORM_BWD2) ? 1 : 0;
+// 1 when that call runs as one launch for the layer
+extern "C" int gs_conv_fwd_pnbwdbwd_is_fused(const GsConv* c) {
+    if (check_conv(c) || c->ksize != 3 || !(c->transposed || c->stride == 1)) return 0;
+    const ConvRole r = conv_role(*c, GS_CONV_FWD);
+    return igemm_norm_fused(r.mode, c->n, r.Hb, r.Wb, r.ICk, r.OCk, c->dtype, IGEMM_NORM_BWD2) ? 1 : 0;
 }
 
 // Data gradient of a conv whose INPUT was y = pixel_norm(z), z = act(...) the previous block's activation (networks.py:41-93: every
@@ -1336,32 +1266,34 @@ extern "C" int gs_conv2d_fwd_pnbwdbwd_is_fused(int n, int h, int w, int ci, int 
 //   gx = (pixel_norm_bwd(B^T(gy, w), z) + addend) * act'(z)       (addend: optional second gradient into z, same shape)
 // i.e. the gradient w.r.t. the previous block's pre-activation in ONE pass.  The epilogue form exists where a tile owns every channel of a
 // pixel (the 32- / 64-channel layers -- where the bytes are); other shapes run the plain data gradient and gs_pixel_norm_bwd_fused in place.
-extern "C" int gs_conv2d_bwd_data_pnbwd(const void* gy, const float* w_hwio, const void* z, const void* addend, int act, float eps, void* gx, int n, int h, int w,
-                                        int ci, int co, int ksize, int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream) {
-    if (int e = check_conv_args(n, h, w, ci, co, ksize, stride, dtype)) return e;
-    GS_CHECK_ARG(z && gx && (act == GS_ACT_NONE || act == GS_ACT_LRELU), "conv2d_bwd_data_pnbwd: z is required, activation none or leaky relu (got %d)", act);
+extern "C" int gs_conv_bwd_data_pnbwd(const GsConv* c, const void* gy, const float* w_hwio, const void* z, const void* addend, int act, float eps, void* gx, void* stream) {
+    if (int e = check_conv(c)) return e;
+    GS_CHECK_ARG(z && gx && (act == GS_ACT_NONE || act == GS_ACT_LRELU), "conv_bwd_data_pnbwd: z is required, activation none or leaky relu (got %d)", act);
     hipStream_t st = as_stream(stream);
-    if (stride == 1 && ksize == 3 && igemm_supported(co, ci, dtype))
-        return run_igemm(MODE_S1, 1, gy, w_hwio, gx, n, h, w, co, ci, ci, co, h, w, alpha, nullptr, GS_ACT_NONE, dtype, w_prepared, ws, ws_bytes, st, z, act, nullptr, eps, addend, 1);
-    if (stride == 1 && thin_expand_pnbwd_ok(ksize, co, ci, dtype)) {   // the colour block (few -> many channels as a gradient): streaming, one pass
-        const long total = (long)ci * co;
-        if (ws_bytes < (size_t)total * 4) return fail(GS_ERR_WORKSPACE, "conv2d_bwd_data_pnbwd: workspace %zu < %zu", ws_bytes, (size_t)total * 4);
-        float* wp = reinterpret_cast<float*>(ws);
-        if (!w_prepared) {
-            hipLaunchKernelGGL((weight_prep_kernel<float>), dim3(cdiv(total, 256)), dim3(256), 0, st, w_hwio, wp, 1, ci, co, 1);
+    const ConvRole r = conv_role(*c, GS_CONV_BWD_DATA);
+    const bool epilogue_map = c->transposed || c->stride == 1;   // (the stride-2 conv's data gradient, MODE_T2, has no norm epilogue)
+    if (epilogue_map && c->ksize == 3 && igemm_supported(r.ICk, r.OCk, c->dtype))
+        return run_igemm(r.mode, r.variant, gy, w_hwio, gx, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Hb, r.Wb, c->alpha, nullptr, GS_ACT_NONE, c->dtype, c->w_prepared, c->ws,
+                         c->ws_bytes, st, z, act, nullptr, eps, addend, 1);
+    if (c->stride == 1 && thin_expand_pnbwd_ok(c->ksize, r.ICk, r.OCk, c->dtype)) {   // the colour block (few -> many channels as a gradient): streaming, one pass
+        const long total = (long)c->ci * c->co;
+        if (c->ws_bytes < (size_t)total * 4) return fail(GS_ERR_WORKSPACE, "conv_bwd_data_pnbwd: workspace %zu < %zu", c->ws_bytes, (size_t)total * 4);
+        float* wp = reinterpret_cast<float*>(c->ws);
+        if (!c->w_prepared) {
+            hipLaunchKernelGGL((weight_prep_kernel<float>), dim3(cdiv(total, 256)), dim3(256), 0, st, w_hwio, wp, 1, c->ci, c->co, 1);
             GS_CHECK_LAUNCH();
         }
-        return run_thin_expand_pnbwd(gy, wp, z, addend, gx, (long)n * h * w, co, ci, alpha, eps, act, dtype, st);
+        return run_thin_expand_pnbwd(gy, wp, z, addend, gx, (long)c->n * r.Ho * r.Wo, r.ICk, r.OCk, c->alpha, eps, act, c->dtype, st);
     }
-    if (int e = gs_conv2d_bwd_data_mask(gy, w_hwio, nullptr, 0, gx, n, h, w, ci, co, ksize, stride, alpha, dtype, w_prepared, ws, ws_bytes, stream)) return e;
-    return gs_pixel_norm_bwd_fused(gx, z, addend, gx, (int64_t)n * h * w, ci, eps, GS_ACT_NONE, act, dtype, stream);
+    if (int e = gs_conv_bwd_data(c, gy, w_hwio, nullptr, 0, gx, stream)) return e;
+    return gs_pixel_norm_bwd_fused(gx, z, addend, gx, (int64_t)c->n * r.Ho * r.Wo, c->ci, eps, GS_ACT_NONE, act, c->dtype, stream);
 }
-// 1 when the call above runs as ONE launch for this shape (the epilogue form), 0 when it is the conv + the norm's backward in place
-extern "C" int gs_conv2d_bwd_data_pnbwd_is_fused(int n, int h, int w, int ci, int co, int ksize, int stride, int transposed, int dtype) {
-    if (ksize == 1) return !transposed && stride == 1 && thin_expand_pnbwd_ok(1, co, ci, dtype) ? 1 : 0;
-    if (ksize != 3) return 0;
-    if (transposed) return stride == 2 && igemm_norm_fused(MODE_S2, n, h, w, co, ci, dtype, IGEMM_NORM_BWD) ? 1 : 0;
-    return stride == 1 && igemm_norm_fused(MODE_S1, n, h, w, co, ci, dtype, IGEMM_NORM_BWD) ? 1 : 0;
+// 1 when the call above runs as ONE launch for the layer (the epilogue form), 0 when it is the conv + the norm's backward in place
+extern "C" int gs_conv_bwd_data_pnbwd_is_fused(const GsConv* c) {
+    if (check_conv(c) || !(c->transposed || c->stride == 1)) return 0;
+    const ConvRole r = conv_role(*c, GS_CONV_BWD_DATA);
+    if (c->ksize == 1) return thin_expand_pnbwd_ok(1, r.ICk, r.OCk, c->dtype) ? 1 : 0;
+    return igemm_norm_fused(r.mode, c->n, r.Hb, r.Wb, r.ICk, r.OCk, c->dtype, IGEMM_NORM_BWD) ? 1 : 0;
 }
 // Which implicit-GEMM configuration a 3x3 layer runs with (kernel-role shape: hb x wb the base grid, ic -> oc the kernel's channels; mode 0 stride
 // 1, 1 stride 2, 2 transposed; want: the epilogue asked for, 0 none, 1 pixel norm, 2 / 3 its first- / second-order backward).  Host arithmetic
@@ -1372,46 +1304,3 @@ extern "C" int gs_conv_igemm_config(int mode, int n, int hb, int wb, int ic, int
 // Row `index` of the table of compiled implicit-GEMM kernels (conv_igemm.hip: GS_IGEMM_CONFIGS), for tests that want one case per kernel.  Host
 // only.  out11: mode, bf16_only, A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC; GS_ERR_ARG past the last row.
 extern "C" int gs_conv_igemm_table(int index, int* out11) { return igemm_table(index, out11); }
-extern "C" int gs_conv2d_transpose_s2_bwd_data_pnbwd(const void* gy, const float* w_hwio, const void* z, const void* addend, int act, float eps, void* gx, int n,
-                                                     int h, int w, int ci, int co, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream) {
-    if (int e = check_conv_args(n, 2 * h, 2 * w, co, ci, 3, 2, dtype)) return e;
-    GS_CHECK_ARG(z && gx && (act == GS_ACT_NONE || act == GS_ACT_LRELU), "conv2d_transpose_s2_bwd_data_pnbwd: z is required, activation none or leaky relu (got %d)", act);
-    hipStream_t st = as_stream(stream);
-    if (igemm_supported(co, ci, dtype))
-        return run_igemm(MODE_S2, 2, gy, w_hwio, gx, n, 2 * h, 2 * w, co, ci, ci, co, h, w, alpha, nullptr, GS_ACT_NONE, dtype, w_prepared, ws, ws_bytes, st, z, act, nullptr, eps, addend, 1);
-    if (int e = gs_conv2d_transpose_s2_bwd_data(gy, w_hwio, gx, n, h, w, ci, co, alpha, dtype, w_prepared, ws, ws_bytes, stream)) return e;
-    return gs_pixel_norm_bwd_fused(gx, z, addend, gx, (int64_t)n * h * w, ci, eps, GS_ACT_NONE, act, dtype, stream);
-}
-
-extern "C" int gs_conv2d_transpose_s2_bwd_weight_multi(const void* const* xs, const void* const* gys, const int* ns, int nsrc, float* gw_hwio, int n, int h,
-                                                       int w, int ci, int co, float alpha, int accumulate, int dtype, void* ws, size_t ws_bytes,
-                                                       GsWgradReduce* pending, void* stream) {
-    if (int e = check_conv_args(n, 2 * h, 2 * w, co, ci, 3, 2, dtype)) return e;
-    GS_CHECK_ARG(xs && gys && nsrc >= 1 && nsrc <= GS_WGRAD_MAX_SRC, "conv2d_transpose_s2_bwd_weight_multi: %d sources (1..%d)", nsrc, GS_WGRAD_MAX_SRC);
-    for (int i = 0; i < nsrc; ++i) GS_CHECK_ARG(xs[i] && gys[i], "conv2d_transpose_s2_bwd_weight_multi: null source %d", i);
-    hipStream_t st = as_stream(stream);
-    if (pending) memset(pending, 0, sizeof(*pending));
-    // gw[k][ci][co] = sum x[i][ci] * gy[2i+k][co]: stride-2 wgrad with (input side = gy, output side = x), transposed
-    if (wgrad_mfma_supported(co, ci, dtype)) {
-        int total = 0;
-        const WgradSrcs srcs = make_srcs(xs, gys, nsrc, n, ns, 0u, true, &total);
-        return run_wgrad_mfma(MODE_S2, srcs, nsrc, gw_hwio, nullptr, total, 2 * h, 2 * w, co, ci, h, w, alpha, 1, accumulate, dtype, ws, ws_bytes, st, pending);
-    }
-    for (int i = 0; i < nsrc; ++i) {   // (direct kernels: one call per source)
-        const int rc = run_wgrad_direct(MODE_S2, 3, gys[i], xs[i], gw_hwio, ns ? ns[i] : n, 2 * h, 2 * w, co, ci, h, w, alpha, 1, i == 0 ? accumulate : 1, dtype, ws, ws_bytes, st,
-                                        nsrc == 1 ? pending : nullptr);
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-extern "C" int gs_conv2d_transpose_s2_bwd_weight_partial(const void* x, const void* gy, float* gw_hwio, int n, int h, int w, int ci,
-                                                         int co, float alpha, int accumulate, int dtype, void* ws, size_t ws_bytes,
-                                                         GsWgradReduce* pending, void* stream) {
-    return gs_conv2d_transpose_s2_bwd_weight_multi(&x, &gy, nullptr, 1, gw_hwio, n, h, w, ci, co, alpha, accumulate, dtype, ws, ws_bytes, pending, stream);
-}
-
-extern "C" int gs_conv2d_transpose_s2_bwd_weight(const void* x, const void* gy, float* gw_hwio, int n, int h, int w, int ci,
-                                                 int co, float alpha, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream) {
-    return gs_conv2d_transpose_s2_bwd_weight_partial(x, gy, gw_hwio, n, h, w, ci, co, alpha, accumulate, dtype, ws, ws_bytes, nullptr, stream);
-}

@@ -7,9 +7,23 @@ namespace gs {
 enum { MODE_S1 = 0, MODE_S2 = 1, MODE_T2 = 2 };
 // the epilogue of an implicit-GEMM launch (conv_igemm_kernel's NORM): none, pixel norm, its first-order backward, its second-order backward
 enum { IGEMM_PLAIN = 0, IGEMM_NORM_FWD = 1, IGEMM_NORM_BWD = 2, IGEMM_NORM_BWD2 = 3 };
-#define GS_WGRAD_MAX_SRC 4   // (x, gy) pairs one weight-gradient launch contracts (gs_conv2d_bwd_weight_bias_multi)
+#define GS_WGRAD_MAX_SRC 4   // (x, gy) pairs one weight-gradient launch contracts (GS_WGRAD_MAX_SOURCES)
 
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// Every weight gradient of a layer is two phases: block-partial sums over pixel slices (in the call's ws), then a reduction over the slices
+// into gw (+ gb).  A call given a GsWgradReduce runs phase 1 only and describes phase 2 in it; wgrad_reduce_batch (conv_api.hip) then folds
+// many pending reductions in a handful of launches (a backward pass has ~70 of them; each is a 10 us launch on its own).  The call's ws must
+// stay untouched until then; nslices == 0 on return means nothing is pending (shapes without the vector reduce ran both phases at once).
+struct GsWgradReduce {
+    const float* partials;   // [nslices][taps*ic*oc (+ oc when gb)] fp32, inside the call's ws
+    float* gw;               // [taps][ic][oc], or [taps][oc][ic] when transpose
+    float* gb;               // optional [oc]
+    int32_t nslices, taps, ic, oc;
+    float alpha;
+    int32_t transpose, accumulate;
+    int32_t ic_ld;           // 0, or the input-channel rows of the stored variable when gw is a channel slice of a wider one (not with transpose)
+};
 
 // Several (x, gy) pairs of ONE layer -- the real and the fake discriminator pass, the second-order contribution -- are contracted
 // by one launch: the images of all sources form one list (source s owns images n_end[s-1] .. n_end[s] - 1), so the layer costs one set of block
@@ -169,7 +183,7 @@ static __global__ __launch_bounds__(256) void wgrad_reduce_scalar_kernel(const f
     gw[dst] = accumulate ? gw[dst] + s : s;
 }
 
-// ---- many reductions per launch (gs_wgrad_reduce_batch): blockIdx.y = entry, blockIdx.x = element chunk of that entry
+// ---- many reductions per launch (wgrad_reduce_batch): blockIdx.y = entry, blockIdx.x = element chunk of that entry
 #define GS_REDUCE_BATCH 16
 struct ReduceBatch {
     GsWgradReduce e[GS_REDUCE_BATCH];
@@ -256,7 +270,7 @@ static inline size_t wgrad_reduce_extra(long nslices, long total) { (void)nslice
 static inline void wgrad_reduce_launch(float* part, float* gw, float* gb, int nslices, int taps, int ic, int oc, float alpha, int transpose, int accumulate, hipStream_t st,
                                        GsWgradReduce* defer = nullptr) {
     const bool vec = !((((long)taps * ic * oc) & 3) != 0 || (gb && (oc & 3) != 0));
-    if (defer && vec) {   // phase 2 is left to gs_wgrad_reduce_batch
+    if (defer && vec) {   // phase 2 is left to wgrad_reduce_batch
         defer->partials = part; defer->gw = gw; defer->gb = gb;
         defer->nslices = nslices; defer->taps = taps; defer->ic = ic; defer->oc = oc;
         defer->alpha = alpha; defer->transpose = transpose; defer->accumulate = accumulate; defer->ic_ld = 0;

@@ -17,7 +17,7 @@ int fail(int code, const char* fmt, ...) {
 }  // namespace gs
 
 extern "C" const char* gs_last_error(void) { return gs::g_err; }
-extern "C" int gs_version(void) { return 100; }
+extern "C" int gs_version(void) { return 101; }
 
 extern "C" int gs_init(void) {
     int dev = 0;

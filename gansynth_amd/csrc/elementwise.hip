@@ -922,9 +922,6 @@ static int pixel_norm_launch(int mode, const void* a0, const void* a1, const voi
 extern "C" int gs_pixel_norm_fwd(const void* x, void* y, int64_t p, int c, float eps, int dtype, void* stream) {
     return pixel_norm_launch(0, x, nullptr, nullptr, y, p, c, eps, dtype, stream);
 }
-extern "C" int gs_pixel_norm_bwd(const void* g, const void* x, void* gx, int64_t p, int c, float eps, int dtype, void* stream) {
-    return pixel_norm_launch(1, g, x, nullptr, gx, p, c, eps, dtype, stream);
-}
 static bool pn_act_ok(int a) { return a == GS_ACT_NONE || a == GS_ACT_LRELU || a == GS_ACT_TANH; }
 extern "C" int gs_pixel_norm_bwd_fused(const void* g, const void* x, const void* addend, void* gx, int64_t p, int c, float eps, int pre_act, int post_act,
                                        int dtype, void* stream) {
@@ -966,9 +963,6 @@ extern "C" int gs_pixel_norm_bwd_bwd_fused(const void* gg, const void* g, const 
                                            int dtype, void* stream) {
     GS_CHECK_ARG(pn_act_ok(pre_act), "pixel_norm_bwd_bwd_fused: bad activation %d", pre_act);
     return pixel_norm_launch(2, gg, g, x, out, p, c, eps, dtype, stream, 0, pre_act, nullptr, out_g);
-}
-extern "C" int gs_pixel_norm_bwd_bwd(const void* gg, const void* g, const void* x, void* out, int64_t p, int c, float eps, int dtype, void* stream) {
-    return pixel_norm_launch(2, gg, g, x, out, p, c, eps, dtype, stream);
 }
 
 extern "C" int gs_upscale2d(const void* x, void* y, int n, int h, int w, int c, int fy, int fx, float scale, int dtype, void* stream) {

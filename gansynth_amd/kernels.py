@@ -447,6 +447,36 @@ class HipKernels(object):
         return sum(len(g["src"]) for g in groups.values())   # (workspaces and sources die here: later launches are stream-ordered behind)
 
     # ------------------------------------------------------------------------------- conv
+    def _conv(self, which, w, alpha, dt, n, ci, h, wd, co, ksize=3, stride=2, transposed=False, device=None):
+        """-> (GsConv of the layer with its workspace for map `which` attached, that workspace).  (n, ci, h, wd): the layer's forward input.
+        A forward / data-gradient map keeps its re-laid weight in a persistent workspace per (weight, map) (_weight_ws); a weight gradient
+        (w None) gets a transient one on `device`."""
+        c = _lib.GsConv(n, h, wd, ci, co, ksize, stride, 1 if transposed else 0, dt, 0, float(alpha), None, 0)
+        nb = self.lib.gs_conv_workspace_bytes(c, which)
+        if which == _lib.CONV_BWD_WEIGHT:
+            ws = _ws(nb, device)
+        elif transposed:
+            tag, prep = (("t_fwd", _lib.PREP_CONVT_FWD) if which == _lib.CONV_FWD else ("t_bwd_data", _lib.PREP_CONVT_BWD_DATA))
+            ws, c.w_prepared = self._weight_ws(w, (tag, dt), nb, (prep, ci, co, 3, 2, dt))
+        else:
+            tag, prep = (("fwd", _lib.PREP_CONV_FWD) if which == _lib.CONV_FWD else ("bwd_data", _lib.PREP_CONV_BWD_DATA))
+            ws, c.w_prepared = self._weight_ws(w, (tag, ksize, stride, dt), nb, (prep, ci, co, ksize, stride, dt))
+        c.ws, c.ws_bytes = ws.data_ptr(), ws.numel()
+        return c, ws
+
+    def _conv_fwd(self, x, w, bias, act, ksize, stride, transposed, alpha, y, y_norm=None, eps=0.0):
+        """The forward map of either conv kind into the outputs the caller allocated (x, w kernel-ready)."""
+        n, ci, h, wd = x.shape
+        c, ws = self._conv(_lib.CONV_FWD, w, alpha, _dt(x), n, ci, h, wd, w.shape[3], ksize, stride, transposed)
+        bp = None if bias is None else _f32c(bias).data_ptr()
+        _lib.check(self.lib.gs_conv_fwd(c, x.data_ptr(), w.data_ptr(), bp, int(act), None if y is None else y.data_ptr(),
+                                        None if y_norm is None else y_norm.data_ptr(), float(eps), _stream()), "gs_conv_fwd")
+
+    @staticmethod
+    def _out_shape(x, co, stride, transposed):
+        n, _, h, wd = x.shape
+        return (n, co, 2 * h, 2 * wd) if transposed else (n, co, h // stride, wd // stride)
+
     def conv2d_fwd(self, x, w, ksize, stride, alpha):
         return self.conv2d_fwd_bias_act(x, w, None, ksize, stride, alpha, _lib.ACT_NONE)
 
@@ -454,168 +484,118 @@ class HipKernels(object):
         """conv2d_fwd(x, w) * mask_act'(.) through `mask` (an activation output of the result's shape) in one pass."""
         x, w, mask = _act(x), _f32c(w), _act(mask)
         n, ci, h, wd = x.shape
-        co = w.shape[3]
-        y = _empty_like_act((n, co, h // stride, wd // stride), x)
+        y = _empty_like_act(self._out_shape(x, w.shape[3], stride, False), x)
         assert mask.shape == y.shape and mask.dtype == y.dtype
-        nb = self.lib.gs_conv2d_workspace_bytes(_lib.CONV_FWD, n, h, wd, ci, co, ksize, stride, _dt(x))
-        ws, prepared = self._weight_ws(w, ("fwd", ksize, stride, _dt(x)), nb, (_lib.PREP_CONV_FWD, ci, co, ksize, stride, _dt(x)))
-        _lib.check(self.lib.gs_conv2d_fwd_mask(x.data_ptr(), w.data_ptr(), mask.data_ptr(), _mask_act(mask, mask_act), y.data_ptr(), n, h, wd, ci, co, ksize, stride,
-                                               float(alpha), _dt(x), prepared, ws.data_ptr(), ws.numel(), _stream()), "gs_conv2d_fwd_mask")
+        c, ws = self._conv(_lib.CONV_FWD, w, alpha, _dt(x), n, ci, h, wd, w.shape[3], ksize, stride)
+        _lib.check(self.lib.gs_conv_fwd_mask(c, x.data_ptr(), w.data_ptr(), mask.data_ptr(), _mask_act(mask, mask_act), y.data_ptr(), _stream()), "gs_conv_fwd_mask")
         return y
 
     def conv2d_fwd_bias_act(self, x, w, bias, ksize, stride, alpha, act, bits=None):
         """`bits` (default: whenever the result qualifies, 1/16 more bytes written): the leaky-relu result carries its sign bits behind it."""
         x, w = _act(x), _f32c(w)
-        n, ci, h, wd = x.shape
         co = w.shape[3]
         bits = _bits_wanted(x, co, act) and bits is not False
-        y = (_empty_act_with_bits if bits else _empty_like_act)((n, co, h // stride, wd // stride), x)
-        nb = self.lib.gs_conv2d_workspace_bytes(_lib.CONV_FWD, n, h, wd, ci, co, ksize, stride, _dt(x))
-        ws, prepared = self._weight_ws(w, ("fwd", ksize, stride, _dt(x)), nb, (_lib.PREP_CONV_FWD, ci, co, ksize, stride, _dt(x)))
-        bp = None
-        if bias is not None:
-            bias = _f32c(bias)
-            bp = bias.data_ptr()
-        _lib.check(self.lib.gs_conv2d_fwd_bias_act(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), n, h, wd, ci, co, ksize, stride,
-                                                   float(alpha), act | (_lib.ACT_WRITE_BITS if bits else 0), _dt(x), prepared, ws.data_ptr(), ws.numel(), _stream()),
-                   "gs_conv2d_fwd_bias_act")
+        y = (_empty_act_with_bits if bits else _empty_like_act)(self._out_shape(x, co, stride, False), x)
+        self._conv_fwd(x, w, bias, act | (_lib.ACT_WRITE_BITS if bits else 0), ksize, stride, False, alpha, y)
         return y
 
     def conv2d_fwd_bias_act_norm(self, x, w, bias, ksize, stride, alpha, act, eps, want_z=True):
         """(z, y): z = act(alpha * conv + bias), y = pixel_norm(z) -- one launch where the conv tile owns all channels of a pixel;
         z is None with want_z=False (no backward will need the activation)."""
+        return self._fwd_bias_act_norm(x, w, bias, ksize, stride, False, alpha, act, eps, want_z)
+
+    def _fwd_bias_act_norm(self, x, w, bias, ksize, stride, transposed, alpha, act, eps, want_z):
         x, w = _act(x), _f32c(w)
-        n, ci, h, wd = x.shape
-        co = w.shape[3]
-        y = _empty_like_act((n, co, h // stride, wd // stride), x)
-        z = _empty_like_act((n, co, h // stride, wd // stride), x) if want_z else None
-        nb = self.lib.gs_conv2d_workspace_bytes(_lib.CONV_FWD, n, h, wd, ci, co, ksize, stride, _dt(x))
-        ws, prepared = self._weight_ws(w, ("fwd", ksize, stride, _dt(x)), nb, (_lib.PREP_CONV_FWD, ci, co, ksize, stride, _dt(x)))
-        bp = None
-        if bias is not None:
-            bias = _f32c(bias)
-            bp = bias.data_ptr()
-        _lib.check(self.lib.gs_conv2d_fwd_bias_act_norm(x.data_ptr(), w.data_ptr(), bp, None if z is None else z.data_ptr(), y.data_ptr(), n, h, wd,
-                                                        ci, co, ksize, stride, float(alpha), act, float(eps), _dt(x), prepared, ws.data_ptr(),
-                                                        ws.numel(), _stream()), "gs_conv2d_fwd_bias_act_norm")
+        shape = self._out_shape(x, w.shape[3], stride, transposed)
+        y = _empty_like_act(shape, x)
+        z = _empty_like_act(shape, x) if want_z else None
+        self._conv_fwd(x, w, bias, act, ksize, stride, transposed, alpha, z, y, eps)
         return z, y
 
     def conv2d_transpose_fwd_bias_act_norm(self, x, w, bias, alpha, act, eps, want_z=True):
-        x, w = _act(x), _f32c(w)
-        n, ci, h, wd = x.shape
-        co = w.shape[3]
-        y = _empty_like_act((n, co, 2 * h, 2 * wd), x)
-        z = _empty_like_act((n, co, 2 * h, 2 * wd), x) if want_z else None
-        nb = self.lib.gs_conv2d_transpose_s2_workspace_bytes(_lib.CONV_FWD, n, h, wd, ci, co, _dt(x))
-        ws, prepared = self._weight_ws(w, ("t_fwd", _dt(x)), nb, (_lib.PREP_CONVT_FWD, ci, co, 3, 2, _dt(x)))
-        bp = None
-        if bias is not None:
-            bias = _f32c(bias)
-            bp = bias.data_ptr()
-        _lib.check(self.lib.gs_conv2d_transpose_s2_fwd_bias_act_norm(x.data_ptr(), w.data_ptr(), bp, None if z is None else z.data_ptr(), y.data_ptr(),
-                                                                     n, h, wd, ci, co, float(alpha), act, float(eps), _dt(x), prepared,
-                                                                     ws.data_ptr(), ws.numel(), _stream()), "gs_conv2d_transpose_s2_fwd_bias_act_norm")
-        return z, y
+        return self._fwd_bias_act_norm(x, w, bias, 3, 2, True, alpha, act, eps, want_z)
 
     def conv2d_bwd_data(self, gy, w, x_shape, ksize, stride, alpha, mask=None, mask_act=0):
         """gx, or with `mask` (the conv's forward input, itself the output of activation `mask_act`) gx * act'(.): the data
         gradient w.r.t. the previous layer's pre-activation in one pass."""
+        return self._bwd_data(gy, w, x_shape, ksize, stride, False, alpha, mask, mask_act)
+
+    def _bwd_data(self, gy, w, x_shape, ksize, stride, transposed, alpha, mask=None, mask_act=0):
         gy, w = _act(gy), _f32c(w)
         n, ci, h, wd = x_shape
-        co = w.shape[3]
         gx = _empty_like_act((n, ci, h, wd), gy)
-        nb = self.lib.gs_conv2d_workspace_bytes(_lib.CONV_BWD_DATA, n, h, wd, ci, co, ksize, stride, _dt(gy))
-        ws, prepared = self._weight_ws(w, ("bwd_data", ksize, stride, _dt(gy)), nb, (_lib.PREP_CONV_BWD_DATA, ci, co, ksize, stride, _dt(gy)))
+        c, ws = self._conv(_lib.CONV_BWD_DATA, w, alpha, _dt(gy), n, ci, h, wd, w.shape[3], ksize, stride, transposed)
         mp = None
         if mask is not None:
             mask = _act(mask)
             assert mask.shape == gx.shape and mask.dtype == gx.dtype
             mp = mask.data_ptr()
-        _lib.check(self.lib.gs_conv2d_bwd_data_mask(gy.data_ptr(), w.data_ptr(), mp, _mask_act(mask, mask_act) if mask is not None else 0, gx.data_ptr(), n, h, wd, ci, co, ksize, stride,
-                                                    float(alpha), _dt(gy), prepared, ws.data_ptr(), ws.numel(), _stream()), "gs_conv2d_bwd_data_mask")
+        _lib.check(self.lib.gs_conv_bwd_data(c, gy.data_ptr(), w.data_ptr(), mp, _mask_act(mask, mask_act) if mask is not None else 0, gx.data_ptr(), _stream()),
+                   "gs_conv_bwd_data")
         return gx
+
+    def _is_fused(self, query, x_shape, co, ksize, stride, transposed, dtype):
+        n, ci, h, wd = (int(v) for v in x_shape)
+        dt = GS_F32 if dtype == torch.float32 else GS_BF16
+        return bool(query(_lib.GsConv(n, h, wd, ci, int(co), int(ksize), int(stride), 1 if transposed else 0, dt)))
 
     def fwd_pnbwdbwd_is_fused(self, x_shape, co, ksize, stride, transposed, dtype):
         """Does conv2d[_transpose]_fwd_pnbwdbwd run as ONE launch for a conv with input x_shape and `co` output channels?"""
-        n, ci, h, wd = x_shape
-        return bool(self.lib.gs_conv2d_fwd_pnbwdbwd_is_fused(int(n), int(h), int(wd), int(ci), int(co), int(ksize), int(stride), 1 if transposed else 0,
-                                                            GS_F32 if dtype == torch.float32 else GS_BF16))
+        return self._is_fused(self.lib.gs_conv_fwd_pnbwdbwd_is_fused, x_shape, co, ksize, stride, transposed, dtype)
 
     def conv2d_fwd_pnbwdbwd(self, x, w, ksize, stride, alpha, g, z, eps, act):
         """(out_z, out_g) = both gradients of u = act'(z) pixel_norm_bwd(g, z) contracted with t = conv2d_fwd(x, w): what pixel_norm_bwd_bwd(t, g, z,
         pre_act=act, with_g=True) returns, from the conv's epilogue where its tile owns all channels of a pixel."""
+        return self._fwd_pnbwdbwd(x, w, ksize, stride, False, alpha, g, z, eps, act)
+
+    def _fwd_pnbwdbwd(self, x, w, ksize, stride, transposed, alpha, g, z, eps, act):
         x, w, g, z = _act(x), _f32c(w), _act(g), _act(z)
         n, ci, h, wd = x.shape
-        co = w.shape[3]
-        out_g = _empty_like_act((n, co, h // stride, wd // stride), x)
+        out_g = _empty_like_act(self._out_shape(x, w.shape[3], stride, transposed), x)
         assert g.shape == out_g.shape == z.shape and g.dtype == x.dtype == z.dtype
         out_z = torch.empty_like(out_g)
-        nb = self.lib.gs_conv2d_workspace_bytes(_lib.CONV_FWD, n, h, wd, ci, co, ksize, stride, _dt(x))
-        ws, prepared = self._weight_ws(w, ("fwd", ksize, stride, _dt(x)), nb, (_lib.PREP_CONV_FWD, ci, co, ksize, stride, _dt(x)))
-        _lib.check(self.lib.gs_conv2d_fwd_pnbwdbwd(x.data_ptr(), w.data_ptr(), g.data_ptr(), z.data_ptr(), int(act), float(eps), out_g.data_ptr(), out_z.data_ptr(), n, h,
-                                                   wd, ci, co, ksize, stride, float(alpha), _dt(x), prepared, ws.data_ptr(), ws.numel(), _stream()), "gs_conv2d_fwd_pnbwdbwd")
+        c, ws = self._conv(_lib.CONV_FWD, w, alpha, _dt(x), n, ci, h, wd, w.shape[3], ksize, stride, transposed)
+        _lib.check(self.lib.gs_conv_fwd_pnbwdbwd(c, x.data_ptr(), w.data_ptr(), g.data_ptr(), z.data_ptr(), int(act), float(eps), out_g.data_ptr(), out_z.data_ptr(),
+                                                 _stream()), "gs_conv_fwd_pnbwdbwd")
         return out_z, out_g
 
     def conv2d_transpose_fwd_pnbwdbwd(self, x, w, alpha, g, z, eps, act):
-        x, w, g, z = _act(x), _f32c(w), _act(g), _act(z)
-        n, ci, h, wd = x.shape
-        co = w.shape[3]
-        out_g = _empty_like_act((n, co, 2 * h, 2 * wd), x)
-        assert g.shape == out_g.shape == z.shape and g.dtype == x.dtype == z.dtype
-        out_z = torch.empty_like(out_g)
-        nb = self.lib.gs_conv2d_transpose_s2_workspace_bytes(_lib.CONV_FWD, n, h, wd, ci, co, _dt(x))
-        ws, prepared = self._weight_ws(w, ("t_fwd", _dt(x)), nb, (_lib.PREP_CONVT_FWD, ci, co, 3, 2, _dt(x)))
-        _lib.check(self.lib.gs_conv2d_transpose_s2_fwd_pnbwdbwd(x.data_ptr(), w.data_ptr(), g.data_ptr(), z.data_ptr(), int(act), float(eps), out_g.data_ptr(),
-                                                                out_z.data_ptr(), n, h, wd, ci, co, float(alpha), _dt(x), prepared, ws.data_ptr(), ws.numel(), _stream()),
-                   "gs_conv2d_transpose_s2_fwd_pnbwdbwd")
-        return out_z, out_g
+        return self._fwd_pnbwdbwd(x, w, 3, 2, True, alpha, g, z, eps, act)
 
     def bwd_data_pnbwd_is_fused(self, x_shape, co, ksize, stride, transposed, dtype):
         """Does conv2d[_transpose]_bwd_data_pnbwd run as ONE launch for a conv with input x_shape = (n, ci, h, w) and `co` output channels?"""
-        n, ci, h, wd = x_shape
-        return bool(self.lib.gs_conv2d_bwd_data_pnbwd_is_fused(int(n), int(h), int(wd), int(ci), int(co), int(ksize), int(stride), 1 if transposed else 0,
-                                                              GS_F32 if dtype == torch.float32 else GS_BF16))
+        return self._is_fused(self.lib.gs_conv_bwd_data_pnbwd_is_fused, x_shape, co, ksize, stride, transposed, dtype)
 
     def conv2d_bwd_data_pnbwd(self, gy, w, x_shape, ksize, stride, alpha, z, eps, act, addend=None):
         """(pixel_norm_bwd(conv2d_bwd_data(gy, w), z) + addend) * act'(z): the data gradient continued through the previous block's pixel norm
         and activation (z: that block's activation output, x_shape's shape) -- one launch where the conv tile owns all channels of a pixel."""
+        return self._bwd_data_pnbwd(gy, w, x_shape, ksize, stride, False, alpha, z, eps, act, addend)
+
+    def _bwd_data_pnbwd(self, gy, w, x_shape, ksize, stride, transposed, alpha, z, eps, act, addend):
         gy, w, z = _act(gy), _f32c(w), _act(z)
         n, ci, h, wd = x_shape
-        co = w.shape[3]
         assert tuple(z.shape) == (n, ci, h, wd) and z.dtype == gy.dtype
         gx = _empty_like_act((n, ci, h, wd), gy)
-        nb = self.lib.gs_conv2d_workspace_bytes(_lib.CONV_BWD_DATA, n, h, wd, ci, co, ksize, stride, _dt(gy))
-        ws, prepared = self._weight_ws(w, ("bwd_data", ksize, stride, _dt(gy)), nb, (_lib.PREP_CONV_BWD_DATA, ci, co, ksize, stride, _dt(gy)))
+        c, ws = self._conv(_lib.CONV_BWD_DATA, w, alpha, _dt(gy), n, ci, h, wd, w.shape[3], ksize, stride, transposed)
         ap = None
         if addend is not None:
             addend = _match(addend, z)
             ap = addend.data_ptr()
-        _lib.check(self.lib.gs_conv2d_bwd_data_pnbwd(gy.data_ptr(), w.data_ptr(), z.data_ptr(), ap, int(act), float(eps), gx.data_ptr(), n, h, wd, ci, co, ksize,
-                                                     stride, float(alpha), _dt(gy), prepared, ws.data_ptr(), ws.numel(), _stream()), "gs_conv2d_bwd_data_pnbwd")
+        _lib.check(self.lib.gs_conv_bwd_data_pnbwd(c, gy.data_ptr(), w.data_ptr(), z.data_ptr(), ap, int(act), float(eps), gx.data_ptr(), _stream()),
+                   "gs_conv_bwd_data_pnbwd")
         return gx
 
     def conv2d_transpose_bwd_data_pnbwd(self, gy, w, alpha, z, eps, act, addend=None):
         """The same behind a transposed conv (its data gradient is the stride-2 conv)."""
-        gy, w, z = _act(gy), _f32c(w), _act(z)
-        n, co, h2, w2 = gy.shape
-        ci = w.shape[2]
-        h, wd = h2 // 2, w2 // 2
-        assert tuple(z.shape) == (n, ci, h, wd) and z.dtype == gy.dtype
-        gx = _empty_like_act((n, ci, h, wd), gy)
-        nb = self.lib.gs_conv2d_transpose_s2_workspace_bytes(_lib.CONV_BWD_DATA, n, h, wd, ci, co, _dt(gy))
-        ws, prepared = self._weight_ws(w, ("t_bwd_data", _dt(gy)), nb, (_lib.PREP_CONVT_BWD_DATA, ci, co, 3, 2, _dt(gy)))
-        ap = None
-        if addend is not None:
-            addend = _match(addend, z)
-            ap = addend.data_ptr()
-        _lib.check(self.lib.gs_conv2d_transpose_s2_bwd_data_pnbwd(gy.data_ptr(), w.data_ptr(), z.data_ptr(), ap, int(act), float(eps), gx.data_ptr(), n, h, wd, ci, co,
-                                                                  float(alpha), _dt(gy), prepared, ws.data_ptr(), ws.numel(), _stream()),
-                   "gs_conv2d_transpose_s2_bwd_data_pnbwd")
-        return gx
+        n, _, h2, w2 = gy.shape
+        return self._bwd_data_pnbwd(gy, w, (n, w.shape[2], h2 // 2, w2 // 2), 3, 2, True, alpha, z, eps, act, addend)
 
     def conv2d_bwd_weight(self, x, gy, ksize, stride, alpha, out=None, bias_out=None):
         """gw (new tensor), or with `out` (fp32, contiguous) the gradient is ADDED into it inside the kernel.  With `bias_out`
         (needs `out`) the bias gradient sum_{n,h,w} gy is added into it by the same launches."""
+        return self._bwd_weight(x, gy, ksize, stride, False, alpha, out, bias_out)
+
+    def _bwd_weight(self, x, gy, ksize, stride, transposed, alpha, out, bias_out):
         x, gy = _act(x), _act(gy)
         n, ci, h, wd = x.shape
         co = gy.shape[1]
@@ -623,15 +603,14 @@ class HipKernels(object):
         if bias_out is not None:
             assert out is not None and bias_out.dtype == torch.float32 and bias_out.is_contiguous()
         if out is not None and self._pending is not None:
-            self._defer_wgrad(("conv", out.data_ptr(), ksize, stride, float(alpha), tuple(x.shape[1:]), tuple(gy.shape[1:]), x.dtype), x, gy, out, bias_out)
+            self._defer_wgrad(("convT" if transposed else "conv", out.data_ptr(), ksize, stride, float(alpha), tuple(x.shape[1:]), tuple(gy.shape[1:]), x.dtype),
+                              x, gy, out, bias_out)
             return gw
-        assert out is None or out.is_contiguous(), "a channel-slice target needs deferred gradients (wgrad_slice_target_ok)"
-        nb = self.lib.gs_conv2d_workspace_bytes(_lib.CONV_BWD_WEIGHT, n, h, wd, ci, co, ksize, stride, _dt(x))
-        ws = _ws(nb, x.device)
+        assert out is None or transposed or out.is_contiguous(), "a channel-slice target needs deferred gradients (wgrad_slice_target_ok)"
+        c, ws = self._conv(_lib.CONV_BWD_WEIGHT, None, alpha, _dt(x), n, ci, h, wd, co, ksize, stride, transposed, device=x.device)
         with self._adds_into(out, bias_out):
-            _lib.check(self.lib.gs_conv2d_bwd_weight_bias(x.data_ptr(), gy.data_ptr(), gw.data_ptr(), None if bias_out is None else bias_out.data_ptr(),
-                                                          n, h, wd, ci, co, ksize, stride, float(alpha), 0 if out is None else 1, _dt(x),
-                                                          ws.data_ptr(), ws.numel(), _stream()), "gs_conv2d_bwd_weight_bias")
+            _lib.check(self.lib.gs_conv_bwd_weight(c, x.data_ptr(), gy.data_ptr(), gw.data_ptr(), None if bias_out is None else bias_out.data_ptr(),
+                                                   0 if out is None else 1, _stream()), "gs_conv_bwd_weight")
         return gw
 
     def conv2d_transpose_fwd(self, x, w, alpha):
@@ -639,47 +618,16 @@ class HipKernels(object):
 
     def conv2d_transpose_fwd_bias_act(self, x, w, bias, alpha, act):
         x, w = _act(x), _f32c(w)
-        n, ci, h, wd = x.shape
-        co = w.shape[3]
-        y = _empty_like_act((n, co, 2 * h, 2 * wd), x)
-        nb = self.lib.gs_conv2d_transpose_s2_workspace_bytes(_lib.CONV_FWD, n, h, wd, ci, co, _dt(x))
-        ws, prepared = self._weight_ws(w, ("t_fwd", _dt(x)), nb, (_lib.PREP_CONVT_FWD, ci, co, 3, 2, _dt(x)))
-        bp = None
-        if bias is not None:
-            bias = _f32c(bias)
-            bp = bias.data_ptr()
-        _lib.check(self.lib.gs_conv2d_transpose_s2_fwd_bias_act(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), n, h, wd, ci, co,
-                                                                float(alpha), act, _dt(x), prepared, ws.data_ptr(), ws.numel(), _stream()),
-                   "gs_conv2d_transpose_s2_fwd_bias_act")
+        y = _empty_like_act(self._out_shape(x, w.shape[3], 2, True), x)
+        self._conv_fwd(x, w, bias, act, 3, 2, True, alpha, y)
         return y
 
     def conv2d_transpose_bwd_data(self, gy, w, alpha):
-        gy, w = _act(gy), _f32c(w)
-        n, co, h2, w2 = gy.shape
-        ci = w.shape[2]
-        h, wd = h2 // 2, w2 // 2
-        gx = _empty_like_act((n, ci, h, wd), gy)
-        nb = self.lib.gs_conv2d_transpose_s2_workspace_bytes(_lib.CONV_BWD_DATA, n, h, wd, ci, co, _dt(gy))
-        ws, prepared = self._weight_ws(w, ("t_bwd_data", _dt(gy)), nb, (_lib.PREP_CONVT_BWD_DATA, ci, co, 3, 2, _dt(gy)))
-        _lib.check(self.lib.gs_conv2d_transpose_s2_bwd_data(gy.data_ptr(), w.data_ptr(), gx.data_ptr(), n, h, wd, ci, co, float(alpha),
-                                                            _dt(gy), prepared, ws.data_ptr(), ws.numel(), _stream()), "gs_conv2d_transpose_s2_bwd_data")
-        return gx
+        n, _, h2, w2 = gy.shape
+        return self._bwd_data(gy, w, (n, w.shape[2], h2 // 2, w2 // 2), 3, 2, True, alpha)
 
     def conv2d_transpose_bwd_weight(self, x, gy, alpha, out=None):
-        x, gy = _act(x), _act(gy)
-        n, ci, h, wd = x.shape
-        co = gy.shape[1]
-        gw = torch.empty((3, 3, ci, co), dtype=torch.float32, device=x.device) if out is None else out
-        if out is not None and self._pending is not None:
-            self._defer_wgrad(("convT", out.data_ptr(), 3, 2, float(alpha), tuple(x.shape[1:]), tuple(gy.shape[1:]), x.dtype), x, gy, out, None)
-            return gw
-        nb = self.lib.gs_conv2d_transpose_s2_workspace_bytes(_lib.CONV_BWD_WEIGHT, n, h, wd, ci, co, _dt(x))
-        ws = _ws(nb, x.device)
-        with self._adds_into(out):
-            _lib.check(self.lib.gs_conv2d_transpose_s2_bwd_weight(x.data_ptr(), gy.data_ptr(), gw.data_ptr(), n, h, wd, ci, co, float(alpha),
-                                                                  0 if out is None else 1, _dt(x), ws.data_ptr(), ws.numel(), _stream()),
-                       "gs_conv2d_transpose_s2_bwd_weight")
-        return gw
+        return self._bwd_weight(x, gy, 3, 2, True, alpha, out, None)
 
     # ------------------------------------------------------------------------------ dense
     def dense_fwd(self, x, w, alpha):
@@ -1111,20 +1059,20 @@ class HipKernels(object):
         return out
 
     def conv2d_fwd_bias_ws(self, x, w, bias, ksize, stride, ws, prepared):
-        """gs_conv2d_fwd_bias_act with alpha = 1, no activation, and a workspace the CALLER keeps with its weight (`prepared`: it still
+        """gs_conv_fwd with alpha = 1, no activation, and a workspace the CALLER keeps with its weight (`prepared`: it still
         holds the re-laid operand of this weight)."""
         x = _act(x)
         n, ci, h, wd = x.shape
         co = w.shape[3]
         y = _empty_like_act((n, co, h // stride, wd // stride), x)
-        bp = None if bias is None else bias.data_ptr()
-        _lib.check(self.lib.gs_conv2d_fwd_bias_act(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), n, h, wd, ci, co, ksize, stride, 1.0, _lib.ACT_NONE,
-                                                   _dt(x), int(prepared), ws.data_ptr(), ws.numel(), _stream()), "gs_conv2d_fwd_bias_act")
+        c = _lib.GsConv(n, h, wd, ci, co, ksize, stride, 0, _dt(x), int(prepared), 1.0, ws.data_ptr(), ws.numel())
+        _lib.check(self.lib.gs_conv_fwd(c, x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(), _lib.ACT_NONE, y.data_ptr(), None, 0.0, _stream()),
+                   "gs_conv_fwd")
         return y
 
     def conv2d_fwd_workspace(self, x_shape, co, ksize, stride, dtype):
         n, ci, h, wd = x_shape
-        return _ws(self.lib.gs_conv2d_workspace_bytes(_lib.CONV_FWD, n, h, wd, ci, co, ksize, stride, dtype), torch.device("cuda"))
+        return _ws(self.lib.gs_conv_workspace_bytes(_lib.GsConv(n, h, wd, ci, co, ksize, stride, 0, dtype), _lib.CONV_FWD), torch.device("cuda"))
 
     def resnet_stem_pool(self, x, w, bias, want_stem=False, want_pool=True):
         """(stem, pool): conv 7x7 / 2 + bias (TF SAME) and max pool 3x3 / 2 of it in one kernel; stem is None unless asked for."""

@@ -37,7 +37,7 @@ enum { GS_ACT_NONE = 0, GS_ACT_LRELU = 1, GS_ACT_TANH = 2 };
 /* 1-bit leaky-relu masks (bf16 activations whose channel count is a multiple of 32).  A forward conv called with `act = GS_ACT_LRELU |
  * GS_ACT_WRITE_BITS` also leaves the SIGN BITS of its result behind it: the caller's buffer holds the activation (numel values) followed by
  * numel / 8 bytes, one 32-bit word per (pixel, 32-channel tile), bit 8 (2 h + q) + k = "channel 16 q + 8 h + k of the tile is > 0".  A masked
- * conv (gs_conv2d_fwd_mask / gs_conv2d_bwd_data_mask) called with `mask_act = GS_ACT_LRELU_BITS` is promised such a buffer as `mask` and reads
+ * conv (gs_conv_fwd_mask / gs_conv_bwd_data) called with `mask_act = GS_ACT_LRELU_BITS` is promised such a buffer as `mask` and reads
  * the words instead of the values where its epilogue can (1 / 16 of the mask bytes); everywhere else it reads the values as with GS_ACT_LRELU.
  * gs_pack_act_bits writes the words for an activation that some other kernel produced. */
 enum { GS_ACT_LRELU_BITS = 5, GS_ACT_WRITE_BITS = 16 };
@@ -99,95 +99,69 @@ int gs_allreduce_sum_f32(gs_comm* comm, float* data, int64_t count, void* stream
 int gs_comm_set_marker_us(gs_comm* comm, double us);
 int gs_broadcast_f32(gs_comm* comm, float* data, int64_t count, int root, void* stream);
 
-/* ------------------------------------------------------------------------------- conv2d
- * tf.nn.conv2d NCHW/HWIO padding=SAME (ops.py:237-243) with ksize in {1,3}, stride in {1,2}
- * (stride 2 only with ksize 3; TF SAME on an even input pads 0 before / 1 after).
- *   x [n][h][w][ci]  w [k][k][ci][co] fp32  y [n][h/stride][w/stride][co]
- *   y = alpha * conv(x, w)                       (bias / activation are separate entry points)
- * The three maps are closed under differentiation (each one's gradient is another one), which is
- * how the Python host gets the second-order terms of models.py:47,60.
+/* ------------------------------------------------------------------------------- conv2d / conv2d_transpose
+ * tf.nn.conv2d NCHW/HWIO padding=SAME (ops.py:237-243) with ksize in {1,3}, stride in {1,2} (stride 2 only with ksize 3; TF SAME on
+ * an even input pads 0 before / 1 after), and tf.nn.conv2d_transpose NCHW, 3x3, stride 2, SAME, output = 2h x 2w (ops.py:266-276: the
+ * gradient-of-conv definition out[2i+k] += x[i] * w[k][ci][co], cropped at the end).
+ *   conv:        x [n][h][w][ci]  w [k][k][ci][co] fp32  y [n][h/stride][w/stride][co]
+ *   transposed:  x [n][h][w][ci]  w [3][3][ci][co] fp32 (the STORED variable of ops.py:259-265)  y [n][2h][2w][co]
+ * A GsConv names the LAYER, in its own forward labelling, whichever of its three maps is asked for:
+ *   fwd       : y = alpha * conv(x, w)
  *   bwd_data  : gx[n][h][w][ci] = alpha * d<gy, conv(x,w)>/dx
  *   bwd_weight: gw[k][k][ci][co] = alpha * d<gy, conv(x,w)>/dw   (fp32 out)
- * (n,h,w) are always the dims of x (the conv INPUT side), for all three.
- * fwd / bwd_data first re-lay the weight into the kernel operand at the start of `ws`; `w_prepared` != 0 says that
- * `ws` still holds that operand from an earlier call with the same weight values (same map, dtype), so the
- * re-layout is skipped -- the caller keeps one persistent ws per (weight, map) between optimizer steps.
- * Every gradient-of-a-parameter entry point (bwd_weight, dense_bwd_weight, channel_sum, act_bwd_bias) takes
- * `accumulate`: 0 overwrites the output, 1 adds into it (tf.gradients sums the contributions of a variable used
- * several times; accumulating in the producing kernel replaces one read-modify-write pass per contribution). */
-size_t gs_conv2d_workspace_bytes(int which, int n, int h, int w, int ci, int co, int ksize, int stride, int dtype);
-int gs_conv2d_fwd(const void* x, const float* w_hwio, void* y, int n, int h, int w, int ci, int co,
-                  int ksize, int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream);
-/* same with the bias add + activation the reference applies right after (ops.py:244-246 + tf.nn.leaky_relu /
- * tf.nn.tanh in networks.py) fused into the GEMM epilogue: y = act(alpha * conv(x, w) + bias); bias may be NULL */
-int gs_conv2d_fwd_bias_act(const void* x, const float* w_hwio, const float* bias, void* y, int n, int h, int w, int ci, int co,
-                           int ksize, int stride, float alpha, int act, int dtype, int w_prepared, void* ws, size_t ws_bytes,
-                           void* stream);
-int gs_conv2d_bwd_data(const void* gy, const float* w_hwio, void* gx, int n, int h, int w, int ci, int co,
-                       int ksize, int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream);
-/* A generator block in one call (networks.py:44-61: conv -> leaky_relu -> pixel_norm): z = act(alpha * conv(x, w) + bias),
- * y = pixel_norm(z, eps) over the channels (ops.py:330).  The norm is fused into the conv epilogue where a tile owns every
- * channel of a pixel (co = 32 / 64 on the MFMA path), a separate pass otherwise; z may be NULL when the caller keeps no copy
- * of the activation (inference, the no-grad generator pass of the D run).  gs_conv2d_transpose_s2_fwd_bias_act_norm: same
- * for the upscaling conv. */
-int gs_conv2d_fwd_bias_act_norm(const void* x, const float* w_hwio, const float* bias, void* z, void* y, int n, int h, int w, int ci, int co,
-                                int ksize, int stride, float alpha, int act, float eps, int dtype, int w_prepared, void* ws,
-                                size_t ws_bytes, void* stream);
-int gs_conv2d_transpose_s2_fwd_bias_act_norm(const void* x, const float* w_hwio, const float* bias, void* z, void* y, int n, int h, int w,
-                                             int ci, int co, float alpha, int act, float eps, int dtype, int w_prepared, void* ws,
-                                             size_t ws_bytes, void* stream);
-/* bwd_data whose result is multiplied by the derivative of the activation that PRODUCED the conv's input, expressed through
- * that input itself: gx = conv2d_bwd_data(gy, w) * act'(.)|mask  (mask = x of the forward conv, same shape as gx; act = LRELU
- * or TANH).  It is the data gradient w.r.t. the previous layer's pre-activation in one pass (the separate act_bwd pass of the
- * previous layer disappears).  mask NULL = gs_conv2d_bwd_data. */
-int gs_conv2d_bwd_data_mask(const void* gy, const float* w_hwio, const void* mask, int mask_act, void* gx, int n, int h, int w, int ci, int co,
-                            int ksize, int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream);
-/* The same on the forward map: y = conv2d(x, w) * act'(.)|mask with mask of y's shape (the second-order pass of a gradient penalty
- * runs the convs forward on cotangents; each result meets the derivative of the activation that follows that conv). */
+ * The maps are closed under differentiation (each one's gradient is another one), which is how the Python host gets the second-order
+ * terms of models.py:47,60 -- and the transposed layer's maps are the stride-2 conv's with the two sides swapped, run by the same
+ * kernels: its fwd is that conv's bwd_data, its bwd_data that conv's fwd, its bwd_weight that conv's with x and gy exchanged, stored
+ * transposed.  The library does that relabelling in one place (conv_api.hip: conv_role).
+ * fwd / bwd_data first re-lay the weight into the kernel operand at the start of `ws`; `w_prepared` != 0 says that `ws` still holds
+ * that operand from an earlier call with the same weight values (same map, dtype), so the re-layout is skipped -- the caller keeps one
+ * persistent ws per (weight, map) between optimizer steps.  `ws` is sized by gs_conv_workspace_bytes for the map.
+ * Every gradient-of-a-parameter entry point (bwd_weight, dense_bwd_weight, channel_sum, act_bwd_bias) takes `accumulate`: 0 overwrites
+ * the output, 1 adds into it (tf.gradients sums the contributions of a variable used several times; accumulating in the producing
+ * kernel replaces one read-modify-write pass per contribution). */
+typedef struct GsConv {
+    int32_t n, h, w;             /* the layer's forward INPUT (a transposed layer's small side) */
+    int32_t ci, co, ksize, stride;
+    int32_t transposed;          /* != 0: the transposed conv (ksize 3, stride 2 only) */
+    int32_t dtype, w_prepared;
+    float alpha;
+    void* ws;
+    size_t ws_bytes;
+} GsConv;
+size_t gs_conv_workspace_bytes(const GsConv* c, int which);   /* which: GS_CONV_*; 0 for a layer the entry points refuse */
+/* y = act(alpha * conv(x, w) + bias): the bias add + activation the reference applies right after (ops.py:244-246 + tf.nn.leaky_relu /
+ * tf.nn.tanh in networks.py) ride in the GEMM epilogue; bias may be NULL, act GS_ACT_NONE.  With y_norm a generator block in one call
+ * (networks.py:44-61: conv -> leaky_relu -> pixel_norm): y_norm = pixel_norm(y, eps) over the channels (ops.py:330), fused into the
+ * conv epilogue where a tile owns every channel of a pixel (co = 32 / 64 on the MFMA path), a separate pass otherwise; y may then be
+ * NULL when the caller keeps no copy of the activation (inference, the no-grad generator pass of the D run). */
+int gs_conv_fwd(const GsConv* c, const void* x, const float* w_hwio, const float* bias, int act, void* y, void* y_norm, float eps, void* stream);
 int gs_pack_act_bits(void* z, int64_t p, int c, int dtype, void* stream);   /* z: [p][c] values followed by p * c / 8 bytes (written here); c % 32 == 0 */
-int gs_conv2d_fwd_mask(const void* x, const float* w_hwio, const void* mask, int mask_act, void* y, int n, int h, int w, int ci, int co,
-                       int ksize, int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream);
-int gs_conv2d_bwd_weight(const void* x, const void* gy, float* gw_hwio, int n, int h, int w, int ci, int co,
-                         int ksize, int stride, float alpha, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream);
-/* bwd_weight that also returns the bias gradient of the block, gb[co] (+)= sum_{n,h,w} gy (fp32; no alpha): for bf16 3x3 convs
- * the sum rides along in the same two launches (one extra MFMA per 16 pixels against an all-ones operand), other shapes fall
- * back to gs_channel_sum inside.  gb may be NULL (= gs_conv2d_bwd_weight).  `accumulate` applies to gw and gb alike. */
-int gs_conv2d_bwd_weight_bias(const void* x, const void* gy, float* gw_hwio, float* gb, int n, int h, int w, int ci, int co,
-                              int ksize, int stride, float alpha, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream);
-
-/* tf.nn.conv2d_transpose NCHW, 3x3, stride 2, SAME, output = 2h x 2w (ops.py:266-276): the
- * gradient-of-conv definition out[2i+k] += x[i] * w[k][ci][co], cropped at the end.
- *   x [n][h][w][ci]  w [3][3][ci][co] fp32 (the STORED variable of ops.py:259-265)  y [n][2h][2w][co]
- * These are thin re-labelings of the stride-2 conv2d maps above (same kernels):
- *   transpose_fwd(x,w)        = conv2d_bwd_data (gy:=x, w^T)     with conv input side = y
- *   transpose_bwd_data(gy,w)  = conv2d_fwd      (x:=gy, w^T)
- *   transpose_bwd_weight(x,gy)= conv2d_bwd_weight(x:=gy, gy:=x)^T
- * (n,h,w) are the dims of x (the LOW resolution side). */
-size_t gs_conv2d_transpose_s2_workspace_bytes(int which, int n, int h, int w, int ci, int co, int dtype);
-int gs_conv2d_transpose_s2_fwd(const void* x, const float* w_hwio, void* y, int n, int h, int w, int ci, int co,
-                               float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream);
-int gs_conv2d_transpose_s2_fwd_bias_act(const void* x, const float* w_hwio, const float* bias, void* y, int n, int h, int w,
-                                        int ci, int co, float alpha, int act, int dtype, int w_prepared, void* ws,
-                                        size_t ws_bytes, void* stream);
-int gs_conv2d_transpose_s2_bwd_data(const void* gy, const float* w_hwio, void* gx, int n, int h, int w, int ci, int co,
-                                    float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream);
+/* The forward map on a cotangent: y = conv(x, w) * act'(.)|mask with mask (an activation OUTPUT) of y's shape -- the second-order pass
+ * of a gradient penalty runs the convs forward on cotangents; each result meets the derivative of the activation that follows that
+ * conv.  mask NULL: the plain forward.  Plain convs only (GS_ERR_UNSUPPORTED for a transposed layer). */
+int gs_conv_fwd_mask(const GsConv* c, const void* x, const float* w_hwio, const void* mask, int mask_act, void* y, void* stream);
+/* The data gradient, optionally multiplied by the derivative of the activation that PRODUCED the layer's input, expressed through that
+ * input itself: gx = bwd_data(gy, w) * act'(.)|mask  (mask = x of the forward, gx's shape; mask_act = LRELU, TANH or LRELU_BITS) -- the
+ * gradient w.r.t. the previous layer's pre-activation in one pass.  mask NULL: plain; a mask is refused for a transposed layer. */
+int gs_conv_bwd_data(const GsConv* c, const void* gy, const float* w_hwio, const void* mask, int mask_act, void* gx, void* stream);
+/* Data gradient continued through the PREVIOUS block's pixel norm and activation (networks.py:41-93: conv -> leaky_relu -> pixel_norm;
+ * the backward tf.gradients builds for ops.py:330-333 behind ops.py:237-243 / 269-276), one pass where a tile owns all channels of a pixel:
+ *   gx = (pixel_norm_bwd(B^T(gy, w), z) + addend) * act'(z);  z: the previous block's activation output (gx's shape), addend: optional
+ * gs_conv_bwd_data_pnbwd_is_fused: 1 when that is one launch for the layer, 0 when it runs as the plain data gradient followed by
+ * gs_pixel_norm_bwd_fused in place. */
+int gs_conv_bwd_data_pnbwd(const GsConv* c, const void* gy, const float* w_hwio, const void* z, const void* addend, int act, float eps, void* gx, void* stream);
+int gs_conv_bwd_data_pnbwd_is_fused(const GsConv* c);
 /* Second-order pass of the mode-seeking term (models.py:57-64: tf.gradients of tf.gradients(fake_images, [latents])): the conv applied to a cotangent
  * yields t = the gradient w.r.t. u = act'(z) pixel_norm_bwd(g, z) (a block's first-order backward); with h = t act'(z) the epilogue writes
  *   out_g = pixel_norm_bwd(h, z)   and   out_z = d<h, pixel_norm_bwd(g, z)>/dz      (g, z, out_g, out_z: the conv's output shape)
- * in one pass where a tile owns all channels of a pixel (gs_conv2d_fwd_pnbwdbwd_is_fused), else as the conv + gs_pixel_norm_bwd_bwd_fused. */
-int gs_conv2d_fwd_pnbwdbwd(const void* x, const float* w_hwio, const void* g, const void* z, int act, float eps, void* out_g, void* out_z, int n, int h, int w,
-                           int ci, int co, int ksize, int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream);
-int gs_conv2d_transpose_s2_fwd_pnbwdbwd(const void* x, const float* w_hwio, const void* g, const void* z, int act, float eps, void* out_g, void* out_z, int n,
-                                        int h, int w, int ci, int co, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream);
-int gs_conv2d_fwd_pnbwdbwd_is_fused(int n, int h, int w, int ci, int co, int ksize, int stride, int transposed, int dtype);
-/* Data gradient continued through the PREVIOUS block's pixel norm and activation (networks.py:41-93: conv -> leaky_relu -> pixel_norm;
- * the backward tf.gradients builds for ops.py:330-333 behind ops.py:237-243 / 269-276), one pass where a tile owns all channels of a pixel:
- *   gx = (pixel_norm_bwd(B^T(gy, w), z) + addend) * act'(z);  z: the previous block's activation output (gx's shape), addend: optional */
-int gs_conv2d_bwd_data_pnbwd(const void* gy, const float* w_hwio, const void* z, const void* addend, int act, float eps, void* gx, int n, int h, int w,
-                             int ci, int co, int ksize, int stride, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream);
-/* 1 when that call is one launch for the shape (n, h, w: the conv's INPUT side, i.e. gx / z; transposed: the s2 transposed conv), 0 when it
- * runs as the plain data gradient followed by gs_pixel_norm_bwd_fused in place */
-int gs_conv2d_bwd_data_pnbwd_is_fused(int n, int h, int w, int ci, int co, int ksize, int stride, int transposed, int dtype);
+ * in one pass where a tile owns all channels of a pixel (gs_conv_fwd_pnbwdbwd_is_fused), else as the conv + gs_pixel_norm_bwd_bwd_fused. */
+int gs_conv_fwd_pnbwdbwd(const GsConv* c, const void* x, const float* w_hwio, const void* g, const void* z, int act, float eps, void* out_g, void* out_z, void* stream);
+int gs_conv_fwd_pnbwdbwd_is_fused(const GsConv* c);
+/* One layer's weight gradient from one (x, gy) pair, at once (a backward pass that wants all of them goes through gs_conv_wgrad_jobs).
+ * gb (optional, plain convs only): the bias gradient of the block, gb[co] (+)= sum_{n,h,w} gy (fp32; no alpha) -- for bf16 3x3 convs the
+ * sum rides along in the same two launches (one extra MFMA per 16 pixels against an all-ones operand), other shapes fall back to
+ * gs_channel_sum inside.  `accumulate` applies to gw and gb alike. */
+int gs_conv_bwd_weight(const GsConv* c, const void* x, const void* gy, float* gw_hwio, float* gb, int accumulate, void* stream);
 /* Which implicit-GEMM tile configuration a 3x3 layer runs with, asked without running it: host arithmetic only, works without a device (the CU
  * count then defaults to the MI355X's 256).  Kernel-role arguments: mode 0 stride 1 / 1 stride 2 / 2 transposed, hb x wb the base grid (the smaller
  * side of a strided map), ic -> oc the channels the kernel contracts / produces; want: the epilogue asked for, 0 none, 1 pixel norm, 2 / 3 its
@@ -198,53 +172,16 @@ int gs_conv_igemm_config(int mode, int n, int hb, int wb, int ic, int oc, int dt
  * 0: for fp32 and bf16), then A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC as above.  0 for 0 <= index < number of rows, GS_ERR_ARG past the end.  Host
  * only: no launch, no device.  tests/test_igemm_cover_*.py run one case per row and dtype. */
 int gs_conv_igemm_table(int index, int* out11);
-int gs_conv2d_transpose_s2_bwd_data_pnbwd(const void* gy, const float* w_hwio, const void* z, const void* addend, int act, float eps, void* gx, int n,
-                                          int h, int w, int ci, int co, float alpha, int dtype, int w_prepared, void* ws, size_t ws_bytes, void* stream);
-int gs_conv2d_transpose_s2_bwd_weight(const void* x, const void* gy, float* gw_hwio, int n, int h, int w, int ci, int co,
-                                      float alpha, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream);
-
-/* Deferred slice reduction of the weight gradients.  Every bwd_weight call is two phases: block-partial sums over pixel slices
- * (in ws), then a reduction over the slices into gw (+ gb).  The `_partial` entry points run phase 1 only and describe phase 2 in
- * `pending`; gs_wgrad_reduce_batch then folds many pending reductions in a handful of launches (a backward pass has ~70 of them;
- * each is a 10 us launch on its own).  Contract: the call's ws must stay untouched until gs_wgrad_reduce_batch has been enqueued
- * on the same stream; pending->nslices == 0 on return means nothing is pending (shapes without the vector reduce ran both
- * phases at once).  Entries that add into the same gw are applied in list order (the sum stays deterministic). */
-typedef struct GsWgradReduce {
-    const float* partials; /* [nslices][taps*ic*oc (+ oc when gb)] fp32, inside the call's ws */
-    float* gw;             /* [taps][ic][oc], or [taps][oc][ic] when transpose */
-    float* gb;             /* optional [oc] */
-    int32_t nslices, taps, ic, oc;
-    float alpha;
-    int32_t transpose, accumulate;
-    int32_t ic_ld;         /* 0, or the input-channel rows of the stored variable when gw is a channel slice of a wider one (not with transpose) */
-} GsWgradReduce;
-int gs_conv2d_bwd_weight_bias_partial(const void* x, const void* gy, float* gw_hwio, float* gb, int n, int h, int w, int ci, int co,
-                                      int ksize, int stride, float alpha, int accumulate, int dtype, void* ws, size_t ws_bytes,
-                                      GsWgradReduce* pending, void* stream);
-int gs_conv2d_transpose_s2_bwd_weight_partial(const void* x, const void* gy, float* gw_hwio, int n, int h, int w, int ci, int co,
-                                              float alpha, int accumulate, int dtype, void* ws, size_t ws_bytes,
-                                              GsWgradReduce* pending, void* stream);
-int gs_wgrad_reduce_batch(const GsWgradReduce* pending, int n, void* stream);   /* `pending`: host array */
-/* Several (x, gy) pairs of ONE layer in one launch: gw (+)= sum_s bwd_weight(xs[s], gys[s]) -- the real and the fake pass of the
- * discriminator, the second-order contribution of a gradient penalty.  All pairs share (h, w, ci, co); pair s has ns[s] images
- * (ns NULL: n each).  The layer then costs one set of block partials and one slice reduction instead of one per pair.  nsrc <= GS_WGRAD_MAX_SOURCES; bit s of bias_mask
- * says whether pair s contributes to gb (ignored when gb is NULL).  `pending` as above (NULL = reduce at once); ws sized by
- * gs_conv2d_workspace_bytes(GS_CONV_BWD_WEIGHT, total images, ...) / gs_conv2d_transpose_s2_workspace_bytes(.., total images, ..). */
-#define GS_WGRAD_MAX_SOURCES 4
-int gs_conv2d_bwd_weight_bias_multi(const void* const* xs, const void* const* gys, const int* ns, int nsrc, unsigned bias_mask, float* gw_hwio,
-                                    float* gb, int n, int h, int w, int ci, int co, int ksize, int stride, float alpha, int accumulate,
-                                    int dtype, void* ws, size_t ws_bytes, GsWgradReduce* pending, void* stream);
-int gs_conv2d_transpose_s2_bwd_weight_multi(const void* const* xs, const void* const* gys, const int* ns, int nsrc, float* gw_hwio, int n, int h,
-                                            int w, int ci, int co, float alpha, int accumulate, int dtype, void* ws, size_t ws_bytes,
-                                            GsWgradReduce* pending, void* stream);
 
 /* Every conv weight gradient of a backward pass in ONE call -- where `minimize` asks for the gradients of all variables of a
- * network at once (models.py:81-89).  A job is one layer: up to GS_WGRAD_MAX_SOURCES (x, gy) pairs with n[s] images each, as in
- * gs_conv2d_bwd_weight_bias_multi (conv: h, w = input size) / gs_conv2d_transpose_s2_bwd_weight_multi (transposed = 1: h, w = the
- * transposed conv's input size; no bias).  bf16 layers with >= 64 channels on both sides are grouped by kernel instantiation and each
+ * network at once (models.py:81-89).  A job is one layer (h, w, ci, co, ksize, stride, transposed as in GsConv; a transposed layer has no
+ * bias) with up to GS_WGRAD_MAX_SOURCES (x, gy) pairs of n[s] images each -- the real and the fake pass of the discriminator, the second-order
+ * contribution of a gradient penalty: gw (+)= sum_s bwd_weight(x[s], gy[s]), bit s of bias_mask says whether pair s contributes to gb.
+ * bf16 layers with >= 64 channels on both sides are grouped by kernel instantiation and each
  * group runs as one stream-K launch over the pixel tiles of all its layers + one fold: partials = blocks + (layer, channel tile)
  * runs per GROUP instead of blocks per layer, summed in a fixed order (deterministic).  Other layers take the per-layer path with
  * their reductions batched at the end.  Jobs that add into the same gw are applied in list order.  `jobs` is a host array. */
+#define GS_WGRAD_MAX_SOURCES 4
 typedef struct GsWgradJob {
     const void* x[GS_WGRAD_MAX_SOURCES];
     const void* gy[GS_WGRAD_MAX_SOURCES];
@@ -360,7 +297,6 @@ int gs_channel_fold_batch(const GsFoldJob* jobs, int njobs, void* ws, size_t ws_
  *   bwd_bwd_x: d<gg, bwd(g,x)>/dx = (r^2/C) * (-(gg.g) y - (y.g) gg - (y.gg) g + 3 (y.gg)(y.g) y / C)
  *   (d<gg, bwd(g,x)>/dg = bwd(gg, x): the Jacobian is symmetric) */
 int gs_pixel_norm_fwd(const void* x, void* y, int64_t p, int c, float eps, int dtype, void* stream);
-int gs_pixel_norm_bwd(const void* g, const void* x, void* gx, int64_t p, int c, float eps, int dtype, void* stream);
 /* The generator blocks are conv -> activation -> pixel norm, i.e. the norm's input x is an activation OUTPUT.  The passes
  * that surround the norm's gradients fold into them (act'(.) is expressed through x; act = NONE / LRELU / TANH):
  *   bwd_fused    : gx = (pixel_norm_bwd(g * pre_act'(x), x) + addend) * post_act'(x)      (addend may be NULL)
@@ -379,7 +315,6 @@ int gs_pixel_norm_bwd_fused_bias(const void* g, const void* x, const void* adden
                                  int post_act, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream);
 int gs_pixel_norm_bwd_bwd_fused(const void* gg, const void* g, const void* x, void* out, void* out_g, int64_t p, int c, float eps, int pre_act,
                                 int dtype, void* stream);
-int gs_pixel_norm_bwd_bwd(const void* gg, const void* g, const void* x, void* out, int64_t p, int c, float eps, int dtype, void* stream);
 
 /* upscale2d / downscale2d (ops.py:283-305).
  *   upscale : y[n][h*fy][w*fx][c] = x[n][h][w][c]                       (bit-exact copy)
@@ -460,7 +395,7 @@ size_t gs_mel_if_to_waveform_workspace_bytes(const gs_spectral_plan* plan, int b
 
 /* ------------------------------------------------------------------- pitch classifier, forward (GANSynth.evaluate)
  * The ResNet of networks.py:293-413 (pitch_classifier_main.py:39-50: 7x7 stem, 3x3 max pool, four stages of pre-activation residual
- * blocks with group normalisation and weight-standardised convs, global mean, dense logits).  Its 3x3 convs are gs_conv2d_fwd_bias_act
+ * blocks with group normalisation and weight-standardised convs, global mean, dense logits).  Its 3x3 convs are gs_conv_fwd
  * with alpha = 1 on standardised weights, its logits gs_dense_fwd_bias_act; the entry points below are the rest.  Deterministic:
  * fixed-order reductions, no float atomics.
  *   weight_standardize  ops.py:53-66 on an HWIO weight viewed as [fan_in][co]: per output channel (w - mean) / sqrt(var + eps),
@@ -492,7 +427,7 @@ int gs_group_norm_relu_mean(const void* x, const float* stats, const float* gamm
 
 /* ------------------------------------------------------------------- pitch classifier, training (models.py:253-299)
  * The backward of the entry points above, softmax cross-entropy and tf.train.MomentumOptimizer.  The 3x3 convs and the logits layer
- * reuse gs_conv2d_bwd_data, gs_conv2d_bwd_weight_bias and gs_dense_bwd_* on the standardised weights with alpha = 1.  Deterministic:
+ * reuse gs_conv_bwd_data, gs_conv_bwd_weight and gs_dense_bwd_* on the standardised weights with alpha = 1.  Deterministic:
  * fixed-order reductions, no float atomics.  `accumulate` != 0: the result is added into its target.
  *   group_norm_relu_bwd       y = relu(group_norm(x)): from x, its stats, gamma, beta and gy -> dx (+ addend, the identity-shortcut
  *                             gradient of a pre-activation block), dgamma [c], dbeta [c] (folded over the images in order).  The ReLU

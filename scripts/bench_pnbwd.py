@@ -1,4 +1,4 @@
-"""Fused data gradient + previous block's pixel-norm backward (gs_conv2d[_transpose_s2]_bwd_data_pnbwd) against the two separate launches,
+"""Fused data gradient + previous block's pixel-norm backward (gs_conv_bwd_data_pnbwd) against the two separate launches,
 on the three full-size shapes that have the epilogue form.  Burst timing (50 back-to-back calls between one event pair)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,4 +1,4 @@
-"""Second-order form: forward conv on a cotangent + both gradients of the block's norm-backward node (gs_conv2d[_transpose_s2]_fwd_pnbwdbwd)
+"""Second-order form: forward conv on a cotangent + both gradients of the block's norm-backward node (gs_conv_fwd_pnbwdbwd)
 against the two separate launches (conv, gs_pixel_norm_bwd_bwd_fused), on the four full-size shapes with the epilogue form.  Burst timing."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

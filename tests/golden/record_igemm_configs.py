@@ -40,28 +40,35 @@ def shapes():
     return out
 
 
-def api_args_is_fused(entry, mode, n, hb, wb, ic, oc, dtype):
-    """Kernel-role shape -> the (n, h, w, ci, co, ksize, stride, transposed, dtype) the `*_is_fused` entry point takes for it."""
+def layer_is_fused(entry, mode, n, hb, wb, ic, oc, dtype):
+    """Kernel-role shape -> the layer (GsConv) the `*_is_fused` entry point is asked about for it."""
     transposed = mode != S1
     ci, co = (oc, ic) if entry == 0 else (ic, oc)   # a data gradient contracts the layer's OUTPUT channels
-    return n, hb, wb, ci, co, 3, 2 if transposed else 1, 1 if transposed else 0, dtype
+    return _lib.GsConv(n, hb, wb, ci, co, 3, 2 if transposed else 1, 1 if transposed else 0, dtype)
 
 
 FUSED_MODES = {0: (S1, S2), 1: (S1, T2)}   # the igemm mode behind each entry point, plain / transposed layer
 
 
 def drive(lib, mode, dtype, n, hb, wb, ic, oc, want):
-    """Calls the entry point that reaches the dispatch with this kernel-role shape and epilogue (tests/igemm_cover.py: api_call names it and
-    layer_args turns the shape into its arguments); False where the ABI has none."""
+    """Calls the entry point that reaches the dispatch with this kernel-role shape and epilogue (tests/igemm_cover.py: api_call says which map of
+    which layer that is and layer_args turns the shape into the layer's); False where the ABI has none."""
     call = api_call(mode, want)
     if call is None:
         return False   # (no data gradient runs as the transposed kernel with a norm behind it)
     P = ctypes.c_void_p(0x10000)   # never dereferenced
     act, eps = _lib.ACT_LRELU, 1e-8
-    tensors = {PLAIN: (P, P, P), NORM_FWD: (P, P, None, P, P), NORM_BWD: (P, P, P, None, act, eps, P), NORM_BWD2: (P, P, P, P, act, eps, P, P)}[want]
-    shape = layer_args(call, n, hb, wb, ic, oc) + (() if call.transposed else (3, call.stride))
-    scalars = (1.0, act, eps) if want == NORM_FWD else (1.0,)
-    getattr(lib, call.name)(*tensors, *shape, *scalars, dtype, 1, P, 1 << 30, None)
+    c = _lib.GsConv(*layer_args(call, n, hb, wb, ic, oc), 3, call.stride, call.transposed, dtype, 1, 1.0, P, 1 << 30)
+    if want == PLAIN and call.data_grad:
+        lib.gs_conv_bwd_data(c, P, P, None, 0, P, None)
+    elif want == PLAIN:
+        lib.gs_conv_fwd(c, P, P, None, _lib.ACT_NONE, P, None, 0.0, None)
+    elif want == NORM_FWD:
+        lib.gs_conv_fwd(c, P, P, None, act, P, P, eps, None)
+    elif want == NORM_BWD:
+        lib.gs_conv_bwd_data_pnbwd(c, P, P, P, None, act, eps, P, None)
+    else:
+        lib.gs_conv_fwd_pnbwdbwd(c, P, P, P, P, act, eps, P, P, None)
     return True
 
 
@@ -95,9 +102,9 @@ def main():
                         if r[9:] not in distinct:
                             distinct.append(r[9:])
                         line += LETTERS[distinct.index(r[9:])]
-                    for entry, fn in enumerate((lib.gs_conv2d_bwd_data_pnbwd_is_fused, lib.gs_conv2d_fwd_pnbwdbwd_is_fused)):
+                    for entry, fn in enumerate((lib.gs_conv_bwd_data_pnbwd_is_fused, lib.gs_conv_fwd_pnbwdbwd_is_fused)):
                         if mode in FUSED_MODES[entry]:
-                            answers[entry] += str(fn(*api_args_is_fused(entry, mode, n, hb, wb, ic, oc, dtype)))
+                            answers[entry] += str(fn(layer_is_fused(entry, mode, n, hb, wb, ic, oc, dtype)))
                 choice.append(line)
                 for entry in (0, 1):
                     if mode in FUSED_MODES[entry]:

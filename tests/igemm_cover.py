@@ -39,7 +39,7 @@ GRID_OC = (32, 64, 96, 128, 256, 352, 512)   # 352: see the module docstring of 
 
 Kernel = namedtuple("Kernel", "mode dtype cfg")          # cfg: the nine IgemmCfg fields as a tuple of ints
 Shape = namedtuple("Shape", "n hb wb ic oc want")        # kernel-role shape: hb x wb the base grid, ic -> oc what the kernel contracts / produces
-# a public entry point and how it sees a kernel-role shape: `transposed` the transposed-conv family, `stride` the layer's, `data_grad` a data
+# a HipKernels method (`name`) and how it sees a kernel-role shape: `transposed` the transposed-conv family, `stride` the layer's, `data_grad` a data
 # gradient (the kernel contracts the layer's OUTPUT channels)
 Call = namedtuple("Call", "name transposed stride data_grad")
 
@@ -137,18 +137,18 @@ def assignment():
 
 _CALLS = {
     # a plain launch is reached through both entry points of its mode: their weight preparation differs
-    (S1, PLAIN): (Call("gs_conv2d_fwd", 0, 1, 0), Call("gs_conv2d_bwd_data", 0, 1, 1)),
-    (S2, PLAIN): (Call("gs_conv2d_fwd", 0, 2, 0), Call("gs_conv2d_transpose_s2_bwd_data", 1, 2, 1)),
-    (T2, PLAIN): (Call("gs_conv2d_transpose_s2_fwd", 1, 2, 0), Call("gs_conv2d_bwd_data", 0, 2, 1)),
-    (S1, NORM_FWD): (Call("gs_conv2d_fwd_bias_act_norm", 0, 1, 0),),
-    (S2, NORM_FWD): (Call("gs_conv2d_fwd_bias_act_norm", 0, 2, 0),),
-    (T2, NORM_FWD): (Call("gs_conv2d_transpose_s2_fwd_bias_act_norm", 1, 2, 0),),
-    (S1, NORM_BWD): (Call("gs_conv2d_bwd_data_pnbwd", 0, 1, 1),),
-    (S2, NORM_BWD): (Call("gs_conv2d_transpose_s2_bwd_data_pnbwd", 1, 2, 1),),
+    (S1, PLAIN): (Call("conv2d_fwd", 0, 1, 0), Call("conv2d_bwd_data", 0, 1, 1)),
+    (S2, PLAIN): (Call("conv2d_fwd", 0, 2, 0), Call("conv2d_transpose_bwd_data", 1, 2, 1)),
+    (T2, PLAIN): (Call("conv2d_transpose_fwd", 1, 2, 0), Call("conv2d_bwd_data", 0, 2, 1)),
+    (S1, NORM_FWD): (Call("conv2d_fwd_bias_act_norm", 0, 1, 0),),
+    (S2, NORM_FWD): (Call("conv2d_fwd_bias_act_norm", 0, 2, 0),),
+    (T2, NORM_FWD): (Call("conv2d_transpose_fwd_bias_act_norm", 1, 2, 0),),
+    (S1, NORM_BWD): (Call("conv2d_bwd_data_pnbwd", 0, 1, 1),),
+    (S2, NORM_BWD): (Call("conv2d_transpose_bwd_data_pnbwd", 1, 2, 1),),
     # (T2, NORM_BWD): no data gradient runs as the transposed kernel with a norm behind it
-    (S1, NORM_BWD2): (Call("gs_conv2d_fwd_pnbwdbwd", 0, 1, 0),),
-    (S2, NORM_BWD2): (Call("gs_conv2d_fwd_pnbwdbwd", 0, 2, 0),),
-    (T2, NORM_BWD2): (Call("gs_conv2d_transpose_s2_fwd_pnbwdbwd", 1, 2, 0),),
+    (S1, NORM_BWD2): (Call("conv2d_fwd_pnbwdbwd", 0, 1, 0),),
+    (S2, NORM_BWD2): (Call("conv2d_fwd_pnbwdbwd", 0, 2, 0),),
+    (T2, NORM_BWD2): (Call("conv2d_transpose_fwd_pnbwdbwd", 1, 2, 0),),
 }
 
 

@@ -71,13 +71,13 @@ def test_is_fused_answers_are_the_recorded_ones_and_the_choosers():
     lib = _lib.load()
     _, fused = _table()
     assert len(fused) == 2720
-    entries = (lib.gs_conv2d_bwd_data_pnbwd_is_fused, lib.gs_conv2d_fwd_pnbwdbwd_is_fused)
+    entries = (lib.gs_conv_bwd_data_pnbwd_is_fused, lib.gs_conv_fwd_pnbwdbwd_is_fused)
     seen = set()
     for entry, mode, dtype, n, hb, wb, ic, oc, answer in fused:
         assert mode in ((S1, S2), (S1, T2))[entry]
         transposed = mode != S1
         ci, co = (oc, ic) if entry == 0 else (ic, oc)   # a data gradient contracts the layer's OUTPUT channels
-        got = entries[entry](n, hb, wb, ci, co, 3, 2 if transposed else 1, 1 if transposed else 0, dtype)
+        got = entries[entry](_lib.GsConv(n, hb, wb, ci, co, 3, 2 if transposed else 1, 1 if transposed else 0, dtype))
         want = (NORM_BWD, NORM_BWD2)[entry]
         assert got == answer, (entry, mode, dtype, n, hb, wb, ic, oc)
         assert bool(got) == (_config(lib, mode, n, hb, wb, ic, oc, dtype, want)[6] == want), (entry, mode, dtype, n, hb, wb, ic, oc)

@@ -78,10 +78,8 @@ def test_reference_agrees_with_the_cpu_emulation(mode, second):
     s = C.Shape(2, 3, 5, 32, 64, C.PLAIN)
     a, wt, alpha = C.plain_inputs(call, s, seed=1)
     n, h, w, ci, co = C.layer_args(call, *s[:5])
-    emu = {"gs_conv2d_fwd": lambda: E.conv2d_fwd(a, wt, 3, call.stride, alpha),
-           "gs_conv2d_bwd_data": lambda: E.conv2d_bwd_data(a, wt, (n, ci, h, w), 3, call.stride, alpha),
-           "gs_conv2d_transpose_s2_fwd": lambda: E.conv2d_transpose_fwd(a, wt, alpha),
-           "gs_conv2d_transpose_s2_bwd_data": lambda: E.conv2d_transpose_bwd_data(a, wt, alpha)}[call.name]()
+    conv = () if call.transposed else (3, call.stride)
+    emu = E.conv2d_bwd_data(a, wt, (n, ci, h, w), *conv, alpha) if (call.data_grad and not call.transposed) else getattr(E, call.name)(a, wt, *conv, alpha)
     ref = C.conv_ref64(call, a, wt, alpha)
     assert tuple(ref.shape) == tuple(emu.shape) and ref.dtype == torch.float64
     assert C.ratio(emu, ref) <= 1e-5   # fp32 accumulation of 9 * 32 resp. 9 * 64 terms

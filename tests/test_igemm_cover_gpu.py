@@ -39,14 +39,10 @@ def _dev(t, dtype=torch.float32):
 
 def _run_plain(K, call, a, wt, alpha, s):
     n, h, w, ci, co = C.layer_args(call, *s[:5])
-    if call.name == "gs_conv2d_fwd":
-        return K.conv2d_fwd(a, wt, 3, call.stride, alpha)
-    if call.name == "gs_conv2d_bwd_data":
-        return K.conv2d_bwd_data(a, wt, (n, ci, h, w), 3, call.stride, alpha)
-    if call.name == "gs_conv2d_transpose_s2_fwd":
-        return K.conv2d_transpose_fwd(a, wt, alpha)
-    assert call.name == "gs_conv2d_transpose_s2_bwd_data"
-    return K.conv2d_transpose_bwd_data(a, wt, alpha)
+    conv = () if call.transposed else (3, call.stride)   # (the transposed methods take no kernel size and stride)
+    if call.data_grad and not call.transposed:
+        return K.conv2d_bwd_data(a, wt, (n, ci, h, w), *conv, alpha)
+    return getattr(K, call.name)(a, wt, *conv, alpha)
 
 
 def check_kernel(K, E, kernel, shapes):

@@ -444,7 +444,7 @@ def test_parameter_gradients_accumulate_in_kernel(K, E, dtype):
 @pytest.mark.parametrize("case", [(2, 32, 32, 8, 128, 3, 1), (2, 64, 64, 8, 64, 3, 1), (2, 64, 128, 8, 64, 3, 2), (2, 32, 64, 8, 128, 3, 2),
                                   (4, 256, 256, 2, 16, 3, 1), (2, 2, 32, 8, 64, 1, 1)])
 def test_bias_gradient_rides_with_weight_gradient(K, E, case, dtype):
-    """gs_conv2d_bwd_weight_bias: gb += sum over pixels of gy from the weight-gradient launches (bf16 MFMA kernels) or the
+    """gs_conv_bwd_weight with gb: gb += sum over pixels of gy from the weight-gradient launches (bf16 MFMA kernels) or the
     channel-sum fallback (fp32 / thin shapes)."""
     n, ci, co, h, w, ks, st = case
     x = rnd(n, ci, h, w, seed=1).to(dtype).float()
@@ -461,7 +461,7 @@ def test_bias_gradient_rides_with_weight_gradient(K, E, case, dtype):
                                   (4, 256, 256, 2, 16, 3, 1), (2, 64, 32, 6, 40, 3, 1), (2, 2, 32, 8, 64, 1, 1)])
 @pytest.mark.parametrize("act", [1, 2])
 def test_conv2d_bwd_data_with_activation_mask(K, E, case, dtype, act):
-    """gs_conv2d_bwd_data_mask: gx = bwd_data(gy, w) * act'(.) through the activation output that was the conv's input."""
+    """gs_conv_bwd_data with a mask: gx = bwd_data(gy, w) * act'(.) through the activation output that was the conv's input."""
     n, ci, co, h, w, ks, st = case
     wt = rnd(ks, ks, ci, co, seed=2)
     wr = wt.to(dtype).float() if (dtype == torch.bfloat16 and ks == 3) else wt
@@ -658,7 +658,7 @@ def test_deferred_bias_gradient_folds_match_immediate_ones(K, dtype):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_deferred_weight_gradient_reductions_match_immediate_ones(K, dtype):
-    """Deferred weight gradients (gs_*_bwd_weight*_multi + gs_wgrad_reduce_batch): the (x, gy) pairs of a layer contracted by one
+    """Deferred weight gradients (gs_conv_wgrad_jobs): the (x, gy) pairs of a layer contracted by one
     launch and the slice partials of all layers folded together -- equal (to fp32 rounding) to one immediate call per pair,
     including sources without a bias contribution, the transposed conv, the thin / direct kernels and more layers than one
     reduction launch holds."""
@@ -700,7 +700,7 @@ def test_deferred_weight_gradient_reductions_match_immediate_ones(K, dtype):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_multi_source_weight_gradient_matches_oracle(K, E, dtype):
-    """gs_conv2d_bwd_weight_bias_multi against the CPU restatement: gw = sum over the pairs, gb over the masked ones."""
+    """The multi-source weight gradient (gs_conv_wgrad_jobs) against the CPU restatement: gw = sum over the pairs, gb over the masked ones."""
     for (n, ci, co, h, w, ks, st) in [(2, 64, 64, 8, 64, 3, 1), (2, 32, 64, 8, 128, 3, 2), (1, 128, 64, 6, 40, 3, 1)]:
         xs = [rnd(n, ci, h, w, seed=70 + i).to(dtype).float() for i in range(3)]
         gys = [rnd(n, co, h // st, w // st, seed=80 + i).to(dtype).float() for i in range(3)]
@@ -846,7 +846,7 @@ def test_throwaway_streams(K):
 @pytest.mark.parametrize("case", [("conv", 2, 32, 32, 8, 128), ("conv", 8, 64, 64, 64, 512), ("conv", 2, 64, 64, 8, 64), ("conv", 2, 256, 256, 4, 32),
                                   ("convT", 2, 64, 32, 8, 64), ("convT", 8, 128, 64, 32, 256), ("convT", 2, 256, 256, 4, 32)])
 def test_conv_bias_act_norm_in_one_call(K, E, case, dtype):
-    """gs_conv2d[_transpose_s2]_fwd_bias_act_norm: (z, y) = (act(conv + b), pixel_norm(z)) -- fused into the conv epilogue for the
+    """gs_conv_fwd with y_norm, both conv kinds: (z, y) = (act(conv + b), pixel_norm(z)) -- fused into the conv epilogue for the
     32- / 64-channel tiles (first, second, fifth and sixth case), conv + separate norm pass otherwise; with and without z."""
     check_conv_bias_act_norm(K, E, case, dtype)
 
@@ -878,7 +878,7 @@ def check_conv_bias_act_norm(K, E, case, dtype):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("case", [(2, 32, 32, 8, 128, 3, 1), (2, 64, 64, 8, 64, 3, 1), (2, 64, 128, 8, 64, 3, 2), (2, 32, 64, 8, 128, 3, 2), (2, 2, 32, 8, 64, 1, 1)])
 def test_conv2d_fwd_with_activation_mask(K, E, case, dtype):
-    """gs_conv2d_fwd_mask: conv2d(x, w) * lrelu'(.) through an activation output of the result's shape (epilogue for >= 64 output
+    """gs_conv_fwd_mask: conv2d(x, w) * lrelu'(.) through an activation output of the result's shape (epilogue for >= 64 output
     channels, in place after the conv otherwise)."""
     n, ci, co, h, w, ks, st = case
     x = rnd(n, ci, h, w, seed=1).to(dtype).float()
@@ -940,7 +940,7 @@ def test_gan_losses_in_one_launch(K, dtype):
                                   ("conv1", 8, 32, 2, 128, 1024), ("conv1", 2, 64, 2, 8, 64), ("conv1", 2, 256, 2, 4, 32), ("conv1", 3, 128, 2, 5, 7)])   # the colour block (1x1)
 @pytest.mark.parametrize("with_addend", [False, True])
 def test_data_gradient_continued_through_the_previous_pixel_norm(K, E, case, dtype, with_addend):
-    """gs_conv2d[_transpose_s2]_bwd_data_pnbwd: (pixel_norm_bwd(B^T(gy, w), z) + addend) * leaky_relu'(z) in the conv's epilogue (the 32- /
+    """gs_conv_bwd_data_pnbwd, both conv kinds: (pixel_norm_bwd(B^T(gy, w), z) + addend) * leaky_relu'(z) in the conv's epilogue (the 32- /
     64-channel full-size layers) or as conv + in-place norm backward (every other shape).  Reference = the float64 definition of the norm
     backward applied to the ORACLE-side data gradient (tests/cpu_kernels.py: torch-CPU autograd of oracle.torch_ref's conv on the same
     inputs -- nothing of the HIP path feeds the reference); second, the two separate HIP kernels.  In bf16 the separate path rounds the
@@ -990,7 +990,7 @@ def check_data_gradient_through_pixel_norm(K, E, case, dtype, with_addend):
                                   ("convT", 8, 128, 64, 32, 256), ("conv", 2, 32, 32, 8, 128), ("conv", 2, 8, 64, 8, 64), ("convT", 2, 16, 32, 8, 64),
                                   ("conv", 2, 256, 256, 4, 32), ("convT", 2, 128, 64, 4, 32), ("conv", 1, 40, 64, 6, 40), ("conv", 3, 5, 8, 5, 7)])
 def test_second_order_norm_gradients_in_the_forward_conv(K, E, case, dtype):
-    """gs_conv2d[_transpose_s2]_fwd_pnbwdbwd: with t = conv(x, w) the cotangent of u = act'(z) pixel_norm_bwd(g, z), both gradients of that
+    """gs_conv_fwd_pnbwdbwd, both conv kinds: with t = conv(x, w) the cotangent of u = act'(z) pixel_norm_bwd(g, z), both gradients of that
     node (w.r.t. g and w.r.t. z) from the conv's epilogue, against a float64 autograd evaluation of the definition on the ORACLE-side fp32
     conv output (tests/cpu_kernels.py: oracle.torch_ref's conv on the same inputs -- nothing of the HIP path feeds the reference) and against
     the two-kernel path (conv, then gs_pixel_norm_bwd_bwd_fused).  bf16: compared at bf16 resolution of each tensor's scale."""
@@ -1058,7 +1058,7 @@ def test_dense_units_to_channels_last_in_the_activation_pass(K, shape, dtype):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("shape", [(8, 2, 32, 128, 1024), (2, 2, 64, 16, 128), (3, 1, 32, 5, 7), (2, 3, 8, 4, 4)])
 def test_colour_block_forward_with_the_next_node_s_mask(K, shape, dtype):
-    """gs_conv2d_fwd_mask on the 1x1 colour -> features conv (second-order pass of the R1 term): the streaming kernel multiplies by
+    """gs_conv_fwd_mask on the 1x1 colour -> features conv (second-order pass of the R1 term): the streaming kernel multiplies by
     leaky_relu'(.) through the mask itself -- same values as the conv followed by gs_act_bwd (one rounding instead of two in bf16)."""
     n, ci, co, h, w = shape
     gen = torch.Generator(device="cuda").manual_seed(6)

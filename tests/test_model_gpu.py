@@ -491,7 +491,7 @@ def test_norm_backward_rides_in_the_data_gradient_convs_at_full_size(gpu_store):
 def test_second_order_norm_kernels_ride_in_the_cotangent_convs_at_full_size(gpu_store):
     """Same shapes: in the second-order pass of the mode-seeking term (models.py:57-64) the convs run forward on cotangents, and where their
     tile owns all channels of a pixel both gradients of the block's (leaky_relu -> pixel_norm) backward node come out of the conv's epilogue
-    (gs_conv2d[_transpose_s2]_fwd_pnbwdbwd) -- the four 32- / 64-channel layers; counted, and the step equals the one with the fusion
+    (gs_conv_fwd_pnbwdbwd) -- the four 32- / 64-channel layers; counted, and the step equals the one with the fusion
     switched off (functional._FUSE_NORM_BWD2) up to bf16 rounding of the cotangent the fused path never stores."""
     from gansynth_amd import functional as F, kernels, variables
     K = kernels.get()
