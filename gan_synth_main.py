@@ -12,6 +12,12 @@ classifier's features of real and generated notes (:111-124); `--classifier` nam
 TensorFlow GraphDef, read without TensorFlow) or the same weights as a .safetensors file:
 
     python gan_synth_main.py --evaluate --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
+
+`--synthesize` (not in the reference) renders a score -- a Standard MIDI File or a JSON list of {"pitch", "velocity", "start", "end"}
+notes -- into one 16 kHz 16-bit WAV: every note generated at its pitch, the timbre gliding between latent anchors, the mixdown on the
+device (GANSynth.synthesize).  It needs no dataset:
+
+    python gan_synth_main.py --synthesize score.mid --model_dir gan_synth_model --output score.wav
 """
 import argparse
 import glob
@@ -37,6 +43,33 @@ parser.add_argument("--save_checkpoint_steps", type=int, default=1000)
 parser.add_argument("--log_tensor_steps", type=int, default=100)
 parser.add_argument("--save_summary_steps", type=int, default=100, help="TensorBoard summaries into --model_dir every this many steps (0: off)")
 parser.add_argument("--num_generate_batches", type=int, default=None, help="stop --generate after this many batches (synthetic input never ends)")
+parser.add_argument("--synthesize", type=str, default=None, metavar="PATH", help="render a score (.mid, .midi or .json) into --output")
+parser.add_argument("--output", type=str, default="synthesized.wav", help="the WAV file --synthesize writes")
+parser.add_argument("--seconds_per_instrument", type=float, default=6.0, help="--synthesize: seconds between two latent anchors")
+parser.add_argument("--release_seconds", type=float, default=1.0, help="--synthesize: length of a note's linear release")
+parser.add_argument("--seed", type=int, default=0, help="--synthesize: seed of the latent anchors (a generator of their own)")
+
+
+def synthesize_to_wav(model, args, pitches, restore=True, log=print):
+    """--synthesize: the score args.synthesize through GANSynth.synthesize into the 16-bit WAV args.output (the kernel's own PCM)."""
+    from scipy.io import wavfile
+    from gansynth_amd import checkpoint
+    if os.path.splitext(args.synthesize)[1].lower() not in (".mid", ".midi", ".json"):
+        raise SystemExit(f"--synthesize takes a .mid, .midi or .json score (got {args.synthesize})")
+    if restore and checkpoint.latest(args.model_dir) is None:
+        log("no checkpoint found: synthesizing from the initial weights")
+        restore = False
+    info = {}
+    _, pcm = model.synthesize(args.synthesize, model_dir=args.model_dir if restore else None, seed=args.seed,
+                              seconds_per_instrument=args.seconds_per_instrument, release_seconds=args.release_seconds,
+                              want_pcm=True, info=info, pitches=pitches, batch_size=args.batch_size)
+    if restore:
+        log(f"restored {model.restored_from}")
+    rate = int(model.spectral_params["sample_rate"])
+    wavfile.write(args.output, rate=rate, data=pcm.cpu().numpy())
+    log(f"{len(info['notes'])} notes kept, {info['dropped']} dropped, {info['total_samples'] / rate:.3f} seconds, "
+        f"peak {info['peak']:.4f}: written to {args.output}")
+    return info
 
 
 def main(args):
@@ -75,7 +108,8 @@ def main(args):
         return nsynth_input_fn(files, args.batch_size, args.num_epochs if train else 1, shuffle=train, pitches=pitches,
                                sources=[0], device=device, seed=rank)
 
-    real_input_fn = real_input_fn_factory(args.train)
+    # (--synthesize alone reads no dataset: its pitches come from the score)
+    real_input_fn = real_input_fn_factory(args.train) if (args.train or args.evaluate or args.generate) else None
     model = GANSynth(
         generator=pggan.generator, discriminator=pggan.discriminator,
         real_input_fn=real_input_fn,
@@ -137,6 +171,11 @@ def main(args):
                 num_waveforms += 1
             batches += 1
         print(f"{num_waveforms} waveforms are generated in `samples` directory")
+
+    if args.synthesize is not None:   # one process
+        if world > 1:
+            raise SystemExit("--synthesize runs in one process: launch it without torch.distributed")
+        synthesize_to_wav(model, args, pitches, restore=not args.train)
 
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -141,6 +141,8 @@ SIGNATURES = {
     "gs_summary_image_u8_workspace_bytes": (Z, [I, L, I]),
     "gs_summary_image_u8": (I, [P, P, I, L, I, I, P, Z, P]),
     "gs_summary_audio_s16": (I, [P, P, I, L, L, I, P]),
+    "gs_note_mix_workspace_bytes": (Z, [L]),
+    "gs_note_mix": (I, [P, I, L, L, P, I, L, I, P, P, P, P, Z, P]),
 }
 
 WGRAD_MAX_SOURCES = 4   # GS_WGRAD_MAX_SOURCES
@@ -169,6 +171,14 @@ class GsWsDesc(ctypes.Structure):
     """include/gansynth_hip.h: one weight of gs_weight_standardize_batch / _bwd_batch (the table lives in device memory)."""
     _fields_ = [("w", c_void_p), ("out", c_void_p), ("rstd", c_void_p), ("gout", c_void_p), ("gw", c_void_p),
                 ("fan_in", ctypes.c_int32), ("co", ctypes.c_int32)]
+
+
+MIX_TILE = 4096   # GS_MIX_TILE: output samples per block of gs_note_mix
+
+
+class GsMixNote(ctypes.Structure):
+    """include/gansynth_hip.h: one note of gs_note_mix's table (24 bytes; the table lives in device memory, sorted by onset)."""
+    _fields_ = [("onset", ctypes.c_int64), ("hold", ctypes.c_int32), ("release", ctypes.c_int32), ("row", ctypes.c_int32), ("gain", c_float)]
 
 
 _lib = None

@@ -178,6 +178,35 @@ __device__ inline float block_sum(float v, float* smem /* >= NT/64 floats */) {
     return r;
 }
 
+// ------------------------------------------------------------- wave64 extremes (summary.hip, synth.hip)
+// v[lane] op v[lane ^ 16] / v[lane ^ 32]: the swaps of swap16_sum / swap32_sum above (same wait states), both halves returned
+__device__ inline void swap16_pair(float v, float& a, float& b) {
+    a = v;
+    asm volatile("v_mov_b32 %1, %0\n\ts_nop 4\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 4" : "+v"(a), "=&v"(b));
+}
+__device__ inline void swap32_pair(float v, float& a, float& b) {
+    a = v;
+    asm volatile("v_mov_b32 %1, %0\n\ts_nop 4\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 4" : "+v"(a), "=&v"(b));
+}
+template <bool MAX> __device__ inline float pick(float a, float b) { return MAX ? fmaxf(a, b) : fminf(a, b); }
+template <bool MAX> __device__ inline float wave_extreme(float v) {   // over the 64 lanes, result in every lane
+    v = pick<MAX>(v, dpp_mov<0xB1>(v));
+    v = pick<MAX>(v, dpp_mov<0x4E>(v));
+    v = pick<MAX>(v, dpp_mov<0x141>(v));
+    v = pick<MAX>(v, dpp_mov<0x140>(v));
+    float a, b;
+    swap16_pair(v, a, b);
+    v = pick<MAX>(a, b);
+    swap32_pair(v, a, b);
+    return pick<MAX>(a, b);
+}
+
+// TF's FloatToInt16Sample: roundf(x * 32768) clamped to the int16 range (the product is exact: a power of two); NaN -> 0
+__device__ inline int quantise_s16(float x) {
+    const float r = fminf(fmaxf(roundf(x * 32768.f), -32768.f), 32767.f);
+    return x != x ? 0 : (int)r;
+}
+
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

@@ -17,28 +17,6 @@ template <typename T, int C> struct Pack { static constexpr int PX = (sizeof(T) 
 
 __device__ inline bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
-// v[lane] op v[lane ^ 16] / v[lane ^ 32]: the swaps of gs_common.h's swap16_sum / swap32_sum (same wait states), both halves returned
-__device__ inline void swap16_pair(float v, float& a, float& b) {
-    a = v;
-    asm volatile("v_mov_b32 %1, %0\n\ts_nop 4\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 4" : "+v"(a), "=&v"(b));
-}
-__device__ inline void swap32_pair(float v, float& a, float& b) {
-    a = v;
-    asm volatile("v_mov_b32 %1, %0\n\ts_nop 4\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 4" : "+v"(a), "=&v"(b));
-}
-template <bool MAX> __device__ inline float pick(float a, float b) { return MAX ? fmaxf(a, b) : fminf(a, b); }
-template <bool MAX> __device__ inline float wave_extreme(float v) {   // over the 64 lanes, result in every lane
-    v = pick<MAX>(v, dpp_mov<0xB1>(v));
-    v = pick<MAX>(v, dpp_mov<0x4E>(v));
-    v = pick<MAX>(v, dpp_mov<0x141>(v));
-    v = pick<MAX>(v, dpp_mov<0x140>(v));
-    float a, b;
-    swap16_pair(v, a, b);
-    v = pick<MAX>(a, b);
-    swap32_pair(v, a, b);
-    return pick<MAX>(a, b);
-}
-
 // PX consecutive pixels of one image, channels interleaved -> v[c][i]; `src` is 16-byte aligned
 template <typename T, int C, int PX> __device__ inline void load_pixels(const T* src, float (&v)[C][PX]) {
     constexpr int W = Wide<T>::N;
@@ -187,12 +165,7 @@ __global__ __launch_bounds__(SUM_NT) void summary_image_u8_kernel(const T* __res
 }
 
 // ------------------------------------------------------------------------------------------------ audio
-// TF's FloatToInt16Sample: roundf(x * 32768) clamped to the int16 range (the product is exact: a power of two); NaN -> 0
-__device__ inline int quantise_s16(float x) {
-    const float r = fminf(fmaxf(roundf(x * 32768.f), -32768.f), 32767.f);
-    return x != x ? 0 : (int)r;
-}
-
+// (quantise_s16, TF's FloatToInt16Sample, lives in gs_common.h: the note mixdown of synth.hip quantises by the same rule)
 constexpr int AUD_STEPS = 4;   // packs per thread
 
 // grid (blocks, n): row `blockIdx.y` of x (stride in elements) -> row of out (contiguous)

@@ -96,6 +96,37 @@ def _rows_cols(x):
     return x.shape[0], x.shape[1]
 
 
+def note_mix_table(table, rows, length, total):
+    """The host side of note_mix: validates `table` -- (onset, hold, release, row, gain) per note -- against the waves' shape and the
+    clip length, sorts it by (onset, position) and returns the rows as a ctypes array of GsMixNote.  ValueError by note index and
+    field name.  (A note may run past `total`: it is clipped there.)"""
+    if len(table) == 0:
+        raise ValueError("note_mix: the table is empty")
+    if int(total) <= 0:
+        raise ValueError(f"note_mix: total must be positive (got {total})")
+    checked = []
+    for i, entry in enumerate(table):
+        if len(entry) != 5:
+            raise ValueError(f"note_mix: note {i} has {len(entry)} fields, not (onset, hold, release, row, gain)")
+        onset, hold, release, row, gain = entry
+        for name, v in (("onset", onset), ("hold", hold), ("release", release), ("row", row)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+                raise ValueError(f"note_mix: note {i} field '{name}' must be an integer (got {v!r})")
+        if not 0 <= onset < total:
+            raise ValueError(f"note_mix: note {i} field 'onset' = {onset} is outside the clip [0, {total})")
+        if not 1 <= hold <= length:
+            raise ValueError(f"note_mix: note {i} field 'hold' = {hold} is outside [1, {length}]")
+        if not 0 <= release <= length - hold:
+            raise ValueError(f"note_mix: note {i} field 'release' = {release} is outside [0, {length} - hold = {length - hold}]")
+        if not 0 <= row < rows:
+            raise ValueError(f"note_mix: note {i} field 'row' = {row} is outside [0, {rows})")
+        if isinstance(gain, bool) or not isinstance(gain, (int, float, np.floating, np.integer)) or not np.isfinite(gain):
+            raise ValueError(f"note_mix: note {i} field 'gain' must be a finite number (got {gain!r})")
+        checked.append((int(onset), int(hold), int(release), int(row), float(gain)))
+    order = sorted(range(len(checked)), key=lambda i: (checked[i][0], i))
+    return (_lib.GsMixNote * len(checked))(*[_lib.GsMixNote(*checked[i]) for i in order])
+
+
 class HipKernels(object):
     def __init__(self):
         self.lib = _lib.load()
@@ -1305,6 +1336,27 @@ class HipKernels(object):
         _lib.check(self.lib.gs_summary_audio_s16(x.data_ptr(), out.data_ptr(), n, length, int(x.stride(0)) if n > 1 else length, _dt(x), _stream()),
                    "gs_summary_audio_s16")
         return out
+
+    def note_mix(self, waves, table, total, normalize=True, want_pcm=False):
+        """gs_note_mix (include/gansynth_hip.h): the notes of `table` -- host rows (onset, hold, release, row, gain) -- mixed from the rows of
+        waves [rows, L] fp32 into one clip.  -> (out [total] fp32, pcm [total] int16 or None, peak [1] fp32 = max |mix|); out is the mix
+        divided by peak when `normalize` and peak > 1."""
+        if waves.dim() != 2 or waves.dtype != torch.float32:
+            raise ValueError(f"note_mix: waves must be [rows, L] fp32 (got {tuple(waves.shape)} {waves.dtype})")
+        rows, length = int(waves.shape[0]), int(waves.shape[1])
+        total = int(total)
+        arr = note_mix_table(table, rows, length, total)
+        if waves.stride(1) != 1 or (rows > 1 and waves.stride(0) < length):
+            waves = waves.contiguous()
+        notes = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(waves.device)   # uploaded once
+        out = torch.empty((total,), dtype=torch.float32, device=waves.device)
+        pcm = torch.empty((total,), dtype=torch.int16, device=waves.device) if want_pcm else None
+        peak = torch.empty((1,), dtype=torch.float32, device=waves.device)
+        ws = _ws(self.lib.gs_note_mix_workspace_bytes(total), waves.device)
+        _lib.check(self.lib.gs_note_mix(waves.data_ptr(), rows, length, int(waves.stride(0)) if rows > 1 else length, notes.data_ptr(), len(arr), total,
+                                        1 if normalize else 0, out.data_ptr(), None if pcm is None else pcm.data_ptr(), peak.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _stream()), "gs_note_mix")
+        return out, pcm, peak
 
     def account(self):
         """bench.py: `with K.account() as calls:` lists every kernel-layer call made inside as (method, argument dict, bytes read,

@@ -788,6 +788,57 @@ class GANSynth(Iterations, DataParallel, Capture):
             images = self.generator(latents.to(self.dtype), labels.to(self.dtype))
         return spectral_ops.convert_images_to_waveform(images, **self.spectral_params)
 
+    # --------------------------------------------------------------------------------------- note sequences
+    def synthesize(self, notes, model_dir=None, latents=None, seed=0, seconds_per_instrument=6.0, release_seconds=1.0, normalize=True,
+                   want_pcm=False, info=None, pitches=range(24, 85), batch_size=8):
+        """A score -> one mixed clip (not in the reference: the rules are this project's own, DESIGN.md "Note sequences").
+
+        `notes`: notes.Note rows, or what notes.read_notes accepts (a .mid / .json file name or bytes).  Restores the latest checkpoint of
+        `model_dir` as `generate` does (None: the weights as they are).  Every note whose pitch is in the label table sorted(`pitches`)
+        is generated -- its latent by spherical interpolation between anchors `seconds_per_instrument` apart, drawn from a generator of
+        their own seeded with `seed`, or from `latents` ([N, 256]: one row per kept note; [256]: one fixed instrument) -- in chunks of
+        `batch_size` (the last one padded by repeating its last row, so that every note runs at the same batch size and tile choice),
+        and all notes are mixed by ONE gs_note_mix call: held for their length, released linearly over `release_seconds`, scaled by
+        velocity / 127, the clip divided by its peak when `normalize` and the peak exceeds 1.
+        Returns the clip [T] fp32 on the device, or (clip, int16 clip) with `want_pcm`.  `info` (a dict) receives notes (the kept ones),
+        dropped, total_samples, latents ([N, 256] fp32, host) and peak.  One process only."""
+        from . import checkpoint, notes as N
+        if self.world > 1:
+            raise RuntimeError("GANSynth.synthesize runs in one process: launch it without torch.distributed (world size 1)")
+        if self.spectral_params is None:
+            raise ValueError("synthesize: the model has no spectral_params (waveform_length, sample_rate, ...)")
+        if not (isinstance(notes, (list, tuple)) and all(isinstance(n, N.Note) for n in notes)):
+            notes = N.read_notes(notes)
+        pitches = sorted(pitches)
+        sr, length = self.spectral_params["sample_rate"], int(self.spectral_params["waveform_length"])
+        kept, table, total, dropped = N.schedule(notes, pitches, sr, length, release_seconds)
+        count, batch = len(kept), int(batch_size)
+        if latents is None:
+            lat = N.schedule_latents(kept, total, sr, seed, seconds_per_instrument)
+        else:
+            lat = torch.as_tensor(latents).detach().float().cpu()
+            if lat.dim() == 1:
+                lat = lat[None].expand(count, -1)
+            if lat.dim() != 2 or lat.shape[0] != count:
+                raise ValueError(f"synthesize: latents must be [{count}, Z] (one row per kept note) or [Z] (got {tuple(lat.shape)})")
+            lat = lat.contiguous()
+        labels = N.labels_for(kept, pitches)
+        dev = self.store.device if hasattr(self.store, "device") else "cuda"
+        if self.g_params is None:
+            self._build(lat[:1].expand(batch, -1).to(dev, self.dtype), labels[:1].expand(batch, -1).to(dev, self.dtype))
+        if model_dir is not None:
+            self.restored_from = checkpoint.restore(self, model_dir)
+        self._join_updates()
+        waves = torch.empty((count, length), dtype=torch.float32, device=dev)
+        for lo in range(0, count, batch):
+            rows = [min(i, count - 1) for i in range(lo, lo + batch)]   # the last chunk repeats its last row
+            wave = self._generate_batch(lat[rows].to(dev), labels[rows].to(dev))
+            waves[lo:lo + batch].copy_(wave[:min(batch, count - lo)])
+        clip, pcm, peak = kernels.get().note_mix(waves, table, total, normalize=normalize, want_pcm=want_pcm)
+        if info is not None:
+            info.update(notes=kept, dropped=dropped, total_samples=total, latents=lat, peak=float(peak))
+        return (clip, pcm) if want_pcm else clip
+
     # ------------------------------------------------------------------------------------------- evaluation
     def evaluate(self, model_dir, config, classifier, input_name="images:0", output_names=("features:0", "logits:0"), batch_size=64,
                  extra_metrics=False, classifier_dtype=torch.float32, features_out=None):

@@ -495,6 +495,34 @@ size_t gs_summary_image_u8_workspace_bytes(int n, int64_t p, int c);
 int gs_summary_image_u8(const void* x, uint8_t* out, int n, int64_t p, int c, int dtype, void* ws, size_t ws_bytes, void* stream);
 int gs_summary_audio_s16(const void* x, int16_t* out, int n, int64_t l, int64_t row_stride, int dtype, void* stream);
 
+/* ---- Note sequences: the mixdown of generated notes into one clip (GANSynth.synthesize; this project's own rules, DESIGN.md "Note
+ * sequences") ---------------------------------------------------------------------------------------------------------------------
+ * waves: [rows] generated notes of `length` fp32 samples, `row_stride` elements apart.  notes: a DEVICE table sorted by onset.  Note n
+ * sounds on the clip's samples onset <= t < onset + hold + release as waves[row][k], k = t - onset, under the envelope
+ *     env(k) = 1 for k < hold,   (release - (k - hold)) / (release + 1) for hold <= k < hold + release
+ * (a linear ramp that would reach 1 at k = hold - 1 and 0 at k = hold + release), and
+ *     mix[t] = sum over the covering notes, in ascending table order, of (gain * env(k)) * waves[row][k]
+ * in fp32, every product and sum rounded on its own (no FMA), env's quotient as a multiplication by fl(1 / (release + 1)).  A sample
+ * no note covers is 0 (out arrives uninitialised).  peak = max |mix[t]| (exact).  out = mix / peak (correctly rounded) when
+ * `normalize` and peak > 1, else mix.  pcm (or NULL): summary_audio_s16's rule applied to out.  peak (or NULL): [1].
+ * Gather form, no atomics: a block owns GS_MIX_TILE consecutive samples and finds the notes that reach into them by two binary
+ * searches on the onsets.  Two launches: the mix with one |max| per block into ws (sized by the query), then every block folds the
+ * block maxima, scales and quantises its own tile; the second is skipped when normalize == 0 and pcm == peak == NULL.
+ * A bad table cannot make the kernel read outside waves or write outside [0, total): a note with row outside [0, rows), hold < 1,
+ * release < 0, hold + release > length or onset < 0 is skipped IN the kernel, and every note is clipped at total.
+ * GS_ERR_ARG without a launch: n_notes, total, rows or length <= 0, row_stride < length, waves / notes / out NULL, a workspace that
+ * is too small. */
+#define GS_MIX_TILE 4096   /* samples per block: 256 lanes x 4 samples x 4 steps */
+typedef struct GsMixNote {
+    int64_t onset;          /* first sample of the note in the clip */
+    int32_t hold, release;  /* samples at full level, then samples of the linear release */
+    int32_t row;            /* which row of waves */
+    float gain;
+} GsMixNote;                /* 24 bytes */
+size_t gs_note_mix_workspace_bytes(int64_t total);
+int gs_note_mix(const float* waves, int rows, int64_t length, int64_t row_stride, const GsMixNote* notes, int n_notes, int64_t total,
+                int normalize, float* out, int16_t* pcm, float* peak, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
