@@ -8,7 +8,7 @@
 namespace gs {
 
 
-// from conv_igemm.hip
+// from conv_igemm.hip / conv_wgrad.hip
 bool igemm_supported(int ic, int oc, int dtype);
 bool igemm_norm_fused(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int want);
 int igemm_config(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int want, int* out);
@@ -29,11 +29,10 @@ int run_wgrad_mfma(int mode, const WgradSrcs& srcs, int nsrc, float* gw, float* 
                    int Wb, float alpha, int transpose, int accumulate, int dtype, void* ws, size_t ws_bytes, hipStream_t st,
                    GsWgradReduce* defer = nullptr);
 bool wgrad_sk_supported(int mode, int dtype, int IC, int OC);
-int wgrad_sk_tile_width(int Wb);
-void wgrad_sk_job_geometry(int mode, int tw, int N, SkJob& q);
+void wgrad_sk_job_geometry(int mode, int N, SkJob& q);
 void wgrad_sk_plan(int mode, SkGroup& g);
 size_t wgrad_sk_bytes(const SkGroup& g);
-int run_wgrad_sk(int mode, int tw, const SkGroup& g, void* ws, size_t ws_bytes, hipStream_t st);
+int run_wgrad_sk(int mode, const SkGroup& g, void* ws, size_t ws_bytes, hipStream_t st);
 
 // ------------------------------------------------------------------------- direct gather conv
 // y[n][oy][ox][oc0..oc0+OCV) = alpha * sum_{tap,ic} x[n][iy][ix][ic] * wp[tap][oc][ic]   (wp fp32)
@@ -808,7 +807,7 @@ static size_t wgrad_direct_bytes(int ks, int N, int Hb, int Wb, int IC, int OC) 
         thin_wgrad_geometry((long)N * Hb * Wb, IC == 2 ? OC : IC, &tns, &tpps);
         if (tns > ns) ns = tns;
     }
-    return align256(((size_t)ns * ks * ks * IC * OC + wgrad_reduce_extra(ns, (long)ks * ks * IC * OC)) * 4);
+    return align256((size_t)ns * ks * ks * IC * OC * 4);
 }
 
 static int run_wgrad_direct(int mode, int ks, const void* x, const void* gy, float* gw, int N, int Hi, int Wi, int IC,
@@ -820,7 +819,7 @@ static int run_wgrad_direct(int mode, int ks, const void* x, const void* gy, flo
     if (thin_wgrad_ok(ks, IC, OC) && mode == MODE_S1) {
         const int C = IC == 2 ? OC : IC;
         thin_wgrad_geometry(npix, C, &ns, &pps);
-        if (ws_bytes < ((size_t)ns * E + wgrad_reduce_extra(ns, E)) * 4) return fail(GS_ERR_WORKSPACE, "conv wgrad thin: workspace too small (%zu)", ws_bytes);
+        if (ws_bytes < (size_t)ns * E * 4) return fail(GS_ERR_WORKSPACE, "conv wgrad thin: workspace too small (%zu)", ws_bytes);
         float* tpart = reinterpret_cast<float*>(ws);
         if (IC == 2) {
             GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((thin_wgrad_kernel<T, false>), dim3((unsigned)ns), dim3(256), 0, st,
@@ -835,7 +834,7 @@ static int run_wgrad_direct(int mode, int ks, const void* x, const void* gy, flo
         return 0;
     }
     wgrad_direct_geometry(npix, &ns, &pps);
-    if (ws_bytes < ((size_t)ns * E + wgrad_reduce_extra(ns, E)) * 4) return fail(GS_ERR_WORKSPACE, "conv wgrad direct: workspace too small (%zu)", ws_bytes);
+    if (ws_bytes < (size_t)ns * E * 4) return fail(GS_ERR_WORKSPACE, "conv wgrad direct: workspace too small (%zu)", ws_bytes);
     float* part = reinterpret_cast<float*>(ws);
     dim3 grid(cdiv(E, 64), (unsigned)ns);
     GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv_wgrad_direct_kernel<T>), grid, dim3(256), 0, st,
@@ -1080,7 +1079,7 @@ static int wgrad_reduce_batch(const GsWgradReduce* pending, int n, void* stream)
     long gx = 0;   // blocks of the entry that needs most (64 element quads per block with 4 slice lanes, 16 with 16: see the kernel)
     auto flush = [&]() {
         if (cnt == 0) return;
-        hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3((unsigned)gx, (unsigned)cnt), dim3(256), 0, st, b);
+        wgrad_reduce_batch_launch(b, cnt, gx, st);
         cnt = 0;
         gx = 0;
     };
@@ -1104,12 +1103,12 @@ static int wgrad_reduce_batch(const GsWgradReduce* pending, int n, void* stream)
 }
 
 // ---- all weight gradients of a backward pass in one call (gs_conv_wgrad_jobs): the layers the 64 x 64-tile bf16 kernel takes are
-// grouped by its instantiation (conv mode, tile width) and each group runs as ONE stream-K launch + one fold (conv_shared.h); every
+// grouped by its instantiation (the conv mode) and each group runs as ONE stream-K launch + one fold (conv_shared.h); every
 // other layer goes through wgrad_layer above, its slice reduction left pending, and one wgrad_reduce_batch folds
 // those at the end.  Workspace: the largest group (groups run one after the other on the stream) + the sum of the per-layer needs.
 namespace gs {
 struct JobPlan {
-    std::vector<std::pair<int, SkGroup>> groups;   // (mode * 64 + tile width, group), in launch order
+    std::vector<std::pair<int, SkGroup>> groups;   // (conv mode, group), in launch order
     std::vector<GsWgradJob> single;               // jobs on the per-layer path (one source each where the layer has no multi-source kernel)
     std::vector<size_t> single_off;               // their workspace offsets
     size_t group_bytes = 0, total_bytes = 0;
@@ -1136,16 +1135,14 @@ static int job_total_images(const GsWgradJob& jb) {
 }
 static int plan_jobs(const GsWgradJob* jobs, int njobs, JobPlan& plan) {
     static const bool no_sk = getenv("GS_NO_WGRAD_GROUPS") != nullptr;   // measurement knob: everything on the per-layer path
-    std::vector<int> open_idx(256, -1);   // key -> index of the group still accepting jobs
+    int open_idx[3] = {-1, -1, -1};   // conv mode -> index of the group still accepting jobs
     for (int i = 0; i < njobs; ++i) {
         const GsWgradJob& jb = jobs[i];
         if (int e = job_check(jb, i)) return e;
         const int total = job_total_images(jb);
         const ConvRole r = conv_role(job_conv(jb, total), GS_CONV_BWD_WEIGHT);
         if (!no_sk && jb.ksize == 3 && wgrad_sk_supported(r.mode, jb.dtype, r.ICk, r.OCk)) {
-            const int tw = wgrad_sk_tile_width(r.Wb);
-            const int key = r.mode * 64 + tw;
-            int gi = open_idx[key];
+            int gi = open_idx[r.mode];
             if (gi >= 0) {   // a full group, or one that already adds into this gradient, is closed (launch order = summation order)
                 const SkGroup& og = plan.groups[gi].second;
                 bool close = og.njobs == GS_SK_MAX_JOBS;
@@ -1155,9 +1152,9 @@ static int plan_jobs(const GsWgradJob* jobs, int njobs, JobPlan& plan) {
             if (gi < 0) {
                 SkGroup ng;
                 memset(&ng, 0, sizeof(ng));
-                plan.groups.push_back(std::make_pair(key, ng));
+                plan.groups.push_back(std::make_pair(r.mode, ng));
                 gi = (int)plan.groups.size() - 1;
-                open_idx[key] = gi;
+                open_idx[r.mode] = gi;
             }
             SkGroup& g = plan.groups[gi].second;
             SkJob& q = g.job[g.njobs++];
@@ -1166,7 +1163,7 @@ static int plan_jobs(const GsWgradJob* jobs, int njobs, JobPlan& plan) {
             q.gw = jb.gw; q.gb = jb.gb; q.alpha = jb.alpha; q.transpose = r.swapped; q.accumulate = jb.accumulate;
             q.Hi = r.Hi; q.Wi = r.Wi; q.IC = r.ICk; q.OC = r.OCk; q.Hb = r.Hb; q.Wb = r.Wb;
             q.ICld = jb.gw_ci_stride > 0 ? jb.gw_ci_stride : r.ICk;
-            wgrad_sk_job_geometry(r.mode, tw, total, q);
+            wgrad_sk_job_geometry(r.mode, total, q);
         } else {
             // layers without a multi-source kernel (direct / thin kernels, fp32 bias sums): one single-source job per pair, each with its own
             // partials so that every slice reduction can stay pending
@@ -1188,7 +1185,7 @@ static int plan_jobs(const GsWgradJob* jobs, int njobs, JobPlan& plan) {
         }
     }
     for (auto& kg : plan.groups) {
-        wgrad_sk_plan(kg.first / 64, kg.second);
+        wgrad_sk_plan(kg.first, kg.second);
         const size_t b = wgrad_sk_bytes(kg.second);
         if (b > plan.group_bytes) plan.group_bytes = b;
     }
@@ -1218,7 +1215,7 @@ extern "C" int gs_conv_wgrad_jobs(const GsWgradJob* jobs, int njobs, void* ws, s
     if (ws_bytes < plan.total_bytes) return fail(GS_ERR_WORKSPACE, "conv_wgrad_jobs: workspace %zu < %zu", ws_bytes, plan.total_bytes);
     hipStream_t st = as_stream(stream);
     for (auto& kg : plan.groups)
-        if (int e = run_wgrad_sk(kg.first / 64, kg.first % 64, kg.second, ws, plan.group_bytes, st)) return e;
+        if (int e = run_wgrad_sk(kg.first, kg.second, ws, plan.group_bytes, st)) return e;
     std::vector<GsWgradReduce> pend;
     for (size_t k = 0; k < plan.single.size(); ++k) {
         const GsWgradJob& jb = plan.single[k];

@@ -1,4 +1,4 @@
-// Kernels and constants shared by conv_igemm.hip and conv_api.hip (each TU gets its own copy).
+// Constants, launch descriptors and the weight-prep kernel shared by conv_igemm.hip, conv_wgrad.hip and conv_api.hip.
 #pragma once
 #include "gs_common.h"
 
@@ -41,7 +41,7 @@ __device__ __forceinline__ int wgrad_source(const WgradSrcs& s, int nn, int& n_l
 }
 
 // ---- grouped weight gradients (gs_conv_wgrad_jobs): the 64 x 64 channel-tile kernel run ONCE over the layers of a backward pass that
-// share its instantiation (conv mode, tile width).  The work of the group is one list of units -- (layer, channel tile, pixel tile), in that
+// share its instantiation (the conv mode: conv_wgrad.hip).  The work of the group is one list of units -- (layer, channel tile, pixel tile), in that
 // order -- cut into equal contiguous ranges, one per block (a "stream-K" schedule).  A block keeps its accumulators across the pixel
 // tiles of one (layer, channel tile) RUN and writes a partial only where its range leaves the run: partials = blocks + runs per
 // launch instead of blocks per LAYER, and the summation order of a run (ascending block index) is a function of the shapes alone.
@@ -90,203 +90,16 @@ __global__ void weight_prep_kernel(const float* __restrict__ w, T* __restrict__ 
     }
 }
 
-// gw[e] = alpha * sum_s part[s][e]; `transpose` swaps the last two dims on output
-// (used by conv2d_transpose's weight gradient, whose stored variable is [k][k][Cin_T][Cout_T]).
-// Block = (256 / L) consecutive elements x L slice lanes; one launch whatever the slice count (L = 4 for a few slices,
-// 16 for the hundreds of slices of the thin top-of-pyramid layers); fixed summation order -> deterministic.
-template <int L>
-static __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ gw, float* __restrict__ gb, int nslices,
-                                                                  int taps, int ic, int oc, float alpha, int transpose, int accumulate) {
-    // a thread sums 4 consecutive elements (one 16-byte load per slice) over its share of the slices; EPB element quads per block
-    constexpr int EPB = 256 / L;
-    __shared__ float4 red[256];
-    const long total = (long)taps * ic * oc;
-    const long pstride = total + (gb ? oc : 0);   // a slice = the taps (+ one row of bias sums when gb is given); multiple of 4
-    const long e = ((long)blockIdx.x * EPB + (threadIdx.x % EPB)) * 4;
-    const int sl = threadIdx.x / EPB;
-    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
-    if (e < pstride) {
-        int k = sl;
-        // eight slices per trip, all eight loads in flight together (the thin colour-block gradients fold 1024 slices of 64 floats in ONE
-        // block: with two loads per trip that was 32 dependent round trips, 12 us)
-        for (; k + 7 * L < nslices; k += 8 * L) {
-            float4 v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const float4*>(part + (long)(k + j * L) * pstride + e);
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-                s0.x += v[j].x; s0.y += v[j].y; s0.z += v[j].z; s0.w += v[j].w;
-                s1.x += v[j + 1].x; s1.y += v[j + 1].y; s1.z += v[j + 1].z; s1.w += v[j + 1].w;
-            }
-        }
-        for (; k + L < nslices; k += 2 * L) {
-            const float4 a = *reinterpret_cast<const float4*>(part + (long)k * pstride + e);
-            const float4 b = *reinterpret_cast<const float4*>(part + (long)(k + L) * pstride + e);
-            s0.x += a.x; s0.y += a.y; s0.z += a.z; s0.w += a.w;
-            s1.x += b.x; s1.y += b.y; s1.z += b.z; s1.w += b.w;
-        }
-        if (k < nslices) {
-            const float4 a = *reinterpret_cast<const float4*>(part + (long)k * pstride + e);
-            s0.x += a.x; s0.y += a.y; s0.z += a.z; s0.w += a.w;
-        }
-    }
-    red[threadIdx.x] = make_float4(s0.x + s1.x, s0.y + s1.y, s0.z + s1.z, s0.w + s1.w);
-    __syncthreads();
-    if (sl == 0 && e < pstride) {
-        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int j = 0; j < L; ++j) {
-            const float4 v = red[threadIdx.x + j * EPB];
-            t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
-        }
-        const float s[4] = {t.x, t.y, t.z, t.w};
-        if (e >= total) {   // bias gradient: no equalized-LR scale
-            float4* o = reinterpret_cast<float4*>(gb + (e - total));
-            const float4 old = accumulate ? *o : make_float4(0.f, 0.f, 0.f, 0.f);
-            *o = make_float4(old.x + s[0], old.y + s[1], old.z + s[2], old.w + s[3]);
-            return;
-        }
-        if (!transpose) {
-            float4* o = reinterpret_cast<float4*>(gw + e);
-            const float4 old = accumulate ? *o : make_float4(0.f, 0.f, 0.f, 0.f);
-            *o = make_float4(old.x + s[0] * alpha, old.y + s[1] * alpha, old.z + s[2] * alpha, old.w + s[3] * alpha);
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const long ee = e + c;
-                const int o = ee % oc;
-                const int i = (ee / oc) % ic;
-                const int tp = ee / ((long)ic * oc);
-                const long dst = ((long)tp * oc + o) * ic + i;
-                gw[dst] = accumulate ? gw[dst] + s[c] * alpha : s[c] * alpha;
-            }
-        }
-    }
-}
-
-// element counts that are not a multiple of 4 (odd channel counts of the direct kernels): one element per thread
-static __global__ __launch_bounds__(256) void wgrad_reduce_scalar_kernel(const float* __restrict__ part, float* __restrict__ gw, int nslices, int taps, int ic,
-                                                                         int oc, float alpha, int transpose, int accumulate) {
-    const long total = (long)taps * ic * oc;
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    float s = 0.f;
-    for (int k = 0; k < nslices; ++k) s += part[(long)k * total + e];
-    s *= alpha;
-    long dst = e;
-    if (transpose) {
-        const int o = e % oc;
-        const int i = (e / oc) % ic;
-        const int t = e / ((long)ic * oc);
-        dst = ((long)t * oc + o) * ic + i;
-    }
-    gw[dst] = accumulate ? gw[dst] + s : s;
-}
-
-// ---- many reductions per launch (wgrad_reduce_batch): blockIdx.y = entry, blockIdx.x = element chunk of that entry
+// ---- slice reductions (kernels and launchers: conv_wgrad.hip)
+// phase 2 of one weight gradient: gw = alpha * sum over the slices of `part` (+ gb), or, given `defer` and a shape with the vector reduce, its description
+void wgrad_reduce_launch(float* part, float* gw, float* gb, int nslices, int taps, int ic, int oc, float alpha, int transpose, int accumulate, hipStream_t st,
+                         GsWgradReduce* defer = nullptr);
+// many reductions per launch (wgrad_reduce_batch): blockIdx.y = entry, blockIdx.x = element chunk of that entry
 #define GS_REDUCE_BATCH 16
 struct ReduceBatch {
     GsWgradReduce e[GS_REDUCE_BATCH];
 };
-// L = 4: block = 64 consecutive element quads (1 KiB per slice row: whole DRAM bursts) x 4 slice lanes; L = 16: 16 quads x 16 slice lanes
-// (the thin top-level layers leave 256 slices of 18 K floats each: with 4 slice lanes that is 72 blocks per entry walking 64 slices per
-// thread, four loads in flight -- 32-37 us for 19 MB; 16 lanes put four times the loads in flight on four times the blocks).  A thread keeps
-// four slice rows in flight.
-// The lane count is a function of the ENTRY (its slice count), never of what else shares the launch: the association of an entry's sum must
-// not depend on how the caller batches the folds (a bucketed flush batches them differently, and two schedules of one iteration must agree).
-static __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(const ReduceBatch b) {
-    const GsWgradReduce& d = b.e[blockIdx.y];
-    const int nslices = d.nslices, oc = d.oc, ic = d.ic;
-    const int L = nslices > 32 ? 16 : 4, EPB = 256 / L;
-    __shared__ float4 red[256];
-    const long total = (long)d.taps * ic * oc;
-    const long pstride = total + (d.gb ? oc : 0);
-    const long e = ((long)blockIdx.x * EPB + (threadIdx.x % EPB)) * 4;
-    if ((long)blockIdx.x * EPB * 4 >= pstride) return;   // (whole block past the end of this entry)
-    const int sl = threadIdx.x / EPB;
-    const float* __restrict__ part = d.partials;
-    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
-    if (e < pstride) {
-        int k = sl;
-        for (; k + 3 * L < nslices; k += 4 * L) {
-            const float4 a0 = *reinterpret_cast<const float4*>(part + (long)k * pstride + e);
-            const float4 a1 = *reinterpret_cast<const float4*>(part + (long)(k + L) * pstride + e);
-            const float4 a2 = *reinterpret_cast<const float4*>(part + (long)(k + 2 * L) * pstride + e);
-            const float4 a3 = *reinterpret_cast<const float4*>(part + (long)(k + 3 * L) * pstride + e);
-            s0.x += a0.x; s0.y += a0.y; s0.z += a0.z; s0.w += a0.w;
-            s1.x += a1.x; s1.y += a1.y; s1.z += a1.z; s1.w += a1.w;
-            s2.x += a2.x; s2.y += a2.y; s2.z += a2.z; s2.w += a2.w;
-            s3.x += a3.x; s3.y += a3.y; s3.z += a3.z; s3.w += a3.w;
-        }
-        for (; k < nslices; k += L) {
-            const float4 a = *reinterpret_cast<const float4*>(part + (long)k * pstride + e);
-            s0.x += a.x; s0.y += a.y; s0.z += a.z; s0.w += a.w;
-        }
-    }
-    s0.x += s2.x; s0.y += s2.y; s0.z += s2.z; s0.w += s2.w;
-    s1.x += s3.x; s1.y += s3.y; s1.z += s3.z; s1.w += s3.w;
-    red[threadIdx.x] = make_float4(s0.x + s1.x, s0.y + s1.y, s0.z + s1.z, s0.w + s1.w);
-    __syncthreads();
-    if (sl != 0 || e >= pstride) return;
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int j = 0; j < L; ++j) {
-        const float4 v = red[threadIdx.x + j * EPB];
-        t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w;
-    }
-    const float s[4] = {t.x, t.y, t.z, t.w};
-    const int accumulate = d.accumulate;
-    if (e >= total) {   // bias gradient: no equalized-LR scale
-        float4* o = reinterpret_cast<float4*>(d.gb + (e - total));
-        const float4 old = accumulate ? *o : make_float4(0.f, 0.f, 0.f, 0.f);
-        *o = make_float4(old.x + s[0], old.y + s[1], old.z + s[2], old.w + s[3]);
-        return;
-    }
-    const float alpha = d.alpha;
-    float* __restrict__ gw = d.gw;
-    if (!d.transpose) {
-        long dst = e;
-        if (d.ic_ld > ic) {   // channel slice of a wider variable: tap t starts at t * ic_ld * oc (a quad never straddles taps: ic * oc % 4 == 0)
-            const long per_tap = (long)ic * oc;
-            const long tp = e / per_tap;
-            dst = tp * d.ic_ld * oc + (e - tp * per_tap);
-        }
-        float4* o = reinterpret_cast<float4*>(gw + dst);
-        const float4 old = accumulate ? *o : make_float4(0.f, 0.f, 0.f, 0.f);
-        *o = make_float4(old.x + s[0] * alpha, old.y + s[1] * alpha, old.z + s[2] * alpha, old.w + s[3] * alpha);
-    } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const long ee = e + c;
-            const int o = ee % oc;
-            const int i = (ee / oc) % ic;
-            const int tp = ee / ((long)ic * oc);
-            const long dst = ((long)tp * oc + o) * ic + i;
-            gw[dst] = accumulate ? gw[dst] + s[c] * alpha : s[c] * alpha;
-        }
-    }
-}
-
-static inline size_t wgrad_reduce_extra(long nslices, long total) { (void)nslices; (void)total; return 0; }
-static inline void wgrad_reduce_launch(float* part, float* gw, float* gb, int nslices, int taps, int ic, int oc, float alpha, int transpose, int accumulate, hipStream_t st,
-                                       GsWgradReduce* defer = nullptr) {
-    const bool vec = !((((long)taps * ic * oc) & 3) != 0 || (gb && (oc & 3) != 0));
-    if (defer && vec) {   // phase 2 is left to wgrad_reduce_batch
-        defer->partials = part; defer->gw = gw; defer->gb = gb;
-        defer->nslices = nslices; defer->taps = taps; defer->ic = ic; defer->oc = oc;
-        defer->alpha = alpha; defer->transpose = transpose; defer->accumulate = accumulate; defer->ic_ld = 0;
-        return;
-    }
-    if (!vec) {
-        const long total = (long)taps * ic * oc;   // (gb never comes with such shapes: the fused bias path needs oc % 32 == 0)
-        hipLaunchKernelGGL(wgrad_reduce_scalar_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part, gw, nslices, taps, ic, oc, alpha, transpose, accumulate);
-        return;
-    }
-    const long n4 = ((long)taps * ic * oc + (gb ? oc : 0)) / 4;   // element quads
-    if (nslices <= 32) {
-        hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, part, gw, gb, nslices, taps, ic, oc, alpha, transpose, accumulate);
-    } else {
-        hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, st, part, gw, gb, nslices, taps, ic, oc, alpha, transpose, accumulate);
-    }
-}
+// the first `count` entries of b in one launch of `blocks_x` element chunks each
+void wgrad_reduce_batch_launch(const ReduceBatch& b, int count, long blocks_x, hipStream_t st);
 
 }  // namespace gs

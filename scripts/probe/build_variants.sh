@@ -5,7 +5,7 @@
 #        build_variants.sh role_check     conv_role_check (host-only: the conv geometry under ASan + UBSan; run it on a CPU, never on a GPU box)
 cd "$(dirname "$0")"
 C=../../gansynth_amd/csrc
-[ "$1" = role_check ] && exec hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -I../../include -I$C -o conv_role_check conv_role_check.hip $C/conv_igemm.hip $C/elementwise.hip -x hip $C/core.cpp
+[ "$1" = role_check ] && exec hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -I../../include -I$C -o conv_role_check conv_role_check.hip $C/conv_igemm.hip $C/conv_wgrad.hip $C/elementwise.hip -x hip $C/core.cpp
 pids=()
 for v in "$@"; do
   IFS='|' read -r tag mode cfg extra <<< "$v"
