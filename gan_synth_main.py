@@ -48,6 +48,11 @@ parser.add_argument("--output", type=str, default="synthesized.wav", help="the W
 parser.add_argument("--seconds_per_instrument", type=float, default=6.0, help="--synthesize: seconds between two latent anchors")
 parser.add_argument("--release_seconds", type=float, default=1.0, help="--synthesize: length of a note's linear release")
 parser.add_argument("--seed", type=int, default=0, help="--synthesize: seed of the latent anchors (a generator of their own)")
+parser.add_argument("--generator_ema_decay", type=float, default=0.0,
+                    help="keep an exponential moving average of the generator's weights with this decay (0.0: off; progressive GAN uses 0.999)")
+parser.add_argument("--weights", choices=["live", "average"], default="live",
+                    help="--generate, --evaluate, --synthesize: the generator's weights as trained, or their moving average "
+                         "(from --generator_ema_decay of this run, or from the checkpoint's averages)")
 
 
 def synthesize_to_wav(model, args, pitches, restore=True, log=print):
@@ -62,7 +67,7 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     info = {}
     _, pcm = model.synthesize(args.synthesize, model_dir=args.model_dir if restore else None, seed=args.seed,
                               seconds_per_instrument=args.seconds_per_instrument, release_seconds=args.release_seconds,
-                              want_pcm=True, info=info, pitches=pitches, batch_size=args.batch_size)
+                              want_pcm=True, info=info, pitches=pitches, batch_size=args.batch_size, weights=args.weights)
     if restore:
         log(f"restored {model.restored_from}")
     rate = int(model.spectral_params["sample_rate"])
@@ -117,7 +122,8 @@ def main(args):
         spectral_params=Dict(waveform_length=64000, sample_rate=16000, spectrogram_shape=[128, 1024], overlap=0.75),
         hyper_params=Dict(generator_learning_rate=8e-4 * global_batch / 8, generator_beta1=0.0, generator_beta2=0.99,
                           discriminator_learning_rate=8e-4 * global_batch / 8, discriminator_beta1=0.0, discriminator_beta2=0.99,
-                          mode_seeking_loss_weight=0.1, real_gradient_penalty_weight=5.0, fake_gradient_penalty_weight=0.0),
+                          mode_seeking_loss_weight=0.1, real_gradient_penalty_weight=5.0, fake_gradient_penalty_weight=0.0,
+                          generator_average_decay=args.generator_ema_decay),
         dtype=dtype, distributed=world > 1, use_graphs=True)
     holder["model"] = model
 
@@ -146,7 +152,8 @@ def main(args):
                 config=None,
                 classifier=args.classifier,    # the frozen pitch-classifier GraphDef (.pb), or its weights as .safetensors
                 input_name="images:0",
-                output_names=["features:0", "logits:0"]))
+                output_names=["features:0", "logits:0"],
+                weights=args.weights))
         finally:
             model.real_input_fn = kept
 
@@ -164,9 +171,12 @@ def main(args):
             latents = model.fake_input_fn()
             model._ensure_built(latents.to(dtype), labels.to(dtype))
             if batches == 0 and not args.train:
-                path = checkpoint.restore(model, args.model_dir)
+                from_file = args.weights == "average" and model.g_params.avg is None   # (no decay in this run: the checkpoint's averages)
+                path = checkpoint.restore(model, args.model_dir, require_average=from_file)
+                if path is None and from_file:
+                    raise SystemExit(f"--weights average: {args.model_dir} holds no checkpoint to take the averaged generator from")
                 print(f"restored {path}" if path else "no checkpoint found: generating from the initial weights")
-            for waveform in model.generate(latents, labels).float().cpu().numpy():
+            for waveform in model.generate(latents, labels, weights=args.weights).float().cpu().numpy():
                 wavfile.write(f"samples/{num_waveforms}.wav", rate=16000, data=waveform)
                 num_waveforms += 1
             batches += 1

@@ -106,6 +106,9 @@ SIGNATURES = {
     "gs_adam_tf_step": (I, [P, P, P, P, L, F, F, F, F, F, P]),
     "gs_adam_tf_step_zero_grad": (I, [P, P, P, P, L, F, F, F, F, F, P]),
     "gs_adam_tf_step_dev": (I, [P, P, P, P, L, P, F, F, F, F, I, P]),
+    "gs_ema_step": (I, [P, P, L, F, P]),
+    "gs_ema_step_dev": (I, [P, P, L, P, P]),
+    "gs_swap_f32": (I, [P, P, L, P]),
     "gs_pack_act_bits": (I, [P, L, I, I, P]),
     "gs_spectral_plan_create": (I, [POINTER(c_void_p), I, I, I, P, P]),
     "gs_spectral_plan_destroy": (I, [P]),

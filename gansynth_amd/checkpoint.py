@@ -6,7 +6,10 @@ A `tf.train.Saver` checkpoint of the reference graph (models.py:123-130) holds, 
   * the Adam slots `<variable>/Adam` (m) and `<variable>/Adam_1` (v) (tf.train.AdamOptimizer slot names);
   * the non-slot accumulators of the two optimizers: `beta1_power`, `beta2_power` for the generator's (created first,
     models.py:81), `beta1_power_1`, `beta2_power_1` for the discriminator's (models.py:86);
-  * `global_step` (int64).
+  * `global_step` (int64);
+  * with an averaged generator (hyper_params.generator_average_decay): `<variable>/ExponentialMovingAverage` for every GENERATOR
+    variable, the shadow-variable name of tf.train.ExponentialMovingAverage, in the variable's shape.  A file without them restores
+    into a model that keeps an average as a fresh shadow variable starts: equal to the restored weights.
 The TF tensor-bundle container cannot be written without TensorFlow; the same names, shapes and layouts are stored in a
 `.safetensors` file; `scripts/tf_checkpoint_convert.py` copies a TF checkpoint into that container (and back) on a machine
 that has TensorFlow -- the only format gap (INTEGRATION.md).  `optimizer_steps[_1]` is an extra key (the exponent t itself);
@@ -30,10 +33,20 @@ except ImportError:   # pragma: no cover
     load_file = save_file = None
 
 
+AVERAGE_SUFFIX = "/ExponentialMovingAverage"
+
+
+def _refuse_while_averaged(model, what):
+    if getattr(model, "_average_in", False):
+        raise RuntimeError(f"checkpoint: {what} while the generator's average is swapped in (inside averaged_generator()): the live "
+                           f"weights and the average have changed places; leave the context first")
+
+
 def state_dict(model):
     """name -> tensor (CPU) for everything a tf.train.Saver would write for `model` (a models.GANSynth after _build)."""
     if model.g_params is None:
         raise RuntimeError("checkpoint: the model has no variables yet (run a step or call _build first)")
+    _refuse_while_averaged(model, "state_dict / save")
     if hasattr(model, "synchronize"):
         model.synchronize()
     hp = model.hyper_params
@@ -51,12 +64,18 @@ def state_dict(model):
         out["beta2_power" + suffix] = torch.tensor(float(b2) ** (params.t + 1), dtype=torch.float32)
         out["optimizer_steps" + suffix] = torch.tensor(params.t, dtype=torch.int64)   # (not a TF variable: the exponent itself)
     out["global_step"] = torch.tensor(model.global_step, dtype=torch.int64)
+    if getattr(model, "average_decay", 0.0) and model.g_params.avg is not None:   # (averaging off: exactly the keys above)
+        for name in model.g_params.named:
+            out[name + AVERAGE_SUFFIX] = model.g_params.avg_view(name).detach().cpu().clone()
     return out
 
 
-def load_state_dict(model, state, strict=True):
+def load_state_dict(model, state, strict=True, require_average=False):
+    """`require_average`: the caller wants the generator's averages FROM THIS FILE (weights="average" on a model built without a decay):
+    a missing one is a ValueError naming it, and the model's average buffer is allocated for them."""
     if model.g_params is None:
         raise RuntimeError("checkpoint: build the model's variables first (GANSynth._build)")
+    _refuse_while_averaged(model, "load_state_dict / restore")
     if hasattr(model, "synchronize"):
         model.synchronize()
     # Two passes: everything that can refuse the file (shapes, missing entries, contradictory step counts) is checked BEFORE the first
@@ -110,10 +129,37 @@ def load_state_dict(model, state, strict=True):
             missing.append(key)
     if "global_step" not in state:
         missing.append("global_step")
+    # The generator's averages: looked at only when the model keeps an average (or is about to: require_average); shapes are checked in
+    # this pass with everything else.  A file with NONE of them -- every checkpoint written without averaging, every converted TF
+    # checkpoint -- is not an error and adds nothing to `missing`: the average then starts at the restored weights, as a fresh TF shadow
+    # variable does.  A file with some but not all is a broken file: those ARE missing.
+    g = model.g_params
+    averages, fresh_average = [], False
+    if g.avg is not None or require_average:
+        have = [name for name in g.named if name + AVERAGE_SUFFIX in state]
+        if require_average and len(have) < len(g.named):
+            first = next(name for name in g.named if name + AVERAGE_SUFFIX not in state) + AVERAGE_SUFFIX
+            raise ValueError(f"checkpoint: weights='average' needs the generator's averages from the file, and {first} is not in it "
+                             f"({len(have)} of {len(g.named)} present): it was written without generator_average_decay")
+        for name in have:
+            src, p = state[name + AVERAGE_SUFFIX], g.named[name]
+            if tuple(src.shape) != tuple(p.shape):
+                raise ValueError(f"checkpoint: {name + AVERAGE_SUFFIX} has shape {tuple(src.shape)}, the variable has {tuple(p.shape)}")
+            averages.append((name, src))
+        if have and len(have) < len(g.named):
+            missing.extend(name + AVERAGE_SUFFIX for name in g.named if name + AVERAGE_SUFFIX not in state)
+        fresh_average = not have
     if strict and missing:
         raise KeyError(f"checkpoint: {len(missing)} entries missing, e.g. {missing[:4]}")
     for dst, src in copies:
         dst.copy_(src.to(dst.device, dst.dtype))
+    if averages and g.avg is None:
+        g.enable_average()
+    for name, src in averages:
+        dst = g.avg_view(name)
+        dst.copy_(src.to(dst.device, dst.dtype))
+    if fresh_average and g.avg is not None:
+        g.avg.copy_(g.flat)
     for params, suffix in ((model.g_params, ""), (model.d_params, "_1")):
         if suffix in steps:
             params.t = steps[suffix]
@@ -187,13 +233,13 @@ def latest(model_dir):
     return max(files, key=lambda p: int(re.findall(r"ckpt-(\d+)", p)[-1])) if files else None
 
 
-def restore(model, model_dir_or_file, strict=True):
+def restore(model, model_dir_or_file, strict=True, require_average=False):
     """Load the latest checkpoint of a directory (or a given file); returns its path, or None when there is none
-    (a fresh run, like tf.train.MonitoredSession with an empty checkpoint_dir)."""
+    (a fresh run, like tf.train.MonitoredSession with an empty checkpoint_dir).  `require_average`: see load_state_dict."""
     if load_file is None:
         raise RuntimeError("checkpoint: the safetensors package is not importable")
     path = model_dir_or_file if os.path.isfile(model_dir_or_file) else latest(model_dir_or_file)
     if path is None:
         return None
-    load_state_dict(model, load_file(path), strict=strict)
+    load_state_dict(model, load_file(path), strict=strict, require_average=require_average)
     return path

@@ -698,6 +698,59 @@ static __global__ void adam_tf_kernel(float* __restrict__ p, float* __restrict__
     }
 }
 
+// ------------------------------------------------------------- averaged weights (EMA)
+// tf.train.ExponentialMovingAverage's assign_sub: shadow -= (shadow - p) * om, om = 1 - decay.  Two fp32 roundings per element: the
+// difference, then ONE fused multiply-add (-om * d + shadow) -- written as fmaf so that the count does not depend on the contraction
+// setting.  DEV: om is read from device memory when the launch executes; anything that is not > 0 (the negative "no step pending" of
+// gs_adam_tf_step_dev, and a decay of exactly 1) leaves the shadow untouched.  12 B / element: two reads, one write.
+template <bool DEV>
+static __global__ void ema_kernel(float* __restrict__ s, const float* __restrict__ p, long n, float om, const float* __restrict__ om_dev) {
+    if (DEV) {
+        om = __builtin_nontemporal_load(om_dev);
+        if (!(om > 0.f)) return;
+    }
+    const long nvec = n >> 2;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
+        float4 sv = reinterpret_cast<float4*>(s)[i];
+        const float4 pv = reinterpret_cast<const float4*>(p)[i];
+        float* ss = &sv.x; const float* pp = &pv.x;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ss[e] = fmaf(-om, ss[e] - pp[e], ss[e]);
+        reinterpret_cast<float4*>(s)[i] = sv;
+    }
+    const long t = nvec * 4 + (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n) s[t] = fmaf(-om, s[t] - p[t], s[t]);
+}
+
+// Two buffers exchanged in place, as words: no arithmetic touches them (NaN payloads and the sign of zero survive).
+static __global__ void swap_kernel(unsigned* __restrict__ a, unsigned* __restrict__ b, long n) {
+    const long nvec = n >> 2;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
+        const uint4 av = reinterpret_cast<uint4*>(a)[i];
+        const uint4 bv = reinterpret_cast<uint4*>(b)[i];
+        reinterpret_cast<uint4*>(a)[i] = bv;
+        reinterpret_cast<uint4*>(b)[i] = av;
+    }
+    const long t = nvec * 4 + (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n) {
+        const unsigned av = a[t], bv = b[t];
+        a[t] = bv;
+        b[t] = av;
+    }
+}
+
+// the checks the three entry points share: both buffers present, 16-byte aligned (float4 accesses) and apart
+static inline const char* pair_refusal(const void* a, const void* b, int64_t numel) {
+    if (numel <= 0) return "numel must be positive";
+    if (a == nullptr || b == nullptr) return "null pointer";
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) return "pointers must be 16-byte aligned";
+    if (a == b) return "the two buffers are the same";
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(a) < reinterpret_cast<uintptr_t>(b) ? reinterpret_cast<uintptr_t>(a) : reinterpret_cast<uintptr_t>(b);
+    const uintptr_t hi = reinterpret_cast<uintptr_t>(a) < reinterpret_cast<uintptr_t>(b) ? reinterpret_cast<uintptr_t>(b) : reinterpret_cast<uintptr_t>(a);
+    if ((hi - lo) / 4 < (uintptr_t)numel) return "the two buffers overlap";
+    return nullptr;
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -1062,6 +1115,35 @@ extern "C" int gs_adam_tf_step_dev(float* p, float* g, float* m, float* v, int64
     else
         hipLaunchKernelGGL((adam_tf_kernel<false, true>), grid, dim3(256), 0, as_stream(stream), p, g, m, v, (long)numel, 0.f, lr_t_dev, beta1, beta2, eps,
                            grad_scale);
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gs_ema_step(float* shadow, const float* p, int64_t numel, float one_minus_decay, void* stream) {
+    const char* why = pair_refusal(shadow, p, numel);
+    GS_CHECK_ARG(why == nullptr, "ema_step: %s", why);
+    GS_CHECK_ARG(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "ema_step: one_minus_decay = %g is outside [0, 1]", (double)one_minus_decay);
+    if (one_minus_decay == 0.f) return 0;   // (a decay of exactly 1: the shadow stays as it is, bit for bit -- nothing to launch)
+    hipLaunchKernelGGL((ema_kernel<false>), dim3(ew_grid((numel >> 2) + 4)), dim3(256), 0, as_stream(stream), shadow, p, (long)numel, one_minus_decay,
+                       (const float*)nullptr);
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gs_ema_step_dev(float* shadow, const float* p, int64_t numel, const float* one_minus_decay_dev, void* stream) {
+    const char* why = pair_refusal(shadow, p, numel);
+    GS_CHECK_ARG(why == nullptr, "ema_step_dev: %s", why);
+    GS_CHECK_ARG(one_minus_decay_dev != nullptr, "ema_step_dev: null pointer (one_minus_decay_dev)");
+    hipLaunchKernelGGL((ema_kernel<true>), dim3(ew_grid((numel >> 2) + 4)), dim3(256), 0, as_stream(stream), shadow, p, (long)numel, 0.f, one_minus_decay_dev);
+    GS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gs_swap_f32(float* a, float* b, int64_t numel, void* stream) {
+    const char* why = pair_refusal(a, b, numel);
+    GS_CHECK_ARG(why == nullptr, "swap_f32: %s", why);
+    hipLaunchKernelGGL(swap_kernel, dim3(ew_grid((numel >> 2) + 4)), dim3(256), 0, as_stream(stream), reinterpret_cast<unsigned*>(a),
+                       reinterpret_cast<unsigned*>(b), (long)numel);
     GS_CHECK_LAUNCH();
     return 0;
 }

@@ -53,6 +53,9 @@ class DataParallel(object):
         params.grad_clean = zero   # (the buckets cover the whole buffer)
         K.invalidate_weights(params.flat)
         K.refresh_weights(params.flat)
+        # the averaged generator: ONE launch over the whole buffer behind the last bucket, not one per bucket.  The average is a function of
+        # the weights alone, and those are identical on every rank after the all-reduce: so is the average, with no communication.
+        self._average_after(params)
 
     def _arm_first_bucket(self, K, params):
         """Data parallel, captured discriminator run, OPT-IN (`bucket_d_reduce`, GS_DP_BUCKET_D=1): the all-reduce of the gradient in two steps.

@@ -30,6 +30,20 @@ class _FlatParams(object):
         self.grad_clean = True   # the flat gradient is all zeros (fresh buffer / cleared by the optimizer step)
         self.buckets = [(0, total)]
         self._offsets = list(zip(offs, sizes, self.named.keys()))
+        self.avg = None          # the exponential moving average of `flat` (enable_average: the generator's only)
+
+    def enable_average(self):
+        """Allocate the shadow buffer of tf.train.ExponentialMovingAverage: a clone of `flat` as it is now (a fresh TF shadow variable starts
+        at its variable's value), same layout -- the padding gaps are zero in both and stay zero under the update (0 - (0 - 0) * x)."""
+        if self.avg is None:
+            self.avg = self.flat.detach().clone()
+        return self.avg
+
+    def avg_view(self, name):
+        """The average of variable `name`, shaped like it (a view into `avg`)."""
+        p = self.named[name]
+        off = (p.data.data_ptr() - self.flat.data_ptr()) // 4
+        return self.avg[off:off + p.numel()].view(p.shape)
 
     def make_buckets(self, max_floats, reverse=False):
         """Split the flat buffer into contiguous ranges of whole tensors, each <= max_floats unless a single tensor is larger

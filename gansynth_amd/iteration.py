@@ -93,7 +93,7 @@ class Iterations(object):
     # (lr_t is a by-value scalar; streaming kernels beside the persistent conv blocks cost the main stream 5 %, measured).
     def _apply_g_pending(self):
         """The generator's pending step (`_g_pending`: its lr_t) on the gradient in its flat buffer, already all-reduced."""
-        lr_t, self._g_pending = self._g_pending, None
+        lr_t, self._g_pending, self._g_pending_om = self._g_pending, None, None
         self._adam(self.g_params, lr_t, self.hyper_params.generator_beta1, self.hyper_params.generator_beta2)
 
     def _join_updates(self):
@@ -196,6 +196,7 @@ class Iterations(object):
         # the generator's step is left pending: its gradient is reduced inside the next D graph (or eagerly by _join_updates)
         self.g_params.t += 1
         self._g_pending = self._lr_t(hp.generator_learning_rate, hp.generator_beta1, hp.generator_beta2, self.g_params.t)
+        self._g_pending_om = self._one_minus(self.g_params.t) if self._averaging() else None
         self.global_step += 1  # models.py:84
         self.discriminator_loss, self.generator_loss = D["loss"], G["loss"]
         return D["loss"], G["loss"]
@@ -229,14 +230,26 @@ class Iterations(object):
     # a checkpoint, a run outside this path, a new growing regime -- goes through _join_updates() first.  A freshly captured Z finds no
     # pending step: its lr slot is negative and the kernel leaves every buffer untouched.
     def _fused_ok(self):
-        return self.fuse_iteration and hasattr(kernels.get(), "adam_tf_step_dev")
+        K = kernels.get()
+        return self.fuse_iteration and hasattr(K, "adam_tf_step_dev") and (not self._averaging() or hasattr(K, "ema_step_dev"))
 
     def _apply_in_graph(self, params, slot, beta1, beta2, reduce_first=False):
-        """The optimizer step as nodes of the graph being captured: [all-reduce] -> Adam with lr_t from the device table -> operand refresh."""
+        """The optimizer step as nodes of the graph being captured: [all-reduce] -> Adam with lr_t from the device table -> operand refresh.
+        The generator's (slot 1) with an averaged generator: the average's update follows on the SAME stream, its 1 - decay_t in slot 2
+        (negative with the step's lr_t: no step pending, no update) -- one node more on the fake pass's branch, no branch more (the graph
+        already uses the runtime's four hardware queues).  Behind the refresh by default: DESIGN.md "Averaged generator"."""
+        K = kernels.get()
         if reduce_first:
             self._reduce_in_capture(params)
-        kernels.get().adam_tf_step_dev(params.flat, params.grad, params.m, params.v, self._opt_scalars.ptr(slot), beta1, beta2, 1.0e-8,
-                                       1.0 / self.world, zero_grad=not self.keep_gradients)
+        average = slot == 1 and self._averaging()
+        early = average and self.ema_before_refresh
+        K.adam_tf_step_dev(params.flat, params.grad, params.m, params.v, self._opt_scalars.ptr(slot), beta1, beta2, 1.0e-8,
+                           1.0 / self.world, refresh=not early, zero_grad=not self.keep_gradients)
+        if average:
+            K.ema_step_dev(params.avg, params.flat, self._opt_scalars.ptr(2))
+        if early:
+            K.invalidate_weights(params.flat)
+            K.refresh_weights(params.flat)
 
     def _capture_merged(self, d_inputs, g_inputs, fused=False):
         """The record of X and Y (`fused`: of Z, "y" is None), or None when the capture refused a collective on some rank."""
@@ -308,7 +321,7 @@ class Iterations(object):
                           reduce=both if with_collective else (), clear=both)
             if fused:
                 if self._opt_scalars is None:
-                    self._opt_scalars = F.DeviceScalars(self.g_params.flat.device, 2)
+                    self._opt_scalars = F.DeviceScalars(self.g_params.flat.device, 3 if self._averaging() else 2)
                 # the per-network refresh launches read descriptor tables that are built (host -> device) on first use: not inside a capture
                 for params in both:
                     K.invalidate_weights(params.flat)
@@ -340,15 +353,19 @@ class Iterations(object):
             self.d_params.t += 1
             self.g_params.t += 1
             lr_d = self._lr_t(hp.discriminator_learning_rate, hp.discriminator_beta1, hp.discriminator_beta2, self.d_params.t)
-            self._opt_scalars.set([lr_d, -1.0 if self._g_pending is None else self._g_pending])   # (stream-ordered before the replay)
+            scalars = [lr_d, -1.0 if self._g_pending is None else self._g_pending]
+            if self._averaging():   # (the average follows the pending step, or nothing)
+                scalars.append(-1.0 if self._g_pending is None else self._g_pending_om)
+            self._opt_scalars.set(scalars)   # (stream-ordered before the replay)
             self._arm(self.d_params)
             if self._g_pending is None:
                 self._arm(self.g_params)      # (no step at the front of this replay: the buffer must already be clean)
-            self._g_pending = None
+            self._g_pending = self._g_pending_om = None
             M["x"].replay()
             self.d_params.grad_clean = not self.keep_gradients
             self.g_params.grad_clean = False   # (holds the gradient of the step that is now pending)
             self._g_pending = self._lr_t(hp.generator_learning_rate, hp.generator_beta1, hp.generator_beta2, self.g_params.t)
+            self._g_pending_om = self._one_minus(self.g_params.t) if self._averaging() else None
         else:
             self._arm(self.d_params)
             M["x"].replay()

@@ -136,6 +136,7 @@ class HipKernels(object):
         self._param_ranges = []   # (ptr, nbytes) of registered flat parameter buffers
         self._wcache = {}         # (weight ptr, map tag) -> (persistent workspace holding the re-laid operand, stamp)
         self._prep_tables = {}    # tuple of cache keys -> device table of GsPrepDesc rows (refresh_weights)
+        self._retired_tables = []  # tables no refresh will use again, kept for the captured graphs that replay them (_weight_ws)
         self._derived = {}        # (parent weight ptr, lo, hi) -> [contiguous slice buffer, stamp, parent, lo, hi] (derived_slice)
         self._folds = None        # deferred bias-gradient folds while deferring: [(partial rows, out, nparts, c)]
         self._pending = None      # deferred weight gradients while deferring: {layer key: {out, bias, [(x, gy, with bias)]}}
@@ -146,6 +147,8 @@ class HipKernels(object):
         self._expected = {}       # pass tag -> {layer key: (pairs of a whole pass, out, bias)}, learned at the final flush of the previous pass
         self._tag = None          # tag of the pass being deferred (defer_wgrad_reductions)
         self._complete = None     # (pred, callback, expected): see complete_rule
+        self.ema_steps = 0        # calls of ema_step / ema_step_dev so far (tests: the averaged generator took the HIP path)
+        self.ema_steps_dev = 0
 
     # --------------------------------------------------------- prepared-weight workspaces
     def register_param_buffer(self, flat):
@@ -175,6 +178,10 @@ class HipKernels(object):
             ent[1] = stamp
             return ent[0], 0
         self._wcache[key] = [_ws(nbytes, w.device), stamp, w, plan, rng]
+        # (a new workspace changes the rows: the tables are built again by the next refresh.  The old ones stay ALIVE: a captured graph
+        #  replays gs_weight_prep_batch on a table's address, and a second model built in the same process -- new weights, new keys -- must
+        #  not hand that memory back to the allocator under the first one's graph.  A few KB each.)
+        self._retired_tables.extend(self._prep_tables.values())
         self._prep_tables.clear()
         return self._wcache[key][0], 0
 
@@ -1069,6 +1076,31 @@ class HipKernels(object):
         if refresh:
             self.invalidate_weights(p)
             self.refresh_weights(p)
+
+    def ema_step(self, shadow, p, one_minus_decay):
+        """tf.train.ExponentialMovingAverage's update of a flat fp32 buffer: shadow -= (shadow - p) * one_minus_decay (gs_ema_step)."""
+        for t in (shadow, p):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        assert shadow.numel() == p.numel()
+        _lib.check(self.lib.gs_ema_step(shadow.data_ptr(), p.data_ptr(), p.numel(), float(one_minus_decay), _stream()), "gs_ema_step")
+        self.ema_steps += 1
+
+    def ema_step_dev(self, shadow, p, one_minus_ptr):
+        """ema_step with the scalar read from device memory when the launch EXECUTES (`one_minus_ptr`: address of one fp32; negative = no
+        step pending): the form a captured graph can hold, as adam_tf_step_dev."""
+        for t in (shadow, p):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        assert shadow.numel() == p.numel()
+        _lib.check(self.lib.gs_ema_step_dev(shadow.data_ptr(), p.data_ptr(), p.numel(), int(one_minus_ptr), _stream()), "gs_ema_step_dev")
+        self.ema_steps_dev += 1
+
+    def swap_(self, a, b):
+        """a and b (flat fp32, same size) exchange their contents in place, bit for bit (gs_swap_f32).  The caller invalidates and
+        refreshes prepared operands where one of them is a parameter buffer."""
+        for t in (a, b):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        assert a.numel() == b.numel()
+        _lib.check(self.lib.gs_swap_f32(a.data_ptr(), b.data_ptr(), a.numel(), _stream()), "gs_swap_f32")
 
     # ------------------------------------------------------------------- more than one stream
     def stream_guard(self):

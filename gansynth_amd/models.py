@@ -47,6 +47,8 @@ _FORK = not config.flag("GS_NO_FORK")   # A/B switch: independent sub-passes of 
 EARLY_FLUSH_DIVS = [int(d) for d in config.value("GS_EARLY_FLUSH_DIV", "16").split(",")]   # a layer is "large" from 1/DIV of the full resolution's pixels (several: one early contraction each)
 EARLY_FLUSH_CUS = int(config.value("GS_EARLY_FLUSH_CUS", "192"))   # see GANSynth._early_flush
 _FORK_EAGER = config.flag("GS_FORK_EAGER")   # tests: the same branches with eager launches (a second stream, event hops)
+_EMA_BEFORE_REFRESH = config.flag("GS_EMA_BEFORE_REFRESH")   # A/B switch: see Iterations._apply_in_graph
+AVERAGE_SUFFIX = "/ExponentialMovingAverage"   # tf.train.ExponentialMovingAverage's shadow variable of <variable>
 
 
 class GANSynth(Iterations, DataParallel, Capture):
@@ -114,6 +116,12 @@ class GANSynth(Iterations, DataParallel, Capture):
         self.split_g_loss = not config.flag("GS_NO_SPLIT_G_LOSS")   # A/B switch, see _g_losses_b
         self.split_final_flush = not config.flag("GS_NO_SPLIT_FINAL_FLUSH")   # A/B switch, see kernels.HipKernels._flush_groups
         self._g_pending = None        # lr_t of a generator step whose gradient is in the flat buffer and whose update has not run yet
+        # The averaged generator (progressive GAN's recipe; DESIGN.md "Averaged generator"): an exponential moving average of the generator's
+        # weights, updated behind every one of its Adam steps.  0 = off: no buffer, no launch, no checkpoint key.
+        self.average_decay = self._checked_decay(hyper_params.get("generator_average_decay"))
+        self.ema_before_refresh = _EMA_BEFORE_REFRESH
+        self._g_pending_om = None     # 1 - decay_t of that pending step (averaging on)
+        self._average_in = False      # inside averaged_generator(): g_params.flat holds the AVERAGE, g_params.avg the live weights
         self._marks = {}
         self._serial_run = False
         self._branched = False
@@ -122,6 +130,98 @@ class GANSynth(Iterations, DataParallel, Capture):
         self.batch_d_tail = None   # None: the discriminator's tail over [real; fake] as one batch unless the runs fork (see _batched_tail)
         self.early_flush_always = False   # (tests: the same flush points without branches -- in place, on the one stream)
         self.early_flushes = 0
+
+    # ---------------------------------------------------------------------- averaged generator
+    @staticmethod
+    def _checked_decay(decay):
+        if decay is None:
+            return 0.0
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:   # (NaN fails both comparisons)
+            raise ValueError(f"hyper_params.generator_average_decay must lie in [0, 1) (0 or None: no averaged generator), got {decay!r}")
+        return decay
+
+    def _averaging(self):
+        return self.average_decay > 0.0
+
+    def _one_minus(self, t):
+        """1 - decay_t of the average's update behind the generator's t-th Adam step, decay_t = min(decay, (1 + t) / (10 + t)): the
+        `num_updates` warm-up of tf.train.ExponentialMovingAverage (without it the average at step 100 is still 90 % initialisation noise
+        at decay 0.999).  Computed in float64 and rounded to fp32 ONCE: the value the kernel multiplies by."""
+        decay_t = min(self.average_decay, (1.0 + t) / (10.0 + t))
+        return float(torch.tensor(1.0 - decay_t, dtype=torch.float64).to(torch.float32))
+
+    def _average_after(self, params):
+        """Behind an Adam step of `params` (params.t counts it): the average follows the generator's; the discriminator has none.
+        Data parallel: the average is a function of the weights alone, which are identical on every rank after the all-reduced step --
+        so is the average, with no communication."""
+        if params is not self.g_params or not self._averaging():
+            return
+        K = kernels.get()
+        one_minus = self._one_minus(params.t)
+        if hasattr(K, "ema_step"):
+            K.ema_step(params.avg, params.flat, one_minus)
+        else:   # (a backend without the kernel -- the tests' CPU emulation: the same rule in torch, fp32)
+            params.avg.sub_((params.avg - params.flat) * one_minus)
+
+    def _swap_average(self):
+        """g_params.flat <-> g_params.avg in place (every pointer a captured graph or a variable view holds stays valid, and there is no
+        third buffer), then the generator's prepared operands are rebuilt from what `flat` holds now."""
+        K = kernels.get()
+        g = self.g_params
+        if hasattr(K, "swap_"):
+            K.swap_(g.flat, g.avg)
+        else:
+            with torch.no_grad():
+                live = g.flat.clone()
+                g.flat.copy_(g.avg)
+                g.avg.copy_(live)
+        if hasattr(K, "invalidate_weights"):
+            K.invalidate_weights(g.flat)
+            K.refresh_weights(g.flat)
+
+    @contextlib.contextmanager
+    def averaged_generator(self):
+        """`with model.averaged_generator():` -- inside, the generator runs on its AVERAGED weights: the pending update is joined, the live
+        weights and the average change places (_swap_average), and they change back on the way out, also when the body raises.  Inside,
+        train_step / discriminator_step / generator_step / state_dict / checkpoint.save / load raise RuntimeError.  Data parallel: entering
+        joins the pending update as the other readers do -- a collective when `collective_pending()`, so every rank enters together."""
+        if self.g_params is None or self.g_params.avg is None:
+            first = "generator/..." if self.g_params is None else next(iter(self.g_params.named))
+            raise ValueError(f"the model keeps no averaged generator ({first}{AVERAGE_SUFFIX} and the rest): build it with "
+                             f"hyper_params.generator_average_decay, or restore a checkpoint that holds the averages (weights='average' "
+                             f"with a model_dir)")
+        self._refuse_while_averaged("averaged_generator (it does not nest)")
+        self._join_updates()
+        self._swap_average()
+        self._average_in = True
+        try:
+            yield self
+        finally:
+            self._average_in = False
+            self._swap_average()
+
+    def _refuse_while_averaged(self, what):
+        if self._average_in:
+            raise RuntimeError(f"{what}: the generator's average is swapped in (inside averaged_generator()); leave the context first")
+
+    def _restore_for(self, model_dir, weights):
+        """The restore of generate / evaluate / synthesize, BEFORE any swap.  weights="average" on a model built without a decay takes the
+        average from the checkpoint (and allocates its buffer): no model_dir, no checkpoint there, or a file without the averages is a
+        ValueError naming the first missing key -- never the live weights under another name."""
+        from . import checkpoint
+        if weights not in ("live", "average"):
+            raise ValueError(f"weights must be 'live' or 'average' (got {weights!r})")
+        need = weights == "average" and self.g_params.avg is None
+        if model_dir is None:
+            restored = None
+        else:
+            restored = checkpoint.restore(self, model_dir, require_average=need)
+        if need and restored is None:
+            first = next(iter(self.g_params.named)) + AVERAGE_SUFFIX
+            where = "no model_dir was given" if model_dir is None else f"{model_dir} holds no checkpoint"
+            raise ValueError(f"weights='average': the model was built without generator_average_decay and {where} to take {first} from")
+        return restored
 
     # ------------------------------------------------------------------------ forked branches
     # A run holds sub-passes that do not depend on each other:
@@ -247,6 +347,10 @@ class GANSynth(Iterations, DataParallel, Capture):
                 # launches that follow them: with the passes apart and the early contraction the world-1 step was no longer bit-identical to
                 # the non-distributed one there (5e-7 on the parameters, cause not found) -- that transport keeps round 4's schedule
                 self.fork = False
+        if self._averaging():
+            # from the initial weights (behind the broadcast: the same on every rank, and it stays the same with no communication --
+            # the average is a function of the weights, _average_after)
+            self.g_params.enable_average()
         K = kernels.get()
         if hasattr(K, "register_param_buffer"):  # lets the conv kernels keep their re-laid weight operands between calls
             K.register_param_buffer(self.g_params.flat)
@@ -436,6 +540,7 @@ class GANSynth(Iterations, DataParallel, Capture):
         zero = not self.keep_gradients
         kernels.get().adam_tf_step(params.flat, params.grad, params.m, params.v, lr_t, beta1, beta2, 1.0e-8, 1.0 / self.world, zero_grad=zero)
         params.grad_clean = zero
+        self._average_after(params)
 
     def _part_a(self, which, *inputs):
         """Own-network part of a run (see _d_losses_a / _g_losses_a); also arms the run: requires_grad flags, zeroed gradients."""
@@ -596,6 +701,7 @@ class GANSynth(Iterations, DataParallel, Capture):
         return owner._head_depth(owner.growing_depth)
 
     def discriminator_step(self, latents, labels, real_images):
+        self._refuse_while_averaged("discriminator_step")
         self._ensure_built(latents, labels)
         hp = self.hyper_params
         loss = self._run("d", latents, labels, real_images)
@@ -604,6 +710,7 @@ class GANSynth(Iterations, DataParallel, Capture):
         return self.discriminator_loss
 
     def generator_step(self, latents, labels):
+        self._refuse_while_averaged("generator_step")
         self._ensure_built(latents, labels)
         hp = self.hyper_params
         loss = self._run("g", latents, labels)
@@ -629,6 +736,7 @@ class GANSynth(Iterations, DataParallel, Capture):
 
     def train_step(self):
         """models.py:191-192: one discriminator run then one generator run, fresh inputs for each."""
+        self._refuse_while_averaged("train_step")
         real_images, labels, d_latents, g_latents, g_labels = self._next_inputs()
         self._ensure_built(d_latents, labels)
         if self.use_graphs:
@@ -758,13 +866,16 @@ class GANSynth(Iterations, DataParallel, Capture):
         fake waveforms [B, waveform_length] per batch of the input functions -- labels of `real_input_fn()`, latents of
         `fake_input_fn()`, as models.py:22-31 wires `fake_waveforms` -- until the input runs dry (OutOfRangeError, :249).  `config`
         (tf.ConfigProto) is accepted and ignored.
-        `generate(latents, labels)` -- fake waveforms (a device tensor) for one given batch."""
+        `generate(latents, labels)` -- fake waveforms (a device tensor) for one given batch.
+        `weights` (keyword, both forms): "live" -- the weights as the last Adam step left them -- or "average": the averaged generator
+        (averaged_generator(); the checkpoint is restored first, and a model built without generator_average_decay takes the averages
+        from it: ValueError when there is nothing to take them from).  Data parallel: as every reader of the weights it joins the pending
+        update first -- a collective when `collective_pending()`."""
         if "model_dir" in kwargs or (args and (args[0] is None or isinstance(args[0], (str, bytes)) or hasattr(args[0], "__fspath__"))):
             return self._generate_from(*args, **kwargs)
         return self._generate_batch(*args, **kwargs)
 
-    def _generate_from(self, model_dir, config=None):
-        from . import checkpoint
+    def _generate_from(self, model_dir, config=None, weights="live"):
         del config
         restored = False
         while True:
@@ -778,11 +889,17 @@ class GANSynth(Iterations, DataParallel, Capture):
             self._ensure_built(latents.to(self.dtype), labels.to(self.dtype))
             if not restored:
                 restored = True
-                self.restored_from = checkpoint.restore(self, model_dir) if model_dir is not None else None
-            yield self._generate_batch(latents, labels).float().cpu().numpy()
+                self.restored_from = self._restore_for(model_dir, weights)
+            # (the swap there and back around EVERY batch: between two yields the caller finds the model as it always is)
+            yield self._generate_batch(latents, labels, weights=weights).float().cpu().numpy()
 
-    def _generate_batch(self, latents, labels):
+    def _generate_batch(self, latents, labels, weights="live"):
         """models.py:22-31 (`fake_waveforms`): fake waveforms for a batch."""
+        if weights not in ("live", "average"):
+            raise ValueError(f"weights must be 'live' or 'average' (got {weights!r})")
+        if weights == "average" and not self._average_in:
+            with self.averaged_generator():
+                return self._generate_batch(latents, labels)
         self._join_updates()
         with torch.no_grad():
             images = self.generator(latents.to(self.dtype), labels.to(self.dtype))
@@ -790,7 +907,7 @@ class GANSynth(Iterations, DataParallel, Capture):
 
     # --------------------------------------------------------------------------------------- note sequences
     def synthesize(self, notes, model_dir=None, latents=None, seed=0, seconds_per_instrument=6.0, release_seconds=1.0, normalize=True,
-                   want_pcm=False, info=None, pitches=range(24, 85), batch_size=8):
+                   want_pcm=False, info=None, pitches=range(24, 85), batch_size=8, weights="live"):
         """A score -> one mixed clip (not in the reference: the rules are this project's own, DESIGN.md "Note sequences").
 
         `notes`: notes.Note rows, or what notes.read_notes accepts (a .mid / .json file name or bytes).  Restores the latest checkpoint of
@@ -801,8 +918,8 @@ class GANSynth(Iterations, DataParallel, Capture):
         and all notes are mixed by ONE gs_note_mix call: held for their length, released linearly over `release_seconds`, scaled by
         velocity / 127, the clip divided by its peak when `normalize` and the peak exceeds 1.
         Returns the clip [T] fp32 on the device, or (clip, int16 clip) with `want_pcm`.  `info` (a dict) receives notes (the kept ones),
-        dropped, total_samples, latents ([N, 256] fp32, host) and peak.  One process only."""
-        from . import checkpoint, notes as N
+        dropped, total_samples, latents ([N, 256] fp32, host) and peak.  `weights`: "live" or "average", as for `generate`.  One process only."""
+        from . import notes as N
         if self.world > 1:
             raise RuntimeError("GANSynth.synthesize runs in one process: launch it without torch.distributed (world size 1)")
         if self.spectral_params is None:
@@ -826,14 +943,16 @@ class GANSynth(Iterations, DataParallel, Capture):
         dev = self.store.device if hasattr(self.store, "device") else "cuda"
         if self.g_params is None:
             self._build(lat[:1].expand(batch, -1).to(dev, self.dtype), labels[:1].expand(batch, -1).to(dev, self.dtype))
+        restored = self._restore_for(model_dir, weights)
         if model_dir is not None:
-            self.restored_from = checkpoint.restore(self, model_dir)
+            self.restored_from = restored
         self._join_updates()
         waves = torch.empty((count, length), dtype=torch.float32, device=dev)
-        for lo in range(0, count, batch):
-            rows = [min(i, count - 1) for i in range(lo, lo + batch)]   # the last chunk repeats its last row
-            wave = self._generate_batch(lat[rows].to(dev), labels[rows].to(dev))
-            waves[lo:lo + batch].copy_(wave[:min(batch, count - lo)])
+        with self.averaged_generator() if weights == "average" else contextlib.nullcontext():
+            for lo in range(0, count, batch):
+                rows = [min(i, count - 1) for i in range(lo, lo + batch)]   # the last chunk repeats its last row
+                wave = self._generate_batch(lat[rows].to(dev), labels[rows].to(dev))
+                waves[lo:lo + batch].copy_(wave[:min(batch, count - lo)])
         clip, pcm, peak = kernels.get().note_mix(waves, table, total, normalize=normalize, want_pcm=want_pcm)
         if info is not None:
             info.update(notes=kept, dropped=dropped, total_samples=total, latents=lat, peak=float(peak))
@@ -841,7 +960,7 @@ class GANSynth(Iterations, DataParallel, Capture):
 
     # ------------------------------------------------------------------------------------------- evaluation
     def evaluate(self, model_dir, config, classifier, input_name="images:0", output_names=("features:0", "logits:0"), batch_size=64,
-                 extra_metrics=False, classifier_dtype=torch.float32, features_out=None):
+                 extra_metrics=False, classifier_dtype=torch.float32, features_out=None, weights="live"):
         """models.py:196-230: the Frechet distance between the pitch classifier's features of real and generated spectrograms.
 
         Restores the latest checkpoint of `model_dir` as `generate` does, then for every batch of `real_input_fn()` until it runs dry:
@@ -852,9 +971,10 @@ class GANSynth(Iterations, DataParallel, Capture):
         "logits:0").  `config` (tf.ConfigProto) is accepted and ignored.  Returns {"frechet_inception_distance": float}; with
         `extra_metrics` also the inception score of the fake logits, the pitch accuracy of their argmax against the conditioning labels
         and, when scikit-learn imports, the number of statistically different bins.  `features_out` (a dict): receives the host arrays
-        real_features, fake_features, real_logits, fake_logits, labels.  One process only."""
+        real_features, fake_features, real_logits, fake_logits, labels.  `weights`: "live" or "average", as for `generate` -- the fake side
+        comes from the averaged generator, swapped in behind the restore and out again at the end.  One process only."""
         import numpy as np
-        from . import checkpoint, metrics, networks
+        from . import metrics, networks
         del config
         if self.world > 1:
             raise RuntimeError("GANSynth.evaluate runs in one process: launch it without torch.distributed (world size 1)")
@@ -878,27 +998,30 @@ class GANSynth(Iterations, DataParallel, Capture):
                 (real_l if which == "real" else fake_l).append(l.cpu().numpy())
 
         restored = False
-        while True:
-            try:
-                data, labels = self.real_input_fn()
-            except StopIteration:
-                break
-            latents = self.fake_input_fn()
-            dev = self.store.device if hasattr(self.store, "device") else labels.device
-            data, latents, labels = data.to(dev), latents.to(dev), labels.to(dev)
-            self._ensure_built(latents.to(self.dtype), labels.to(self.dtype))
-            if not restored:
-                restored = True
-                self.restored_from = checkpoint.restore(self, model_dir) if model_dir is not None else None
-            self._join_updates()
-            with torch.no_grad():
-                real = spectral_ops.convert_to_images(data, **self.spectral_params, dtype=self.dtype) if data.dim() == 2 else data
-                fake = self.generator(latents.to(self.dtype), labels.to(self.dtype))
-            pending["real"].append(real)
-            pending["fake"].append(fake)
-            labs.append(labels.float().cpu().numpy())
-            flush("real")
-            flush("fake")
+        with contextlib.ExitStack() as swapped:   # (the average goes in behind the restore of the first batch, out at the end)
+            while True:
+                try:
+                    data, labels = self.real_input_fn()
+                except StopIteration:
+                    break
+                latents = self.fake_input_fn()
+                dev = self.store.device if hasattr(self.store, "device") else labels.device
+                data, latents, labels = data.to(dev), latents.to(dev), labels.to(dev)
+                self._ensure_built(latents.to(self.dtype), labels.to(self.dtype))
+                if not restored:
+                    restored = True
+                    self.restored_from = self._restore_for(model_dir, weights)
+                    if weights == "average":
+                        swapped.enter_context(self.averaged_generator())
+                self._join_updates()
+                with torch.no_grad():
+                    real = spectral_ops.convert_to_images(data, **self.spectral_params, dtype=self.dtype) if data.dim() == 2 else data
+                    fake = self.generator(latents.to(self.dtype), labels.to(self.dtype))
+                pending["real"].append(real)
+                pending["fake"].append(fake)
+                labs.append(labels.float().cpu().numpy())
+                flush("real")
+                flush("fake")
         flush("real", True)
         flush("fake", True)
         if not real_f:

@@ -372,6 +372,23 @@ int gs_adam_tf_step_zero_grad(float* p, float* g, float* m, float* v, int64_t nu
 int gs_adam_tf_step_dev(float* p, float* g, float* m, float* v, int64_t numel, const float* lr_t_dev, float beta1,
                         float beta2, float eps, float grad_scale, int zero_grad, void* stream);
 
+/* The averaged generator: one step of tf.train.ExponentialMovingAverage over a flat fp32 buffer, TF's assign_sub form
+ *   shadow -= (shadow - p) * one_minus_decay          (one_minus_decay = 1 - decay_t, computed and rounded to fp32 by the caller)
+ * per element in fp32 with TWO roundings: the difference d = shadow - p, then one fused multiply-add fma(-one_minus_decay, d, shadow).
+ * |shadow - p| beyond FLT_MAX overflows as it does in TF; a NaN or an infinity in p reaches the shadow at that element only.
+ * one_minus_decay must lie in [0, 1]; with exactly 0 nothing is launched and the shadow keeps every bit.
+ * Refused (GS_ERR_ARG, nothing launched): numel <= 0, a null pointer, a pointer that is not 16-byte aligned, shadow == p or any overlap
+ * of the two ranges, one_minus_decay outside [0, 1] (NaN included).  12 bytes of traffic per element. */
+int gs_ema_step(float* shadow, const float* p, int64_t numel, float one_minus_decay, void* stream);
+/* the same step with the scalar READ FROM DEVICE MEMORY at execution time, under the contract of gs_adam_tf_step_dev: written by the
+ * caller stream-ordered ahead of the launch, so that the step can be a node of a captured hipGraph; a NEGATIVE value means "no step
+ * pending" and the launch leaves the shadow untouched (so does 0, and anything else that is not > 0).  Values above 1 are the caller's
+ * error and are not detected.  Same refusals, and a null one_minus_decay_dev. */
+int gs_ema_step_dev(float* shadow, const float* p, int64_t numel, const float* one_minus_decay_dev, void* stream);
+/* a and b exchange their contents in place, word by word: no arithmetic, NaN payloads and the sign of zero survive.  Swapping the live
+ * weights with their average keeps every pointer a captured graph holds valid and needs no third buffer.  Same refusals (a == b). */
+int gs_swap_f32(float* a, float* b, int64_t numel, void* stream);
+
 /* ------------------------------------------------------------------------------ spectral
  * spectral_ops.py:45-94.  Plan = immutable per-device tables (Hann window, twiddles, CSR mel matrix
  * supplied by the caller as built by linear_to_mel_weight_matrix, dense pinv for the inverse). */

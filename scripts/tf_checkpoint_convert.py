@@ -5,7 +5,9 @@ Needs TensorFlow on the machine that runs it (not available in the build image, 
     python scripts/tf_checkpoint_convert.py to-tf           <in.safetensors>        <tf checkpoint prefix>
 
 Reference side: models.py:123-130 (tf.train.Saver of the whole graph: trainable variables, `<var>/Adam`, `<var>/Adam_1`,
-beta1_power[_1], beta2_power[_1], global_step)."""
+beta1_power[_1], beta2_power[_1], global_step).  A graph that applies tf.train.ExponentialMovingAverage to the generator's variables also
+saves `<var>/ExponentialMovingAverage`: gansynth_amd/checkpoint.py reads and writes the averaged generator under that name, and both
+directions here copy every tensor by name, these included."""
 import sys
 
 import numpy as np
