@@ -60,6 +60,8 @@ SIGNATURES = {
     "gs_conv_wgrad_jobs_workspace_bytes": (Z, [P, I]),
     "gs_conv_wgrad_jobs": (I, [P, I, P, Z, P]),
     "gs_wgrad_cu_cap": (I, [I]),
+    "gs_conv_wgrad_plan": (I, [C, POINTER(c_int)]),
+    "gs_conv_wgrad_jobs_plan": (I, [P, I, POINTER(c_int), I]),
     "gs_conv_igemm_config": (I, [I, I, I, I, I, I, I, I, POINTER(c_int)]),
     "gs_conv_igemm_table": (I, [I, POINTER(c_int)]),
     "gs_units_bias_act_to_nhwc": (I, [P, P, P, P, I, I, I, I, I, P]),
@@ -149,6 +151,8 @@ SIGNATURES = {
 }
 
 WGRAD_MAX_SOURCES = 4   # GS_WGRAD_MAX_SOURCES
+WGRAD_DIRECT, WGRAD_THIN, WGRAD_F32, WGRAD_BF16, WGRAD_THIN_DMA, WGRAD_TILE64 = range(6)   # GS_WGRAD_* families of gs_conv_wgrad_plan
+WGRAD_PLAN_INTS = 16   # GS_WGRAD_PLAN_INTS
 
 
 SUM_PARTIALS = 2   # GS_SUM_PARTIALS

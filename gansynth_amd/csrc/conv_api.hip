@@ -15,7 +15,6 @@ int igemm_config(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int
 int igemm_table(int index, int* out);
 extern "C" int gs_pixel_norm_bwd_bwd_fused(const void* gg, const void* g, const void* x, void* out, void* out_g, int64_t p, int c, float eps, int pre_act,
                                            int dtype, void* stream);
-bool wgrad_mfma_supported(int ic, int oc, int dtype);
 size_t igemm_prep_bytes(int ic, int oc, int dtype);
 int run_igemm(int mode, int variant, const void* x, const float* w_hwio, void* y, int N, int Hi, int Wi, int ICk,
               int OCk, int w_ci, int w_co, int Hb, int Wb, float alpha, const float* bias, int act, int dtype, int w_prepared,
@@ -24,11 +23,9 @@ int run_igemm(int mode, int variant, const void* x, const float* w_hwio, void* y
 extern "C" int gs_pixel_norm_bwd_fused(const void* g, const void* x, const void* addend, void* gx, int64_t p, int c, float eps, int pre_act, int post_act, int dtype,
                                        void* stream);
 size_t wgrad_mfma_bytes(int mode, int dtype, int N, int Hb, int Wb, int IC, int OC);
-bool wgrad_mfma_has_bias(int dtype);
 int run_wgrad_mfma(int mode, const WgradSrcs& srcs, int nsrc, float* gw, float* gb, int N, int Hi, int Wi, int IC, int OC, int Hb,
                    int Wb, float alpha, int transpose, int accumulate, int dtype, void* ws, size_t ws_bytes, hipStream_t st,
                    GsWgradReduce* defer = nullptr);
-bool wgrad_sk_supported(int mode, int dtype, int IC, int OC);
 void wgrad_sk_job_geometry(int mode, int N, SkJob& q);
 void wgrad_sk_plan(int mode, SkGroup& g);
 size_t wgrad_sk_bytes(const SkGroup& g);
@@ -777,51 +774,24 @@ __global__ __launch_bounds__(256) void thin_wgrad_kernel(const T* __restrict__ w
     }
 }
 
-static bool thin_wgrad_ok(int ks, int ci, int co) {
-    if (ks != 1) return false;
-    const int c = ci == 2 ? co : (co == 2 ? ci : 0);
-    return c >= 4 && c <= 1024 && (c & 3) == 0 && 256 % (c >> 2) == 0 && !(ci == 2 && co == 2);
-}
-static void thin_wgrad_geometry(long npix, int c, long* nslices, long* pps) {
-    const long rpi = 256 / (c >> 2);
-    long ns = (npix + rpi * 32 - 1) / (rpi * 32);
-    if (ns > 1024) ns = 1024;
-    if (ns < 1) ns = 1;
-    *pps = (npix + ns - 1) / ns;
-    *nslices = (npix + *pps - 1) / *pps;
-}
-
-static void wgrad_direct_geometry(long npix, long* nslices, long* pps) {
-    long ns = (npix + 63) / 64;   // a thread walks its slice serially (index arithmetic + two dependent loads per pixel): keep it short
-    if (ns > 1024) ns = 1024;
-    if (ns < 1) ns = 1;
-    *pps = (npix + ns - 1) / ns;
-    *nslices = (npix + *pps - 1) / *pps;
-}
-
-static size_t wgrad_direct_bytes(int ks, int N, int Hb, int Wb, int IC, int OC) {
-    long ns, pps;
-    wgrad_direct_geometry((long)N * Hb * Wb, &ns, &pps);
-    if (thin_wgrad_ok(ks, IC, OC)) {
-        long tns, tpps;
-        thin_wgrad_geometry((long)N * Hb * Wb, IC == 2 ? OC : IC, &tns, &tpps);
-        if (tns > ns) ns = tns;
-    }
-    return align256((size_t)ns * ks * ks * IC * OC * 4);
+static size_t wgrad_direct_bytes(int mode, int ks, int dtype, int N, int Hb, int Wb, int IC, int OC) {
+    const WgradPlan p = wgrad_plan(mode, ks, dtype, N, Hb, Wb, IC, OC);
+    return align256((size_t)p.ws_slices * ks * ks * IC * OC * 4);
 }
 
 static int run_wgrad_direct(int mode, int ks, const void* x, const void* gy, float* gw, int N, int Hi, int Wi, int IC,
                             int OC, int Hb, int Wb, float alpha, int transpose, int accumulate, int dtype, void* ws, size_t ws_bytes,
                             hipStream_t st, GsWgradReduce* defer = nullptr) {
-    long ns, pps;
+    const WgradPlan p = wgrad_plan(mode, ks, dtype, N, Hb, Wb, IC, OC);
+    if (p.family > WG_THIN) return fail(GS_ERR_UNSUPPORTED, "conv wgrad direct: %d -> %d channels belong to the MFMA kernels", IC, OC);
+    const long ns = p.nslices, pps = p.pps;
     const long npix = (long)N * Hb * Wb;
     const long E = (long)ks * ks * IC * OC;
-    if (thin_wgrad_ok(ks, IC, OC) && mode == MODE_S1) {
+    if (p.family == WG_THIN) {
         const int C = IC == 2 ? OC : IC;
-        thin_wgrad_geometry(npix, C, &ns, &pps);
         if (ws_bytes < (size_t)ns * E * 4) return fail(GS_ERR_WORKSPACE, "conv wgrad thin: workspace too small (%zu)", ws_bytes);
         float* tpart = reinterpret_cast<float*>(ws);
-        if (IC == 2) {
+        if (!p.ot) {
             GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((thin_wgrad_kernel<T, false>), dim3((unsigned)ns), dim3(256), 0, st,
                                                         reinterpret_cast<const T*>(gy), reinterpret_cast<const T*>(x), tpart, C, npix, pps));
         } else {
@@ -833,7 +803,6 @@ static int run_wgrad_direct(int mode, int ks, const void* x, const void* gy, flo
         GS_CHECK_LAUNCH();
         return 0;
     }
-    wgrad_direct_geometry(npix, &ns, &pps);
     if (ws_bytes < (size_t)ns * E * 4) return fail(GS_ERR_WORKSPACE, "conv wgrad direct: workspace too small (%zu)", ws_bytes);
     float* part = reinterpret_cast<float*>(ws);
     dim3 grid(cdiv(E, 64), (unsigned)ns);
@@ -906,8 +875,9 @@ extern "C" size_t gs_conv_workspace_bytes(const GsConv* c, int which) {
     if (check_conv(c)) return 0;
     if (which != GS_CONV_BWD_WEIGHT) return align256((size_t)c->ksize * c->ksize * c->ci * c->co * 4);   // the re-laid weight
     const ConvRole r = conv_role(*c, GS_CONV_BWD_WEIGHT);
-    const size_t wg = c->ksize == 3 && wgrad_mfma_supported(r.ICk, r.OCk, c->dtype) ? wgrad_mfma_bytes(r.mode, c->dtype, c->n, r.Hb, r.Wb, r.ICk, r.OCk)
-                                                                                      : wgrad_direct_bytes(c->ksize, c->n, r.Hb, r.Wb, r.ICk, r.OCk);
+    const size_t wg = wgrad_plan(r.mode, c->ksize, c->dtype, c->n, r.Hb, r.Wb, r.ICk, r.OCk).family >= WG_F32
+                          ? wgrad_mfma_bytes(r.mode, c->dtype, c->n, r.Hb, r.Wb, r.ICk, r.OCk)
+                          : wgrad_direct_bytes(r.mode, c->ksize, c->dtype, c->n, r.Hb, r.Wb, r.ICk, r.OCk);
     if (c->transposed) return wg;   // (no bias)
     const size_t cs = align256(gs_channel_sum_workspace_bytes((int64_t)c->n * r.Hb * r.Wb, c->co));   // bias-gradient fallback of gs_conv_bwd_weight
     return wg > cs ? wg : cs;
@@ -1032,10 +1002,11 @@ static int wgrad_layer(const GsConv& c, const void* const* xs, const void* const
     for (int i = 0; i < nsrc; ++i) GS_CHECK_ARG(xs[i] && gys[i], "conv_bwd_weight: null source %d", i);
     hipStream_t st = as_stream(stream);
     const ConvRole r = conv_role(c, GS_CONV_BWD_WEIGHT);
-    const bool mfma = c.ksize == 3 && wgrad_mfma_supported(r.ICk, r.OCk, c.dtype);
+    const WgradPlan lp = wgrad_plan(r.mode, c.ksize, c.dtype, c.n, r.Hb, r.Wb, r.ICk, r.OCk);   // (family and bias form: functions of the layer, not of n)
+    const bool mfma = lp.family >= WG_F32;
     if (pending) memset(pending, 0, sizeof(*pending));
     if (!gb) bias_mask = 0;
-    if (nsrc > 1 && !(mfma && (!gb || wgrad_mfma_has_bias(c.dtype)))) {
+    if (nsrc > 1 && !(mfma && (!gb || lp.fused_bias))) {
         // shapes without the multi-source kernels: one call per source (the first applies `accumulate`, the rest add)
         for (int i = 0; i < nsrc; ++i) {
             GsConv one = c;
@@ -1045,7 +1016,7 @@ static int wgrad_layer(const GsConv& c, const void* const* xs, const void* const
         }
         return 0;
     }
-    const bool fused_bias = bias_mask && mfma && wgrad_mfma_has_bias(c.dtype);
+    const bool fused_bias = bias_mask && lp.fused_bias;
     // the channel-sum fallback of the bias gradient reuses ws: such calls cannot leave their partials pending
     GsWgradReduce* defer = (bias_mask && !fused_bias) ? nullptr : pending;
     int rc;
@@ -1093,7 +1064,7 @@ static int wgrad_reduce_batch(const GsWgradReduce* pending, int n, void* stream)
         if (clash) flush();
         b.e[cnt++] = d;
         const long pstride = (long)d.taps * d.ic * d.oc + (d.gb ? d.oc : 0);
-        const long epb = d.nslices > 32 ? 16 : 64;
+        const long epb = 256 / wgrad_fold_lanes(d.nslices);
         const long blocks = (pstride / 4 + epb - 1) / epb;
         if (blocks > gx) gx = blocks;
     }
@@ -1111,6 +1082,8 @@ struct JobPlan {
     std::vector<std::pair<int, SkGroup>> groups;   // (conv mode, group), in launch order
     std::vector<GsWgradJob> single;               // jobs on the per-layer path (one source each where the layer has no multi-source kernel)
     std::vector<size_t> single_off;               // their workspace offsets
+    std::vector<std::vector<int>> group_jobs;      // per group: the index in the caller's list of each of its jobs (gs_conv_wgrad_jobs_plan)
+    std::vector<std::pair<int, int>> single_src;   // per single job: (index in the caller's list, source it was split off for or -1)
     size_t group_bytes = 0, total_bytes = 0;
 };
 static GsConv job_conv(const GsWgradJob& jb, int n) {   // the job's layer, with n images
@@ -1141,7 +1114,8 @@ static int plan_jobs(const GsWgradJob* jobs, int njobs, JobPlan& plan) {
         if (int e = job_check(jb, i)) return e;
         const int total = job_total_images(jb);
         const ConvRole r = conv_role(job_conv(jb, total), GS_CONV_BWD_WEIGHT);
-        if (!no_sk && jb.ksize == 3 && wgrad_sk_supported(r.mode, jb.dtype, r.ICk, r.OCk)) {
+        const WgradPlan lp = wgrad_plan(r.mode, jb.ksize, jb.dtype, total, r.Hb, r.Wb, r.ICk, r.OCk);
+        if (!no_sk && lp.family == WG_TILE64) {
             int gi = open_idx[r.mode];
             if (gi >= 0) {   // a full group, or one that already adds into this gradient, is closed (launch order = summation order)
                 const SkGroup& og = plan.groups[gi].second;
@@ -1153,11 +1127,13 @@ static int plan_jobs(const GsWgradJob* jobs, int njobs, JobPlan& plan) {
                 SkGroup ng;
                 memset(&ng, 0, sizeof(ng));
                 plan.groups.push_back(std::make_pair(r.mode, ng));
+                plan.group_jobs.push_back(std::vector<int>());
                 gi = (int)plan.groups.size() - 1;
                 open_idx[r.mode] = gi;
             }
             SkGroup& g = plan.groups[gi].second;
             SkJob& q = g.job[g.njobs++];
+            plan.group_jobs[gi].push_back(i);
             int tot = 0;
             q.srcs = make_srcs(jb.x, jb.gy, jb.nsrc, 0, jb.n, jb.gb ? jb.bias_mask : 0u, r.swapped != 0, &tot);
             q.gw = jb.gw; q.gb = jb.gb; q.alpha = jb.alpha; q.transpose = r.swapped; q.accumulate = jb.accumulate;
@@ -1167,10 +1143,10 @@ static int plan_jobs(const GsWgradJob* jobs, int njobs, JobPlan& plan) {
         } else {
             // layers without a multi-source kernel (direct / thin kernels, fp32 bias sums): one single-source job per pair, each with its own
             // partials so that every slice reduction can stay pending
-            const bool mfma = jb.ksize == 3 && wgrad_mfma_supported(r.ICk, r.OCk, jb.dtype);
-            const bool multi = mfma && (!jb.gb || wgrad_mfma_has_bias(jb.dtype));
+            const bool multi = lp.family >= WG_F32 && (!jb.gb || lp.fused_bias);
             if (jb.nsrc == 1 || multi) {
                 plan.single.push_back(jb);
+                plan.single_src.push_back(std::make_pair(i, -1));
             } else {
                 for (int sidx = 0; sidx < jb.nsrc; ++sidx) {
                     GsWgradJob one = jb;
@@ -1180,6 +1156,7 @@ static int plan_jobs(const GsWgradJob* jobs, int njobs, JobPlan& plan) {
                     if (!one.bias_mask) one.gb = nullptr;
                     if (sidx > 0) one.accumulate = 1;
                     plan.single.push_back(one);
+                    plan.single_src.push_back(std::make_pair(i, sidx));
                 }
             }
         }
@@ -1301,3 +1278,45 @@ extern "C" int gs_conv_igemm_config(int mode, int n, int hb, int wb, int ic, int
 // Row `index` of the table of compiled implicit-GEMM kernels (conv_igemm.hip: GS_IGEMM_CONFIGS), for tests that want one case per kernel.  Host
 // only.  out11: mode, bf16_only, A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC; GS_ERR_ARG past the last row.
 extern "C" int gs_conv_igemm_table(int index, int* out11) { return igemm_table(index, out11); }
+
+// ---- what the weight-gradient entry points WOULD launch, asked without launching (host arithmetic on wgrad_plan / plan_jobs, the structs the
+// launchers themselves read; no device needed: the CU count then defaults to 256).  tests/test_wgrad_cover_*.py key their cases by these answers.
+static void layer_plan_ints(const GsConv& c, int* out) {   // c.n: images of all sources
+    const ConvRole r = conv_role(c, GS_CONV_BWD_WEIGHT);
+    const WgradPlan p = wgrad_plan(r.mode, c.ksize, c.dtype, c.n, r.Hb, r.Wb, r.ICk, r.OCk);
+    const int v[GS_WGRAD_PLAN_INTS] = {p.family, p.mode, p.tw, p.ot, r.swapped, r.ICk, r.OCk, r.Hb, r.Wb, p.ntiles, p.nslices, p.fold, p.batch_lanes,
+                                       p.fused_bias, p.tiles_x, p.tiles_y};
+    memcpy(out, v, sizeof(v));
+}
+extern "C" int gs_conv_wgrad_plan(const GsConv* c, int* out) {
+    if (int e = check_conv(c)) return e;
+    GS_CHECK_ARG(out != nullptr, "conv_wgrad_plan: no output");
+    layer_plan_ints(*c, out);
+    return 0;
+}
+extern "C" int gs_conv_wgrad_jobs_plan(const GsWgradJob* jobs, int njobs, int* out, int out_len) {
+    GS_CHECK_ARG(njobs >= 0 && (njobs == 0 || jobs) && out && out_len >= 2, "conv_wgrad_jobs_plan: bad args");
+    JobPlan plan;
+    if (njobs > 0)
+        if (int e = plan_jobs(jobs, njobs, plan)) return e;
+    std::vector<int> v;
+    v.push_back((int)plan.groups.size());
+    v.push_back((int)plan.single.size());
+    for (size_t gi = 0; gi < plan.groups.size(); ++gi) {
+        const SkGroup& g = plan.groups[gi].second;
+        const int head[5] = {plan.groups[gi].first, g.njobs, g.total_units, g.total_runs, g.nblocks};
+        v.insert(v.end(), head, head + 5);
+        for (int j = 0; j < g.njobs; ++j) {
+            const int row[5] = {plan.group_jobs[gi][j], g.job[j].unit_base, g.job[j].run_base, g.job[j].ntiles, g.job[j].nct};
+            v.insert(v.end(), row, row + 5);
+        }
+    }
+    for (size_t k = 0; k < plan.single.size(); ++k) {
+        int row[2 + GS_WGRAD_PLAN_INTS] = {plan.single_src[k].first, plan.single_src[k].second};
+        layer_plan_ints(job_conv(plan.single[k], job_total_images(plan.single[k])), row + 2);
+        v.insert(v.end(), row, row + 2 + GS_WGRAD_PLAN_INTS);
+    }
+    if ((int)v.size() > out_len) return fail(GS_ERR_ARG, "conv_wgrad_jobs_plan: %d ints needed, room for %d", (int)v.size(), out_len);
+    memcpy(out, v.data(), v.size() * sizeof(int));
+    return (int)v.size();
+}

@@ -90,6 +90,27 @@ __global__ void weight_prep_kernel(const float* __restrict__ w, T* __restrict__ 
     }
 }
 
+// ---- THE selection of a layer's weight-gradient kernel (conv_wgrad.hip: wgrad_plan): which kernel takes a kernel-role shape, its tiling, its
+// slice count and the fold behind it.  The launchers (run_wgrad_mfma, run_wgrad_direct), the workspace sizes, plan_jobs and the host-only
+// queries gs_conv_wgrad_plan / gs_conv_wgrad_jobs_plan all read this struct; nobody decides a second time.
+enum { WG_DIRECT = 0, WG_THIN = 1, WG_F32 = 2, WG_BF16 = 3, WG_THIN_DMA = 4, WG_TILE64 = 5 };   // GS_WGRAD_* of include/gansynth_hip.h
+struct WgradPlan {
+    int family;                    // WG_*
+    int mode;                      // MODE_S1 / MODE_S2
+    int tw;                        // pixel-tile width of the MFMA kernels (16 / 32); 0: direct / thin
+    int ot;                        // MFMA: 32-channel output tiles per block (1 / 2; 2 x 2 for WG_TILE64); WG_THIN: 1 when x is the wide side
+    int tiles_x, tiles_y, ntiles;  // MFMA: pixel tiles over all images; direct / thin: ntiles = output pixels
+    int nslices;                   // block partials the fold sums
+    int ws_slices;                 // partials the workspace is sized for (>= nslices)
+    long pps;                      // direct / thin: pixels per slice
+    int fold;                      // the immediate fold: 0 the scalar kernel, else wgrad_reduce_kernel's slice lanes (4 / 16)
+    int batch_lanes;               // slice lanes of wgrad_reduce_batch_kernel for this entry (4 / 16); 0: the fold cannot stay pending
+    int fused_bias;                // 1: the kernel produces the bias gradient on the side (a bias row per slice)
+};
+WgradPlan wgrad_plan(int mode, int ks, int dtype, int N, int Hb, int Wb, int IC, int OC);
+// slice lanes of the vector folds for a reduction over `nslices` partials (immediate and batched alike)
+static inline int wgrad_fold_lanes(int nslices) { return nslices > 32 ? 16 : 4; }
+
 // ---- slice reductions (kernels and launchers: conv_wgrad.hip)
 // phase 2 of one weight gradient: gw = alpha * sum over the slices of `part` (+ gb), or, given `defer` and a shape with the vector reduce, its description
 void wgrad_reduce_launch(float* part, float* gw, float* gb, int nslices, int taps, int ic, int oc, float alpha, int transpose, int accumulate, hipStream_t st,

@@ -1160,7 +1160,7 @@ void wgrad_reduce_launch(float* part, float* gw, float* gb, int nslices, int tap
         return;
     }
     const long n4 = ((long)taps * ic * oc + (gb ? oc : 0)) / 4;   // element quads
-    if (nslices <= 32) {
+    if (wgrad_fold_lanes(nslices) == 4) {
         hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, part, gw, gb, nslices, taps, ic, oc, alpha, transpose, accumulate);
     } else {
         hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, st, part, gw, gb, nslices, taps, ic, oc, alpha, transpose, accumulate);
@@ -1180,7 +1180,7 @@ static int wgrad_cus() {
     return g_wgrad_cu_cap > 0 && g_wgrad_cu_cap < n ? g_wgrad_cu_cap : n;
 }
 
-bool wgrad_mfma_supported(int ic, int oc, int dtype) { return (dtype == GS_F32 || dtype == GS_BF16) && ic % 32 == 0 && oc % 32 == 0; }
+static bool wgrad_mfma_supported(int ic, int oc, int dtype) { return (dtype == GS_F32 || dtype == GS_BF16) && ic % 32 == 0 && oc % 32 == 0; }
 
 static int patch_dim_rt(int mode, int t) { return mode == MODE_S1 ? t + 2 : (mode == MODE_S2 ? 2 * t + 1 : t + 1); }
 // ---- weight gradient (fp32 MFMA path)
@@ -1196,46 +1196,104 @@ static bool wgrad_thin_dma(int mode, int dtype, int IC, int OC, int Wb) {
     (void)mode;
     return !off && dtype == GS_BF16 && IC == 32 && (OC == 32 || OC == 64) && Wb >= 32;
 }
-static void wgrad_geometry(int mode, int dtype, int N, int Hb, int Wb, int IC, int OC, int* tw, int* tiles_x, int* tiles_y,
-                           int* ntiles, int* nslices) {
-    int np = (mode == MODE_S2 ? 64 : 128) * (dtype == GS_BF16 ? 2 : 1);
-    if (mode == MODE_S2 && wgrad_2x2(mode, dtype, IC, OC)) np = 64;
-    if (wgrad_thin_dma(mode, dtype, IC, OC, Wb)) {   // 256-pixel tiles, 64 at stride 2; two double-buffered blocks per CU
-        np = mode == MODE_S2 ? 64 : 256;
-        *tw = 32;
-        const int th = np / 32;
-        *tiles_x = cdiv(Wb, 32);
-        *tiles_y = cdiv(Hb, th);
-        *ntiles = N * *tiles_x * *tiles_y;
-        const int lds = 2 * (((patch_dim_rt(mode, th) * patch_dim_rt(mode, 32) + 15) / 16) * 1024 + (OC / 32) * np * 64);
-        int per_cu = (160 * 1024) / lds;
-        if (per_cu > 2) per_cu = 2;
-        if (per_cu < 1) per_cu = 1;
-        int ns = per_cu * wgrad_cus();
-        if (ns > *ntiles) ns = *ntiles;
-        *nslices = ns;
-        return;
-    }
-    *tw = Wb >= 32 ? 32 : 16;
-    const int th = np / *tw;
-    *tiles_x = cdiv(Wb, *tw);
-    *tiles_y = cdiv(Hb, th);
-    *ntiles = N * *tiles_x * *tiles_y;
-    int pairs = (IC / 32) * (OC / 32);
-    int target = dtype == GS_BF16 ? 768 : 512;
-    if (wgrad_2x2(mode, dtype, IC, OC)) { pairs /= 4; target = 256; }   // 64 x 64 tiles, double-buffered: one block of 4 waves per CU
-    else if (wgrad_thin_pairs(mode, dtype, IC, OC)) pairs /= 2;
-    int ns = target / pairs;
+// the 1 x 1 colour layers (2 channels on one side): thin_wgrad_kernel of conv_api.hip
+static bool thin_wgrad_ok(int ks, int ci, int co) {
+    if (ks != 1) return false;
+    const int c = ci == 2 ? co : (co == 2 ? ci : 0);
+    return c >= 4 && c <= 1024 && (c & 3) == 0 && 256 % (c >> 2) == 0 && !(ci == 2 && co == 2);
+}
+static void thin_wgrad_geometry(long npix, int c, int* nslices, long* pps) {
+    const long rpi = 256 / (c >> 2);
+    long ns = (npix + rpi * 32 - 1) / (rpi * 32);
+    if (ns > 1024) ns = 1024;
     if (ns < 1) ns = 1;
-    if (ns > *ntiles) ns = *ntiles;
-    *nslices = ns;
+    *pps = (npix + ns - 1) / ns;
+    *nslices = (int)((npix + *pps - 1) / *pps);
+}
+static void wgrad_direct_geometry(long npix, int* nslices, long* pps) {
+    long ns = (npix + 63) / 64;   // a thread walks its slice serially (index arithmetic + two dependent loads per pixel): keep it short
+    if (ns > 1024) ns = 1024;
+    if (ns < 1) ns = 1;
+    *pps = (npix + ns - 1) / ns;
+    *nslices = (int)((npix + *pps - 1) / *pps);
 }
 
-bool wgrad_mfma_has_bias(int dtype) { return dtype == GS_BF16; }   // the bf16 kernels produce the bias gradient on the side
+// THE selection (conv_shared.h: WgradPlan) for a kernel-role shape; N = images of all sources
+WgradPlan wgrad_plan(int mode, int ks, int dtype, int N, int Hb, int Wb, int IC, int OC) {
+    WgradPlan p;
+    memset(&p, 0, sizeof(p));
+    p.mode = mode;
+    const long elems = (long)ks * ks * IC * OC;
+    if (!(ks == 3 && wgrad_mfma_supported(IC, OC, dtype))) {
+        const long npix = (long)N * Hb * Wb;
+        p.ntiles = (int)npix;
+        if (thin_wgrad_ok(ks, IC, OC) && mode == MODE_S1) {
+            p.family = WG_THIN;
+            p.ot = IC == 2 ? 0 : 1;
+            thin_wgrad_geometry(npix, IC == 2 ? OC : IC, &p.nslices, &p.pps);
+            long dpps;   // (the workspace of a colour layer holds the direct kernel's partials as well, should they be more)
+            wgrad_direct_geometry(npix, &p.ws_slices, &dpps);
+        } else {
+            p.family = WG_DIRECT;
+            wgrad_direct_geometry(npix, &p.nslices, &p.pps);
+        }
+    } else {
+        p.fused_bias = dtype == GS_BF16;   // the bf16 kernels produce the bias gradient on the side
+        int np = (mode == MODE_S2 ? 64 : 128) * (dtype == GS_BF16 ? 2 : 1);
+        if (wgrad_thin_dma(mode, dtype, IC, OC, Wb)) {   // 256-pixel tiles, 64 at stride 2; two double-buffered blocks per CU
+            p.family = WG_THIN_DMA;
+            p.ot = OC / 32;
+            np = mode == MODE_S2 ? 64 : 256;
+            p.tw = 32;
+            const int th = np / 32;
+            p.tiles_x = cdiv(Wb, 32);
+            p.tiles_y = cdiv(Hb, th);
+            p.ntiles = N * p.tiles_x * p.tiles_y;
+            const int lds = 2 * (((patch_dim_rt(mode, th) * patch_dim_rt(mode, 32) + 15) / 16) * 1024 + (OC / 32) * np * 64);
+            int per_cu = (160 * 1024) / lds;
+            if (per_cu > 2) per_cu = 2;
+            if (per_cu < 1) per_cu = 1;
+            int ns = per_cu * wgrad_cus();
+            if (ns > p.ntiles) ns = p.ntiles;
+            p.nslices = ns;
+        } else {
+            int pairs = (IC / 32) * (OC / 32);
+            int target = dtype == GS_BF16 ? 768 : 512;
+            if (dtype == GS_F32) {
+                p.family = WG_F32;
+                p.ot = 1;
+            } else if (wgrad_2x2(mode, dtype, IC, OC)) {   // 64 x 64 tiles, double-buffered: one block of 4 waves per CU
+                p.family = WG_TILE64;
+                p.ot = 2;
+                if (mode == MODE_S2) np = 64;
+                pairs /= 4;
+                target = 256;
+            } else {
+                p.family = WG_BF16;
+                p.ot = wgrad_thin_pairs(mode, dtype, IC, OC) ? 2 : 1;
+                pairs /= p.ot;
+            }
+            p.tw = Wb >= 32 ? 32 : 16;
+            const int th = np / p.tw;
+            p.tiles_x = cdiv(Wb, p.tw);
+            p.tiles_y = cdiv(Hb, th);
+            p.ntiles = N * p.tiles_x * p.tiles_y;
+            int ns = target / pairs;
+            if (ns < 1) ns = 1;
+            if (ns > p.ntiles) ns = p.ntiles;
+            p.nslices = ns;
+        }
+    }
+    if (p.ws_slices < p.nslices) p.ws_slices = p.nslices;
+    const bool vec = (elems & 3) == 0;   // (a bias row comes with oc % 32 == 0 only)
+    p.fold = vec ? wgrad_fold_lanes(p.nslices) : 0;
+    p.batch_lanes = p.fold;
+    return p;
+}
+
 size_t wgrad_mfma_bytes(int mode, int dtype, int N, int Hb, int Wb, int IC, int OC) {
-    int tw, tx, ty, nt, ns;
-    wgrad_geometry(mode, dtype, N, Hb, Wb, IC, OC, &tw, &tx, &ty, &nt, &ns);
-    return align256((size_t)ns * (9 * (size_t)IC * OC + OC) * sizeof(float));
+    const WgradPlan p = wgrad_plan(mode, 3, dtype, N, Hb, Wb, IC, OC);
+    return align256((size_t)p.ws_slices * (9 * (size_t)IC * OC + OC) * sizeof(float));
 }
 
 // x: conv input side [N][Hi][Wi][IC]; gy: [N][Hb][Wb][OC]; gw[9][IC][OC] (or transposed)
@@ -1245,9 +1303,10 @@ int run_wgrad_mfma(int mode, const WgradSrcs& srcs, int nsrc, float* gw, float* 
                    GsWgradReduce* defer) {
     // N = images of ALL sources
     if (nsrc < 1 || nsrc > GS_WGRAD_MAX_SRC || srcs.n_end[nsrc - 1] != N) return fail(GS_ERR_ARG, "conv wgrad: %d sources ending at image %d for N=%d", nsrc, srcs.n_end[nsrc > 0 ? nsrc - 1 : 0], N);
-    int tw, tiles_x, tiles_y, ntiles, nslices;
-    wgrad_geometry(mode, dtype, N, Hb, Wb, IC, OC, &tw, &tiles_x, &tiles_y, &ntiles, &nslices);
-    if (gb && !wgrad_mfma_has_bias(dtype)) return fail(GS_ERR_UNSUPPORTED, "conv wgrad: fused bias gradient needs the bf16 kernels");
+    const WgradPlan p = wgrad_plan(mode, 3, dtype, N, Hb, Wb, IC, OC);
+    if (p.family < WG_F32) return fail(GS_ERR_UNSUPPORTED, "conv wgrad: no MFMA kernel for %d -> %d channels", IC, OC);
+    const int tw = p.tw, tiles_x = p.tiles_x, tiles_y = p.tiles_y, ntiles = p.ntiles, nslices = p.nslices;
+    if (gb && !p.fused_bias) return fail(GS_ERR_UNSUPPORTED, "conv wgrad: fused bias gradient needs the bf16 kernels");
     const int with_bias = gb != nullptr;
     const size_t need = (size_t)nslices * (9 * (size_t)IC * OC + (with_bias ? OC : 0)) * sizeof(float);
     if (ws_bytes < need) return fail(GS_ERR_WORKSPACE, "conv wgrad: workspace %zu < %zu", ws_bytes, need);
@@ -1266,12 +1325,12 @@ int run_wgrad_mfma(int mode, const WgradSrcs& srcs, int nsrc, float* gw, float* 
         if (mode == MODE_S1) { if (tw == 32) GS_WG(TT, MODE_S1, 32); else GS_WG(TT, MODE_S1, 16); } \
         else { if (tw == 32) GS_WG(TT, MODE_S2, 32); else GS_WG(TT, MODE_S2, 16); }          \
     } while (0)
-        if (dtype == GS_F32) {
+        if (p.family == WG_F32) {
             GS_WG_ALL(float);
         } else {
 #define GS_WGB(M, TWV)                                                                                                  \
     do {                                                                                                                \
-        if (wgrad_thin_pairs(mode, dtype, IC, OC))                                                                      \
+        if (p.ot == 2)                                                                                                  \
             hipLaunchKernelGGL((conv_wgrad_bf16_kernel<M, TWV, 2>), dim3((IC / 32) * (OC / 64), nslices), dim3(192), 0, st, srcs, \
                                part, N, Hi, Wi, IC, OC, Hb, Wb, tiles_x, tiles_y, ntiles, nslices, with_bias);         \
         else                                                                                                            \
@@ -1307,10 +1366,10 @@ int run_wgrad_mfma(int mode, const WgradSrcs& srcs, int nsrc, float* gw, float* 
         hipLaunchKernelGGL(kern_, dim3(1, nslices), dim3(256), lds_, st, srcs,                                          \
                            part, N, Hi, Wi, IC, OC, Hb, Wb, tiles_x, tiles_y, ntiles, nslices, with_bias);              \
     } while (0)
-            if (wgrad_thin_dma(mode, dtype, IC, OC, Wb)) {
-                if (mode == MODE_S1) { if (OC == 32) GS_WGT(MODE_S1, 1); else GS_WGT(MODE_S1, 2); }
-                else { if (OC == 32) GS_WGT(MODE_S2, 1); else GS_WGT(MODE_S2, 2); }
-            } else if (wgrad_2x2(mode, dtype, IC, OC)) {
+            if (p.family == WG_THIN_DMA) {
+                if (mode == MODE_S1) { if (p.ot == 1) GS_WGT(MODE_S1, 1); else GS_WGT(MODE_S1, 2); }
+                else { if (p.ot == 1) GS_WGT(MODE_S2, 1); else GS_WGT(MODE_S2, 2); }
+            } else if (p.family == WG_TILE64) {
                 if (mode == MODE_S1) { if (tw == 32) GS_WGB2(MODE_S1, 32); else GS_WGB2(MODE_S1, 16); }
                 else { if (tw == 32) GS_WGB2(MODE_S2, 32); else GS_WGB2(MODE_S2, 16); }
             } else {
@@ -1331,7 +1390,6 @@ int run_wgrad_mfma(int mode, const WgradSrcs& srcs, int nsrc, float* gw, float* 
 }
 
 // ---- grouped weight gradients: planning and launch of one group (the layers of one conv mode; tiles are 32 pixels wide)
-bool wgrad_sk_supported(int mode, int dtype, int IC, int OC) { return wgrad_2x2(mode, dtype, IC, OC); }
 // fills the tiling of job q (its srcs / channel counts / image sizes already set; N = images of all sources)
 void wgrad_sk_job_geometry(int mode, int N, SkJob& q) {
     const int np = mode == MODE_S2 ? 64 : 256;

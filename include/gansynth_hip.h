@@ -204,6 +204,28 @@ int gs_conv_wgrad_jobs(const GsWgradJob* jobs, int njobs, void* ws, size_t ws_by
  * previous setting.  For a call whose launches run on a forked branch of a hipGraph beside a latency-bound chain of few-block kernels,
  * which then finds CUs to land on.  Host-side state, read when a launch is planned (workspace query and launch alike). */
 int gs_wgrad_cu_cap(int cap);
+/* What gs_conv_bwd_weight would launch for a layer, asked without launching: host arithmetic on the very plan the launcher reads, no device
+ * needed (the CU count then defaults to the MI355X's 256; gs_wgrad_cu_cap is honoured).  out[GS_WGRAD_PLAN_INTS] =
+ *    0 family   GS_WGRAD_DIRECT / THIN (the VALU kernels of the 1- / 2-channel layers), F32, BF16, THIN_DMA, TILE64 (the MFMA kernels)
+ *    1 mode     0 stride 1, 1 stride 2 (a transposed layer runs as the stride-2 kernel with its sides swapped)
+ *    2 TW       pixel-tile width of an MFMA kernel (16 / 32), 0 otherwise
+ *    3 OT       32-channel output tiles per block (TILE64: 2 on both sides); THIN: 1 when x is the wide side, 0 when gy is
+ *    4 swapped  1: x and gy change places and gw is stored transposed (the transposed layer)
+ *    5-8        kernel-role ICk, OCk, Hb, Wb (what the kernel contracts / the gradient side / the base grid)
+ *    9 ntiles   pixel tiles over all images (DIRECT / THIN: output pixels),   10 nslices: block partials the fold sums
+ *   11 fold     the fold run at once: 0 the scalar kernel, else its slice lanes (4 / 16)
+ *   12 batch    slice lanes of the batched fold when the reduction is left pending (gs_conv_wgrad_jobs); 0: it cannot be deferred
+ *   13 bias     1: the kernel produces the bias gradient on the side,   14-15 tiles_x, tiles_y (MFMA)
+ * c->n counts the images of all sources. */
+enum { GS_WGRAD_DIRECT = 0, GS_WGRAD_THIN = 1, GS_WGRAD_F32 = 2, GS_WGRAD_BF16 = 3, GS_WGRAD_THIN_DMA = 4, GS_WGRAD_TILE64 = 5 };
+#define GS_WGRAD_PLAN_INTS 16
+int gs_conv_wgrad_plan(const GsConv* c, int* out);
+/* What gs_conv_wgrad_jobs would do with a job list (same planning code, nothing dereferenced, nothing launched).  out, a stream of ints:
+ *   ngroups, nsingle,
+ *   per stream-K group: mode, njobs, total_units, total_runs, nblocks, then per job: index in `jobs`, unit_base, run_base, ntiles, nct
+ *   per per-layer job:  index in `jobs`, the source it was split off for (-1: the whole job), then the GS_WGRAD_PLAN_INTS of gs_conv_wgrad_plan.
+ * Returns the number of ints written (>= 2), or a negative GS_ERR_* (GS_ERR_ARG when out_len is too small). */
+int gs_conv_wgrad_jobs_plan(const GsWgradJob* jobs, int njobs, int* out, int out_len);
 
 /* Refreshing many prepared weight operands in one launch (after an optimizer step: ~60 conv maps, one kernel instead of
  * one re-layout launch in front of each conv).  A descriptor names the fp32 HWIO master weight, the persistent workspace

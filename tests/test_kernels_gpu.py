@@ -45,7 +45,9 @@ def close(got, ref, rel=1e-3, name=""):
 # (n, ci, co, h, w, ksize, stride): the layer shapes of the small networks -- all three maps of a layer, the direct kernels included.  Every one
 # of these 3x3 cases is a few-block layer, so between them they launch only the few-block ("small", TG = 9) implicit-GEMM kernels and the
 # resident A = 1 one; which compiled kernel a shape runs is the chooser's answer (gs_conv_igemm_config), and tests/test_igemm_cover_gpu.py
-# holds EVERY compiled kernel to a float64 reference at shapes it finds through that chooser.
+# holds EVERY compiled kernel to a float64 reference at shapes it finds through that chooser.  The same for the weight gradients: which of the 28
+# kernels takes a shape is gs_conv_wgrad_plan's answer, and tests/test_wgrad_cover_gpu.py holds every one of them, every trip of the slice folds and
+# every kind of stream-K cut to a float64 reference.
 CONV_CASES = [
     (2, 32, 32, 8, 128, 3, 1),    # 32 -> 32 at width >= 64: the resident 32-channel tile (top-level shape class)
     (2, 32, 32, 4, 32, 3, 1),
@@ -559,8 +561,8 @@ def test_ragged_and_single_image_shapes(K, E, case, dtype):
     tol = 1e-3 if dtype == torch.float32 else 2e-2
     close(K.conv2d_fwd(dev(x, dtype), dev(wt), ks, st, alpha), E.conv2d_fwd(x, wr, ks, st, alpha), rel=tol, name="fwd")
     close(K.conv2d_bwd_data(dev(gy, dtype), dev(wt), x.shape, ks, st, alpha), E.conv2d_bwd_data(gy, wr, x.shape, ks, st, alpha), rel=tol, name="bwd_data")
-    close(K.conv2d_bwd_weight(dev(x, dtype), dev(gy, dtype), ks, st, alpha), E.conv2d_bwd_weight(x, gy, ks, st, alpha), rel=1e-3 if dtype == torch.float32 else 1e-2,
-          name="bwd_weight")
+    # (1e-4 like every other weight-gradient test: measured 1.0e-7 .. 9.9e-7 over these cases and both dtypes on the MI355X)
+    close(K.conv2d_bwd_weight(dev(x, dtype), dev(gy, dtype), ks, st, alpha), E.conv2d_bwd_weight(x, gy, ks, st, alpha), rel=1e-4, name="bwd_weight")
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
