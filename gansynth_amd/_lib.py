@@ -28,6 +28,25 @@ class GsConv(ctypes.Structure):
 
 C = POINTER(GsConv)
 
+
+class GsSpectralKnobs(ctypes.Structure):
+    """include/gansynth_hip.h: the measurement switches of the spectral kernels (GS_SPECTRAL_GENERIC, GS_INVERSE_*)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("generic", "fp32_gemm", "mag_6terms", "gemm_256", "gemm_kb", "gemm_kb3", "block_fft", "separate_ola")]
+
+
+class GsSpectralRoute(ctypes.Structure):
+    """include/gansynth_hip.h: which kernels a spectral call runs (gs_spectral_route)."""
+    _fields_ = [("fwd_workspace_bytes", ctypes.c_int64), ("fwd_kind", ctypes.c_int32), ("maxnz", ctypes.c_int32), ("mz", ctypes.c_int32),
+                ("mel_cnt", ctypes.c_int32 * 8), ("runs", ctypes.c_int32), ("q", ctypes.c_int32), ("rem", ctypes.c_int32),
+                ("exchange", ctypes.c_int32), ("span_examples", ctypes.c_int32), ("gemm_kind", ctypes.c_int32), ("gemm_launches", ctypes.c_int32),
+                ("gemm_nj", ctypes.c_int32 * 2), ("gemm_np", ctypes.c_int32 * 2), ("gemm_kb", ctypes.c_int32 * 2), ("istft_kind", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+SPEC_FWD_GENERIC, SPEC_FWD_WAVE = 0, 1                                                                        # GS_SPEC_FWD_*
+SPEC_GEMM_NONE, SPEC_GEMM_F32_64, SPEC_GEMM_F32_128, SPEC_GEMM_SPLIT_ALL, SPEC_GEMM_SPLIT_TWO, SPEC_GEMM_WIDE_256 = range(6)   # GS_SPEC_GEMM_*
+SPEC_ISTFT_NONE, SPEC_ISTFT_WAVE_OLA, SPEC_ISTFT_WAVE_FRAMES, SPEC_ISTFT_BLOCK_FFT = range(4)                # GS_SPEC_ISTFT_*
+
 # name -> (restype, argtypes); every symbol include/gansynth_hip.h declares
 SIGNATURES = {
     "gs_last_error": (c_char_p, []),
@@ -121,6 +140,7 @@ SIGNATURES = {
     "gs_stft_mel_if_workspace_bytes": (Z, [P, I]),
     "gs_mel_if_to_waveform": (I, [P, P, I, I, I, P, I, P, Z, P]),
     "gs_mel_if_to_waveform_workspace_bytes": (Z, [P, I]),
+    "gs_spectral_route": (I, [I, I, I, P, I, I, I, I, I, I, Z, POINTER(GsSpectralKnobs), POINTER(GsSpectralRoute)]),
     "gs_weight_standardize": (I, [P, P, I, I, F, P]),
     "gs_resnet_stem_pool": (I, [P, P, P, P, P, I, I, I, I, I, P]),
     "gs_max_pool2d": (I, [P, P, I, I, I, I, I, P]),

@@ -533,9 +533,10 @@ extern "C" int gs_spectral_plan_create(gs_spectral_plan** out, int frame_length,
     std::vector<float2> tw(H / 2), twp(H + 1);
     for (int k = 0; k < H / 2; ++k) tw[k] = make_float2((float)cos(-2.0 * M_PI * k / H), (float)sin(-2.0 * M_PI * k / H));
     for (int k = 0; k <= H; ++k) twp[k] = make_float2((float)cos(-2.0 * M_PI * k / frame_length), (float)sin(-2.0 * M_PI * k / frame_length));
-    int maxnz = 1;
-    for (int m = 0; m < H; ++m) { int c = 0; for (int f = 0; f < H; ++f) if (mel_dense[(long)f * H + m] != 0.f) ++c; if (c > maxnz) maxnz = c; }
-    if (maxnz <= 8) maxnz = (maxnz + 1) & ~1;   // even widths have an unrolled kernel instantiation (padding = weight 0 on bin 0)
+    p->digest = spectral_mel_digest(mel_dense, H);
+    p->generic = spectral_knobs_env().generic;
+    const GsSpectralRoute route = plan_route(p, 0, 0, 0, GS_F32, 0);   // (no call yet: the fields the plan fixes)
+    const int maxnz = route.maxnz;
     std::vector<int> idx((long)H * maxnz, 0);
     std::vector<float> val((long)H * maxnz, 0.f);
     for (int m = 0; m < H; ++m) { int c = 0; for (int f = 0; f < H; ++f) { const float w = mel_dense[(long)f * H + m]; if (w != 0.f) { idx[(long)c * H + m] = f; val[(long)c * H + m] = w; ++c; } } }
@@ -552,40 +553,30 @@ extern "C" int gs_spectral_plan_create(gs_spectral_plan** out, int frame_length,
     GS_HIP_OK(hipMemcpy(p->twp, twp.data(), (H + 1) * sizeof(float2), hipMemcpyHostToDevice));
     GS_HIP_OK(hipMemcpy(p->mel_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
     GS_HIP_OK(hipMemcpy(p->mel_val, val.data(), val.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (H == 1024 && !getenv("GS_SPECTRAL_GENERIC")) {
-        // wave-per-frame path (spectral_wave.hip): every mel column's non-zeros must be ONE run of linear bins, the longest run
-        // of each 128-column block as in the reference configuration
-        std::vector<int> lo(H, 0), len(H, 0);
-        bool ok = true;
-        for (int m = 0; m < H && ok; ++m) {
-            int first = -1, last = -1, c = 0;
-            for (int f = 0; f < H; ++f) if (mel_dense[(long)f * H + m] != 0.f) { if (first < 0) first = f; last = f; ++c; }
-            if (c) { lo[m] = first; len[m] = last - first + 1; ok = len[m] <= 8; }
-        }
-        if (ok) {
-            int tot = 0;
-            for (int j = 0; j < 8; ++j) {
-                int c = 1;
-                for (int m = 128 * j; m < 128 * (j + 1); ++m) c = len[m] > c ? len[m] : c;
-                p->mel_cnt[j] = c; p->mel_off[j] = tot; tot += c * 128;
+    if (route.fwd_kind == GS_SPEC_FWD_WAVE) {
+        // wave-per-frame path (spectral_wave.hip): every mel column's non-zeros are ONE run of linear bins, the longest run of each
+        // 128-column block as the kernel's unrolled gather expects
+        std::vector<int> lo(H, 0);
+        for (int m = 0; m < H; ++m)
+            for (int f = 0; f < H; ++f) if (mel_dense[(long)f * H + m] != 0.f) { lo[m] = f; break; }
+        int tot = 0;
+        for (int j = 0; j < 8; ++j) { p->mel_cnt[j] = route.mel_cnt[j]; p->mel_off[j] = tot; tot += route.mel_cnt[j] * 128; }
+        std::vector<float> w(tot, 0.f);
+        for (int j = 0; j < 8; ++j)
+            for (int m = 128 * j; m < 128 * (j + 1); ++m) {
+                if (lo[m] + p->mel_cnt[j] > H) lo[m] = H - p->mel_cnt[j];   // keep every gathered bin inside the row (weight 0 there)
+                for (int e = 0; e < p->mel_cnt[j]; ++e) w[p->mel_off[j] + e * 128 + (m - 128 * j)] = mel_dense[(long)(lo[m] + e) * H + m];
             }
-            std::vector<float> w(tot, 0.f);
-            for (int j = 0; j < 8; ++j)
-                for (int m = 128 * j; m < 128 * (j + 1); ++m) {
-                    if (lo[m] + p->mel_cnt[j] > H) lo[m] = H - p->mel_cnt[j];   // keep every gathered bin inside the row (weight 0 there)
-                    for (int e = 0; e < p->mel_cnt[j]; ++e) w[p->mel_off[j] + e * 128 + (m - 128 * j)] = mel_dense[(long)(lo[m] + e) * H + m];
-                }
-            std::vector<float2> t1k(1024);
-            for (int k = 0; k < 1024; ++k) t1k[k] = make_float2((float)cos(-2.0 * M_PI * k / 1024.0), (float)sin(-2.0 * M_PI * k / 1024.0));
-            p->mel_wtot = tot;
-            GS_HIP_OK(hipMalloc(&p->tw1k, 1024 * sizeof(float2)));
-            GS_HIP_OK(hipMalloc(&p->mel_lo, H * sizeof(int)));
-            GS_HIP_OK(hipMalloc(&p->mel_w, (size_t)tot * sizeof(float)));
-            GS_HIP_OK(hipMemcpy(p->tw1k, t1k.data(), 1024 * sizeof(float2), hipMemcpyHostToDevice));
-            GS_HIP_OK(hipMemcpy(p->mel_lo, lo.data(), H * sizeof(int), hipMemcpyHostToDevice));
-            GS_HIP_OK(hipMemcpy(p->mel_w, w.data(), (size_t)tot * sizeof(float), hipMemcpyHostToDevice));
-            p->fast = stft_wave_shape_ok(p->mel_cnt) ? 1 : 0;   // (the kernel's gather is unrolled for the reference configuration's shape)
-        }
+        std::vector<float2> t1k(1024);
+        for (int k = 0; k < 1024; ++k) t1k[k] = make_float2((float)cos(-2.0 * M_PI * k / 1024.0), (float)sin(-2.0 * M_PI * k / 1024.0));
+        p->mel_wtot = tot;
+        GS_HIP_OK(hipMalloc(&p->tw1k, 1024 * sizeof(float2)));
+        GS_HIP_OK(hipMalloc(&p->mel_lo, H * sizeof(int)));
+        GS_HIP_OK(hipMalloc(&p->mel_w, (size_t)tot * sizeof(float)));
+        GS_HIP_OK(hipMemcpy(p->tw1k, t1k.data(), 1024 * sizeof(float2), hipMemcpyHostToDevice));
+        GS_HIP_OK(hipMemcpy(p->mel_lo, lo.data(), H * sizeof(int), hipMemcpyHostToDevice));
+        GS_HIP_OK(hipMemcpy(p->mel_w, w.data(), (size_t)tot * sizeof(float), hipMemcpyHostToDevice));
+        p->fast = 1;
     }
     if (mel_pinv) {
         GS_HIP_OK(hipMalloc(&p->pinv, (size_t)H * H * sizeof(float)));
@@ -630,7 +621,8 @@ extern "C" int gs_spectral_plan_destroy(gs_spectral_plan* p) {
 extern "C" int gs_stft_fwd(const gs_spectral_plan* p, const float* wave, int batch, int wave_len, int front_pad, float* magnitude,
                            float* phase, void* stream) {
     GS_CHECK_ARG(p && batch > 0 && wave_len > 0, "stft_fwd: bad args");
-    if (p->fast) return launch_stft_wave_magphase(p, wave, batch, wave_len, front_pad, magnitude, phase, as_stream(stream));
+    const GsSpectralRoute r = plan_route(p, batch, wave_len, front_pad, GS_F32, 0);
+    if (r.fwd_kind == GS_SPEC_FWD_WAVE) return launch_stft_wave_magphase(p, r, wave, batch, wave_len, front_pad, magnitude, phase, as_stream(stream));
     hipLaunchKernelGGL((stft_kernel<float, 0, 0>), dim3(p->time_steps, batch), dim3(256), 0, as_stream(stream), *p, wave, wave_len, front_pad,
                        magnitude, phase, (float*)nullptr);
     GS_CHECK_LAUNCH();
@@ -655,20 +647,20 @@ extern "C" int gs_if_unwrap(const gs_spectral_plan* p, const float* mel_phase, f
 }
 
 extern "C" size_t gs_stft_mel_if_workspace_bytes(const gs_spectral_plan* p, int batch) {
-    if (p && p->fast) return stft_wave_edge_bytes(p, batch);   // the mel phases stay in registers; 4 KB per run for the run-edge exchange
-    return p ? (size_t)batch * p->time_steps * p->nbins * sizeof(float) : 0;
+    return p && batch > 0 ? (size_t)plan_route(p, batch, 0, 0, GS_F32, 0).fwd_workspace_bytes : 0;
 }
 
 extern "C" int gs_stft_mel_if_fwd(const gs_spectral_plan* p, const float* wave, int batch, int wave_len, int front_pad, void* images,
                                   int dtype, void* ws, size_t ws_bytes, void* stream) {
     GS_CHECK_ARG(p && batch > 0 && wave_len > 0, "stft_mel_if_fwd: bad args");
-    if (p->fast) return launch_stft_wave_fused(p, wave, batch, wave_len, front_pad, images, dtype, ws, ws_bytes, as_stream(stream));
-    if (ws_bytes < gs_stft_mel_if_workspace_bytes(p, batch)) return fail(GS_ERR_WORKSPACE, "stft_mel_if_fwd: workspace too small");
+    const GsSpectralRoute r = plan_route(p, batch, wave_len, front_pad, dtype, ws_bytes);
+    if (r.fwd_kind == GS_SPEC_FWD_WAVE) return launch_stft_wave_fused(p, r, wave, batch, wave_len, front_pad, images, dtype, ws, as_stream(stream));
+    if (ws_bytes < (size_t)r.fwd_workspace_bytes) return fail(GS_ERR_WORKSPACE, "stft_mel_if_fwd: workspace too small");
     hipStream_t st = as_stream(stream);
     float* mel_phase = (float*)ws;
 #define GS_STFT(MZV) hipLaunchKernelGGL((stft_kernel<T, 1, MZV>), dim3(p->time_steps, batch), dim3(256), 0, st, *p, wave, wave_len, front_pad, mel_phase, (float*)nullptr, (T*)images)
     GS_DISPATCH_DTYPE(dtype, {
-        if (p->maxnz == 2) GS_STFT(2); else if (p->maxnz == 4) GS_STFT(4); else if (p->maxnz == 6) GS_STFT(6); else if (p->maxnz == 8) GS_STFT(8); else GS_STFT(0);
+        if (r.mz == 2) GS_STFT(2); else if (r.mz == 4) GS_STFT(4); else if (r.mz == 6) GS_STFT(6); else if (r.mz == 8) GS_STFT(8); else GS_STFT(0);
         hipLaunchKernelGGL((if_unwrap_kernel<T, 1>), dim3(cdiv((long)batch * p->nbins, 256)), dim3(256), 0, st, *p, mel_phase, (float*)nullptr, (T*)images, batch);
     });
 #undef GS_STFT
@@ -696,12 +688,12 @@ extern "C" int gs_mel_if_to_waveform(const gs_spectral_plan* p, const void* imag
     float* mag = mel_mag + 3 * rows * H;
     float* ph = mag + rows * H;
     float* frames = ph + rows * H;
-    static const bool no_split = getenv("GS_INVERSE_FP32_GEMM") != nullptr;   // measurement knob: the exact-fp32 MFMA kernel
-    const bool split = (2 * rows) % 128 == 0 && H % 128 == 0 && H % 32 == 0 && p->pinv_split && !no_split;
+    // the route (spectral_route.h; the measurement knobs GS_INVERSE_* enter there): which contraction, which inverse transform
+    const GsSpectralRoute r = plan_route(p, batch, wave_len, front_pad, dtype, 0);
+    const bool split = r.gemm_kind == GS_SPEC_GEMM_SPLIT_ALL || r.gemm_kind == GS_SPEC_GEMM_SPLIT_TWO || r.gemm_kind == GS_SPEC_GEMM_WIDE_256;
     // (the three bf16 planes of the stacked pair take 3 x 2 x rows x H x 2 bytes = the first 3 rows x H floats of the workspace)
     unsigned short* a_split = split ? reinterpret_cast<unsigned short*>(mel_mag) : nullptr;
-    static const bool full_mag = getenv("GS_INVERSE_MAG_6TERMS") != nullptr;   // measurement knob: six terms for the magnitude rows too
-    const bool two = split && rows % 128 == 0 && !full_mag;   // magnitude rows [0, rows): two planes, three terms
+    const bool two = split && r.gemm_launches == 2;   // magnitude rows [0, rows): two planes, three terms
     // (two mel bins per thread with 4-byte plane stores and an unrolled time loop measured the same 121-124 us: 603 MB at ~5 TB/s, the chip's
     //  mixed read / write rate -- the one-bin form stays)
     GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((inv_prep_kernel<T>), dim3(cdiv((long)batch * H, 256)), dim3(256), 0, st, *p, (const T*)images, mel_mag, mel_ph, batch, a_split, two ? 2 : 3));
@@ -713,49 +705,52 @@ extern "C" int gs_mel_if_to_waveform(const gs_spectral_plan* p, const void* imag
         // measured 1 % SLOWER: the kernel is not L2-bound.  PMC (profiles/r02_u_inverse_pmc.txt): the MFMA pipe is busy 54 % of the phase rows'
         // launch and 34 % of the magnitude rows'; the loop is 48 MFMAs + 24 ds_read_b128 + 12 global loads + 12 ds_write_b128 + 2 barriers, and
         // the two barriers of the single-buffered LDS tile are what the second block of the CU does not fully cover)
-        static const bool wide = getenv("GS_INVERSE_GEMM_256") != nullptr;
         const int M2 = (int)(2 * rows);
-        const unsigned gw = (unsigned)(H / (wide && H % 256 == 0 ? 256 : 128));
+        const unsigned gw = (unsigned)(H / (r.gemm_kind == GS_SPEC_GEMM_WIDE_256 ? 256 : 128));
         const unsigned blocks_mag = (unsigned)(rows / 128) * gw, blocks_all = (unsigned)(2 * rows / 128) * gw;
-        if (H % 256 == 0 && wide) {
+        // launch i of the route: gemm_bf16x6_kernel<NJ, NP, KB> on the magnitude rows, the phase rows, or all of them
+        auto gemm = [&](int i, unsigned blocks, int m_begin) -> int {
+            const int nj = r.gemm_nj[i], np = r.gemm_np[i], kb = r.gemm_kb[i];
+#define GS_GEMM(NJ, NP, KB)                                                                                                                       \
+    if (nj == NJ && np == NP && kb == KB) {                                                                                                      \
+        hipLaunchKernelGGL((gemm_bf16x6_kernel<NJ, NP, KB>), dim3(blocks), dim3(256), 0, st, a_split, p->pinv_split, mag, M2, H, H, m_begin);   \
+        return 0;                                                                                                                                \
+    }
+            GS_GEMM(4, 2, 2) GS_GEMM(4, 3, 2) GS_GEMM(2, 2, 4) GS_GEMM(2, 2, 2) GS_GEMM(2, 3, 4) GS_GEMM(2, 3, 2)
+#undef GS_GEMM
+            return fail(GS_ERR_ARG, "mel_if_to_waveform: no gemm_bf16x6_kernel<%d, %d, %d>", nj, np, kb);
+        };
+        if (r.gemm_kind == GS_SPEC_GEMM_WIDE_256) {
             if (two) {
-                hipLaunchKernelGGL((gemm_bf16x6_kernel<4, 2>), dim3(blocks_mag), dim3(256), 0, st, a_split, p->pinv_split, mag, M2, H, H, 0);
-                hipLaunchKernelGGL((gemm_bf16x6_kernel<4, 3>), dim3(blocks_mag), dim3(256), 0, st, a_split, p->pinv_split, mag, M2, H, H, (int)rows);
-            } else {
-                hipLaunchKernelGGL((gemm_bf16x6_kernel<4, 3>), dim3(blocks_all), dim3(256), 0, st, a_split, p->pinv_split, mag, M2, H, H, 0);
-            }
+                if (int e = gemm(0, blocks_mag, 0)) return e;
+                if (int e = gemm(1, blocks_mag, (int)rows)) return e;
+            } else if (int e = gemm(0, blocks_all, 0)) return e;
         } else if (two) {
             // (profiling records: kind 30 = magnitude rows, three bf16 products per multiply-add; 31 = phase rows, six; 32 = all rows, six.
             //  flops = EXECUTED bf16 MFMA flops, bytes = operand planes read once + fp32 result written once)
             const double half = 2.0 * (double)rows * H * H;
             {
                 ProfScope ps(st, 3.0 * half, (double)rows * H * 4 + 2.0 * H * H * 2 + (double)rows * H * 4, 30, batch, p->time_steps, H, H, H, 0, 0);
-                static const int kb_mag = getenv("GS_INVERSE_GEMM_KB") ? atoi(getenv("GS_INVERSE_GEMM_KB")) : 4;
-                if (kb_mag == 4 && H % 64 == 0) hipLaunchKernelGGL((gemm_bf16x6_kernel<2, 2, 4>), dim3(blocks_mag), dim3(256), 0, st, a_split, p->pinv_split, mag, M2, H, H, 0);
-                else hipLaunchKernelGGL((gemm_bf16x6_kernel<2, 2>), dim3(blocks_mag), dim3(256), 0, st, a_split, p->pinv_split, mag, M2, H, H, 0);
+                if (int e = gemm(0, blocks_mag, 0)) return e;
             }
             {
                 ProfScope ps(st, 6.0 * half, (double)rows * H * 6 + 3.0 * H * H * 2 + (double)rows * H * 4, 31, batch, p->time_steps, H, H, H, 0, 0);
-                static const int kb_ph = getenv("GS_INVERSE_GEMM_KB3") ? atoi(getenv("GS_INVERSE_GEMM_KB3")) : 2;
-                if (kb_ph == 4 && H % 64 == 0) hipLaunchKernelGGL((gemm_bf16x6_kernel<2, 3, 4>), dim3(blocks_mag), dim3(256), 0, st, a_split, p->pinv_split, mag, M2, H, H, (int)rows);
-                else hipLaunchKernelGGL((gemm_bf16x6_kernel<2, 3>), dim3(blocks_mag), dim3(256), 0, st, a_split, p->pinv_split, mag, M2, H, H, (int)rows);
+                if (int e = gemm(1, blocks_mag, (int)rows)) return e;
             }
         } else {
             ProfScope ps(st, 12.0 * (double)rows * H * H, 2.0 * rows * H * 6 + 3.0 * H * H * 2 + 2.0 * rows * H * 4, 32, batch, p->time_steps, H, H, H, 0, 0);
-            hipLaunchKernelGGL((gemm_bf16x6_kernel<2, 3>), dim3(blocks_all), dim3(256), 0, st, a_split, p->pinv_split, mag, M2, H, H, 0);
+            if (int e = gemm(0, blocks_all, 0)) return e;
         }
-    } else if ((2 * rows) % 128 == 0 && H % 128 == 0) {
+    } else if (r.gemm_kind == GS_SPEC_GEMM_F32_128) {
         hipLaunchKernelGGL(gemm_f32_128_kernel, dim3((unsigned)((2 * rows / 128) * (H / 128))), dim3(256), 0, st, mel_mag, p->pinv, mag, (int)(2 * rows), H, H);
     } else {
         dim3 gg(cdiv(H, 64), cdiv(2 * rows, 64));
         hipLaunchKernelGGL(gemm_f32_kernel, gg, dim3(256), 0, st, mel_mag, p->pinv, mag, (int)(2 * rows), H, H);
     }
     GS_CHECK_LAUNCH();
-    static const bool no_wave = getenv("GS_INVERSE_BLOCK_FFT") != nullptr;   // measurement knob: the block-per-frame radix-2 kernel
-    static const bool no_ola = getenv("GS_INVERSE_SEPARATE_OLA") != nullptr;   // measurement knob: frames through memory + the gather kernel
-    if (p->fast && H == 1024 && !no_wave && !no_ola && istft_wave_ola_ok(p, wave_len, front_pad))
+    if (r.istft_kind == GS_SPEC_ISTFT_WAVE_OLA)
         return launch_istft_wave_ola(p, mag, ph, wave, batch, wave_len, front_pad, st);   // overlap-add and crop inside: done
-    if (p->fast && H == 1024 && !no_wave) {
+    if (r.istft_kind == GS_SPEC_ISTFT_WAVE_FRAMES) {
         if (int e = launch_istft_wave(p, mag, ph, frames, rows, st)) return e;
     } else {
         hipLaunchKernelGGL(istft_kernel, dim3(p->time_steps, batch), dim3(256), 0, st, *p, mag, ph, frames);
@@ -763,5 +758,19 @@ extern "C" int gs_mel_if_to_waveform(const gs_spectral_plan* p, const void* imag
     }
     hipLaunchKernelGGL(overlap_add_kernel, dim3(cdiv((long)batch * wave_len, 256)), dim3(256), 0, st, *p, frames, wave, batch, wave_len, front_pad);
     GS_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int gs_spectral_route(int frame_length, int frame_step, int time_steps, const float* mel_dense, int has_pinv, int batch, int count,
+                                 int wave_len, int front_pad, int dtype, size_t fwd_ws_bytes, const GsSpectralKnobs* knobs, GsSpectralRoute* out) {
+    GS_CHECK_ARG(mel_dense && out, "spectral_route: null argument");
+    const int H = frame_length / 2;
+    GS_CHECK_ARG(H >= 64 && H <= 1024 && (H & (H - 1)) == 0 && frame_length == 2 * H, "spectral_route: frame_length %d must be 2*2^k, 128..2048", frame_length);
+    GS_CHECK_ARG(frame_step > 0 && time_steps > 0 && batch > 0 && count > 0 && wave_len > 0, "spectral_route: bad frame_step/time_steps/batch/count/wave_len");
+    GS_CHECK_ARG(dtype == GS_F32 || dtype == GS_BF16, "spectral_route: bad dtype %d", dtype);
+    const SpectralMel mel = spectral_mel_digest(mel_dense, H);
+    const GsSpectralKnobs k = knobs ? *knobs : spectral_knobs_env();
+    for (int i = 0; i < count; ++i)
+        out[i] = spectral_route(frame_length, frame_step, time_steps, mel, has_pinv != 0, batch + i, wave_len, front_pad, dtype, fwd_ws_bytes, k);
     return 0;
 }

@@ -2,6 +2,7 @@
 // inverse path) and spectral_wave.hip (the wave-per-frame forward path for 2048-sample frames).
 #pragma once
 #include "gs_common.h"
+#include "spectral_route.h"
 
 struct gs_spectral_plan {
     int frame_length, frame_step, time_steps, nbins, log2h, maxnz;
@@ -21,17 +22,23 @@ struct gs_spectral_plan {
     int mel_cnt[8];     // run length used for block j (max over its 128 columns)
     int mel_off[8];     // float offset of block j in mel_w
     int mel_wtot;       // floats in mel_w
+    // what spectral_route (spectral_route.h) reads of the mel matrix, and GS_SPECTRAL_GENERIC as it stood when the plan was created
+    gs::SpectralMel digest;
+    int generic;
 };
 
 namespace gs {
+// the route of a call on this plan (spectral_route.h): what every launcher and workspace query below reads
+inline GsSpectralRoute plan_route(const gs_spectral_plan* p, int batch, int wave_len, int front_pad, int dtype, size_t fwd_ws_bytes) {
+    GsSpectralKnobs k = spectral_knobs_env();
+    k.generic = p->generic;
+    return spectral_route(p->frame_length, p->frame_step, p->time_steps, p->digest, p->pinv != nullptr, batch, wave_len, front_pad, dtype, fwd_ws_bytes, k);
+}
 // spectral_wave.hip
-bool stft_wave_shape_ok(const int* mel_cnt);
-size_t stft_wave_edge_bytes(const gs_spectral_plan* p, int batch);
-int launch_stft_wave_fused(const gs_spectral_plan* p, const float* wave, int batch, int wave_len, int front_pad, void* images, int dtype,
-                           void* ws, size_t ws_bytes, hipStream_t st);
+int launch_stft_wave_fused(const gs_spectral_plan* p, const GsSpectralRoute& r, const float* wave, int batch, int wave_len, int front_pad, void* images,
+                           int dtype, void* ws, hipStream_t st);
 int launch_istft_wave(const gs_spectral_plan* p, const float* mag, const float* phase, float* frames, long nframes, hipStream_t st);
-bool istft_wave_ola_ok(const gs_spectral_plan* p, int wave_len, int front_pad);
 int launch_istft_wave_ola(const gs_spectral_plan* p, const float* mag, const float* phase, float* wave, int batch, int wave_len, int front_pad, hipStream_t st);
-int launch_stft_wave_magphase(const gs_spectral_plan* p, const float* wave, int batch, int wave_len, int front_pad, float* mag, float* phase,
-                              hipStream_t st);
+int launch_stft_wave_magphase(const gs_spectral_plan* p, const GsSpectralRoute& r, const float* wave, int batch, int wave_len, int front_pad, float* mag,
+                              float* phase, hipStream_t st);
 }  // namespace gs

@@ -26,9 +26,8 @@
 
 namespace gs {
 
-#ifndef SW_WAVES
-#define SW_WAVES 12         // waves per block = per CU.  Measured at batch 256: 12 waves (3 per SIMD, <= 168 VGPRs) 126 us, 16 waves
-#endif                      // (128 VGPRs, Hann / run starts through L1) 149 us, 8 waves (256 VGPRs) 156 us: the LDS pipe is the bound
+// SW_WAVES (spectral_route.h): waves per block = per CU, 12.  Measured at batch 256: 12 waves (3 per SIMD, <= 168 VGPRs) 126 us, 16 waves
+// (128 VGPRs, Hann / run starts through L1) 149 us, 8 waves (256 VGPRs) 156 us: the LDS pipe is the bound
 #if SW_WAVES > 12           // 16 waves x 8.5 KB leave 24 KB of LDS for tables: the Hann window and the mel run starts stay in L1 / L2
 #define SW_TABLES_IN_LDS 0
 #else
@@ -40,8 +39,7 @@ namespace gs {
 
 // run lengths of the mel columns per 128-column block in the reference configuration (1024 mel bins over 0..8 kHz at 16 kHz):
 // compile-time, so the gather has no branch per bin.  Other mel shapes use the generic kernels of spectral.hip.
-__device__ constexpr int SW_SHAPE[8] = {1, 1, 2, 2, 3, 3, 4, 6};
-static const int SW_SHAPE_HOST[8] = {1, 1, 2, 2, 3, 3, 4, 6};
+__device__ constexpr int SW_SHAPE[8] = {1, 1, 2, 2, 3, 3, 4, 6};   // (= SW_SHAPE_HOST of spectral_route.h, which admits a plan to this path)
 
 // 8-byte LDS read that the backend will not pair into ds_read2_b64: the paired form moves 128 B/clk, two ds_read_b64 256 B/clk
 // (MI355X_MICROARCH.md, LDS table), and the LDS pipe is what bounds this kernel
@@ -422,15 +420,6 @@ __global__ __launch_bounds__(64 * SW_WAVES) void stft_wave_kernel(const float* _
     }
 }
 
-// runs per example: enough wave-runs to fill SW_WAVES waves on every CU (a run of R frames costs R + 1 transforms), at most one per frame
-static int runs_per_example(int batch, int time_steps) {
-    int runs = (256 * SW_WAVES + batch - 1) / batch;
-    if (runs > time_steps) runs = time_steps;
-    if (runs < 1) runs = 1;
-    if (runs >= SW_WAVES) runs -= runs % SW_WAVES;   // whole blocks per example: neighbouring runs exchange their edge phases in the block
-    return runs;
-}
-
 template <typename KernT>
 static int set_lds(KernT kern, size_t bytes) {
     static bool done = false;   // per kernel instantiation
@@ -639,10 +628,7 @@ int launch_istft_wave(const gs_spectral_plan* p, const float* mag, const float* 
     return 0;
 }
 
-// frames of a whole example per block, overlap-add and crop included: needs >= 3 frames per run and even crop offsets
-bool istft_wave_ola_ok(const gs_spectral_plan* p, int wave_len, int front_pad) {
-    return p->frame_length == 2048 && p->frame_step == 512 && p->time_steps >= 3 * SW_WAVES && (wave_len & 1) == 0 && (front_pad & 1) == 0;
-}
+// frames of a whole example per block, overlap-add and crop included (GS_SPEC_ISTFT_WAVE_OLA: >= 3 frames per run and even crop offsets)
 int launch_istft_wave_ola(const gs_spectral_plan* p, const float* mag, const float* phase, float* wave, int batch, int wave_len, int front_pad, hipStream_t st) {
     auto kern = istft_wave_kernel<true>;
     if (int e = set_lds(kern, SWI_LDS_TOTAL + 64)) return e;
@@ -652,19 +638,10 @@ int launch_istft_wave_ola(const gs_spectral_plan* p, const float* mag, const flo
     return 0;
 }
 
-bool stft_wave_shape_ok(const int* cnt) {
-    for (int j = 0; j < 8; ++j) if (cnt[j] != SW_SHAPE_HOST[j]) return false;
-    return true;
-}
-
-size_t stft_wave_edge_bytes(const gs_spectral_plan* p, int batch) {
-    return (size_t)batch * runs_per_example(batch, p->time_steps) * 1024 * sizeof(float);
-}
-
-int launch_stft_wave_fused(const gs_spectral_plan* p, const float* wave, int batch, int wave_len, int front_pad, void* images, int dtype,
-                           void* ws, size_t ws_bytes, hipStream_t st) {
-    const int runs = runs_per_example(batch, p->time_steps);
-    float* edge = ws_bytes >= stft_wave_edge_bytes(p, batch) ? reinterpret_cast<float*>(ws) : nullptr;   // (no scratch: every run recomputes its lead frame)
+int launch_stft_wave_fused(const gs_spectral_plan* p, const GsSpectralRoute& r, const float* wave, int batch, int wave_len, int front_pad, void* images,
+                           int dtype, void* ws, hipStream_t st) {
+    const int runs = r.runs;
+    float* edge = r.exchange ? reinterpret_cast<float*>(ws) : nullptr;   // (no exchange: every run recomputes its lead frame)
     const long nruns = (long)batch * runs;
     GS_DISPATCH_DTYPE(dtype, {
         auto kern = stft_wave_kernel<T, 1>;
@@ -677,9 +654,9 @@ int launch_stft_wave_fused(const gs_spectral_plan* p, const float* wave, int bat
     return 0;
 }
 
-int launch_stft_wave_magphase(const gs_spectral_plan* p, const float* wave, int batch, int wave_len, int front_pad, float* mag, float* phase,
-                              hipStream_t st) {
-    const int runs = runs_per_example(batch, p->time_steps);
+int launch_stft_wave_magphase(const gs_spectral_plan* p, const GsSpectralRoute& r, const float* wave, int batch, int wave_len, int front_pad, float* mag,
+                              float* phase, hipStream_t st) {
+    const int runs = r.runs;
     const long nruns = (long)batch * runs;
     auto kern = stft_wave_kernel<float, 0>;
     if (int e = set_lds(kern, SW_LDS_TOTAL)) return e;

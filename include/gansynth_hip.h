@@ -431,6 +431,38 @@ size_t gs_stft_mel_if_workspace_bytes(const gs_spectral_plan* plan, int batch);
 int gs_mel_if_to_waveform(const gs_spectral_plan* plan, const void* images, int batch, int wave_len, int front_pad,
                           float* wave, int dtype, void* ws, size_t ws_bytes, void* stream);
 size_t gs_mel_if_to_waveform_workspace_bytes(const gs_spectral_plan* plan, int batch);
+/* The measurement switches of the spectral kernels, as the library reads them from the environment (once per process; GS_SPECTRAL_GENERIC
+ * when a plan is created): generic GS_SPECTRAL_GENERIC, fp32_gemm GS_INVERSE_FP32_GEMM, mag_6terms GS_INVERSE_MAG_6TERMS, gemm_256
+ * GS_INVERSE_GEMM_256, gemm_kb GS_INVERSE_GEMM_KB (default 4), gemm_kb3 GS_INVERSE_GEMM_KB3 (default 2), block_fft GS_INVERSE_BLOCK_FFT,
+ * separate_ola GS_INVERSE_SEPARATE_OLA. */
+typedef struct GsSpectralKnobs {
+    int32_t generic, fp32_gemm, mag_6terms, gemm_256, gemm_kb, gemm_kb3, block_fft, separate_ola;
+} GsSpectralKnobs;
+enum { GS_SPEC_FWD_GENERIC = 0, GS_SPEC_FWD_WAVE = 1 };
+enum { GS_SPEC_GEMM_NONE = 0, GS_SPEC_GEMM_F32_64 = 1, GS_SPEC_GEMM_F32_128 = 2, GS_SPEC_GEMM_SPLIT_ALL = 3, GS_SPEC_GEMM_SPLIT_TWO = 4,
+       GS_SPEC_GEMM_WIDE_256 = 5 };
+enum { GS_SPEC_ISTFT_NONE = 0, GS_SPEC_ISTFT_WAVE_OLA = 1, GS_SPEC_ISTFT_WAVE_FRAMES = 2, GS_SPEC_ISTFT_BLOCK_FFT = 3 };
+/* Which kernels a spectral call runs: the one decision the plan, the launchers and the workspace queries read. */
+typedef struct GsSpectralRoute {
+    int64_t fwd_workspace_bytes;   /* what gs_stft_mel_if_workspace_bytes answers: wave path 4 KB per run, generic path the mel phases */
+    int32_t fwd_kind;              /* GS_SPEC_FWD_*: stft_wave_kernel, or stft_kernel + if_unwrap_kernel */
+    int32_t maxnz, mz;             /* ELL width of the mel tables, and the stft_kernel<.., 1, MZ> instantiation (0: run-time width) */
+    int32_t mel_cnt[8];            /* 1024 bins: longest run of non-zeros per 128-column block of the mel matrix (0 otherwise) */
+    int32_t runs, q, rem;          /* wave path: runs per example, frames per run, runs with one frame more */
+    int32_t exchange;              /* wave path, fused: neighbouring runs exchange their edge phases (else every run recomputes its lead frame) */
+    int32_t span_examples;         /* wave path: runs < waves per block, a block holds runs of several examples */
+    int32_t gemm_kind;             /* GS_SPEC_GEMM_* of the pinv(mel) contraction (NONE: the plan has no pinv) */
+    int32_t gemm_launches;         /* 1 or 2 (magnitude rows, then phase rows) */
+    int32_t gemm_nj[2], gemm_np[2], gemm_kb[2];   /* gemm_bf16x6_kernel<NJ, NP, KB> per launch (0 for the fp32 kernels) */
+    int32_t istft_kind;            /* GS_SPEC_ISTFT_* */
+    int32_t reserved;
+} GsSpectralRoute;
+/* What the spectral entry points would run for a geometry, asked without a plan and without a device: host arithmetic on the very
+ * function the launchers read.  mel_dense as for gs_spectral_plan_create; fwd_ws_bytes: the workspace gs_stft_mel_if_fwd would be
+ * given; knobs NULL: the process's environment.  out[count]: the routes of the batch sizes batch, batch + 1 ... batch + count - 1 (the
+ * matrix is read once per call). */
+int gs_spectral_route(int frame_length, int frame_step, int time_steps, const float* mel_dense, int has_pinv, int batch, int count,
+                      int wave_len, int front_pad, int dtype, size_t fwd_ws_bytes, const GsSpectralKnobs* knobs, GsSpectralRoute* out);
 
 /* ------------------------------------------------------------------- pitch classifier, forward (GANSynth.evaluate)
  * The ResNet of networks.py:293-413 (pitch_classifier_main.py:39-50: 7x7 stem, 3x3 max pool, four stages of pre-activation residual

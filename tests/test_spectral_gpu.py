@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import spectral_np as S
+from tests.spectral_cover import check_branch_bins, check_if, if_conditioning, near_branch, wrap2  # noqa: F401  (the conditioning helpers live there)
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -18,68 +19,6 @@ def waves():
     tone = 0.5 * np.sin(2 * np.pi * 440.0 * t) + 0.25 * np.sin(2 * np.pi * 880.0 * t)
     noise = np.clip(np.random.default_rng(4000).normal(0.0, 0.1, 64000), -1, 1)
     return np.stack([tone, noise]).astype(np.float32)
-
-
-def wrap2(d):
-    """An IF difference modulo 2 (a +-pi branch flip is a 2.0 jump) -- only applied to bins PROVEN ill-conditioned, see
-    if_conditioning."""
-    return (d + 1.0) % 2.0 - 1.0
-
-
-def if_conditioning(st64, margin=1e-3, cut=1e-4):
-    """Where the reference's IF (spectral_ops.py:21-44) is discontinuous in its input, from the float64 oracle:
-      on_cut[b,t,m]  the wrapped phase difference sits within `margin` rad of +-pi: wrap() may take either branch (IF = +-1);
-      branch[b,t,m]  a linear bin feeding mel column m has |arg X| within `cut` of pi at frame t or t-1 (with magnitude): atan2
-                     may return +pi or -pi there, which moves the mel phase by 2 pi w -- NOT a multiple of 2 pi.
-    Everything else is well conditioned and must agree plainly."""
-    ph = st64["mel_phase"]
-    d = np.diff(ph, axis=-2)
-    md = np.mod(d + np.pi, 2 * np.pi) - np.pi
-    on_cut = np.zeros(ph.shape, bool)
-    on_cut[:, 1:] = np.pi - np.abs(md) < margin
-    near = near_branch(st64, cut)
-    hit = (near.astype(np.float64) @ (st64["mel"] != 0).astype(np.float64)) > 0          # [b, t, m]
-    branch = hit.copy()
-    branch[:, 1:] |= hit[:, :-1]
-    return on_cut, branch
-
-
-def near_branch(st64, cut=1e-4):
-    """[b, t, k]: linear bin k of frame t (with magnitude) has |arg X| within `cut` of pi -- atan2 may land on either side."""
-    lin, mag = st64["phase"], st64["magnitude"]
-    return (np.pi - np.abs(lin) < cut) & (mag > 1e-6 * mag.max())
-
-
-def check_branch_bins(got, ref, st64, b, branch, where=None, tol=2e-3):
-    """The bins check_if leaves out are not unchecked: where a linear bin k sits on the atan2 branch cut at frame t or t - 1, the mel
-    phase of column m moves by +-2 pi w[k, m] (w = the mel weight) and IF = wrap(p[t] - p[t-1]) / pi by +-2 w[k, m] modulo 2.  Every
-    such bin must equal the oracle's value up to a signed sum of those quanta over the (few) hit bins of its column."""
-    import itertools
-    where = np.ones(ref.shape, bool) if where is None else where
-    near, mel = near_branch(st64)[b], st64["mel"]
-    ts, ms = np.nonzero(branch & where)
-    worst = 0.0
-    for t, m in zip(ts, ms):
-        ks = [k for k in np.nonzero(mel[:, m])[0] if near[t, k] or (t > 0 and near[t - 1, k])]
-        quanta = [2.0 * float(mel[k, m]) for k in ks]
-        # a bin on the cut at t AND t - 1 may flip at either frame or both: coefficients -2 .. 2 per hit bin (columns have <= 6 non-zeros)
-        best = min(abs(float(wrap2(np.float64(got[t, m] - ref[t, m] - sum(c * q for c, q in zip(cs, quanta))))))
-                   for cs in itertools.product((-2, -1, 0, 1, 2), repeat=len(quanta)))
-        worst = max(worst, best)
-        assert best < tol, (b, t, m, float(got[t, m]), float(ref[t, m]), quanta)
-    return len(ts), worst
-
-
-def check_if(got, ref, on_cut, branch, where=None, tol=1e-3, max_branch=2e-3):
-    """IF parity: plain on the well-conditioned bins, modulo 2 on the branch cut of wrap(), nothing on atan2 branch hits; the
-    ill-conditioned sets must stay the small sets they are."""
-    where = np.ones(ref.shape, bool) if where is None else where
-    plain = where & ~on_cut & ~branch
-    assert np.abs(got - ref)[plain].max() < tol, np.abs(got - ref)[plain].max()
-    cut = where & on_cut & ~branch
-    if cut.any():
-        assert np.abs(wrap2(got - ref))[cut].max() < tol
-    assert on_cut[where].mean() < 2e-3 and branch[where].mean() < max_branch, (on_cut[where].mean(), branch[where].mean())
 
 
 def test_stagewise_vs_oracle():
