@@ -83,6 +83,7 @@ SIGNATURES = {
     "gs_conv_wgrad_jobs_plan": (I, [P, I, POINTER(c_int), I]),
     "gs_conv_igemm_config": (I, [I, I, I, I, I, I, I, I, POINTER(c_int)]),
     "gs_conv_igemm_table": (I, [I, POINTER(c_int)]),
+    "gs_conv_thin_route": (I, [C, I, I, I, I, I, I, POINTER(c_int), POINTER(c_int)]),
     "gs_units_bias_act_to_nhwc": (I, [P, P, P, P, I, I, I, I, I, P]),
     "gs_nhwc_act_bwd_to_units": (I, [P, P, P, I, I, I, I, I, P]),
     "gs_dense_fwd_workspace_bytes": (Z, [I, I, I]),
@@ -173,6 +174,9 @@ SIGNATURES = {
 WGRAD_MAX_SOURCES = 4   # GS_WGRAD_MAX_SOURCES
 WGRAD_DIRECT, WGRAD_THIN, WGRAD_F32, WGRAD_BF16, WGRAD_THIN_DMA, WGRAD_TILE64 = range(6)   # GS_WGRAD_* families of gs_conv_wgrad_plan
 WGRAD_PLAN_INTS = 16   # GS_WGRAD_PLAN_INTS
+THIN_EXPAND, THIN_REDUCE, THIN_EXPAND_PNBWD, THIN_SINGLE3, THIN_SINGLE, THIN_DIRECT = range(6)   # GS_THIN_* kernels of gs_conv_thin_route
+THIN_PLAIN, THIN_FWD_MASK, THIN_BWD_PNBWD = range(3)   # GS_THIN_* forms
+THIN_ROUTE_INTS = 14   # GS_THIN_ROUTE_INTS
 
 
 SUM_PARTIALS = 2   # GS_SUM_PARTIALS

@@ -1,15 +1,13 @@
-// C-ABI entry points of the conv family + the generic direct (VALU) kernels used for the
-// channel counts the MFMA implicit GEMM does not take: the 2-channel colour 1x1 convs
-// (networks.py:98-105, 233-240) and the 1-channel minibatch-stddev plane (networks.py:174-176).
-#include "conv_shared.h"
+// C-ABI entry points of the conv family: the layer -> kernel-role relabelling (conv_role), the hand-over to the implicit GEMM (conv_igemm.hip), to
+// the VALU convs (conv_thin.hip, through thin_route) or to the weight gradients (conv_wgrad.hip), the planning of gs_conv_wgrad_jobs, the host-only
+// queries, and the batched weight re-layout (gs_weight_prep_batch) with its kernel -- the only kernel of this file.
+#include "conv_thin_route.h"
 #include <utility>
 #include <vector>
 
 namespace gs {
 
-
 // from conv_igemm.hip / conv_wgrad.hip
-bool igemm_supported(int ic, int oc, int dtype);
 bool igemm_norm_fused(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int want);
 int igemm_config(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int want, int* out);
 int igemm_table(int index, int* out);
@@ -23,6 +21,9 @@ int run_igemm(int mode, int variant, const void* x, const float* w_hwio, void* y
 extern "C" int gs_pixel_norm_bwd_fused(const void* g, const void* x, const void* addend, void* gx, int64_t p, int c, float eps, int pre_act, int post_act, int dtype,
                                        void* stream);
 size_t wgrad_mfma_bytes(int mode, int dtype, int N, int Hb, int Wb, int IC, int OC);
+size_t wgrad_direct_bytes(int mode, int ks, int dtype, int N, int Hb, int Wb, int IC, int OC);
+int run_wgrad_direct(int mode, int ks, const void* x, const void* gy, float* gw, int N, int Hi, int Wi, int IC, int OC, int Hb, int Wb, float alpha, int transpose,
+                     int accumulate, int dtype, void* ws, size_t ws_bytes, hipStream_t st, GsWgradReduce* defer = nullptr);
 int run_wgrad_mfma(int mode, const WgradSrcs& srcs, int nsrc, float* gw, float* gb, int N, int Hi, int Wi, int IC, int OC, int Hb,
                    int Wb, float alpha, int transpose, int accumulate, int dtype, void* ws, size_t ws_bytes, hipStream_t st,
                    GsWgradReduce* defer = nullptr);
@@ -31,569 +32,12 @@ void wgrad_sk_plan(int mode, SkGroup& g);
 size_t wgrad_sk_bytes(const SkGroup& g);
 int run_wgrad_sk(int mode, const SkGroup& g, void* ws, size_t ws_bytes, hipStream_t st);
 
-// ------------------------------------------------------------------------- direct gather conv
-// y[n][oy][ox][oc0..oc0+OCV) = alpha * sum_{tap,ic} x[n][iy][ix][ic] * wp[tap][oc][ic]   (wp fp32)
-template <typename T, int OCV, int VEC>
-__global__ void conv_direct_kernel(const T* __restrict__ x, const float* __restrict__ wp, T* __restrict__ y, int mode,
-                                   int ks, int N, int Hi, int Wi, int IC, int OC, int Ho, int Wo, float alpha) {
-    const int ngrp = OC / OCV;
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long total = (long)N * Ho * Wo * ngrp;
-    if (idx >= total) return;
-    const int g = idx % ngrp;
-    long pix = idx / ngrp;
-    const int ox = pix % Wo;
-    pix /= Wo;
-    const int oy = pix % Ho;
-    const int n = pix / Ho;
-    const int oc = g * OCV;
-    float acc[OCV];
-#pragma unroll
-    for (int v = 0; v < OCV; ++v) acc[v] = 0.f;
-    for (int ky = 0; ky < ks; ++ky) {
-        int iy;
-        if (mode == MODE_S1) iy = oy + ky - (ks >> 1);
-        else if (mode == MODE_S2) iy = 2 * oy + ky;
-        else { const int d = oy - ky; if (d < 0 || (d & 1)) continue; iy = d >> 1; }
-        if (iy < 0 || iy >= Hi) continue;
-        for (int kx = 0; kx < ks; ++kx) {
-            int ix;
-            if (mode == MODE_S1) ix = ox + kx - (ks >> 1);
-            else if (mode == MODE_S2) ix = 2 * ox + kx;
-            else { const int d = ox - kx; if (d < 0 || (d & 1)) continue; ix = d >> 1; }
-            if (ix < 0 || ix >= Wi) continue;
-            const T* xp = x + (((long)n * Hi + iy) * Wi + ix) * IC;
-            const float* wr = wp + ((long)(ky * ks + kx) * OC + oc) * IC;
-            if (VEC == 4) {
-                for (int ic = 0; ic < IC; ic += 4) {
-                    float xv[4];
-                    ld4(xp + ic, xv);
-#pragma unroll
-                    for (int v = 0; v < OCV; ++v) {
-                        const float4 wv = *reinterpret_cast<const float4*>(wr + (long)v * IC + ic);
-                        acc[v] += xv[0] * wv.x + xv[1] * wv.y + xv[2] * wv.z + xv[3] * wv.w;
-                    }
-                }
-            } else {
-                for (int ic = 0; ic < IC; ++ic) {
-                    const float xv = DT<T>::ld(xp + ic);
-#pragma unroll
-                    for (int v = 0; v < OCV; ++v) acc[v] += xv * wr[(long)v * IC + ic];
-                }
-            }
-        }
-    }
-    T* yp = y + (((long)n * Ho + oy) * Wo + ox) * OC + oc;
-    if (OCV == 4) {
-        float o[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) o[v] = acc[v < OCV ? v : 0] * alpha;
-        st4(yp, o);
-    } else {
-#pragma unroll
-        for (int v = 0; v < OCV; ++v) DT<T>::st(yp + v, acc[v] * alpha);
-    }
-}
-
-template <typename T>
-static int launch_direct(const T* x, const float* wp, T* y, int mode, int ks, int N, int Hi, int Wi, int IC, int OC,
-                         int Ho, int Wo, float alpha, hipStream_t st) {
-    const int ocv = OC % 4 == 0 ? 4 : (OC % 2 == 0 ? 2 : 1);
-    const int vec = IC % 4 == 0 ? 4 : 1;
-    const long total = (long)N * Ho * Wo * (OC / ocv);
-    dim3 grid(cdiv(total, 256)), block(256);
-#define GS_DL(OCVV, VECV)                                                                                              \
-    hipLaunchKernelGGL((conv_direct_kernel<T, OCVV, VECV>), grid, block, 0, st, x, wp, y, mode, ks, N, Hi, Wi, IC, OC, Ho, \
-                       Wo, alpha)
-    if (ocv == 4 && vec == 4) GS_DL(4, 4);
-    else if (ocv == 4) GS_DL(4, 1);
-    else if (ocv == 2 && vec == 4) GS_DL(2, 4);
-    else if (ocv == 2) GS_DL(2, 1);
-    else if (vec == 4) GS_DL(1, 4);
-    else GS_DL(1, 1);
-#undef GS_DL
-    GS_CHECK_LAUNCH();
-    return 0;
-}
-
-
-// ------------------------------------------------------------------ thin 1x1 convolutions
-// The colour blocks (ops.py:237-243 with a [1,1,C,2] / [1,1,2,C] kernel) are pure streaming: 64 bytes in and 4 out per
-// pixel, or the reverse.  One lane per 16 bytes of the wide side keeps every access coalesced; the bias / activation
-// epilogue of the block is applied in the same pass.
-// The activation of a streaming kernel is a TEMPLATE parameter: as a run-time argument the three-way choice (tanhf's own branches
-// included) was compiled into the pixel loop once per output VALUE -- ~6 scalar branches per value in thin_expand_kernel's hot loop
-// (hipcc -S), 23 us for the 67 MB of the top-level colour block where the write rate allows ~14.
-template <int ACT> __device__ inline float thin_act(float v) {
-    if constexpr (ACT == GS_ACT_LRELU) return fmaxf(v, 0.2f * v);
-    else if constexpr (ACT == GS_ACT_TANH) return fast_tanh(v);
-    else return v;
-}
-// few -> many channels: y[p][oc] = act(alpha * sum_ic x[p][ic] wp[oc][ic] + bias[oc]),  IC <= 4, OC % Wide::N == 0, 256 % (OC / N) == 0.
-// A thread keeps its Wide::N output channels (weights + bias in registers) and strides over pixels.
-template <typename T, int IC, int ACT, bool MASKED>
-// `mask` (MASKED, y's shape): y *= mask_act'(.) through that activation output -- the second-order pass of the R1 penalty runs the colour
-// block forward on a cotangent and the next node's first step is that multiplication (gs_conv_fwd_mask)
-__global__ __launch_bounds__(256) void thin_expand_kernel(const T* __restrict__ x, const float* __restrict__ wp, const float* __restrict__ bias,
-                                                          T* __restrict__ y, long P, int OC, float alpha,
-                                                          const T* __restrict__ mask = nullptr, int mask_act = 0, unsigned* __restrict__ bits = nullptr) {
-    // `bits` (bf16 leaky relu, OC % 32 == 0): the sign words of the result behind it (include/gansynth_hip.h, GS_ACT_WRITE_BITS) -- a lane's 8 channels
-    // are one byte of the pixel's word, the four lanes of a 32-channel tile are a DPP quad
-    constexpr int WN = Wide<T>::N;
-    const int groups = OC / WN;
-    const int oc0 = (threadIdx.x % groups) * WN;
-    float wr[WN][IC], br[WN];
-    {   // this lane's WN x IC weights and WN biases: contiguous floats, fetched as 16-byte vectors (a scalar load each made the prologue of
-        // a block cost as much as its pixels: 22.8 us at 4096 blocks, 51 us at 16384, scripts/bench_thin.py)
-        typedef float f4_t __attribute__((ext_vector_type(4)));
-        float flat[WN * IC];
-        if constexpr ((WN * IC) % 4 == 0) {
-#pragma unroll
-            for (int q = 0; q < WN * IC / 4; ++q) {
-                const f4_t t = *reinterpret_cast<const f4_t*>(wp + (long)oc0 * IC + 4 * q);
-                flat[4 * q] = t.x; flat[4 * q + 1] = t.y; flat[4 * q + 2] = t.z; flat[4 * q + 3] = t.w;
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < WN * IC; ++q) flat[q] = wp[(long)oc0 * IC + q];
-        }
-#pragma unroll
-        for (int v = 0; v < WN; ++v)
-#pragma unroll
-            for (int i = 0; i < IC; ++i) wr[v][i] = flat[v * IC + i] * alpha;
-#pragma unroll
-        for (int q = 0; q < WN / 4; ++q) {
-            f4_t t = {0.f, 0.f, 0.f, 0.f};
-            if (bias) t = *reinterpret_cast<const f4_t*>(bias + oc0 + 4 * q);
-            br[4 * q] = t.x; br[4 * q + 1] = t.y; br[4 * q + 2] = t.z; br[4 * q + 3] = t.w;
-        }
-    }
-    const long ppb = 256 / groups;  // pixels per block pass
-    const long stride = (long)gridDim.x * ppb;
-    long pix = (long)blockIdx.x * ppb + threadIdx.x / groups;
-    auto one = [&](long px, const float* xv) __attribute__((always_inline)) {
-        float o[WN];
-        // two output channels per instruction (v_pk_fma_f32 / v_pk_mul_f32): the kernel's time IS its VALU count -- 50 instructions per 16
-        // bytes stored with scalar arithmetic (hipcc split every multiply-add into a packed multiply and an add), ~30 like this
-        typedef float f2_t __attribute__((ext_vector_type(2)));
-#pragma unroll
-        for (int v = 0; v < WN; v += 2) {
-            f2_t a = {br[v], br[v + 1]};
-#pragma unroll
-            for (int i = 0; i < IC; ++i) {
-                const f2_t xx = {xv[i], xv[i]}, ww = {wr[v][i], wr[v + 1][i]};
-                a = __builtin_elementwise_fma(xx, ww, a);
-            }
-            if constexpr (ACT == GS_ACT_LRELU) {
-                const f2_t t = a * 0.2f;
-                o[v] = fmaxf(a.x, t.x);
-                o[v + 1] = fmaxf(a.y, t.y);
-            } else {
-                o[v] = thin_act<ACT>(a.x);
-                o[v + 1] = thin_act<ACT>(a.y);
-            }
-        }
-        if constexpr (MASKED) {
-            float mv[WN];
-            ld_wide<T>(mask + px * OC + oc0, mv);
-#pragma unroll
-            for (int v = 0; v < WN; ++v) o[v] *= mask_act == GS_ACT_LRELU ? (mv[v] > 0.f ? 1.f : 0.2f) : (mask_act == GS_ACT_TANH ? 1.f - mv[v] * mv[v] : 1.f);
-        }
-        if constexpr (ACT == GS_ACT_LRELU && !MASKED && sizeof(T) == 2) {
-            if (bits) {
-                uint4 v;
-                v.x = pack_bf16x2(o[0], o[1]); v.y = pack_bf16x2(o[2], o[3]); v.z = pack_bf16x2(o[4], o[5]); v.w = pack_bf16x2(o[6], o[7]);
-                *reinterpret_cast<uint4*>(y + px * OC + oc0) = v;
-                const unsigned b8 = ((int)(v.x << 16) > 0 ? 1u : 0u) | ((int)v.x >= 0x10000 ? 2u : 0u) | ((int)(v.y << 16) > 0 ? 4u : 0u) | ((int)v.y >= 0x10000 ? 8u : 0u) |
-                                    ((int)(v.z << 16) > 0 ? 16u : 0u) | ((int)v.z >= 0x10000 ? 32u : 0u) | ((int)(v.w << 16) > 0 ? 64u : 0u) | ((int)v.w >= 0x10000 ? 128u : 0u);
-                const int piece = (oc0 >> 3) & 3;   // 16-byte piece of the tile: channels 8 piece .. -> byte 2 (piece & 1) + (piece >> 1) of the word
-                unsigned word = b8 << (8 * (2 * (piece & 1) + (piece >> 1)));
-                word |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)word, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-                word |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)word, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-                if (piece == 0) bits[(px * OC + oc0) >> 5] = word;
-                return;
-            }
-        }
-        st_wide<T>(y + px * OC + oc0, o);
-    };
-    auto ldpix = [&](long px, float* xv) __attribute__((always_inline)) {
-        if constexpr (IC == 2 && sizeof(T) == 2) {   // both colour channels of a pixel in one 4-byte load
-            const unsigned u = *reinterpret_cast<const unsigned*>(x + px * 2);
-            xv[0] = __uint_as_float(u << 16);
-            xv[1] = __uint_as_float(u & 0xffff0000u);
-        } else {
-#pragma unroll
-            for (int i = 0; i < IC; ++i) xv[i] = DT<T>::ld(x + px * IC + i);
-        }
-    };
-    for (; pix + 3 * stride < P; pix += 4 * stride) {   // four pixels per trip (loads first)
-        float xv[4][IC];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ldpix(pix + k * stride, xv[k]);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) one(pix + k * stride, xv[k]);
-    }
-    for (; pix < P; pix += stride) {
-        float xv[IC];
-        ldpix(pix, xv);
-        one(pix, xv);
-    }
-}
-
-// The same map as a DATA GRADIENT continued through the pixel norm and activation of the block that produced the conv's input
-// (gs_conv_bwd_data_pnbwd for the colour block, networks.py:98-104): g[p][oc] = alpha * sum_ic x[p][ic] wp[oc][ic] is the gradient
-// w.r.t. pixel_norm(z); out = (r (g - z r^2 mean_c(z g)) + addend) * act'(z), r = rsqrt(mean_c z^2 + eps).  The OC / Wide::N lanes of
-// a pixel are neighbours in the wave: two xor-shuffle folds give the pixel's sums.  One pass instead of thin_expand + a 4-tensor norm pass.
-template <typename T, int IC>
-__global__ __launch_bounds__(256) void thin_expand_pnbwd_kernel(const T* __restrict__ x, const float* __restrict__ wp, const T* __restrict__ z,
-                                                                const T* __restrict__ addend, T* __restrict__ y, long P, int OC, float alpha, float eps, int act) {
-    constexpr int WN = Wide<T>::N;
-    const int groups = OC / WN;   // a power of two <= 64 dividing 256 (checked by the launcher)
-    const int oc0 = (threadIdx.x % groups) * WN;
-    float wr[WN][IC];
-#pragma unroll
-    for (int v = 0; v < WN; ++v)
-#pragma unroll
-        for (int i = 0; i < IC; ++i) wr[v][i] = wp[(long)(oc0 + v) * IC + i] * alpha;
-    const long ppb = 256 / groups;
-    const long stride = (long)gridDim.x * ppb;
-    const long npass = (P + stride - 1) / stride;   // same trip count for every lane (shuffles)
-    const float inv_c = 1.f / (float)OC;
-    for (long k = 0; k < npass; ++k) {
-        const long pix = (long)blockIdx.x * ppb + threadIdx.x / groups + k * stride;
-        const long px = pix < P ? pix : P - 1;      // (clamped: loads and shuffles stay unconditional)
-        float xv[IC], zv[WN], av[WN], g[WN];
-        if constexpr (IC == 2 && sizeof(T) == 2) {
-            const unsigned u = *reinterpret_cast<const unsigned*>(x + px * 2);
-            xv[0] = __uint_as_float(u << 16);
-            xv[1] = __uint_as_float(u & 0xffff0000u);
-        } else {
-#pragma unroll
-            for (int i = 0; i < IC; ++i) xv[i] = DT<T>::ld(x + px * IC + i);
-        }
-        ld_wide<T>(z + px * OC + oc0, zv);
-        if (addend) ld_wide<T>(addend + px * OC + oc0, av);
-        float ssq = 0.f, szg = 0.f;
-#pragma unroll
-        for (int v = 0; v < WN; ++v) {
-            float a = 0.f;
-#pragma unroll
-            for (int i = 0; i < IC; ++i) a += xv[i] * wr[v][i];
-            g[v] = a;
-            ssq += zv[v] * zv[v];
-            szg += zv[v] * a;
-        }
-        ssq = group_sum(ssq, groups);
-        szg = group_sum(szg, groups);
-        const float r = rsqrtf(ssq * inv_c + eps);
-        const float m = szg * inv_c * r * r;
-        float out[WN];
-#pragma unroll
-        for (int v = 0; v < WN; ++v) {
-            float t = r * (g[v] - zv[v] * m);
-            if (addend) t += av[v];
-            out[v] = act == GS_ACT_LRELU ? (zv[v] > 0.f ? t : 0.2f * t) : t;
-        }
-        if (pix < P) st_wide<T>(y + pix * OC + oc0, out);
-    }
-}
-static bool thin_expand_pnbwd_ok(int ks, int ICk, int OCk, int dtype) {
-    const int wn = dtype == GS_F32 ? 4 : 8;
-    if (ks != 1 || ICk < 1 || ICk > 4 || OCk % wn != 0) return false;
-    const int groups = OCk / wn;
-    return groups >= 1 && groups <= 64 && (groups & (groups - 1)) == 0;
-}
-// x: the thin gradient [P][ICk], wp: fp32 [OCk][ICk] (bwd-data layout of the 1x1 kernel), z / addend / y: [P][OCk]
-static int run_thin_expand_pnbwd(const void* x, const float* wp, const void* z, const void* addend, void* y, long P, int ICk, int OCk, float alpha, float eps, int act,
-                                 int dtype, hipStream_t st) {
-    const int wn = dtype == GS_F32 ? 4 : 8;
-    long nb = cdiv(P * (OCk / wn), 256);
-    if (nb > 4096) nb = 4096;
-    const unsigned grid = (unsigned)nb;
-#define GS_TEP(TT, ICV) hipLaunchKernelGGL((thin_expand_pnbwd_kernel<TT, ICV>), dim3(grid), dim3(256), 0, st, (const TT*)x, wp, (const TT*)z, (const TT*)addend, (TT*)y, P, OCk, alpha, eps, act)
-#define GS_TEP_ALL(TT) do { if (ICk == 1) GS_TEP(TT, 1); else if (ICk == 2) GS_TEP(TT, 2); else if (ICk == 3) GS_TEP(TT, 3); else GS_TEP(TT, 4); } while (0)
-    GS_DISPATCH_DTYPE(dtype, GS_TEP_ALL(T));
-#undef GS_TEP_ALL
-#undef GS_TEP
-    GS_CHECK_LAUNCH();
-    return 0;
-}
-
-// many -> few channels: a pixel is read by L = IC / Wide::N lanes (a power of two <= 64), partial dots are folded with
-// xor-shuffles, lane 0 of the group writes the OC <= 4 results.  Weights stay in registers across the pixel loop.
-// LC: the lanes per pixel as a compile-time constant (4: the 32-channel bf16 colour block; 8: 64 bf16 / 32 fp32 channels; 0: any power of
-// two, run-time) -- with a run-time lane count the folds are loops of ds_bpermute round trips through the LDS pipe, with a constant one
-// they unroll into DPP moves.
-template <typename T, int OC, int ACT, int LC>
-__global__ __launch_bounds__(256) void thin_reduce_kernel(const T* __restrict__ x, const float* __restrict__ wp, const float* __restrict__ bias,
-                                                          T* __restrict__ y, long P, int IC, float alpha) {
-    constexpr int WN = Wide<T>::N;
-    const int L = LC ? LC : IC / WN;
-    const int l = threadIdx.x % L;
-    float wr[OC][WN];
-#pragma unroll
-    for (int v = 0; v < OC; ++v)
-#pragma unroll
-        for (int i = 0; i < WN; ++i) wr[v][i] = wp[v * IC + l * WN + i] * alpha;
-    const long ppb = 256 / L;
-    const long npass = (P + (long)gridDim.x * ppb - 1) / ((long)gridDim.x * ppb);  // same trip count for every lane (shuffles)
-    float bv[OC];
-#pragma unroll
-    for (int v = 0; v < OC; ++v) bv[v] = bias ? bias[v] : 0.f;
-    auto fold = [&](float* a) __attribute__((always_inline)) {
-        // VALU only (DPP inside a row, permlane swaps across rows; gs_common.h: a __shfl_xor is a ds_bpermute whatever its offset)
-#pragma unroll
-        for (int v = 0; v < OC; ++v) a[v] = group_sum(a[v], LC != 0 ? LC : L);
-    };
-    auto finish = [&](long pix, float* a) __attribute__((always_inline)) {
-        fold(a);
-        if (pix < P && l == 0) {
-            if constexpr (OC == 2 && sizeof(T) == 2) {   // both colour channels of a pixel in one 4-byte store
-                *reinterpret_cast<unsigned*>(y + pix * 2) = pack_bf16x2(thin_act<ACT>(a[0] + bv[0]), thin_act<ACT>(a[1] + bv[1]));
-            } else {
-#pragma unroll
-                for (int v = 0; v < OC; ++v) DT<T>::st(y + pix * OC + v, thin_act<ACT>(a[v] + bv[v]));
-            }
-        }
-    };
-    constexpr int U = 4;   // pixels per trip: their loads go out together
-    long k = 0;
-    for (; k + U <= npass; k += U) {
-        float xv[U][WN], a[U][OC];
-        long pix[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            pix[u] = ((k + u) * gridDim.x + blockIdx.x) * ppb + threadIdx.x / L;
-            ld_wide<T>(x + (pix[u] < P ? pix[u] : 0) * IC + l * WN, xv[u]);   // (clamped: the loads stay unconditional)
-        }
-        if constexpr (LC == U) {
-            // after the folds each of the pixel's LC lanes holds the sums of all U pixels of the trip: lane l finishes pixel l -- bias,
-            // activation (a tanh on the generator's colour block) and the store run ONCE per lane instead of U times on a quarter of them
-            float mine[OC];
-            long mypix = pix[0];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int v = 0; v < OC; ++v) {
-                    a[u][v] = 0.f;
-#pragma unroll
-                    for (int i = 0; i < WN; ++i) a[u][v] += xv[u][i] * wr[v][i];
-                }
-                fold(a[u]);
-#pragma unroll
-                for (int v = 0; v < OC; ++v) mine[v] = (u == 0 || l == u) ? a[u][v] : mine[v];
-                mypix = l == u ? pix[u] : mypix;
-            }
-            if (mypix < P) {
-                if constexpr (OC == 2 && sizeof(T) == 2) {
-                    *reinterpret_cast<unsigned*>(y + mypix * 2) = pack_bf16x2(thin_act<ACT>(mine[0] + bv[0]), thin_act<ACT>(mine[1] + bv[1]));
-                } else {
-#pragma unroll
-                    for (int v = 0; v < OC; ++v) DT<T>::st(y + mypix * OC + v, thin_act<ACT>(mine[v] + bv[v]));
-                }
-            }
-            continue;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-#pragma unroll
-            for (int v = 0; v < OC; ++v) {
-                a[u][v] = 0.f;
-#pragma unroll
-                for (int i = 0; i < WN; ++i) a[u][v] += xv[u][i] * wr[v][i];
-            }
-            finish(pix[u], a[u]);
-        }
-    }
-    for (; k < npass; ++k) {
-        const long pix = (k * gridDim.x + blockIdx.x) * ppb + threadIdx.x / L;
-        float a[OC];
-#pragma unroll
-        for (int v = 0; v < OC; ++v) a[v] = 0.f;
-        if (pix < P) {
-            float xv[WN];
-            ld_wide<T>(x + pix * IC + l * WN, xv);
-#pragma unroll
-            for (int v = 0; v < OC; ++v)
-#pragma unroll
-                for (int i = 0; i < WN; ++i) a[v] += xv[i] * wr[v][i];
-        }
-        finish(pix, a);
-    }
-}
-
-// one output channel, many input channels, any tap geometry (the data gradient of the minibatch-stddev plane of the last
-// discriminator block): a wave per output pixel, lanes over the input channels.
-template <typename T>
-__global__ __launch_bounds__(256) void thin_single_kernel(const T* __restrict__ x, const float* __restrict__ wp, T* __restrict__ y, int mode,
-                                                          int ks, int N, int Hi, int Wi, int IC, int Ho, int Wo, float alpha) {
-    const long pix = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (pix >= (long)N * Ho * Wo) return;
-    const int ox = pix % Wo;
-    const int oy = (pix / Wo) % Ho;
-    const int n = pix / ((long)Wo * Ho);
-    float a = 0.f;
-    for (int ky = 0; ky < ks; ++ky) {
-        int iy;
-        if (mode == MODE_S1) iy = oy + ky - (ks >> 1);
-        else if (mode == MODE_S2) iy = 2 * oy + ky;
-        else { const int d = oy - ky; if (d < 0 || (d & 1)) continue; iy = d >> 1; }
-        if (iy < 0 || iy >= Hi) continue;
-        for (int kx = 0; kx < ks; ++kx) {
-            int ix;
-            if (mode == MODE_S1) ix = ox + kx - (ks >> 1);
-            else if (mode == MODE_S2) ix = 2 * ox + kx;
-            else { const int d = ox - kx; if (d < 0 || (d & 1)) continue; ix = d >> 1; }
-            if (ix < 0 || ix >= Wi) continue;
-            const T* xp = x + (((long)n * Hi + iy) * Wi + ix) * IC;
-            const float* wr = wp + (long)(ky * ks + kx) * IC;
-            for (int ic = lane; ic < IC; ic += 64) a += DT<T>::ld(xp + ic) * wr[ic];
-        }
-    }
-    a = wave_sum(a);
-    if (lane == 0) DT<T>::st(y + pix, a * alpha);
-}
-
-// the same for 3x3 kernels with IC a multiple of 256: a lane owns 4 consecutive channels per 256-channel block and ALL its loads (9 taps x
-// IC / 256 blocks, inputs and weights) are issued before the first multiply -- the generic kernel above walks 9 x IC / 64 dependent
-// load pairs (11.6 us for the 256-channel stddev-plane gradient at 2 x 16: a pure latency chain)
-template <typename T, int NB>
-__global__ __launch_bounds__(256) void thin_single3_kernel(const T* __restrict__ x, const float* __restrict__ wp, T* __restrict__ y, int mode,
-                                                           int N, int Hi, int Wi, int Ho, int Wo, float alpha) {
-    constexpr int IC = 256 * NB;
-    const long pix = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (pix >= (long)N * Ho * Wo) return;
-    const int ox = pix % Wo;
-    const int oy = (pix / Wo) % Ho;
-    const int n = pix / ((long)Wo * Ho);
-    float xv[9][NB][4];
-    float4 wv[9][NB];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        const int ky = t / 3, kx = t % 3;
-        int iy, ix;
-        bool ok = true;
-        if (mode == MODE_S1) { iy = oy + ky - 1; ix = ox + kx - 1; }
-        else if (mode == MODE_S2) { iy = 2 * oy + ky; ix = 2 * ox + kx; }
-        else {
-            const int dy = oy - ky, dx = ox - kx;
-            ok = dy >= 0 && dx >= 0 && !(dy & 1) && !(dx & 1);
-            iy = dy >> 1; ix = dx >> 1;
-        }
-        ok = ok && iy >= 0 && iy < Hi && ix >= 0 && ix < Wi;
-        const T* xp = x + (((long)n * Hi + (ok ? iy : 0)) * Wi + (ok ? ix : 0)) * IC + 4 * lane;   // (clamped: the loads stay unconditional)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            ld4(xp + 256 * b, xv[t][b]);
-            wv[t][b] = ok ? *reinterpret_cast<const float4*>(wp + (long)t * IC + 256 * b + 4 * lane) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    float a = 0.f;
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int b = 0; b < NB; ++b) a += xv[t][b][0] * wv[t][b].x + xv[t][b][1] * wv[t][b].y + xv[t][b][2] * wv[t][b].z + xv[t][b][3] * wv[t][b].w;
-    a = wave_sum(a);
-    if (lane == 0) DT<T>::st(y + pix, a * alpha);
-}
-
-// direct conv through the fp32 prepped weights living in ws; *fused is set when bias / act went into the same pass
-static int run_direct(int mode, int ks, int variant, const void* x, const float* w_hwio, void* y, int N, int Hi, int Wi,
-                      int ICk, int OCk, int w_ci, int w_co, int Ho, int Wo, float alpha, int dtype, int w_prepared, void* ws,
-                      size_t ws_bytes, hipStream_t st, const float* bias = nullptr, int act = GS_ACT_NONE, bool* fused = nullptr,
-                      const void* mask = nullptr, int mask_act = 0, bool* mask_fused = nullptr, unsigned* bits_out = nullptr, bool* bits_done = nullptr) {
-    const long total = (long)ks * ks * w_ci * w_co;
-    if (ws_bytes < (size_t)total * 4) return fail(GS_ERR_WORKSPACE, "conv direct: workspace %zu < %zu", ws_bytes, (size_t)total * 4);
-    float* wp = reinterpret_cast<float*>(ws);
-    if (!w_prepared) {
-        hipLaunchKernelGGL((weight_prep_kernel<float>), dim3(cdiv(total, 256)), dim3(256), 0, st, w_hwio, wp, ks * ks, w_ci, w_co, variant);
-        GS_CHECK_LAUNCH();
-    }
-    if (fused) *fused = false;
-    const long P = (long)N * Ho * Wo;
-    const int wn = dtype == GS_F32 ? 4 : 8;
-    if (ks == 1 && mode == MODE_S1 && ICk <= 4 && OCk % wn == 0 && 256 % (OCk / wn) == 0) {   // colour -> features
-        long nb = cdiv(P * (OCk / wn), 256);
-        // (2048 blocks: 18.5 us for the 67 MB of the top level against 19.4 at 4096 and 23.0 at 8192 -- every block pays the weight prologue)
-        static const long te_cap = getenv("GS_THIN_EXPAND_BLOCKS") ? atol(getenv("GS_THIN_EXPAND_BLOCKS")) : 2048;
-        if (nb > te_cap) nb = te_cap;
-        const unsigned grid = (unsigned)nb;
-        unsigned* te_bits = (bits_out && bits_done && !mask && act == GS_ACT_LRELU && dtype == GS_BF16 && OCk % 32 == 0) ? bits_out : nullptr;
-        if (te_bits) *bits_done = true;
-#define GS_TE(TT, ICV, ACTV, MK) hipLaunchKernelGGL((thin_expand_kernel<TT, ICV, ACTV, MK>), dim3(grid), dim3(256), 0, st, (const TT*)x, wp, bias, (TT*)y, P, OCk, alpha, (const TT*)mask, mask_act, te_bits)
-#define GS_TE_ACT(TT, ICV)                                                                                               \
-    do {                                                                                                                 \
-        if (mask) {   /* (masked: a forward on a cotangent -- the activation, if any, is applied by the slower generic form) */ \
-            if (act == GS_ACT_NONE) GS_TE(TT, ICV, GS_ACT_NONE, true);                                                   \
-            else if (act == GS_ACT_LRELU) GS_TE(TT, ICV, GS_ACT_LRELU, true);                                            \
-            else GS_TE(TT, ICV, GS_ACT_TANH, true);                                                                      \
-        } else if (act == GS_ACT_LRELU) GS_TE(TT, ICV, GS_ACT_LRELU, false);                                             \
-        else if (act == GS_ACT_TANH) GS_TE(TT, ICV, GS_ACT_TANH, false);                                                 \
-        else GS_TE(TT, ICV, GS_ACT_NONE, false);                                                                         \
-    } while (0)
-#define GS_TE_ALL(TT) do { if (ICk == 1) GS_TE_ACT(TT, 1); else if (ICk == 2) GS_TE_ACT(TT, 2); else if (ICk == 3) GS_TE_ACT(TT, 3); else GS_TE_ACT(TT, 4); } while (0)
-        GS_DISPATCH_DTYPE(dtype, GS_TE_ALL(T));
-#undef GS_TE_ALL
-#undef GS_TE_ACT
-#undef GS_TE
-        GS_CHECK_LAUNCH();
-        if (mask_fused) *mask_fused = mask != nullptr;
-        if (fused) *fused = true;
-        else if (bias || act != GS_ACT_NONE) return fail(GS_ERR_ARG, "conv direct: epilogue requested without a fused flag");
-        return 0;
-    }
-    const int lanes = ICk / wn;
-    if (ks == 1 && mode == MODE_S1 && OCk <= 4 && ICk % wn == 0 && lanes <= 64 && (lanes & (lanes - 1)) == 0) {  // features -> colour
-        long nb = cdiv(P * lanes, 256);
-        static const long tr_cap = getenv("GS_THIN_REDUCE_BLOCKS") ? atol(getenv("GS_THIN_REDUCE_BLOCKS")) : 4096;
-        if (nb > tr_cap) nb = tr_cap;
-        const unsigned grid = (unsigned)nb;
-#define GS_TRL(TT, OCV, ACTV, LV) hipLaunchKernelGGL((thin_reduce_kernel<TT, OCV, ACTV, LV>), dim3(grid), dim3(256), 0, st, (const TT*)x, wp, bias, (TT*)y, P, ICk, alpha)
-#define GS_TR(TT, OCV, ACTV) do { if (lanes == 4) GS_TRL(TT, OCV, ACTV, 4); else if (lanes == 8) GS_TRL(TT, OCV, ACTV, 8); else GS_TRL(TT, OCV, ACTV, 0); } while (0)
-#define GS_TR_ACT(TT, OCV) do { if (act == GS_ACT_LRELU) GS_TR(TT, OCV, GS_ACT_LRELU); else if (act == GS_ACT_TANH) GS_TR(TT, OCV, GS_ACT_TANH); else GS_TR(TT, OCV, GS_ACT_NONE); } while (0)
-#define GS_TR_ALL(TT) do { if (OCk == 1) GS_TR_ACT(TT, 1); else if (OCk == 2) GS_TR_ACT(TT, 2); else if (OCk == 3) GS_TR_ACT(TT, 3); else GS_TR_ACT(TT, 4); } while (0)
-        GS_DISPATCH_DTYPE(dtype, GS_TR_ALL(T));
-#undef GS_TR_ALL
-#undef GS_TR_ACT
-#undef GS_TR
-#undef GS_TRL
-        GS_CHECK_LAUNCH();
-        if (fused) *fused = true;
-        return 0;
-    }
-    if (OCk == 1 && ICk == 256 && ks == 3) {
-        GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((thin_single3_kernel<T, 1>), dim3((unsigned)cdiv(P, 4)), dim3(256), 0, st, (const T*)x, wp, (T*)y, mode,
-                                                    N, Hi, Wi, Ho, Wo, alpha));
-        GS_CHECK_LAUNCH();
-        return 0;
-    }
-    if (OCk == 1 && ICk >= 64) {
-        GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((thin_single_kernel<T>), dim3((unsigned)cdiv(P, 4)), dim3(256), 0, st, (const T*)x, wp, (T*)y, mode,
-                                                    ks, N, Hi, Wi, ICk, Ho, Wo, alpha));
-        GS_CHECK_LAUNCH();
-        return 0;
-    }
-    GS_DISPATCH_DTYPE(dtype, return launch_direct<T>(reinterpret_cast<const T*>(x), wp, reinterpret_cast<T*>(y), mode, ks,
-                                                     N, Hi, Wi, ICk, OCk, Ho, Wo, alpha, st));
-}
-
 // ------------------------------------------------------------------ batched weight re-layout
 // which operand a map's entry point builds: (variant of weight_prep_kernel, fp32 storage for the direct kernels / T for MFMA)
 __device__ __host__ inline void prep_plan(int map, int ci, int co, int ksize, int dtype, int* variant, bool* store_f32) {
-    const int bk = dtype == GS_F32 ? 16 : 32;
-    bool mfma;
-    if (map == GS_PREP_CONV_FWD || map == GS_PREP_CONVT_FWD) {
-        *variant = 0;
-        mfma = ksize == 3 && ci % bk == 0 && co % 32 == 0;
-    } else if (map == GS_PREP_CONV_BWD_DATA) {   // stride 1: flipped taps; stride 2: transposed-conv walk (set by the caller)
-        *variant = 1;
-        mfma = ksize == 3 && co % bk == 0 && ci % 32 == 0;
-    } else {
-        *variant = 2;
-        mfma = co % bk == 0 && ci % 32 == 0;
-    }
+    const bool fwd = map == GS_PREP_CONV_FWD || map == GS_PREP_CONVT_FWD;   // (a data gradient contracts the layer's output channels)
+    *variant = fwd ? 0 : (map == GS_PREP_CONV_BWD_DATA ? 1 : 2);            // bwd_data, stride 1: flipped taps; stride 2: transposed-conv walk (set by the caller)
+    const bool mfma = (ksize == 3 || map == GS_PREP_CONVT_BWD_DATA) && (fwd ? igemm_supported(ci, co, dtype) : igemm_supported(co, ci, dtype));   // (that map's descriptors: ksize unread, as before)
     *store_f32 = !mfma || dtype == GS_F32;
 }
 // One 64 x 64 (ci x co) tile of one tap per trip, staged through LDS so that both sides move whole 256-byte rows: the forward operand
@@ -675,146 +119,6 @@ extern "C" int gs_weight_prep_batch(const GsPrepDesc* descs, int n, void* stream
     return 0;
 }
 
-// ------------------------------------------------------------------ direct weight gradient
-// part[slice][t][ic][oc] = sum over the slice's output pixels of x[in(p,t)][ic] * gy[p][oc]
-template <typename T>
-__global__ __launch_bounds__(256) void conv_wgrad_direct_kernel(const T* __restrict__ x, const T* __restrict__ gy,
-                                                                float* __restrict__ part, int mode, int ks, int N, int Hi,
-                                                                int Wi, int IC, int OC, int Hb, int Wb, long E, long npix,
-                                                                long pps) {
-    __shared__ float red[256];
-    const int tid = threadIdx.x;
-    const long e = (long)blockIdx.x * 64 + (tid & 63);
-    const int sub = tid >> 6;
-    const int slice = blockIdx.y;
-    float acc = 0.f;
-    if (e < E) {
-        const int oc = e % OC;
-        const int ic = (e / OC) % IC;
-        const int t = e / ((long)IC * OC);
-        const int ky = t / ks, kx = t % ks;
-        const long p0 = (long)slice * pps;
-        long p1 = p0 + pps;
-        if (p1 > npix) p1 = npix;
-        // (branch-free body, clamped addresses: unrolled, the loads of four pixels are in flight together -- with a `continue` per pixel the
-        //  loop was a chain of dependent load pairs: 10 us for the 256 pixels of the stddev-plane conv at 2 x 16)
-#pragma unroll 4
-        for (long p = p0 + sub; p < p1; p += 4) {
-            const int px = (int)(p % Wb);
-            const long q = p / Wb;
-            const int py = (int)(q % Hb);
-            const int n = (int)(q / Hb);
-            int iy, ix;
-            if (mode == MODE_S1) { iy = py + ky - (ks >> 1); ix = px + kx - (ks >> 1); }
-            else { iy = 2 * py + ky; ix = 2 * px + kx; }
-            const bool ok = iy >= 0 && iy < Hi && ix >= 0 && ix < Wi;
-            const float xv = DT<T>::ld(x + (((long)n * Hi + (ok ? iy : 0)) * Wi + (ok ? ix : 0)) * IC + ic);
-            const float gv = DT<T>::ld(gy + p * OC + oc);
-            acc += ok ? xv * gv : 0.f;
-        }
-    }
-    red[tid] = acc;
-    __syncthreads();
-    if (sub == 0 && e < E) part[(long)slice * E + e] = red[tid] + red[tid + 64] + red[tid + 128] + red[tid + 192];
-}
-
-// ------------------------------------------------------------- thin 1x1 weight gradient
-// The colour convs have 2 channels on one side: gw = sum_p wide[p][C] (x) thin[p][2].  One streaming pass:
-// C/4 lanes per pixel hold 4 wide channels x 2 thin values = 8 accumulators, pixel lanes reduce through LDS.
-// WIDE_IS_X: x is the wide tensor (gw[c][j], Cout = 2), else gy is (gw[j][c], Cin = 2).
-template <typename T, bool WIDE_IS_X>
-__global__ __launch_bounds__(256) void thin_wgrad_kernel(const T* __restrict__ wide, const T* __restrict__ thin, float* __restrict__ part,
-                                                         int C, long npix, long pps) {
-    __shared__ float red[256 * 8];
-    const int quads = C >> 2;
-    const int rpi = 256 / quads;  // pixel lanes per iteration
-    const int q = threadIdx.x % quads, r = threadIdx.x / quads;
-    const long p0 = (long)blockIdx.x * pps;
-    long p1 = p0 + pps;
-    if (p1 > npix) p1 = npix;
-    float acc[4][2] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-    if (r < rpi) {
-        long p = p0 + r;
-        for (; p + 3 * rpi < p1; p += 4 * rpi) {   // four pixels per trip: their loads are in flight together
-            float w4[4][4], t[4][2];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                ld4(wide + (p + k * rpi) * C + q * 4, w4[k]);
-                t[k][0] = DT<T>::ld(thin + (p + k * rpi) * 2);
-                t[k][1] = DT<T>::ld(thin + (p + k * rpi) * 2 + 1);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { acc[e][0] += w4[k][e] * t[k][0]; acc[e][1] += w4[k][e] * t[k][1]; }
-        }
-        for (; p < p1; p += rpi) {
-            float w4[4];
-            ld4(wide + p * C + q * 4, w4);
-            const float t0 = DT<T>::ld(thin + p * 2), t1 = DT<T>::ld(thin + p * 2 + 1);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { acc[e][0] += w4[e] * t0; acc[e][1] += w4[e] * t1; }
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { red[threadIdx.x * 8 + e * 2] = acc[e][0]; red[threadIdx.x * 8 + e * 2 + 1] = acc[e][1]; }
-    __syncthreads();
-    if (threadIdx.x < quads) {
-        float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int k = 0; k < rpi; ++k)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s[e] += red[(k * quads + threadIdx.x) * 8 + e];
-        float* out = part + (long)blockIdx.x * C * 2;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int c = threadIdx.x * 4 + e;
-            if (WIDE_IS_X) { out[c * 2] = s[e * 2]; out[c * 2 + 1] = s[e * 2 + 1]; }
-            else { out[c] = s[e * 2]; out[C + c] = s[e * 2 + 1]; }
-        }
-    }
-}
-
-static size_t wgrad_direct_bytes(int mode, int ks, int dtype, int N, int Hb, int Wb, int IC, int OC) {
-    const WgradPlan p = wgrad_plan(mode, ks, dtype, N, Hb, Wb, IC, OC);
-    return align256((size_t)p.ws_slices * ks * ks * IC * OC * 4);
-}
-
-static int run_wgrad_direct(int mode, int ks, const void* x, const void* gy, float* gw, int N, int Hi, int Wi, int IC,
-                            int OC, int Hb, int Wb, float alpha, int transpose, int accumulate, int dtype, void* ws, size_t ws_bytes,
-                            hipStream_t st, GsWgradReduce* defer = nullptr) {
-    const WgradPlan p = wgrad_plan(mode, ks, dtype, N, Hb, Wb, IC, OC);
-    if (p.family > WG_THIN) return fail(GS_ERR_UNSUPPORTED, "conv wgrad direct: %d -> %d channels belong to the MFMA kernels", IC, OC);
-    const long ns = p.nslices, pps = p.pps;
-    const long npix = (long)N * Hb * Wb;
-    const long E = (long)ks * ks * IC * OC;
-    if (p.family == WG_THIN) {
-        const int C = IC == 2 ? OC : IC;
-        if (ws_bytes < (size_t)ns * E * 4) return fail(GS_ERR_WORKSPACE, "conv wgrad thin: workspace too small (%zu)", ws_bytes);
-        float* tpart = reinterpret_cast<float*>(ws);
-        if (!p.ot) {
-            GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((thin_wgrad_kernel<T, false>), dim3((unsigned)ns), dim3(256), 0, st,
-                                                        reinterpret_cast<const T*>(gy), reinterpret_cast<const T*>(x), tpart, C, npix, pps));
-        } else {
-            GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((thin_wgrad_kernel<T, true>), dim3((unsigned)ns), dim3(256), 0, st,
-                                                        reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(gy), tpart, C, npix, pps));
-        }
-        GS_CHECK_LAUNCH();
-        wgrad_reduce_launch(tpart, gw, nullptr, (int)ns, 1, IC, OC, alpha, transpose, accumulate, st, defer);
-        GS_CHECK_LAUNCH();
-        return 0;
-    }
-    if (ws_bytes < (size_t)ns * E * 4) return fail(GS_ERR_WORKSPACE, "conv wgrad direct: workspace too small (%zu)", ws_bytes);
-    float* part = reinterpret_cast<float*>(ws);
-    dim3 grid(cdiv(E, 64), (unsigned)ns);
-    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv_wgrad_direct_kernel<T>), grid, dim3(256), 0, st,
-                                                reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(gy), part, mode,
-                                                ks, N, Hi, Wi, IC, OC, Hb, Wb, E, npix, pps));
-    GS_CHECK_LAUNCH();
-    wgrad_reduce_launch(part, gw, nullptr, (int)ns, ks * ks, IC, OC, alpha, transpose, accumulate, st, defer);
-    GS_CHECK_LAUNCH();
-    return 0;
-}
-
 static int check_conv(const GsConv* c) {
     GS_CHECK_ARG(c != nullptr, "conv: no layer descriptor");
     GS_CHECK_ARG(c->n > 0 && c->h > 0 && c->w > 0 && c->ci > 0 && c->co > 0, "conv: non-positive dim");
@@ -871,6 +175,55 @@ extern "C" int gs_channel_sum(const void* g, float* out, int64_t p, int c, int a
 extern "C" int gs_bias_act_fwd(const void* x, const float* bias, void* y, int64_t p, int c, int act, int dtype, void* stream);   // the epilogue of the shapes without the MFMA kernel
 extern "C" int gs_act_bwd(const void* g, const void* y, void* gx, int64_t numel, int act, int dtype, void* stream);
 
+// Does the implicit GEMM take this map of the layer (a tanh behind the conv is not among its epilogues)?  Otherwise: thin_conv below.
+static bool on_igemm(const GsConv& c, const ConvRole& r, int act = GS_ACT_NONE) { return c.ksize == 3 && igemm_supported(r.ICk, r.OCk, c.dtype) && act != GS_ACT_TANH; }
+
+static ThinCall thin_call(const GsConv& c, const ConvRole& r, int form, int act, bool has_bias, int mask_act, bool want_bits) {
+    ThinCall t;
+    t.mode = r.mode; t.ks = c.ksize; t.ICk = r.ICk; t.OCk = r.OCk; t.dtype = c.dtype;
+    t.P = (long)c.n * r.Ho * r.Wo;
+    t.form = form; t.act = act; t.has_bias = has_bias; t.mask_act = mask_act; t.want_bits = want_bits;
+    return t;
+}
+
+// The optional operands of a conv outside the implicit GEMM: what rides with it (t.form says how z / addend / eps are meant)
+struct ThinExtras {
+    const float* bias;
+    const void* mask;      // with t.mask_act: y *= mask_act'(.) through it
+    const void* z;         // GS_THIN_BWD_PNBWD: the norm the gradient continues through
+    const void* addend;
+    float eps;
+};
+
+// Every conv the implicit GEMM does not take, for all four entry points: the fp32 weight [tap][OCk][ICk] at the start of the layer's workspace
+// (prepared here unless w_prepared), the one launch thin_route chooses, then whatever of the request that kernel left open, as passes in place.
+static int thin_conv(const GsConv& c, const ConvRole& r, const ThinCall& t, const void* x, const float* w_hwio, void* y, const ThinExtras& e, void* stream) {
+    hipStream_t st = as_stream(stream);
+    const long total = (long)c.ksize * c.ksize * c.ci * c.co;
+    if (c.ws_bytes < (size_t)total * 4) return fail(GS_ERR_WORKSPACE, "conv direct: workspace %zu < %zu", c.ws_bytes, (size_t)total * 4);
+    float* wp = reinterpret_cast<float*>(c.ws);
+    if (!c.w_prepared) {
+        hipLaunchKernelGGL((weight_prep_kernel<float>), dim3(cdiv(total, 256)), dim3(256), 0, st, w_hwio, wp, c.ksize * c.ksize, c.ci, c.co, r.variant);
+        GS_CHECK_LAUNCH();
+    }
+    const ThinRoute route = thin_route(t, thin_knobs_env());
+    ThinArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.wp = wp; a.y = y; a.bias = e.bias; a.mask = e.mask; a.mask_act = t.mask_act; a.z = e.z; a.addend = e.addend; a.eps = e.eps; a.act = t.act;
+    a.bits = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned short*>(y) + (size_t)t.P * r.OCk);   // (behind the values: include/gansynth_hip.h, GS_ACT_WRITE_BITS)
+    a.dtype = c.dtype; a.mode = r.mode; a.ks = c.ksize; a.N = c.n; a.Hi = r.Hi; a.Wi = r.Wi; a.ICk = r.ICk; a.OCk = r.OCk; a.Ho = r.Ho; a.Wo = r.Wo;
+    a.P = t.P; a.alpha = c.alpha;
+    if (int rc = run_thin(route, a, st)) return rc;
+    if (t.form == GS_THIN_BWD_PNBWD)
+        return route.epilogue_fused ? 0 : gs_pixel_norm_bwd_fused(y, e.z, e.addend, y, t.P, r.OCk, e.eps, GS_ACT_NONE, t.act, c.dtype, stream);
+    if (!route.epilogue_fused && (e.bias || t.act != GS_ACT_NONE))
+        if (int rc = gs_bias_act_fwd(y, e.bias, y, t.P, r.OCk, t.act, c.dtype, stream)) return rc;
+    if (e.mask && !route.mask_fused)
+        if (int rc = gs_act_bwd(y, e.mask, y, t.P * r.OCk, t.mask_act, c.dtype, stream)) return rc;
+    if (t.want_bits && !route.bits_fused) return gs_pack_act_bits(y, t.P, r.OCk, c.dtype, stream);
+    return 0;
+}
+
 extern "C" size_t gs_conv_workspace_bytes(const GsConv* c, int which) {
     if (check_conv(c)) return 0;
     if (which != GS_CONV_BWD_WEIGHT) return align256((size_t)c->ksize * c->ksize * c->ci * c->co * 4);   // the re-laid weight
@@ -901,23 +254,16 @@ extern "C" int gs_conv_fwd(const GsConv* c, const void* x, const float* w_hwio, 
     GS_CHECK_ARG(y || y_norm, "conv_fwd: no output");
     hipStream_t st = as_stream(stream);
     const ConvRole r = conv_role(*c, GS_CONV_FWD);
-    if (c->ksize == 3 && igemm_supported(r.ICk, r.OCk, c->dtype) && act != GS_ACT_TANH)
+    if (on_igemm(*c, r, act))
         return run_igemm(r.mode, r.variant, x, w_hwio, y, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Hb, r.Wb, c->alpha, bias, act | (want_bits ? GS_ACT_WRITE_BITS : 0),
                          c->dtype, c->w_prepared, c->ws, c->ws_bytes, st, nullptr, 0, y_norm, eps);
     void* z = y ? y : y_norm;
-    const int64_t P = (int64_t)c->n * r.Ho * r.Wo;
-    bool fused = false;
-    bool bits_done = false;
-    unsigned* bits_out = (want_bits && !y_norm) ? reinterpret_cast<unsigned*>(reinterpret_cast<unsigned short*>(y) + (size_t)P * c->co) : nullptr;
-    if (int e = run_direct(r.mode, c->ksize, r.variant, x, w_hwio, z, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Ho, r.Wo, c->alpha, c->dtype, c->w_prepared, c->ws,
-                           c->ws_bytes, st, bias, act, &fused, nullptr, 0, nullptr, bits_out, &bits_done))
+    const bool bits_now = want_bits && !y_norm;   // (with a norm pass behind it the words are packed last)
+    if (int e = thin_conv(*c, r, thin_call(*c, r, GS_THIN_PLAIN, act, bias != nullptr, GS_ACT_NONE, bits_now), x, w_hwio, z, ThinExtras{bias, nullptr, nullptr, nullptr, 0.f}, stream))
         return e;
-    if (!fused && (bias || act != GS_ACT_NONE))
-        if (int e = gs_bias_act_fwd(z, bias, z, P, c->co, act, c->dtype, stream)) return e;
-    if (y_norm)
-        if (int e = gs_pixel_norm_fwd(z, y_norm, P, c->co, eps, c->dtype, stream)) return e;
-    if (want_bits && !bits_done) return gs_pack_act_bits(y, P, c->co, c->dtype, stream);   // (direct kernels other than the colour block's)
-    return 0;
+    if (!y_norm) return 0;
+    if (int e = gs_pixel_norm_fwd(z, y_norm, (int64_t)c->n * r.Ho * r.Wo, c->co, eps, c->dtype, stream)) return e;
+    return want_bits ? gs_pack_act_bits(y, (int64_t)c->n * r.Ho * r.Wo, c->co, c->dtype, stream) : 0;
 }
 
 // y = conv(x, w) * mask_act'(.) through `mask` (an activation OUTPUT of y's shape): the second-order pass of the R1 penalty runs
@@ -929,20 +275,14 @@ extern "C" int gs_conv_fwd_mask(const GsConv* c, const void* x, const float* w_h
     GS_CHECK_ARG(mask == nullptr || mask_act_ok(mask_act), "conv_fwd_mask: bad activation %d", mask_act);
     hipStream_t st = as_stream(stream);
     const ConvRole r = conv_role(*c, GS_CONV_FWD);
-    const bool mfma = c->ksize == 3 && igemm_supported(r.ICk, r.OCk, c->dtype);
-    const bool fused = mask != nullptr && c->co >= mask_fuse_min_channels() && mfma;
-    int rc;
     const int bits_act = mask_act;   // (only the MFMA epilogue reads the sign bits; every other path reads the values they stand behind)
     if (mask_act == GS_ACT_LRELU_BITS) mask_act = GS_ACT_LRELU;
-    if (mfma)
-        rc = run_igemm(r.mode, r.variant, x, w_hwio, y, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Hb, r.Wb, c->alpha, nullptr, GS_ACT_NONE, c->dtype, c->w_prepared, c->ws,
-                       c->ws_bytes, st, fused ? mask : nullptr, bits_act);
-    else {   // (the colour block's streaming kernel applies the mask itself; the other direct kernels leave it to the pass below)
-        bool epi = false, mdone = false;
-        rc = run_direct(r.mode, c->ksize, r.variant, x, w_hwio, y, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Ho, r.Wo, c->alpha, c->dtype, c->w_prepared, c->ws, c->ws_bytes,
-                        st, nullptr, GS_ACT_NONE, &epi, mask, mask_act, &mdone);
-        if (rc || !mask || mdone) return rc;
-    }
+    if (!on_igemm(*c, r))   // (the colour block's streaming kernel applies the mask itself; the other VALU kernels leave it to a pass in place)
+        return thin_conv(*c, r, thin_call(*c, r, mask ? GS_THIN_FWD_MASK : GS_THIN_PLAIN, GS_ACT_NONE, false, mask ? mask_act : GS_ACT_NONE, false), x, w_hwio, y,
+                         ThinExtras{nullptr, mask, nullptr, nullptr, 0.f}, stream);
+    const bool fused = mask != nullptr && c->co >= mask_fuse_min_channels();
+    const int rc = run_igemm(r.mode, r.variant, x, w_hwio, y, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Hb, r.Wb, c->alpha, nullptr, GS_ACT_NONE, c->dtype, c->w_prepared,
+                             c->ws, c->ws_bytes, st, fused ? mask : nullptr, bits_act);
     if (rc || !mask || fused) return rc;
     return gs_act_bwd(y, mask, y, (int64_t)c->n * r.Ho * r.Wo * c->co, mask_act, c->dtype, stream);
 }
@@ -956,20 +296,17 @@ extern "C" int gs_conv_bwd_data(const GsConv* c, const void* gy, const float* w_
     if (mask_act == GS_ACT_LRELU_BITS) mask_act = GS_ACT_LRELU;
     hipStream_t st = as_stream(stream);
     const ConvRole r = conv_role(*c, GS_CONV_BWD_DATA);
-    int rc;
+    if (!on_igemm(*c, r))   // (the mask: a pass in place behind the kernel)
+        return thin_conv(*c, r, thin_call(*c, r, GS_THIN_PLAIN, GS_ACT_NONE, false, mask ? mask_act : GS_ACT_NONE, false), gy, w_hwio, gx, ThinExtras{nullptr, mask, nullptr, nullptr, 0.f},
+                         stream);
     // In the epilogue the mask costs one more read of gx's size; with the mask vectors fetched ahead of the epilogue arithmetic
     // (conv_igemm.hip) that beats the separate in-place pass on every MFMA-path layer, the HBM-bound 32-channel top included
     // (+1.6 % on the step against fusing from 64 channels up).
-    bool fused = mask != nullptr && c->ci >= mask_fuse_min_channels();
-    if (c->ksize == 3 && igemm_supported(r.ICk, r.OCk, c->dtype))
-        rc = run_igemm(r.mode, r.variant, gy, w_hwio, gx, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Hb, r.Wb, c->alpha, nullptr, GS_ACT_NONE, c->dtype, c->w_prepared, c->ws,
-                       c->ws_bytes, st, fused ? mask : nullptr, bits_act);
-    else {
-        rc = run_direct(r.mode, c->ksize, r.variant, gy, w_hwio, gx, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Ho, r.Wo, c->alpha, c->dtype, c->w_prepared, c->ws, c->ws_bytes, st);
-        fused = false;
-    }
+    const bool fused = mask != nullptr && c->ci >= mask_fuse_min_channels();
+    const int rc = run_igemm(r.mode, r.variant, gy, w_hwio, gx, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Hb, r.Wb, c->alpha, nullptr, GS_ACT_NONE, c->dtype, c->w_prepared,
+                             c->ws, c->ws_bytes, st, fused ? mask : nullptr, bits_act);
     if (rc || !mask || fused) return rc;
-    return gs_act_bwd(gx, mask, gx, (int64_t)c->n * r.Ho * r.Wo * c->ci, mask_act, c->dtype, stream);   // shapes without the MFMA kernel: in place
+    return gs_act_bwd(gx, mask, gx, (int64_t)c->n * r.Ho * r.Wo * c->ci, mask_act, c->dtype, stream);
 }
 
 // the (x, gy) pairs of one launch, as the kernels want them; for the transposed conv the roles of the two sides swap
@@ -1222,7 +559,7 @@ extern "C" int gs_conv_fwd_pnbwdbwd(const GsConv* c, const void* x, const float*
     if (int e = check_conv(c)) return e;
     GS_CHECK_ARG(g && z && out_g && out_z && (act == GS_ACT_NONE || act == GS_ACT_LRELU), "conv_fwd_pnbwdbwd: g, z and both outputs are required, activation none or leaky relu (got %d)", act);
     const ConvRole r = conv_role(*c, GS_CONV_FWD);
-    if (c->ksize == 3 && igemm_supported(r.ICk, r.OCk, c->dtype))
+    if (on_igemm(*c, r))
         return run_igemm(r.mode, r.variant, x, w_hwio, out_g, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Hb, r.Wb, c->alpha, nullptr, GS_ACT_NONE, c->dtype, c->w_prepared, c->ws,
                          c->ws_bytes, as_stream(stream), z, act, out_z, eps, g, 2);
     if (int e = gs_conv_fwd(c, x, w_hwio, nullptr, GS_ACT_NONE, out_g, nullptr, 0.f, stream)) return e;
@@ -1246,19 +583,11 @@ extern "C" int gs_conv_bwd_data_pnbwd(const GsConv* c, const void* gy, const flo
     hipStream_t st = as_stream(stream);
     const ConvRole r = conv_role(*c, GS_CONV_BWD_DATA);
     const bool epilogue_map = c->transposed || c->stride == 1;   // (the stride-2 conv's data gradient, MODE_T2, has no norm epilogue)
-    if (epilogue_map && c->ksize == 3 && igemm_supported(r.ICk, r.OCk, c->dtype))
+    if (epilogue_map && on_igemm(*c, r))
         return run_igemm(r.mode, r.variant, gy, w_hwio, gx, c->n, r.Hi, r.Wi, r.ICk, r.OCk, c->ci, c->co, r.Hb, r.Wb, c->alpha, nullptr, GS_ACT_NONE, c->dtype, c->w_prepared, c->ws,
                          c->ws_bytes, st, z, act, nullptr, eps, addend, 1);
-    if (c->stride == 1 && thin_expand_pnbwd_ok(c->ksize, r.ICk, r.OCk, c->dtype)) {   // the colour block (few -> many channels as a gradient): streaming, one pass
-        const long total = (long)c->ci * c->co;
-        if (c->ws_bytes < (size_t)total * 4) return fail(GS_ERR_WORKSPACE, "conv_bwd_data_pnbwd: workspace %zu < %zu", c->ws_bytes, (size_t)total * 4);
-        float* wp = reinterpret_cast<float*>(c->ws);
-        if (!c->w_prepared) {
-            hipLaunchKernelGGL((weight_prep_kernel<float>), dim3(cdiv(total, 256)), dim3(256), 0, st, w_hwio, wp, 1, c->ci, c->co, 1);
-            GS_CHECK_LAUNCH();
-        }
-        return run_thin_expand_pnbwd(gy, wp, z, addend, gx, (long)c->n * r.Ho * r.Wo, r.ICk, r.OCk, c->alpha, eps, act, c->dtype, st);
-    }
+    if (!on_igemm(*c, r))   // the colour block (few -> many channels as a gradient) streams it in one pass; other shapes: the plain kernel + the norm's backward in place
+        return thin_conv(*c, r, thin_call(*c, r, GS_THIN_BWD_PNBWD, act, false, GS_ACT_NONE, false), gy, w_hwio, gx, ThinExtras{nullptr, nullptr, z, addend, eps}, stream);
     if (int e = gs_conv_bwd_data(c, gy, w_hwio, nullptr, 0, gx, stream)) return e;
     return gs_pixel_norm_bwd_fused(gx, z, addend, gx, (int64_t)c->n * r.Ho * r.Wo, c->ci, eps, GS_ACT_NONE, act, c->dtype, stream);
 }
@@ -1266,7 +595,7 @@ extern "C" int gs_conv_bwd_data_pnbwd(const GsConv* c, const void* gy, const flo
 extern "C" int gs_conv_bwd_data_pnbwd_is_fused(const GsConv* c) {
     if (check_conv(c) || !(c->transposed || c->stride == 1)) return 0;
     const ConvRole r = conv_role(*c, GS_CONV_BWD_DATA);
-    if (c->ksize == 1) return thin_expand_pnbwd_ok(1, r.ICk, r.OCk, c->dtype) ? 1 : 0;
+    if (!on_igemm(*c, r)) return thin_route(thin_call(*c, r, GS_THIN_BWD_PNBWD, GS_ACT_NONE, false, GS_ACT_NONE, false), thin_knobs_env()).epilogue_fused;
     return igemm_norm_fused(r.mode, c->n, r.Hb, r.Wb, r.ICk, r.OCk, c->dtype, IGEMM_NORM_BWD) ? 1 : 0;
 }
 // Which implicit-GEMM configuration a 3x3 layer runs with (kernel-role shape: hb x wb the base grid, ic -> oc the kernel's channels; mode 0 stride
@@ -1278,6 +607,29 @@ extern "C" int gs_conv_igemm_config(int mode, int n, int hb, int wb, int ic, int
 // Row `index` of the table of compiled implicit-GEMM kernels (conv_igemm.hip: GS_IGEMM_CONFIGS), for tests that want one case per kernel.  Host
 // only.  out11: mode, bf16_only, A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC; GS_ERR_ARG past the last row.
 extern "C" int gs_conv_igemm_table(int index, int* out11) { return igemm_table(index, out11); }
+
+// Which VALU kernel a call runs (include/gansynth_hip.h), from the route the entry points above read.  Host only.
+extern "C" int gs_conv_thin_route(const GsConv* c, int map, int form, int act, int has_bias, int mask_act, int want_bits, const int* caps_or_null, int* out) {
+    if (int e = check_conv(c)) return e;
+    GS_CHECK_ARG(out && (map == GS_CONV_FWD || map == GS_CONV_BWD_DATA) && form >= GS_THIN_PLAIN && form <= GS_THIN_BWD_PNBWD, "conv_thin_route: bad map %d / form %d / no output", map, form);
+    GS_CHECK_ARG(act >= GS_ACT_NONE && act <= GS_ACT_TANH && mask_act >= GS_ACT_NONE && mask_act <= GS_ACT_TANH, "conv_thin_route: bad activation %d / %d", act, mask_act);
+    GS_CHECK_ARG(!caps_or_null || (caps_or_null[0] > 0 && caps_or_null[1] > 0), "conv_thin_route: grid caps are positive");
+    // the forms as the entry points have them: a masked forward is a forward of a plain conv, the norm's backward rides on a data gradient (none / leaky relu)
+    GS_CHECK_ARG(form != GS_THIN_FWD_MASK || (map == GS_CONV_FWD && !c->transposed), "conv_thin_route: a masked forward is the forward map of a plain conv");
+    GS_CHECK_ARG(form != GS_THIN_BWD_PNBWD || (map == GS_CONV_BWD_DATA && act != GS_ACT_TANH), "conv_thin_route: the norm's backward goes with a data gradient, activation none or leaky relu");
+    const ConvRole r = conv_role(*c, map);
+    // (only gs_conv_fwd leaves the implicit GEMM for a tanh; every other entry point decides by the layer alone)
+    if (on_igemm(*c, r, map == GS_CONV_FWD && form == GS_THIN_PLAIN ? act : GS_ACT_NONE)) {
+        memset(out, 0, GS_THIN_ROUTE_INTS * sizeof(int));
+        out[0] = -1;
+        return 0;
+    }
+    const ThinKnobs knobs = caps_or_null ? ThinKnobs{caps_or_null[0], caps_or_null[1]} : thin_knobs_env();
+    const ThinRoute t = thin_route(thin_call(*c, r, form, act, has_bias != 0, mask_act, want_bits != 0), knobs);
+    static_assert(sizeof(ThinRoute) == GS_THIN_ROUTE_INTS * sizeof(int), "ThinRoute is the ints the query reports");
+    memcpy(out, &t, sizeof(t));
+    return 0;
+}
 
 // ---- what the weight-gradient entry points WOULD launch, asked without launching (host arithmetic on wgrad_plan / plan_jobs, the structs the
 // launchers themselves read; no device needed: the CU count then defaults to 256).  tests/test_wgrad_cover_*.py key their cases by these answers.

@@ -1,4 +1,5 @@
-// Device primitives and geometry shared by the MFMA conv kernels (conv_igemm.hip) and the weight-gradient kernels (conv_wgrad.hip).
+// Device primitives and geometry shared by the MFMA conv kernels (conv_igemm.hip), the weight-gradient kernels (conv_wgrad.hip) and the VALU
+// convs (conv_thin.hip).
 #pragma once
 #include <type_traits>
 #include "conv_shared.h"
@@ -43,6 +44,16 @@ template <int MODE> __host__ __device__ constexpr int tap_phase(int i) {
 }
 template <int MODE> __host__ __device__ constexpr int tap_off(int k) {  // patch offset for kernel index k
     return MODE == MODE_T2 ? (k == 2 ? 0 : 1) : k;
+}
+
+// One axis of a tap with the mode at run time (conv_thin.hip): output index o, kernel index k of ks -> the input index i the tap reads; false
+// where it reads nothing on this axis (outside the n_in inputs, or, transposed, an output of the other parity -- i is then still d >> 1).
+__device__ inline bool tap_input(int mode, int ks, int o, int k, int n_in, int& i) {
+    bool ok = true;
+    if (mode == MODE_S1) i = o + k - (ks >> 1);
+    else if (mode == MODE_S2) i = 2 * o + k;
+    else { const int d = o - k; ok = d >= 0 && !(d & 1); i = d >> 1; }
+    return ok && i >= 0 && i < n_in;
 }
 
 // compile-time loop: f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>)

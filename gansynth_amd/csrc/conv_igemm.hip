@@ -1154,10 +1154,6 @@ static int dispatch_igemm(ConvP p, hipStream_t st) {
                 c.A, c.B, c.TW, c.TG, (int)c.RESIDENT, c.D, c.NORM, c.RB, (int)c.SPEC);
 }
 
-bool igemm_supported(int ic, int oc, int dtype) {
-    const int bk = dtype == GS_F32 ? 16 : 32;
-    return ic % bk == 0 && oc % 32 == 0;
-}
 // does the layer get the epilogue `want` (IGEMM_NORM_*), i.e. run as one launch?
 bool igemm_norm_fused(int mode, int N, int Hb, int Wb, int IC, int OC, int dtype, int want) {
     return igemm_supported(IC, OC, dtype) && choose_igemm(mode, dtype, N, Hb, Wb, IC, OC, want, num_cus(), igemm_knobs()).NORM == want;

@@ -1,4 +1,5 @@
-// Constants, launch descriptors and the weight-prep kernel shared by conv_igemm.hip, conv_wgrad.hip and conv_api.hip.
+// What the conv translation units share (conv_igemm.hip, conv_wgrad.hip, conv_thin.hip, conv_api.hip): the kernel-role constants, which layers the
+// implicit GEMM takes (igemm_supported), the weight-gradient launch descriptors and plan (WgradPlan), and the weight-prep kernel.
 #pragma once
 #include "gs_common.h"
 
@@ -10,6 +11,13 @@ enum { IGEMM_PLAIN = 0, IGEMM_NORM_FWD = 1, IGEMM_NORM_BWD = 2, IGEMM_NORM_BWD2 
 #define GS_WGRAD_MAX_SRC 4   // (x, gy) pairs one weight-gradient launch contracts (GS_WGRAD_MAX_SOURCES)
 
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The channel counts the implicit-GEMM kernels take (3x3 layers; kernel-role ic -> oc): 64-byte channel chunks in, 32-channel tiles out.
+// Everything else runs the VALU kernels of conv_thin.hip (conv_thin_route.h) and stores its prepared weight as fp32 (prep_plan).
+__host__ __device__ inline bool igemm_supported(int ic, int oc, int dtype) {
+    const int bk = dtype == GS_F32 ? 16 : 32;
+    return ic % bk == 0 && oc % 32 == 0;
+}
 
 // Every weight gradient of a layer is two phases: block-partial sums over pixel slices (in the call's ws), then a reduction over the slices
 // into gw (+ gb).  A call given a GsWgradReduce runs phase 1 only and describes phase 2 in it; wgrad_reduce_batch (conv_api.hip) then folds

@@ -1,5 +1,6 @@
-// Weight gradients of the 3x3 convs on the MFMA units (channels-last activations, K = pixels), their host planning and the slice reductions
-// that fold every weight gradient's block partials (the direct kernels of conv_api.hip included).
+// Every conv weight gradient: the 3x3 convs on the MFMA units (channels-last activations, K = pixels), the direct VALU kernels of the 1- / 2-channel
+// layers (conv_wgrad_direct_kernel, thin_wgrad_kernel), the host planning that chooses among them (wgrad_plan) and the slice reductions that fold
+// every kernel's block partials.
 #include "conv_device.h"
 #include "gs_prof.h"
 
@@ -1196,7 +1197,7 @@ static bool wgrad_thin_dma(int mode, int dtype, int IC, int OC, int Wb) {
     (void)mode;
     return !off && dtype == GS_BF16 && IC == 32 && (OC == 32 || OC == 64) && Wb >= 32;
 }
-// the 1 x 1 colour layers (2 channels on one side): thin_wgrad_kernel of conv_api.hip
+// the 1 x 1 colour layers (2 channels on one side): thin_wgrad_kernel below
 static bool thin_wgrad_ok(int ks, int ci, int co) {
     if (ks != 1) return false;
     const int c = ci == 2 ? co : (co == 2 ? ci : 0);
@@ -1289,6 +1290,146 @@ WgradPlan wgrad_plan(int mode, int ks, int dtype, int N, int Hb, int Wb, int IC,
     p.fold = vec ? wgrad_fold_lanes(p.nslices) : 0;
     p.batch_lanes = p.fold;
     return p;
+}
+
+// ------------------------------------------------------------------ direct weight gradient (the layers outside the MFMA kernels: WG_DIRECT / WG_THIN)
+// part[slice][t][ic][oc] = sum over the slice's output pixels of x[in(p,t)][ic] * gy[p][oc]
+template <typename T>
+__global__ __launch_bounds__(256) void conv_wgrad_direct_kernel(const T* __restrict__ x, const T* __restrict__ gy,
+                                                                float* __restrict__ part, int mode, int ks, int N, int Hi,
+                                                                int Wi, int IC, int OC, int Hb, int Wb, long E, long npix,
+                                                                long pps) {
+    __shared__ float red[256];
+    const int tid = threadIdx.x;
+    const long e = (long)blockIdx.x * 64 + (tid & 63);
+    const int sub = tid >> 6;
+    const int slice = blockIdx.y;
+    float acc = 0.f;
+    if (e < E) {
+        const int oc = e % OC;
+        const int ic = (e / OC) % IC;
+        const int t = e / ((long)IC * OC);
+        const int ky = t / ks, kx = t % ks;
+        const long p0 = (long)slice * pps;
+        long p1 = p0 + pps;
+        if (p1 > npix) p1 = npix;
+        // (branch-free body, clamped addresses: unrolled, the loads of four pixels are in flight together -- with a `continue` per pixel the
+        //  loop was a chain of dependent load pairs: 10 us for the 256 pixels of the stddev-plane conv at 2 x 16)
+#pragma unroll 4
+        for (long p = p0 + sub; p < p1; p += 4) {
+            const int px = (int)(p % Wb);
+            const long q = p / Wb;
+            const int py = (int)(q % Hb);
+            const int n = (int)(q / Hb);
+            int iy, ix;
+            if (mode == MODE_S1) { iy = py + ky - (ks >> 1); ix = px + kx - (ks >> 1); }
+            else { iy = 2 * py + ky; ix = 2 * px + kx; }
+            const bool ok = iy >= 0 && iy < Hi && ix >= 0 && ix < Wi;
+            const float xv = DT<T>::ld(x + (((long)n * Hi + (ok ? iy : 0)) * Wi + (ok ? ix : 0)) * IC + ic);
+            const float gv = DT<T>::ld(gy + p * OC + oc);
+            acc += ok ? xv * gv : 0.f;
+        }
+    }
+    red[tid] = acc;
+    __syncthreads();
+    if (sub == 0 && e < E) part[(long)slice * E + e] = red[tid] + red[tid + 64] + red[tid + 128] + red[tid + 192];
+}
+
+// ------------------------------------------------------------- thin 1x1 weight gradient
+// The colour convs have 2 channels on one side: gw = sum_p wide[p][C] (x) thin[p][2].  One streaming pass:
+// C/4 lanes per pixel hold 4 wide channels x 2 thin values = 8 accumulators, pixel lanes reduce through LDS.
+// WIDE_IS_X: x is the wide tensor (gw[c][j], Cout = 2), else gy is (gw[j][c], Cin = 2).
+template <typename T, bool WIDE_IS_X>
+__global__ __launch_bounds__(256) void thin_wgrad_kernel(const T* __restrict__ wide, const T* __restrict__ thin, float* __restrict__ part,
+                                                         int C, long npix, long pps) {
+    __shared__ float red[256 * 8];
+    const int quads = C >> 2;
+    const int rpi = 256 / quads;  // pixel lanes per iteration
+    const int q = threadIdx.x % quads, r = threadIdx.x / quads;
+    const long p0 = (long)blockIdx.x * pps;
+    long p1 = p0 + pps;
+    if (p1 > npix) p1 = npix;
+    float acc[4][2] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+    if (r < rpi) {
+        long p = p0 + r;
+        for (; p + 3 * rpi < p1; p += 4 * rpi) {   // four pixels per trip: their loads are in flight together
+            float w4[4][4], t[4][2];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                ld4(wide + (p + k * rpi) * C + q * 4, w4[k]);
+                t[k][0] = DT<T>::ld(thin + (p + k * rpi) * 2);
+                t[k][1] = DT<T>::ld(thin + (p + k * rpi) * 2 + 1);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { acc[e][0] += w4[k][e] * t[k][0]; acc[e][1] += w4[k][e] * t[k][1]; }
+        }
+        for (; p < p1; p += rpi) {
+            float w4[4];
+            ld4(wide + p * C + q * 4, w4);
+            const float t0 = DT<T>::ld(thin + p * 2), t1 = DT<T>::ld(thin + p * 2 + 1);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { acc[e][0] += w4[e] * t0; acc[e][1] += w4[e] * t1; }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { red[threadIdx.x * 8 + e * 2] = acc[e][0]; red[threadIdx.x * 8 + e * 2 + 1] = acc[e][1]; }
+    __syncthreads();
+    if (threadIdx.x < quads) {
+        float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int k = 0; k < rpi; ++k)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e] += red[(k * quads + threadIdx.x) * 8 + e];
+        float* out = part + (long)blockIdx.x * C * 2;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = threadIdx.x * 4 + e;
+            if (WIDE_IS_X) { out[c * 2] = s[e * 2]; out[c * 2 + 1] = s[e * 2 + 1]; }
+            else { out[c] = s[e * 2]; out[C + c] = s[e * 2 + 1]; }
+        }
+    }
+}
+
+size_t wgrad_direct_bytes(int mode, int ks, int dtype, int N, int Hb, int Wb, int IC, int OC) {
+    const WgradPlan p = wgrad_plan(mode, ks, dtype, N, Hb, Wb, IC, OC);
+    return align256((size_t)p.ws_slices * ks * ks * IC * OC * 4);
+}
+
+int run_wgrad_direct(int mode, int ks, const void* x, const void* gy, float* gw, int N, int Hi, int Wi, int IC,
+                            int OC, int Hb, int Wb, float alpha, int transpose, int accumulate, int dtype, void* ws, size_t ws_bytes,
+                            hipStream_t st, GsWgradReduce* defer) {
+    const WgradPlan p = wgrad_plan(mode, ks, dtype, N, Hb, Wb, IC, OC);
+    if (p.family > WG_THIN) return fail(GS_ERR_UNSUPPORTED, "conv wgrad direct: %d -> %d channels belong to the MFMA kernels", IC, OC);
+    const long ns = p.nslices, pps = p.pps;
+    const long npix = (long)N * Hb * Wb;
+    const long E = (long)ks * ks * IC * OC;
+    if (p.family == WG_THIN) {
+        const int C = IC == 2 ? OC : IC;
+        if (ws_bytes < (size_t)ns * E * 4) return fail(GS_ERR_WORKSPACE, "conv wgrad thin: workspace too small (%zu)", ws_bytes);
+        float* tpart = reinterpret_cast<float*>(ws);
+        if (!p.ot) {
+            GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((thin_wgrad_kernel<T, false>), dim3((unsigned)ns), dim3(256), 0, st,
+                                                        reinterpret_cast<const T*>(gy), reinterpret_cast<const T*>(x), tpart, C, npix, pps));
+        } else {
+            GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((thin_wgrad_kernel<T, true>), dim3((unsigned)ns), dim3(256), 0, st,
+                                                        reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(gy), tpart, C, npix, pps));
+        }
+        GS_CHECK_LAUNCH();
+        wgrad_reduce_launch(tpart, gw, nullptr, (int)ns, 1, IC, OC, alpha, transpose, accumulate, st, defer);
+        GS_CHECK_LAUNCH();
+        return 0;
+    }
+    if (ws_bytes < (size_t)ns * E * 4) return fail(GS_ERR_WORKSPACE, "conv wgrad direct: workspace too small (%zu)", ws_bytes);
+    float* part = reinterpret_cast<float*>(ws);
+    dim3 grid(cdiv(E, 64), (unsigned)ns);
+    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((conv_wgrad_direct_kernel<T>), grid, dim3(256), 0, st,
+                                                reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(gy), part, mode,
+                                                ks, N, Hi, Wi, IC, OC, Hb, Wb, E, npix, pps));
+    GS_CHECK_LAUNCH();
+    wgrad_reduce_launch(part, gw, nullptr, (int)ns, ks * ks, IC, OC, alpha, transpose, accumulate, st, defer);
+    GS_CHECK_LAUNCH();
+    return 0;
 }
 
 size_t wgrad_mfma_bytes(int mode, int dtype, int N, int Hb, int Wb, int IC, int OC) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/gansynth_hip.h"
 
@@ -217,5 +218,12 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
         else if ((dtype) == GS_BF16) { using T = gs::bf16_t; __VA_ARGS__; } \
         else return gs::fail(GS_ERR_ARG, "bad dtype %d", (int)(dtype)); \
     } while (0)
+
+// a run-time value as a compile-time constant from a fixed list: f(std::integral_constant<int, V>{}) for the V that v equals, and what f
+// answers (a bool: nested calls pass it up); false when v is none of them.  with_constant<1, 2, 4>(n, [&](auto c) { launch<decltype(c)::value>(); return true; })
+template <int... Vs, typename F>
+inline bool with_constant(int v, F&& f) {
+    return ((v == Vs && f(std::integral_constant<int, Vs>{})) || ...);
+}
 
 }  // namespace gs

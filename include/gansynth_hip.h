@@ -172,6 +172,24 @@ int gs_conv_igemm_config(int mode, int n, int hb, int wb, int ic, int oc, int dt
  * 0: for fp32 and bf16), then A, B, TW, TG, RESIDENT, D, NORM, RB, SPEC as above.  0 for 0 <= index < number of rows, GS_ERR_ARG past the end.  Host
  * only: no launch, no device.  tests/test_igemm_cover_*.py run one case per row and dtype. */
 int gs_conv_igemm_table(int index, int* out11);
+/* Which VALU kernel a conv call outside the implicit GEMM would run -- the 1x1 colour convs, the one-output-channel gradients of the stddev plane, the
+ * generic direct conv -- asked without running it: host arithmetic on the very route the entry points and the launcher read (csrc/conv_thin_route.h),
+ * no launch, no device.  map: GS_CONV_FWD or GS_CONV_BWD_DATA of layer c; form: what is asked of that map -- GS_THIN_PLAIN (gs_conv_fwd,
+ * gs_conv_bwd_data), GS_THIN_FWD_MASK (gs_conv_fwd_mask with mask_act), GS_THIN_BWD_PNBWD (gs_conv_bwd_data_pnbwd; act: none or leaky relu); act,
+ * has_bias, want_bits: the epilogue asked for.  caps_or_null: {grid cap of EXPAND, of REDUCE}, NULL for the environment's (GS_THIN_EXPAND_BLOCKS,
+ * GS_THIN_REDUCE_BLOCKS: 2048, 4096).  out[GS_THIN_ROUTE_INTS] =
+ *    0 kernel   GS_THIN_* below; -1 (and nothing else) when the call belongs to the implicit GEMM -- decided as the form's entry point decides: a tanh
+ *               behind the conv takes only gs_conv_fwd off it.  GS_ERR_ARG for a map / form / activation no entry point has
+ *    1 C        the few-channel side as a template constant: input channels of EXPAND / EXPAND_PNBWD, output channels of REDUCE
+ *    2 ACT, 3 MASKED (EXPAND, REDUCE),   4 LC (REDUCE: lanes per pixel as a constant, 0 = run time),   5 OCV, 6 VEC (DIRECT)
+ *    7 grid (blocks of 256 threads),   8 pixels per block pass (DIRECT: 0)
+ *    9 full four-pass trips (EXPAND, REDUCE), 10 single passes a block makes
+ *   11 epilogue fused (bias + activation, or the norm's backward), 12 mask fused, 13 sign bits fused: what the kernel does of the request itself;
+ *      the entry point adds the rest as passes of their own. */
+enum { GS_THIN_EXPAND = 0, GS_THIN_REDUCE = 1, GS_THIN_EXPAND_PNBWD = 2, GS_THIN_SINGLE3 = 3, GS_THIN_SINGLE = 4, GS_THIN_DIRECT = 5 };
+enum { GS_THIN_PLAIN = 0, GS_THIN_FWD_MASK = 1, GS_THIN_BWD_PNBWD = 2 };
+#define GS_THIN_ROUTE_INTS 14
+int gs_conv_thin_route(const GsConv* c, int map, int form, int act, int has_bias, int mask_act, int want_bits, const int* caps_or_null, int* out);
 
 /* Every conv weight gradient of a backward pass in ONE call -- where `minimize` asks for the gradients of all variables of a
  * network at once (models.py:81-89).  A job is one layer (h, w, ci, co, ksize, stride, transposed as in GsConv; a transposed layer has no
