@@ -29,6 +29,15 @@ class GsConv(ctypes.Structure):
 C = POINTER(GsConv)
 
 
+class GsDense(ctypes.Structure):
+    """include/gansynth_hip.h: one dense LAYER, whichever of its maps is asked for; c, hw != 0: a channels-last input side."""
+    _fields_ = [("b", ctypes.c_int32), ("inp", ctypes.c_int32), ("out", ctypes.c_int32), ("c", ctypes.c_int32), ("hw", ctypes.c_int32),
+                ("dtype", ctypes.c_int32), ("alpha", c_float), ("ws", c_void_p), ("ws_bytes", c_size_t)]
+
+
+D = POINTER(GsDense)
+
+
 class GsSpectralKnobs(ctypes.Structure):
     """include/gansynth_hip.h: the measurement switches of the spectral kernels (GS_SPECTRAL_GENERIC, GS_INVERSE_*)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("generic", "fp32_gemm", "mag_6terms", "gemm_256", "gemm_kb", "gemm_kb3", "block_fft", "separate_ola")]
@@ -86,15 +95,12 @@ SIGNATURES = {
     "gs_conv_thin_route": (I, [C, I, I, I, I, I, I, POINTER(c_int), POINTER(c_int)]),
     "gs_units_bias_act_to_nhwc": (I, [P, P, P, P, I, I, I, I, I, P]),
     "gs_nhwc_act_bwd_to_units": (I, [P, P, P, I, I, I, I, I, P]),
-    "gs_dense_fwd_workspace_bytes": (Z, [I, I, I]),
-    "gs_dense_fwd": (I, [P, P, P, I, I, I, F, I, P, Z, P]),
-    "gs_dense_fwd_bias_act": (I, [P, P, P, P, I, I, I, F, I, I, P, Z, P]),
-    "gs_dense_fwd_bias_act_nhwc": (I, [P, P, P, P, I, I, I, I, F, I, I, P, Z, P]),
-    "gs_dense_bwd_data": (I, [P, P, P, I, I, I, F, I, P]),
-    "gs_dense_bwd_weight": (I, [P, P, P, I, I, I, F, I, I, P]),
-    "gs_dense_fwd_nhwc": (I, [P, P, P, I, I, I, I, F, I, P, Z, P]),
-    "gs_dense_bwd_data_nhwc": (I, [P, P, P, I, I, I, I, F, I, P]),
-    "gs_dense_bwd_weight_nhwc": (I, [P, P, P, I, I, I, I, F, I, I, P]),
+    # dense entry points: D = POINTER(GsDense), the layer
+    "gs_dense_fwd_workspace_bytes": (Z, [D]),
+    "gs_dense_fwd": (I, [D, P, P, P, I, P, P]),
+    "gs_dense_bwd_data": (I, [D, P, P, P, P]),
+    "gs_dense_bwd_weight": (I, [D, P, P, P, I, P]),
+    "gs_dense_route": (I, [D, I, I, POINTER(c_int)]),
     "gs_embedding_fwd": (I, [P, P, P, I, I, I, F, I, P]),
     "gs_embedding_onehot_fwd": (I, [P, P, P, P, I, I, I, F, I, P]),
     "gs_embedding_bwd": (I, [P, P, P, I, I, I, F, I, P]),
@@ -177,6 +183,10 @@ WGRAD_PLAN_INTS = 16   # GS_WGRAD_PLAN_INTS
 THIN_EXPAND, THIN_REDUCE, THIN_EXPAND_PNBWD, THIN_SINGLE3, THIN_SINGLE, THIN_DIRECT = range(6)   # GS_THIN_* kernels of gs_conv_thin_route
 THIN_PLAIN, THIN_FWD_MASK, THIN_BWD_PNBWD = range(3)   # GS_THIN_* forms
 THIN_ROUTE_INTS = 14   # GS_THIN_ROUTE_INTS
+DENSE_MAP_FWD, DENSE_MAP_BWD_DATA, DENSE_MAP_BWD_WEIGHT = range(3)   # GS_DENSE_MAP_*
+(DENSE_FWD, DENSE_FWD_SMALL, DENSE_FWD_FAST, DENSE_FWD_MFMA, DENSE_FINALIZE, DENSE_BWD_DATA, DENSE_BWD_DATA_WIDE, DENSE_BWD_DATA_FAST, DENSE_BWD_DATA_MFMA,
+ DENSE_BWD_WEIGHT, DENSE_BWD_WEIGHT_FAST) = range(11)   # GS_DENSE_* kernels of gs_dense_route
+DENSE_ROUTE_INTS = 12   # GS_DENSE_ROUTE_INTS
 
 
 SUM_PARTIALS = 2   # GS_SUM_PARTIALS

@@ -11,9 +11,11 @@ OUT=${1:-..}
 mkdir -p obj
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result $GS_EXTRA_FLAGS"
 pids=()
-for f in conv_igemm conv_wgrad conv_thin conv_api elementwise small_ops spectral spectral_wave classifier classifier_bwd summary synth; do
+for f in conv_igemm conv_wgrad conv_thin conv_api elementwise small_ops dense spectral spectral_wave classifier classifier_bwd summary synth; do
   [ -f $f.hip ] || continue
-  if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ gs_common.h -nt obj/$f.o ] || [ gs_prof.h -nt obj/$f.o ] || [ conv_shared.h -nt obj/$f.o ] || [ conv_device.h -nt obj/$f.o ] || [ spectral_plan.h -nt obj/$f.o ] || [ conv_thin_route.h -nt obj/$f.o ] || [ spectral_route.h -nt obj/$f.o ] || [ classifier_shared.h -nt obj/$f.o ] || [ ../../include/gansynth_hip.h -nt obj/$f.o ]; then
+  stale=0   # (-nt also holds when the object is missing)
+  for s in $f.hip *.h ../../include/gansynth_hip.h; do [ $s -nt obj/$f.o ] && stale=1; done
+  if [ $stale = 1 ]; then
     EXTRA=""
     # MFMA accumulators in VGPRs (hipcc otherwise parks them in AGPRs and every epilogue value costs a v_accvgpr_read)
     { [ $f = conv_igemm ] || [ $f = conv_wgrad ]; } && EXTRA="-mllvm -amdgpu-mfma-vgpr-form $GS_IGEMM_FLAGS"

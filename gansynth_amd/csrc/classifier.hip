@@ -1,6 +1,6 @@
 // Pitch classifier (reference networks.py:293-413, a pre-activation ResNet-34 with group normalisation and weight standardisation)
 // for GANSynth.evaluate: the operators the GAN itself never uses.  Inference only; the 3x3 convs go through the implicit-GEMM family
-// (gs_conv_fwd), the logits through gs_dense_fwd_bias_act.  Every reduction here runs in a fixed order with no float
+// (gs_conv_fwd), the logits through gs_dense_fwd.  Every reduction here runs in a fixed order with no float
 // atomics, so two runs on the same input are bit-identical.
 #include <math.h>
 

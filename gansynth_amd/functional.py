@@ -227,7 +227,7 @@ class _DenseKind(object):
 
 class _DenseFlatKind(object):
     """tf.matmul on tf.layers.flatten(x) of an NCHW activation (networks.py:185-186) with x kept in channels-last memory: the three
-    maps take / return the 4-D activation, the flatten is a row map inside the kernels (gs_dense_*_nhwc)."""
+    maps take / return the 4-D activation, the flatten is a row map inside the kernels (a GsDense with c, hw set)."""
 
     def fwd(self, x, w, alpha):
         return _K().dense_fwd_nhwc(x, w, alpha)

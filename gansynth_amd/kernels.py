@@ -668,97 +668,74 @@ class HipKernels(object):
         return self._bwd_weight(x, gy, 3, 2, True, alpha, out, None)
 
     # ------------------------------------------------------------------------------ dense
-    def dense_fwd(self, x, w, alpha):
+    # x is [b, in], or the channels-last [n, c, h, w] activation whose tf.layers.flatten (NCHW) feeds the layer (networks.py:185-186): w stays
+    # [c * h * w, out] in the reference's row order, the flatten is a row map inside the kernels
+    @staticmethod
+    def _dense(x, out, alpha, like):
+        """The GsDense of a layer from its input side (a tensor or its shape), its width and a tensor of the activations' dtype."""
+        shape = tuple(x.shape) if isinstance(x, torch.Tensor) else tuple(x)
+        c, hw = (shape[1], shape[2] * shape[3]) if len(shape) == 4 else (0, 0)
+        return _lib.GsDense(shape[0], c * hw if c else shape[1], out, c, hw, _dt(like), float(alpha), None, 0)
+
+    def _dense_fwd(self, x, w, bias, alpha, act):
         x, w = _act(x), _f32c(w)
-        b, i = x.shape
-        o = w.shape[1]
-        y = torch.empty((b, o), dtype=x.dtype, device=x.device)
-        ws = _ws(self.lib.gs_dense_fwd_workspace_bytes(b, i, o), x.device)
-        _lib.check(self.lib.gs_dense_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), b, i, o, float(alpha), _dt(x),
-                                         ws.data_ptr(), ws.numel(), _stream()), "gs_dense_fwd")
+        d = self._dense(x, w.shape[1], alpha, x)
+        y = torch.empty((d.b, d.out), dtype=x.dtype, device=x.device)
+        ws = _ws(self.lib.gs_dense_fwd_workspace_bytes(d), x.device)
+        d.ws, d.ws_bytes = ws.data_ptr(), ws.numel()
+        _lib.check(self.lib.gs_dense_fwd(d, x.data_ptr(), w.data_ptr(), None if bias is None else _f32c(bias).data_ptr(), int(act), y.data_ptr(), _stream()), "gs_dense_fwd")
         return y
+
+    def _dense_bwd_data(self, gy, w, x_shape, alpha):
+        gy, w = _act(gy), _f32c(w)
+        d = self._dense(x_shape, gy.shape[1], alpha, gy)
+        gx = torch.empty(tuple(x_shape), dtype=gy.dtype, device=gy.device, memory_format=CL if len(x_shape) == 4 else torch.contiguous_format)
+        _lib.check(self.lib.gs_dense_bwd_data(d, gy.data_ptr(), w.data_ptr(), gx.data_ptr(), _stream()), "gs_dense_bwd_data")
+        return gx
+
+    # (dense weight gradients deferred to the final contraction like the convs' -- off the backward's chain, beside the MFMA-bound jobs: measured
+    #  neutral, 5.083 -> 5.09 ms, round 6; they are launched where autograd produces them)
+    def _dense_bwd_weight(self, x, gy, alpha, out):
+        x, gy = _act(x), _act(gy)
+        d = self._dense(x, gy.shape[1], alpha, x)
+        gw = torch.empty((d.inp, d.out), dtype=torch.float32, device=x.device) if out is None else out
+        with self._adds_into(out):
+            _lib.check(self.lib.gs_dense_bwd_weight(d, x.data_ptr(), gy.data_ptr(), gw.data_ptr(), 0 if out is None else 1, _stream()), "gs_dense_bwd_weight")
+        return gw
+
+    def dense_fwd(self, x, w, alpha):
+        return self._dense_fwd(x, w, None, alpha, _lib.ACT_NONE)
 
     def dense_fwd_bias_act(self, x, w, bias, alpha, act):
         """act(alpha * x @ w + bias): bias / activation where the forward writes its result (x 2-D, or a channels-last 4-D activation
         whose NCHW flatten feeds the layer)."""
-        x, w = _act(x), _f32c(w)
-        o = w.shape[1]
-        y = torch.empty((x.shape[0], o), dtype=x.dtype, device=x.device)
-        bp = None if bias is None else _f32c(bias).data_ptr()
-        if x.dim() == 4:
-            b, c, h, wd = x.shape
-            ws = _ws(self.lib.gs_dense_fwd_workspace_bytes(b, c * h * wd, o), x.device)
-            _lib.check(self.lib.gs_dense_fwd_bias_act_nhwc(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), b, c, h * wd, o, float(alpha), int(act), _dt(x),
-                                                           ws.data_ptr(), ws.numel(), _stream()), "gs_dense_fwd_bias_act_nhwc")
-        else:
-            b, i = x.shape
-            ws = _ws(self.lib.gs_dense_fwd_workspace_bytes(b, i, o), x.device)
-            _lib.check(self.lib.gs_dense_fwd_bias_act(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), b, i, o, float(alpha), int(act), _dt(x),
-                                                      ws.data_ptr(), ws.numel(), _stream()), "gs_dense_fwd_bias_act")
-        return y
+        return self._dense_fwd(x, w, bias, alpha, act)
 
     def dense_bwd_data(self, gy, w, alpha):
-        gy, w = _act(gy), _f32c(w)
-        b, o = gy.shape
-        i = w.shape[0]
-        gx = torch.empty((b, i), dtype=gy.dtype, device=gy.device)
-        _lib.check(self.lib.gs_dense_bwd_data(gy.data_ptr(), w.data_ptr(), gx.data_ptr(), b, i, o, float(alpha), _dt(gy), _stream()),
-                   "gs_dense_bwd_data")
-        return gx
+        return self._dense_bwd_data(gy, w, (gy.shape[0], w.shape[0]), alpha)
 
-    def drop_deferred(self):
-        """Forget every deferred job (a backward pass that raised in the middle of a capture: capture.Capture._abandon_capture)."""
-        self._pending, self._folds = None, None
-        self._seen, self._complete = None, None
-
-    # (dense weight gradients deferred to the final contraction like the convs' -- off the backward's chain, beside the MFMA-bound jobs: measured
-    #  neutral, 5.083 -> 5.09 ms, round 6; they are launched where autograd produces them)
     def dense_bwd_weight(self, x, gy, alpha, out=None):
-        x, gy = _act(x), _act(gy)
-        b, i = x.shape
-        o = gy.shape[1]
-        gw = torch.empty((i, o), dtype=torch.float32, device=x.device) if out is None else out
-        with self._adds_into(out):
-            _lib.check(self.lib.gs_dense_bwd_weight(x.data_ptr(), gy.data_ptr(), gw.data_ptr(), b, i, o, float(alpha),
-                                                    0 if out is None else 1, _dt(x), _stream()), "gs_dense_bwd_weight")
-        return gw
+        return self._dense_bwd_weight(x, gy, alpha, out)
 
-    # the dense layer behind tf.layers.flatten of an NCHW activation (networks.py:185-186), fed with the channels-last activation
-    # itself: x is [n, c, h, w] in channels-last memory, w stays [c * h * w, out] in the reference's row order
     @staticmethod
-    def dense_nhwc_ok(x, out, batch_for_weight=None):
+    def dense_nhwc_ok(x, out):
         if config.value("GS_NO_DENSE_NHWC"):   # measurement knob: the flatten copy + the plain kernels
             return False
         return x.dim() == 4 and x.is_contiguous(memory_format=CL) and out % 256 == 0 and (x.shape[1] * x.shape[2] * x.shape[3]) % 4 == 0 and x.shape[0] <= 16
 
     def dense_fwd_nhwc(self, x, w, alpha):
-        x, w = _act(x), _f32c(w)
-        b, c, h, wd = x.shape
-        o = w.shape[1]
-        y = torch.empty((b, o), dtype=x.dtype, device=x.device)
-        ws = _ws(self.lib.gs_dense_fwd_workspace_bytes(b, c * h * wd, o), x.device)
-        _lib.check(self.lib.gs_dense_fwd_nhwc(x.data_ptr(), w.data_ptr(), y.data_ptr(), b, c, h * wd, o, float(alpha), _dt(x),
-                                              ws.data_ptr(), ws.numel(), _stream()), "gs_dense_fwd_nhwc")
-        return y
+        return self._dense_fwd(x, w, None, alpha, _lib.ACT_NONE)
 
     def dense_bwd_data_nhwc(self, gy, w, x_shape, alpha):
-        gy, w = _act(gy), _f32c(w)
-        b, c, h, wd = x_shape
-        o = gy.shape[1]
-        gx = torch.empty((b, c, h, wd), dtype=gy.dtype, device=gy.device, memory_format=CL)
-        _lib.check(self.lib.gs_dense_bwd_data_nhwc(gy.data_ptr(), w.data_ptr(), gx.data_ptr(), b, c, h * wd, o, float(alpha), _dt(gy), _stream()),
-                   "gs_dense_bwd_data_nhwc")
-        return gx
+        return self._dense_bwd_data(gy, w, x_shape, alpha)
 
     def dense_bwd_weight_nhwc(self, x, gy, alpha, out=None):
-        x, gy = _act(x), _act(gy)
-        b, c, h, wd = x.shape
-        o = gy.shape[1]
-        gw = torch.empty((c * h * wd, o), dtype=torch.float32, device=x.device) if out is None else out
-        with self._adds_into(out):
-            _lib.check(self.lib.gs_dense_bwd_weight_nhwc(x.data_ptr(), gy.data_ptr(), gw.data_ptr(), b, c, h * wd, o, float(alpha),
-                                                         0 if out is None else 1, _dt(x), _stream()), "gs_dense_bwd_weight_nhwc")
-        return gw
+        return self._dense_bwd_weight(x, gy, alpha, out)
+
+    def drop_deferred(self):
+        """Forget every deferred job (a backward pass that raised in the middle of a capture: capture.Capture._abandon_capture)."""
+        self._pending, self._folds = None, None
+        self._seen, self._complete = None, None
 
     def embedding_fwd(self, idx, w, alpha, dtype):
         w = _f32c(w)

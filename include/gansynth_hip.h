@@ -259,31 +259,46 @@ typedef struct GsPrepDesc {
 int gs_weight_prep_batch(const GsPrepDesc* descs, int n, void* stream);
 
 /* -------------------------------------------------------------------------------- dense
- * tf.matmul (ops.py:197): y[b][out] = alpha * x[b][in] @ w[in][out] (split-K partials live in ws).
- * bwd_data: gx = alpha * gy @ w^T ; bwd_weight: gw = alpha * x^T @ gy (fp32). */
-size_t gs_dense_fwd_workspace_bytes(int b, int in, int out);
-int gs_dense_fwd(const void* x, const float* w, void* y, int b, int in, int out, float alpha, int dtype,
-                 void* ws, size_t ws_bytes, void* stream);
-int gs_dense_bwd_data(const void* gy, const float* w, void* gx, int b, int in, int out, float alpha, int dtype, void* stream);
-int gs_dense_bwd_weight(const void* x, const void* gy, float* gw, int b, int in, int out, float alpha, int accumulate, int dtype,
-                        void* stream);
-/* ops.py:183-201 as the reference calls it -- dense, bias_add, activation (networks.py:185-187: the discriminator's 8192 -> 256 dense
- * + leaky_relu and its 256 -> 61 logits layer): y = act(alpha * x @ w + bias) with bias (may be NULL) and activation applied where the
- * forward writes its result (the split-K finalize pass or the direct store): one or two launches instead of three.  fp32: the same
- * operations in the same order as gs_dense_fwd + gs_bias_act_fwd (bit-identical); bf16: one rounding instead of two. */
-int gs_dense_fwd_bias_act(const void* x, const float* w, const float* bias, void* y, int b, int in, int out, float alpha, int act,
-                          int dtype, void* ws, size_t ws_bytes, void* stream);
-/* The same three maps with the INPUT side in channels-last memory: x / gx are the [b][hw][c] memory of an activation whose
- * tf.layers.flatten (NCHW: column c * hw + p, networks.py:185) feeds the layer, w stays [c * hw][out] as stored.  The flatten is a
- * row-index map inside the kernels -- no NCHW copy of the activation, no copy of its gradient back.  Vector-path shapes only
- * (out % 256 == 0, batch <= 16 for bwd_weight; GS_ERR_UNSUPPORTED otherwise). */
-int gs_dense_fwd_nhwc(const void* x, const float* w, void* y, int b, int c, int hw, int out, float alpha, int dtype,
-                      void* ws, size_t ws_bytes, void* stream);
-int gs_dense_fwd_bias_act_nhwc(const void* x, const float* w, const float* bias, void* y, int b, int c, int hw, int out, float alpha,
-                               int act, int dtype, void* ws, size_t ws_bytes, void* stream);
-int gs_dense_bwd_data_nhwc(const void* gy, const float* w, void* gx, int b, int c, int hw, int out, float alpha, int dtype, void* stream);
-int gs_dense_bwd_weight_nhwc(const void* x, const void* gy, float* gw, int b, int c, int hw, int out, float alpha, int accumulate,
-                             int dtype, void* stream);
+ * tf.matmul (ops.py:197).  A GsDense names the LAYER, whichever of its three maps is asked for:
+ *   fwd       : y[b][out] = act(alpha * x[b][in] @ w[in][out] + bias)   (split-K partials live in ws)
+ *   bwd_data  : gx[b][in] = alpha * gy @ w^T
+ *   bwd_weight: gw[in][out] (+)= alpha * x^T @ gy   (fp32 out)
+ * fwd is ops.py:183-201 as the reference calls it -- dense, bias_add, activation (networks.py:185-187: the discriminator's 8192 -> 256 dense
+ * + leaky_relu and its 256 -> 61 logits layer): bias (may be NULL) and activation (GS_ACT_NONE: none) are applied where the forward writes
+ * its result (the split-K finalize pass or the direct store): one or two launches instead of three.  fp32: the same operations in the
+ * same order as the plain product + gs_bias_act_fwd (bit-identical); bf16: one rounding instead of two.
+ * c, hw != 0: the INPUT side is in channels-last memory -- x / gx are the [b][hw][c] memory of an activation whose tf.layers.flatten
+ * (NCHW: column c * hw + p, networks.py:185) feeds the layer, in == c * hw, w stays [c * hw][out] as stored.  The flatten is a row-index
+ * map inside the kernels -- no NCHW copy of the activation, no copy of its gradient back.  Vector-path shapes only (fwd: in % 4 == 0 and
+ * out % 32 == 0; bwd_data: out % 256 == 0; bwd_weight: out % 256 == 0 and b <= 16; GS_ERR_UNSUPPORTED otherwise). */
+typedef struct GsDense {
+    int32_t b, in, out;
+    int32_t c, hw;               /* != 0: the input side is a channels-last [b][hw][c] activation, in == c * hw, weight rows in NCHW-flatten order */
+    int32_t dtype;
+    float alpha;
+    void* ws;                    /* fwd only, sized by gs_dense_fwd_workspace_bytes */
+    size_t ws_bytes;
+} GsDense;
+size_t gs_dense_fwd_workspace_bytes(const GsDense* d);   /* 0 for a layer gs_dense_fwd refuses */
+int gs_dense_fwd(const GsDense* d, const void* x, const float* w, const float* bias, int act, void* y, void* stream);
+int gs_dense_bwd_data(const GsDense* d, const void* gy, const float* w, void* gx, void* stream);
+int gs_dense_bwd_weight(const GsDense* d, const void* x, const void* gy, float* gw, int accumulate, void* stream);
+/* Which kernel a map of layer d would run, asked without running it: host arithmetic on the very route the three entry points read
+ * (csrc/dense_route.h), no launch, no device.  map: GS_DENSE_MAP_*; no_mfma_or_minus1: the GS_NO_DENSE_MFMA switch as 0 / 1, -1 for the
+ * process's environment.  A layer the map's entry point refuses is refused here with the same code.  out[GS_DENSE_ROUTE_INTS] =
+ *    0 kernel   GS_DENSE_* below, one per kernel template (GS_DENSE_FINALIZE never leads a route: see 9)
+ *    1 FB, 2 WPR          template constants: batch rows per pass of the FAST kernels (8 / 16 / 24), waves per weight row of BWD_DATA_FAST
+ *                         (1 / 4); 0 where the kernel has none
+ *    3 step, 4 passes     batch rows per launch, launches over the batch
+ *    5 grid x, 6 grid y   blocks of 256 threads
+ *    7 ksplit, 8 ipb      fwd: slices of the reduction, input rows per slice (no split: 1, in); the gradients: 0
+ *    9 finalize           a GS_DENSE_FINALIZE launch follows: it folds the ksplit partials and applies alpha, bias and activation
+ *   10, 11 ws_bytes       fwd: what gs_dense_fwd_workspace_bytes answers, low word first */
+enum { GS_DENSE_MAP_FWD = 0, GS_DENSE_MAP_BWD_DATA = 1, GS_DENSE_MAP_BWD_WEIGHT = 2 };
+enum { GS_DENSE_FWD = 0, GS_DENSE_FWD_SMALL = 1, GS_DENSE_FWD_FAST = 2, GS_DENSE_FWD_MFMA = 3, GS_DENSE_FINALIZE = 4, GS_DENSE_BWD_DATA = 5,
+       GS_DENSE_BWD_DATA_WIDE = 6, GS_DENSE_BWD_DATA_FAST = 7, GS_DENSE_BWD_DATA_MFMA = 8, GS_DENSE_BWD_WEIGHT = 9, GS_DENSE_BWD_WEIGHT_FAST = 10 };
+#define GS_DENSE_ROUTE_INTS 12
+int gs_dense_route(const GsDense* d, int map, int no_mfma_or_minus1, int* out);
 
 /* tf.nn.embedding_lookup(w*alpha, argmax(labels,1)) (ops.py:217): idx[b] are the argmax indices.
  * fwd: y[b][units] = alpha * w[idx[b]][:]  ; bwd: gw[rows][units] = alpha * scatter_add(gy) (gw zero-filled here). */
@@ -485,7 +500,7 @@ int gs_spectral_route(int frame_length, int frame_step, int time_steps, const fl
 /* ------------------------------------------------------------------- pitch classifier, forward (GANSynth.evaluate)
  * The ResNet of networks.py:293-413 (pitch_classifier_main.py:39-50: 7x7 stem, 3x3 max pool, four stages of pre-activation residual
  * blocks with group normalisation and weight-standardised convs, global mean, dense logits).  Its 3x3 convs are gs_conv_fwd
- * with alpha = 1 on standardised weights, its logits gs_dense_fwd_bias_act; the entry points below are the rest.  Deterministic:
+ * with alpha = 1 on standardised weights, its logits gs_dense_fwd; the entry points below are the rest.  Deterministic:
  * fixed-order reductions, no float atomics.
  *   weight_standardize  ops.py:53-66 on an HWIO weight viewed as [fan_in][co]: per output channel (w - mean) / sqrt(var + eps),
  *                       population variance; fp32 in, fp32 out (run once per loaded weight set, not per batch)

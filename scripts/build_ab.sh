@@ -1,6 +1,6 @@
 #!/bin/bash
 # builds ab/lib_<tag>.so variants of the library that differ in the compile flags of ONE kernel file (A/B measurements inside one GPU job).
-# usage: scripts/build_ab.sh [-f conv_wgrad | conv_thin] "tag|flags" ...      (-f: the file to rebuild, default conv_igemm; ab/ is git-ignored; delete
+# usage: scripts/build_ab.sh [-f conv_wgrad | conv_thin | dense] "tag|flags" ...      (-f: the file to rebuild, default conv_igemm; ab/ is git-ignored; delete
 #        it when done: it travels with the tree)
 F=conv_igemm
 if [ "$1" = "-f" ]; then F=$2; shift 2; fi

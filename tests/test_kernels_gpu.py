@@ -47,7 +47,8 @@ def close(got, ref, rel=1e-3, name=""):
 # resident A = 1 one; which compiled kernel a shape runs is the chooser's answer (gs_conv_igemm_config), and tests/test_igemm_cover_gpu.py
 # holds EVERY compiled kernel to a float64 reference at shapes it finds through that chooser.  The same for the weight gradients: which of the 28
 # kernels takes a shape is gs_conv_wgrad_plan's answer, and tests/test_wgrad_cover_gpu.py holds every one of them, every trip of the slice folds and
-# every kind of stream-K cut to a float64 reference.
+# every kind of stream-K cut to a float64 reference.  The dense tests below are layer shapes as well: which of the 36 dense kernels a shape runs is
+# gs_dense_route's answer, and tests/test_dense_cover_gpu.py holds every one of them to a float64 reference.
 CONV_CASES = [
     (2, 32, 32, 8, 128, 3, 1),    # 32 -> 32 at width >= 64: the resident 32-channel tile (top-level shape class)
     (2, 32, 32, 4, 32, 3, 1),
@@ -121,7 +122,8 @@ def test_dense(K, E, b, i, o):
 def test_dense_with_bias_and_activation_where_the_forward_writes(K, E, b, i, o, act, dtype):
     """gs_dense_fwd_bias_act (ops.py:183-201: matmul, bias_add, activation as the reference calls them -- the discriminator's dense + leaky_relu
     and its logits layer): against the oracle-side emulation, and in fp32 bit-identical to the two separate entry points (same operations,
-    same order) on every kernel path (MFMA split-K + finalize, one-launch small layer, wide direct, generic)."""
+    same order) on the paths these shapes take (MFMA split-K + finalize, one-launch small layer, wide direct; the generic kernel and the fast split:
+    tests/test_dense_cover_gpu.py)."""
     x, w, bias = rnd(b, i, seed=1).to(dtype).float(), rnd(i, o, seed=2), rnd(o, seed=3)
     alpha = float(np.sqrt(2.0 / i))
     want = E.bias_act_fwd(E.dense_fwd(x, w, alpha), bias, act)
