@@ -18,6 +18,12 @@ notes -- into one 16 kHz 16-bit WAV: every note generated at its pitch, the timb
 device (GANSynth.synthesize).  It needs no dataset:
 
     python gan_synth_main.py --synthesize score.mid --model_dir gan_synth_model --output score.wav
+
+`--pack_bank` / `--bank` (not in the reference): the notes packed once into one file (on any machine, no GPU needed), then held on the
+device and drawn there, batch for batch what `--filenames` yields (gansynth_amd/bank.py, DESIGN.md "Resident notes"):
+
+    python gan_synth_main.py --pack_bank nsynth_train.bank --filenames 'nsynth_train*.tfrecord'
+    python gan_synth_main.py --train --model_dir gan_synth_model --bank nsynth_train.bank
 """
 import argparse
 import glob
@@ -50,6 +56,10 @@ parser.add_argument("--release_seconds", type=float, default=1.0, help="--synthe
 parser.add_argument("--seed", type=int, default=0, help="--synthesize: seed of the latent anchors (a generator of their own)")
 parser.add_argument("--generator_ema_decay", type=float, default=0.0,
                     help="keep an exponential moving average of the generator's weights with this decay (0.0: off; progressive GAN uses 0.999)")
+parser.add_argument("--pack_bank", type=str, default=None, metavar="PATH",
+                    help="pack the notes of --filenames (pitches 24-84, acoustic sources) into PATH and exit; needs no GPU")
+parser.add_argument("--bank", type=str, default=None, metavar="PATH",
+                    help="serve --train / --evaluate / --generate from the packed notes of PATH, resident on the device, instead of --filenames")
 parser.add_argument("--weights", choices=["live", "average"], default="live",
                     help="--generate, --evaluate, --synthesize: the generator's weights as trained, or their moving average "
                          "(from --generator_ema_decay of this run, or from the checkpoint's averages)")
@@ -77,7 +87,21 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     return info
 
 
+def pack_bank(args, pitches, sources, log=print):
+    """--pack_bank: host work only (gansynth_amd.bank.pack), before any device is touched."""
+    from gansynth_amd import bank
+    files = sorted(glob.glob(args.filenames))
+    if not files:
+        raise SystemExit(f"--pack_bank: --filenames {args.filenames} matches no file")
+    header = bank.pack(files, args.pack_bank, pitches=pitches, sources=sources)
+    log(f"{header['rows']} of {header['total_records']} notes packed into {args.pack_bank}")
+    return header
+
+
 def main(args):
+    if args.pack_bank is not None:
+        pack_bank(args, range(24, 85), [0])
+        return
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -87,6 +111,7 @@ def main(args):
         torch.distributed.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
 
     from gansynth_amd import checkpoint, variables
+    from gansynth_amd.bank import NoteBank, bank_input_fn
     from gansynth_amd.dataset import nsynth_input_fn, synthetic_nsynth_input_fn
     from gansynth_amd.models import GANSynth
     from gansynth_amd.networks import PGGAN
@@ -107,6 +132,11 @@ def main(args):
         if args.synthetic:
             return synthetic_nsynth_input_fn(args.batch_size, pitches, device=device, seed=rank,
                                              num_batches=None if train else args.num_generate_batches)
+        if args.bank is not None:   # every rank holds the whole bank and draws its own order from it
+            if "bank" not in holder:     # (--train, --evaluate and --generate in one run share one upload)
+                holder["bank"] = NoteBank.open(args.bank)
+            return bank_input_fn(holder["bank"], args.batch_size, args.num_epochs if train else 1,
+                                 shuffle=train, pitches=pitches, sources=[0], device=device, seed=rank)
         files = sorted(glob.glob(args.filenames))
         if world > 1:
             files = files[rank::world] or files
@@ -165,7 +195,8 @@ def main(args):
         num_waveforms, batches = 0, 0
         while args.num_generate_batches is None or batches < args.num_generate_batches:
             try:
-                _, labels = real_input_fn()   # models.py:232-250: labels of the dataset, fresh latents
+                # models.py:232-250: labels of the dataset, fresh latents (a resident bank hands over the labels alone)
+                labels = real_input_fn.next_labels() if hasattr(real_input_fn, "next_labels") else real_input_fn()[1]
             except StopIteration:
                 break
             latents = model.fake_input_fn()

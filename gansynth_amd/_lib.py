@@ -175,6 +175,7 @@ SIGNATURES = {
     "gs_summary_audio_s16": (I, [P, P, I, L, L, I, P]),
     "gs_note_mix_workspace_bytes": (Z, [L]),
     "gs_note_mix": (I, [P, I, L, L, P, I, L, I, P, P, P, P, Z, P]),
+    "gs_bank_gather": (I, [P, L, L, L, P, P, L, L, I, I, P, P, P]),
 }
 
 WGRAD_MAX_SOURCES = 4   # GS_WGRAD_MAX_SOURCES

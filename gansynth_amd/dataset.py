@@ -12,7 +12,8 @@ Record sources: the reference's own `*.tfrecord` files (read by the small TFReco
 parser below -- features path / pitch / source, dataset.py:19-25), or NSynth's `examples.json` index next to an `audio/`
 directory.  `synthetic_nsynth_input_fn` produces notes of the same shapes and ranges without any file (bench, tests).
 Decoding runs in a background thread (the step consumes a batch in ~4 ms; a WAV decode is host work) into pinned
-buffers, so the copy to the GPU overlaps the previous step.
+buffers, so the copy to the GPU overlaps the previous step.  `gansynth_amd/bank.py` serves the same batches in the same order from notes
+packed once and held on the device; the two feeds share `epoch_order` and `decode_wav_pcm`.
 """
 import json
 import os
@@ -126,9 +127,8 @@ def _records(filename):
         yield ex["path"].decode(), int(ex["pitch"]), int(ex["source"])
 
 
-def decode_wav(path, desired_samples=WAVEFORM_LENGTH):
-    """audio_ops.decode_wav(desired_channels=1, desired_samples=64000) (dataset.py:32-37): 16-bit PCM scaled by 1/32768, first
-    channel, cropped or zero-padded to `desired_samples`."""
+def decode_wav_pcm(path, desired_samples=WAVEFORM_LENGTH):
+    """The int16 samples decode_wav scales: first channel, cropped to `desired_samples` (shorter files come back shorter)."""
     with wave.open(path, "rb") as w:
         if w.getsampwidth() != 2:
             raise ValueError(f"{path}: decode_wav handles 16-bit PCM only")
@@ -136,6 +136,13 @@ def decode_wav(path, desired_samples=WAVEFORM_LENGTH):
         pcm = np.frombuffer(w.readframes(min(w.getnframes(), desired_samples)), dtype="<i2")
     if channels > 1:
         pcm = pcm.reshape(-1, channels)[:, 0]
+    return pcm
+
+
+def decode_wav(path, desired_samples=WAVEFORM_LENGTH):
+    """audio_ops.decode_wav(desired_channels=1, desired_samples=64000) (dataset.py:32-37): 16-bit PCM scaled by 1/32768, first
+    channel, cropped or zero-padded to `desired_samples`."""
+    pcm = decode_wav_pcm(path, desired_samples)
     out = np.zeros(desired_samples, dtype=np.float32)
     out[:len(pcm)] = pcm.astype(np.float32) * np.float32(1.0 / 32768.0)
     return out
@@ -179,6 +186,28 @@ class _Prefetcher(object):
         return wav, lab
 
 
+def epoch_order(count, rng, shuffle, buffer_size=None):
+    """The order in which one epoch visits its `count` records (positions in the record list), drawing from `rng` exactly what the
+    reference's shuffle draws.  One function for every feed (nsynth_input_fn here, bank.bank_input_fn on the device): two feeds with the
+    same seed visit the same records in the same order because they run the same code."""
+    order = np.arange(count)
+    if shuffle:   # buffer_size=None = a full shuffle (dataset.py:52-55), reshuffled each epoch
+        if buffer_size is None or buffer_size >= count:
+            rng.shuffle(order)
+        else:     # tf.data's streaming shuffle: a buffer of `buffer_size` records, random pick, refill
+            buf, out, it = list(order[:buffer_size]), [], iter(order[buffer_size:])
+            while buf:
+                j = int(rng.integers(len(buf)))
+                out.append(buf[j])
+                nxt = next(it, None)
+                if nxt is None:
+                    buf.pop(j)
+                else:
+                    buf[j] = nxt
+            order = np.asarray(out)
+    return order
+
+
 def nsynth_input_fn(filenames, batch_size, num_epochs, shuffle, buffer_size=None, pitches=None, sources=None, device=None, seed=0,
                     prefetch=2):
     """dataset.py:12-91.  -> callable returning (waveforms [B, 64000], labels [B, len(pitches)]); StopIteration at the end."""
@@ -197,22 +226,7 @@ def nsynth_input_fn(filenames, batch_size, num_epochs, shuffle, buffer_size=None
         epoch = 0
         wavs, labs = [], []
         while num_epochs is None or epoch < num_epochs:
-            order = np.arange(len(records))
-            if shuffle:   # buffer_size=None = a full shuffle (dataset.py:52-55), reshuffled each epoch
-                if buffer_size is None or buffer_size >= len(records):
-                    rng.shuffle(order)
-                else:     # tf.data's streaming shuffle: a buffer of `buffer_size` records, random pick, refill
-                    buf, out, it = list(order[:buffer_size]), [], iter(order[buffer_size:])
-                    while buf:
-                        j = int(rng.integers(len(buf)))
-                        out.append(buf[j])
-                        nxt = next(it, None)
-                        if nxt is None:
-                            buf.pop(j)
-                        else:
-                            buf[j] = nxt
-                    order = np.asarray(out)
-            for k in order:
+            for k in epoch_order(len(records), rng, shuffle, buffer_size):
                 path, pitch, source = records[k]
                 if not (lo <= pitch <= hi) or (src_ok is not None and source not in src_ok) or pitch not in table:
                     continue

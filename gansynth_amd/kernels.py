@@ -1367,6 +1367,31 @@ class HipKernels(object):
                                         ws.data_ptr(), ws.numel(), _stream()), "gs_note_mix")
         return out, pcm, peak
 
+    def bank_gather(self, pcm, class_of_row, order, first, batch, n_classes, want_waves=True):
+        """gs_bank_gather (include/gansynth_hip.h): the batch order[first : first + batch] of the resident bank pcm [rows, L] int16.
+        -> (waves [batch, L] fp32 = pcm * 2^-15, or None without `want_waves`; labels [batch, n_classes] fp32 one-hot of class_of_row)."""
+        if pcm.dim() != 2 or pcm.dtype != torch.int16:
+            raise ValueError(f"bank_gather: pcm must be [rows, L] int16 (got {tuple(pcm.shape)} {pcm.dtype})")
+        rows, length = int(pcm.shape[0]), int(pcm.shape[1])
+        for name, t, n in (("class_of_row", class_of_row, rows), ("order", order, None)):
+            if t.dim() != 1 or t.dtype != torch.int32 or not t.is_contiguous() or (n is not None and t.numel() != n):
+                raise ValueError(f"bank_gather: {name} must be a contiguous int32 vector{'' if n is None else f' of {n} rows'} "
+                                 f"(got {tuple(t.shape)} {t.dtype})")
+        for name, t in (("pcm", pcm), ("class_of_row", class_of_row), ("order", order)):
+            if not t.is_cuda or t.device != pcm.device:
+                raise ValueError(f"bank_gather: {name} is on {t.device}, not on the bank's HIP device")
+        if pcm.stride(1) != 1 or (rows > 1 and pcm.stride(0) < length):
+            raise ValueError(f"bank_gather: pcm rows must be contiguous (strides {tuple(pcm.stride())}); the bank is not copied per draw")
+        first, batch, n_classes = int(first), int(batch), int(n_classes)
+        if batch <= 0 or n_classes <= 0 or first < 0 or first + batch > order.numel():
+            raise ValueError(f"bank_gather: batch {batch} at first {first} with {n_classes} classes does not fit an order of {order.numel()}")
+        waves = torch.empty((batch, length), dtype=torch.float32, device=pcm.device) if want_waves else None
+        labels = torch.empty((batch, n_classes), dtype=torch.float32, device=pcm.device)
+        _lib.check(self.lib.gs_bank_gather(pcm.data_ptr(), rows, length, int(pcm.stride(0)) if rows > 1 else length, class_of_row.data_ptr(),
+                                           order.data_ptr(), order.numel(), first, batch, n_classes,
+                                           None if waves is None else waves.data_ptr(), labels.data_ptr(), _stream()), "gs_bank_gather")
+        return waves, labels
+
     def account(self):
         """bench.py: `with K.account() as calls:` lists every kernel-layer call made inside as (method, argument dict, bytes read,
         bytes written) -- the algorithmic traffic of SURVEY.md 8(d): every tensor argument read once, every result written once
@@ -1431,6 +1456,8 @@ class _Accounting(object):
                 except TypeError:
                     args = {}
                 read = sum(self._nbytes(v) for k, v in args.items() if k not in ("out", "bias_out"))
+                if name == "bank_gather":   # a draw reads `batch` rows of the bank (none for labels alone), their classes and order entries
+                    read = int(args["batch"]) * (8 + (2 * args["pcm"].shape[1] if args.get("want_waves", True) else 0))
                 acc = sum(self._nbytes(args.get(k)) for k in ("out", "bias_out"))   # accumulated into: read + written
                 written = self._nbytes(out) if acc == 0 or not isinstance(out, torch.Tensor) else 0
                 meta = {k: (tuple(v.shape) if isinstance(v, torch.Tensor) else (tuple(v) if isinstance(v, (tuple, list, torch.Size)) else v))

@@ -730,7 +730,10 @@ class GANSynth(Iterations, DataParallel, Capture):
             return out
         real_images, labels = self._real_batch()
         d_latents = self.fake_input_fn().to(self.dtype)
-        _, g_labels = self.real_input_fn()  # the G run only consumes the labels of its batch (waveform branch is pruned)
+        # the G run only consumes the labels of its batch (waveform branch is pruned): a feed that can advance one batch and hand
+        # over its labels alone (bank.BankFeed.next_labels) is asked for just that -- the same batch position either way
+        next_labels = getattr(self.real_input_fn, "next_labels", None)
+        g_labels = next_labels() if next_labels is not None else self.real_input_fn()[1]
         g_latents, g_labels = self.fake_input_fn().to(self.dtype), g_labels.to(self.dtype)
         return real_images, labels, d_latents, g_latents, g_labels
 

@@ -627,6 +627,20 @@ size_t gs_note_mix_workspace_bytes(int64_t total);
 int gs_note_mix(const float* waves, int rows, int64_t length, int64_t row_stride, const GsMixNote* notes, int n_notes, int64_t total,
                 int normalize, float* out, int16_t* pcm, float* peak, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Resident notes: one batch drawn from the int16 bank on the device (gansynth_amd/bank.py, DESIGN.md "Resident notes") ----------
+ * pcm: [rows] notes of `length` int16 samples, `row_stride` elements apart.  class_of_row: [rows] int32, the label index of a row or -1.
+ * order: [n_order] int32 row numbers; the batch is order[first .. first + batch).  For b in [0, batch), r = order[first + b]:
+ *     waves[b][i]  = (float)pcm[r * row_stride + i] * 2^-15       (exact in fp32: dataset.decode_wav's value bit for bit)
+ *     labels[b][c] = (c == class_of_row[r]) ? 1 : 0
+ * waves == NULL writes the labels only.  An r outside [0, rows) reads nothing: zeros and an all-zero label.  A class outside
+ * [0, n_classes) gives an all-zero label.  Every row offset is 64-bit.  One launch, no workspace, no atomics.  16-byte loads of eight
+ * samples per lane when length % 8 == 0, row_stride % 8 == 0 and pcm and waves are 16-byte aligned (chosen here, on the host), one
+ * sample per lane otherwise.
+ * GS_ERR_ARG without a launch: pcm / class_of_row / order / labels NULL, rows / length / batch / n_classes <= 0, row_stride < length,
+ * first < 0 or first + batch > n_order, pcm not 2-byte or waves / labels not 4-byte aligned, a batch too large for one grid. */
+int gs_bank_gather(const int16_t* pcm, int64_t rows, int64_t length, int64_t row_stride, const int32_t* class_of_row, const int32_t* order,
+                   int64_t n_order, int64_t first, int batch, int n_classes, float* waves, float* labels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

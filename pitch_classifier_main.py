@@ -7,7 +7,8 @@ Same flags, defaults and hyper-parameters (:71-81: weight decay 1e-4, Nesterov m
 by 0.1 every 70000 * epochs / 4 / batch steps).  `--synthetic` replaces `--filenames` by generated notes of the same shapes;
 `--evaluate --synthetic` needs `--num_evaluate_batches` (one flag more than gan_synth_main.py's set: the generated input never ends).  The latest
 checkpoint of `--model_dir` is also what `gan_synth_main.py --evaluate --classifier <file>` takes.  Training runs with fp32
-activations; `--dtype` is the activation storage of `--evaluate`.
+activations; `--dtype` is the activation storage of `--evaluate`.  `--pack_bank PATH` packs `--filenames` into one file and exits (no
+GPU needed); `--bank PATH` serves the same batches from that file, resident on the device (gansynth_amd/bank.py).
 """
 import argparse
 import glob
@@ -28,6 +29,10 @@ parser.add_argument("--dtype", choices=["f32", "bf16"], default="f32", help="act
 parser.add_argument("--save_checkpoint_steps", type=int, default=1000)
 parser.add_argument("--log_tensor_steps", type=int, default=100)
 parser.add_argument("--save_summary_steps", type=int, default=100, help="TensorBoard summaries into --model_dir every this many steps (0: off)")
+parser.add_argument("--pack_bank", type=str, default=None, metavar="PATH",
+                    help="pack the notes of --filenames (pitches 24-84, acoustic sources) into PATH and exit; needs no GPU")
+parser.add_argument("--bank", type=str, default=None, metavar="PATH",
+                    help="serve --train / --evaluate from the packed notes of PATH, resident on the device, instead of --filenames")
 parser.add_argument("--num_evaluate_batches", type=int, default=None, help="stop --evaluate --synthetic after this many batches (synthetic input never ends)")
 
 
@@ -42,8 +47,17 @@ def hyper_params(batch_size, num_epochs):
 
 
 def main(args):
+    if args.pack_bank is not None:   # host work only, before any device is touched
+        from gansynth_amd import bank
+        files = sorted(glob.glob(args.filenames))
+        if not files:
+            raise SystemExit(f"--pack_bank: --filenames {args.filenames} matches no file")
+        header = bank.pack(files, args.pack_bank, pitches=range(24, 85), sources=[0])
+        print(f"{header['rows']} of {header['total_records']} notes packed into {args.pack_bank}")
+        return
     torch.cuda.set_device(0)
     from gansynth_amd import variables
+    from gansynth_amd.bank import NoteBank, bank_input_fn
     from gansynth_amd.dataset import nsynth_input_fn, synthetic_nsynth_input_fn
     from gansynth_amd.models import PitchClassifier
     from gansynth_amd.networks import ResNet
@@ -52,12 +66,18 @@ def main(args):
     torch.manual_seed(0)   # tf.set_random_seed(0) (:37)
     device = torch.device("cuda", 0)
     pitches = range(24, 85)
+    banks = {}   # (--train and --evaluate in one run share one upload)
 
     def input_fn_factory(train):
         if args.synthetic:
             if not train and args.num_evaluate_batches is None:
                 raise SystemExit("--evaluate --synthetic needs --num_evaluate_batches (synthetic input never ends)")
             return synthetic_nsynth_input_fn(args.batch_size, pitches, device=device, seed=0, num_batches=None if train else args.num_evaluate_batches)
+        if args.bank is not None:
+            if "open" not in banks:
+                banks["open"] = NoteBank.open(args.bank)
+            return bank_input_fn(banks["open"], args.batch_size, args.num_epochs if train else 1, shuffle=train, pitches=pitches,
+                                 sources=[0], device=device, seed=0)
         return nsynth_input_fn(sorted(glob.glob(args.filenames)), args.batch_size, args.num_epochs if train else 1, shuffle=train,
                                pitches=pitches, sources=[0], device=device, seed=0)
 
