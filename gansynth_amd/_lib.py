@@ -128,6 +128,7 @@ SIGNATURES = {
     "gs_sumsq_rows_workspace_bytes": (Z, [I]),
     "gs_sumsq_rows": (I, [P, P, I, L, I, P, Z, P]),
     "gs_row_scale": (I, [P, P, F, P, I, L, I, P]),
+    "gs_elementwise_route": (I, [I, I, L, I, I, I, I, I, POINTER(c_int)]),
     "gs_weight_prep_batch": (I, [P, I, P]),
     "gs_gan_d_loss": (I, [P, P, P, P, F, I, I, P, P, P, P, I, P]),
     "gs_gan_g_loss": (I, [P, P, P, F, F, I, I, P, P, P, I, P]),
@@ -188,6 +189,14 @@ DENSE_MAP_FWD, DENSE_MAP_BWD_DATA, DENSE_MAP_BWD_WEIGHT = range(3)   # GS_DENSE_
 (DENSE_FWD, DENSE_FWD_SMALL, DENSE_FWD_FAST, DENSE_FWD_MFMA, DENSE_FINALIZE, DENSE_BWD_DATA, DENSE_BWD_DATA_WIDE, DENSE_BWD_DATA_FAST, DENSE_BWD_DATA_MFMA,
  DENSE_BWD_WEIGHT, DENSE_BWD_WEIGHT_FAST) = range(11)   # GS_DENSE_* kernels of gs_dense_route
 DENSE_ROUTE_INTS = 12   # GS_DENSE_ROUTE_INTS
+(EW_OP_BIAS_ACT, EW_OP_ACT_BWD, EW_OP_TANH_BWD_BWD, EW_OP_AXPBY, EW_OP_AXPBY_DEV, EW_OP_UPSCALE, EW_OP_ROW_SCALE, EW_OP_CHANNEL_SUM, EW_OP_ACT_BWD_BIAS,
+ EW_OP_PIXEL_NORM_FWD, EW_OP_PIXEL_NORM_BWD, EW_OP_PIXEL_NORM_BWD_BIAS, EW_OP_PIXEL_NORM_BWD_BWD, EW_OP_BLOCKSUM, EW_OP_SUMSQ_ROWS, EW_OP_BATCH_STDDEV_FWD,
+ EW_OP_BATCH_STDDEV_BWD, EW_OP_BATCH_STDDEV_BWD_BWD) = range(18)   # GS_EW_OP_* operations of gs_elementwise_route
+(EW_BIAS_ACT, EW_BIAS_ACT_SCALAR, EW_ACT_BWD, EW_TANH_BWD_BWD, EW_AXPBY, EW_AXPBY_DEV, EW_UPSCALE, EW_ROW_SCALE, EW_CHANNEL_SUM, EW_CHANNEL_SUM_ROWS,
+ EW_ACT_BWD_SUM, EW_PIXEL_NORM, EW_BLOCKSUM, EW_BLOCKSUM_SMALL, EW_SUMSQ_ROWS, EW_BATCH_STDDEV_FWD, EW_BATCH_STDDEV_BWD,
+ EW_BATCH_STDDEV_BWD_BWD) = range(18)   # GS_EW_* kernel templates
+EW_PATH_NONE, EW_PATH_COLOUR, EW_PATH_QUADS, EW_PATH_GENERIC, EW_PATH_VECTOR, EW_PATH_SCALAR = range(6)   # GS_EW_PATH_*
+EW_ROUTE_INTS = 18   # GS_EW_ROUTE_INTS
 
 
 SUM_PARTIALS = 2   # GS_SUM_PARTIALS

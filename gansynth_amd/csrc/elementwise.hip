@@ -7,17 +7,13 @@
 //   TF-form Adam                                             models.py:67-89
 // All are one-read/one-write streaming kernels with 16-byte (f32) / 8-byte (bf16) accesses and
 // wave64 shuffle reductions; none goes near the MFMA.
-#include "gs_common.h"
+// Which kernel, path, template constants and grid a call gets is elementwise_route's answer (elementwise_route.h): the entry points below read it.
+#include "elementwise_route.h"
 
 namespace gs {
 
-static inline int ew_grid(long nvec) {
-    long g = (nvec + 255) / 256;
-    static const long cap = getenv("GS_EW_GRID_CAP") ? atol(getenv("GS_EW_GRID_CAP")) : 8192;   // (measurement knob)
-    if (g > cap) g = cap;  // grid-stride the rest (256 CUs x 8 blocks x 4)
-    if (g < 1) g = 1;
-    return (int)g;
-}
+// (Adam, EMA and swap: grid-stride kernels outside the route)
+static inline int ew_grid(long nvec) { return ew_grid(nvec, ew_knobs_env().ew_cap); }
 
 // ------------------------------------------------------------------ bias + activation
 template <typename T, int ACT, bool BIAS>
@@ -97,9 +93,26 @@ __global__ void axpby_kernel(const T* __restrict__ a, const T* __restrict__ b, T
 }
 
 // ------------------------------------------------------------------------ channel sum
+// g * act'(y) through the activation output y (ACT = GS_ACT_NONE: g itself, y is not read)
+template <int ACT> __device__ inline float act_grad(float g, float y) {
+    if (ACT == GS_ACT_LRELU) return y > 0.f ? g : 0.2f * g;
+    if (ACT == GS_ACT_TANH) return g * (1.f - y * y);
+    return g;
+}
+template <typename T, int ACT> __device__ inline void ld4_act(const T* g, const T* y, long off, float (&v)[4]) {
+    ld4(g + off, v);
+    if (ACT != GS_ACT_NONE) {
+        float w[4];
+        ld4(y + off, w);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = act_grad<ACT>(v[e], w[e]);
+    }
+}
 // out[c] = sum_p g[p][c].  Pass 1: block b sums rows b, b+G, ... into part[b][c]; pass 2 sums parts.
-template <typename T>
-__global__ __launch_bounds__(256) void channel_sum_kernel(const T* __restrict__ g, float* __restrict__ part, long p, int c) {
+// ACT != 0: the summands are g * act'(y) -- the second pass of the two-pass gs_act_bwd_bias, which sums the gradient as the first pass COMPUTED
+// it and not as it stored it (a bf16 gx is rounded; the one-pass kernel sums unrounded values too).
+template <typename T, int ACT>
+__global__ __launch_bounds__(256) void channel_sum_kernel(const T* __restrict__ g, const T* __restrict__ y, float* __restrict__ part, long p, int c) {
     // thread handles channel quad q = tid % (c/4) (or single channels when c%4 != 0), row lane r = tid / quads
     __shared__ float red[256 * 4];
     const int tid = threadIdx.x;
@@ -110,8 +123,8 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const T* __restrict__ 
         float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         for (long i = (long)blockIdx.x * 256 + tid; i < n8; i += (long)gridDim.x * 256) {
             float v[8];
-            ld4(g + i * 8, *reinterpret_cast<float(*)[4]>(v));
-            ld4(g + i * 8 + 4, *reinterpret_cast<float(*)[4]>(v + 4));
+            ld4_act<T, ACT>(g, y, i * 8, *reinterpret_cast<float(*)[4]>(v));
+            ld4_act<T, ACT>(g, y, i * 8 + 4, *reinterpret_cast<float(*)[4]>(v + 4));
 #pragma unroll
             for (int k = 0; k < 8; ++k) a[k] += v[k];
         }
@@ -134,16 +147,16 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const T* __restrict__ 
             long row = (long)blockIdx.x * rl + r;
             for (; row + 3 * step < p; row += 4 * step) {
                 float v0[4], v1[4], v2[4], v3[4];
-                ld4(g + row * c + q * 4, v0);
-                ld4(g + (row + step) * c + q * 4, v1);
-                ld4(g + (row + 2 * step) * c + q * 4, v2);
-                ld4(g + (row + 3 * step) * c + q * 4, v3);
+                ld4_act<T, ACT>(g, y, row * c + q * 4, v0);
+                ld4_act<T, ACT>(g, y, (row + step) * c + q * 4, v1);
+                ld4_act<T, ACT>(g, y, (row + 2 * step) * c + q * 4, v2);
+                ld4_act<T, ACT>(g, y, (row + 3 * step) * c + q * 4, v3);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) a[e] += (v0[e] + v1[e]) + (v2[e] + v3[e]);
             }
             for (; row < p; row += step) {
                 float v[4];
-                ld4(g + row * c + q * 4, v);
+                ld4_act<T, ACT>(g, y, row * c + q * 4, v);
                 a[0] += v[0]; a[1] += v[1]; a[2] += v[2]; a[3] += v[3];
             }
         }
@@ -166,7 +179,10 @@ __global__ __launch_bounds__(256) void channel_sum_kernel(const T* __restrict__ 
         for (int c0 = 0; c0 < c; c0 += cl) {
             float a = 0.f;
             if (r < rl && c0 + ch < c)
-                for (long row = (long)blockIdx.x * rl + r; row < p; row += (long)gridDim.x * rl) a += DT<T>::ld(g + row * c + c0 + ch);
+                for (long row = (long)blockIdx.x * rl + r; row < p; row += (long)gridDim.x * rl) {
+                    const long off = row * c + c0 + ch;
+                    a += act_grad<ACT>(DT<T>::ld(g + off), ACT != GS_ACT_NONE ? DT<T>::ld(y + off) : 0.f);
+                }
             __syncthreads();
             red[tid] = a;
             __syncthreads();
@@ -255,7 +271,7 @@ static __global__ __launch_bounds__(256) void channel_sum_final_kernel(const flo
         *o = accumulate ? *o + t : t;
     }
 }
-constexpr int CS_SLAB = 64;  // parts per first-level block
+// (CS_SLAB parts per first-level block: elementwise_route.h)
 static int channel_sum_finalize(float* part, float* out, int nparts, int c, int accumulate, hipStream_t st) {
     if (nparts <= CS_SLAB) {
         hipLaunchKernelGGL(channel_sum_final_kernel, dim3(cdiv(c, 32), 1), dim3(256), 0, st, part, out, nparts, c, nparts, accumulate);
@@ -382,22 +398,13 @@ extern "C" int gs_channel_fold_batch(const GsFoldJob* jobs, int njobs, void* ws,
 extern "C" int gs_bias_partial_rows(int producer, int64_t p, int c, int dtype);
 
 // few rows, many channels (dense-layer biases: [batch][8192]): a thread per channel, no partials
-template <typename T>
-__global__ __launch_bounds__(256) void channel_sum_rows_kernel(const T* __restrict__ g, float* __restrict__ out, int p, int c, int accumulate) {
+template <typename T, int ACT>
+__global__ __launch_bounds__(256) void channel_sum_rows_kernel(const T* __restrict__ g, const T* __restrict__ y, float* __restrict__ out, int p, int c, int accumulate) {
     const int ch = blockIdx.x * 256 + threadIdx.x;
     if (ch >= c) return;
     float s = 0.f;
-    for (int r = 0; r < p; ++r) s += DT<T>::ld(g + (long)r * c + ch);
+    for (int r = 0; r < p; ++r) s += act_grad<ACT>(DT<T>::ld(g + (long)r * c + ch), ACT != GS_ACT_NONE ? DT<T>::ld(y + (long)r * c + ch) : 0.f);
     out[ch] = accumulate ? out[ch] + s : s;
-}
-
-static int channel_sum_parts(long p, int c) {
-    long rows_per_block = 256 / (c >= 4 ? ((c & 3) == 0 ? c / 4 : (c < 256 ? c : 256)) : c);
-    if (rows_per_block < 1) rows_per_block = 1;
-    long nb = (p + rows_per_block * 8 - 1) / (rows_per_block * 8);
-    if (nb > 2048) nb = 2048;
-    if (nb < 1) nb = 1;
-    return (int)nb;
 }
 
 // ------------------------------------------------------------------------- pixel norm
@@ -621,13 +628,14 @@ __global__ void blocksum_small_kernel(const T* __restrict__ x, T* __restrict__ y
 // --------------------------------------------------------------------- row reductions
 // out[r] = sum_j x[r][j]^2.  A row is split over SSQ_CHUNKS blocks (8 rows of 262144 elements would otherwise keep 8 CUs busy);
 // pass 1 writes one partial per (row, chunk), pass 2 (one wave per row) sums them in a fixed order: deterministic.
-constexpr int SSQ_CHUNKS = 64;
+// Rows of cols % 4 != 0 behind the first start off the 4-element alignment ld4 asks for: such a call (elementwise_route: the scalar path) reads
+// every row through the scalar tail loop of its last chunk.
 template <typename T>
 __global__ __launch_bounds__(256) void sumsq_rows_kernel(const T* __restrict__ x, float* __restrict__ part, long cols) {
     __shared__ float red[4];
     const int r = blockIdx.y, ck = blockIdx.x;
     const T* xr = x + (long)r * cols;
-    const long nvec = cols >> 2;
+    const long nvec = ((cols & 3) == 0 || gridDim.y == 1) ? cols >> 2 : 0;
     const long per = (nvec + SSQ_CHUNKS - 1) / SSQ_CHUNKS;
     const long i0 = ck * per, i1 = i0 + per < nvec ? i0 + per : nvec;
     float s = 0.f;
@@ -757,11 +765,13 @@ using namespace gs;
 
 extern "C" int gs_bias_act_fwd(const void* x, const float* bias, void* y, int64_t p, int c, int act, int dtype, void* stream) {
     GS_CHECK_ARG(p > 0 && c > 0 && act >= 0 && act <= 2, "bias_act: bad args");
+    EwRoute r;
+    if (int e = ew_plan("bias_act", GS_EW_OP_BIAS_ACT, dtype, p, c, 0, 0, &r)) return e;
     hipStream_t st = as_stream(stream);
     const long n = (long)p * c;
-    if ((c & 3) == 0) {
+    if (r.kernel == GS_EW_BIAS_ACT) {
         const long nvec = n >> 2;
-        dim3 grid(ew_grid(nvec));
+        dim3 grid(r.grid_x);
 #define GS_BA(ACT, B) hipLaunchKernelGGL((bias_act_kernel<T, ACT, B>), grid, dim3(256), 0, st, (const T*)x, bias, (T*)y, nvec, c >> 2)
         GS_DISPATCH_DTYPE(dtype, {
             if (bias) { if (act == 0) GS_BA(0, true); else if (act == 1) GS_BA(1, true); else GS_BA(2, true); }
@@ -769,7 +779,7 @@ extern "C" int gs_bias_act_fwd(const void* x, const float* bias, void* y, int64_
         });
 #undef GS_BA
     } else {
-        GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bias_act_scalar_kernel<T>), dim3(ew_grid(n)), dim3(256), 0, st, (const T*)x, bias, (T*)y, n, c, act));
+        GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bias_act_scalar_kernel<T>), dim3(r.grid_x), dim3(256), 0, st, (const T*)x, bias, (T*)y, n, c, act));
     }
     GS_CHECK_LAUNCH();
     return 0;
@@ -777,8 +787,10 @@ extern "C" int gs_bias_act_fwd(const void* x, const float* bias, void* y, int64_
 
 extern "C" int gs_act_bwd(const void* g, const void* y, void* gx, int64_t numel, int act, int dtype, void* stream) {
     GS_CHECK_ARG(numel > 0 && (act == 1 || act == 2), "act_bwd: bad args");
+    EwRoute r;
+    if (int e = ew_plan("act_bwd", GS_EW_OP_ACT_BWD, dtype, numel, 0, 0, 0, &r)) return e;
     hipStream_t st = as_stream(stream);
-    dim3 grid(ew_grid((numel >> 2) + 4));
+    dim3 grid(r.grid_x);
     GS_DISPATCH_DTYPE(dtype, {
         if (act == 1) hipLaunchKernelGGL((act_bwd_kernel<T, 1>), grid, dim3(256), 0, st, (const T*)g, (const T*)y, (T*)gx, (long)numel);
         else hipLaunchKernelGGL((act_bwd_kernel<T, 2>), grid, dim3(256), 0, st, (const T*)g, (const T*)y, (T*)gx, (long)numel);
@@ -841,8 +853,9 @@ extern "C" int gs_nhwc_act_bwd_to_units(const void* g, const void* z, void* gu, 
 }
 
 extern "C" int gs_tanh_bwd_bwd(const void* gg, const void* g, const void* y, void* out, int64_t numel, int dtype, void* stream) {
-    GS_CHECK_ARG(numel > 0, "tanh_bwd_bwd: bad args");
-    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((tanh_bwd_bwd_kernel<T>), dim3(ew_grid(numel)), dim3(256), 0, as_stream(stream),
+    EwRoute r;
+    if (int e = ew_plan("tanh_bwd_bwd", GS_EW_OP_TANH_BWD_BWD, dtype, numel, 0, 0, 0, &r)) return e;
+    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((tanh_bwd_bwd_kernel<T>), dim3(r.grid_x), dim3(256), 0, as_stream(stream),
                                                 (const T*)gg, (const T*)g, (const T*)y, (T*)out, (long)numel));
     GS_CHECK_LAUNCH();
     return 0;
@@ -868,58 +881,74 @@ __global__ void axpby_dev_kernel(const T* __restrict__ a, const T* __restrict__ 
 
 extern "C" int gs_axpby_dev(const void* a, const void* b, void* out, int64_t numel, const float* coef, int ia, int ib, int dtype, void* stream) {
     GS_CHECK_ARG(numel > 0 && coef && ia >= 0 && ib >= 0, "axpby_dev: bad args");
-    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((axpby_dev_kernel<T>), dim3(ew_grid((numel >> 2) + 4)), dim3(256), 0, as_stream(stream),
+    EwRoute r;
+    if (int e = ew_plan("axpby_dev", GS_EW_OP_AXPBY_DEV, dtype, numel, 0, 0, 0, &r)) return e;
+    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((axpby_dev_kernel<T>), dim3(r.grid_x), dim3(256), 0, as_stream(stream),
                                                 (const T*)a, (const T*)b, (T*)out, (long)numel, coef, ia, ib));
     GS_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int gs_axpby(const void* a, const void* b, void* out, int64_t numel, float ca, float cb, int dtype, void* stream) {
-    GS_CHECK_ARG(numel > 0, "axpby: bad args");
-    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((axpby_kernel<T>), dim3(ew_grid((numel >> 2) + 4)), dim3(256), 0, as_stream(stream),
+    EwRoute r;
+    if (int e = ew_plan("axpby", GS_EW_OP_AXPBY, dtype, numel, 0, 0, 0, &r)) return e;
+    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((axpby_kernel<T>), dim3(r.grid_x), dim3(256), 0, as_stream(stream),
                                                 (const T*)a, (const T*)b, (T*)out, (long)numel, ca, cb));
     GS_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" size_t gs_channel_sum_workspace_bytes(int64_t p, int c) {
-    const int np = channel_sum_parts(p, c);
-    return (size_t)(np + cdiv(np, CS_SLAB)) * c * sizeof(float);
+    EwRoute r;
+    const char* why = "";
+    return elementwise_route(EwCall{GS_EW_OP_CHANNEL_SUM, GS_F32, p, c, 0, 0}, ew_knobs_env(), &r, &why) ? 0 : r.ws_bytes;
 }
 
-extern "C" int gs_channel_sum(const void* g, float* out, int64_t p, int c, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream) {
-    GS_CHECK_ARG(p > 0 && c > 0, "channel_sum: bad args");
+// out (+)= sum_p g[p][c] * act'(y[p][c])   (act = GS_ACT_NONE, y = NULL: the plain sum)
+static int channel_sum_run(const void* g, const void* y, int act, float* out, int64_t p, int c, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream) {
     const bool partials_only = (accumulate & GS_SUM_PARTIALS) != 0;
     accumulate &= 1;
-    if (p <= 64 && c >= 256) {
-        GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((channel_sum_rows_kernel<T>), dim3(cdiv(c, 256)), dim3(256), 0, as_stream(stream), (const T*)g, out, (int)p, c, accumulate));
+    EwRoute r;
+    if (int e = ew_plan("channel_sum", GS_EW_OP_CHANNEL_SUM, dtype, p, c, 0, 0, &r)) return e;
+    if (r.kernel == GS_EW_CHANNEL_SUM_ROWS) {
+#define GS_CSR(ACT) hipLaunchKernelGGL((channel_sum_rows_kernel<T, ACT>), dim3(r.grid_x), dim3(256), 0, as_stream(stream), (const T*)g, (const T*)y, out, (int)p, c, accumulate)
+        GS_DISPATCH_DTYPE(dtype, { if (act == 0) GS_CSR(0); else if (act == 1) GS_CSR(1); else GS_CSR(2); });
+#undef GS_CSR
         GS_CHECK_LAUNCH();
         return 0;
     }
-    const int nparts = channel_sum_parts(p, c);
-    if (ws_bytes < (partials_only ? (size_t)nparts * c * sizeof(float) : gs_channel_sum_workspace_bytes(p, c))) return fail(GS_ERR_WORKSPACE, "channel_sum: workspace too small");
+    const int nparts = r.nparts;
+    if (ws_bytes < (partials_only ? (size_t)nparts * c * sizeof(float) : r.ws_bytes)) return fail(GS_ERR_WORKSPACE, "channel_sum: workspace too small");
     hipStream_t st = as_stream(stream);
     float* part = (float*)ws;
-    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((channel_sum_kernel<T>), dim3(nparts), dim3(256), 0, st, (const T*)g, part, (long)p, c));
+#define GS_CS(ACT) hipLaunchKernelGGL((channel_sum_kernel<T, ACT>), dim3(nparts), dim3(256), 0, st, (const T*)g, (const T*)y, part, (long)p, c)
+    GS_DISPATCH_DTYPE(dtype, { if (act == 0) GS_CS(0); else if (act == 1) GS_CS(1); else GS_CS(2); });
+#undef GS_CS
     GS_CHECK_LAUNCH();
     if (partials_only) return 0;
     return channel_sum_finalize(part, out, nparts, c, accumulate, st);
 }
+extern "C" int gs_channel_sum(const void* g, float* out, int64_t p, int c, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream) {
+    GS_CHECK_ARG(p > 0 && c > 0, "channel_sum: bad args");
+    return channel_sum_run(g, nullptr, GS_ACT_NONE, out, p, c, accumulate, dtype, ws, ws_bytes, stream);
+}
 
-extern "C" int gs_act_bwd(const void* g, const void* y, void* gx, int64_t numel, int act, int dtype, void* stream);
-extern "C" size_t gs_channel_sum_workspace_bytes(int64_t p, int c);
 
 extern "C" int gs_act_bwd_bias(const void* g, const void* y, void* gx, float* gb, int64_t p, int c, int act, int accumulate, int dtype,
                                void* ws, size_t ws_bytes, void* stream) {
     GS_CHECK_ARG(p > 0 && c > 0 && (act == 1 || act == 2), "act_bwd_bias: bad args");
-    if ((c & 3) != 0 || c > 1024 || 256 % (c >> 2) != 0) {  // generic shapes: two passes
-        if (int e = gs_act_bwd(g, y, gx, p * c, act, dtype, stream)) return e;
-        return gs_channel_sum(gx, gb, p, c, accumulate, dtype, ws, ws_bytes, stream);
+    EwRoute r;
+    if (int e = ew_plan("act_bwd_bias", GS_EW_OP_ACT_BWD_BIAS, dtype, p, c, 0, 0, &r)) return e;
+    if (r.two_pass) {
+        // generic shapes: two passes.  The sums are of g * act'(y) as computed in fp32, like the one-pass kernel's, not of the stored gx (bf16:
+        // rounded, 1e-4 .. 4e-3 of the largest sum away); taken first, so that gx may be g itself
+        if (int e = channel_sum_run(g, y, act, gb, p, c, accumulate, dtype, ws, ws_bytes, stream)) return e;
+        return gs_act_bwd(g, y, gx, p * c, act, dtype, stream);
     }
     const bool partials_only = (accumulate & GS_SUM_PARTIALS) != 0;
     accumulate &= 1;
-    const int nparts = channel_sum_parts(p, c);
-    if (ws_bytes < (partials_only ? (size_t)nparts * c * sizeof(float) : gs_channel_sum_workspace_bytes(p, c))) return fail(GS_ERR_WORKSPACE, "act_bwd_bias: workspace too small");
+    const int nparts = r.nparts;
+    if (ws_bytes < (partials_only ? (size_t)nparts * c * sizeof(float) : r.ws_bytes)) return fail(GS_ERR_WORKSPACE, "act_bwd_bias: workspace too small");
     hipStream_t st = as_stream(stream);
     float* part = (float*)ws;
     GS_DISPATCH_DTYPE(dtype, {
@@ -931,43 +960,35 @@ extern "C" int gs_act_bwd_bias(const void* g, const void* y, void* gx, float* gb
     return channel_sum_finalize(part, gb, nparts, c, accumulate, st);
 }
 
-static int pixel_norm_grid(long p, int c, int wn, bool bias_sums = false) {
-    const int E = c % wn == 0 ? wn : 4;
-    const int vecs = c / E, L = vecs < 64 ? vecs : 64, P = vecs / L;
-    const int U = P == 1 ? 2 : 1;
-    const long rows_per_block = 4L * (64 / L) * U;
-    int g = ew_grid((p + rows_per_block - 1) / rows_per_block * 256);
-    if (bias_sums) {   // every block ends with a cross-lane + LDS fold of its channel sums and one partial row: as many trips per block as
-        static const int cap = getenv("GS_PN_BIAS_GRID_CAP") ? atoi(getenv("GS_PN_BIAS_GRID_CAP")) : 1024;   // the plain pass has blocks
-        if (g > cap) g = cap;   // (top level, 32 channels: 61.5 us at 8192 blocks, 50.5 at 1024 -- 42.3 without the sums; scripts/bench_ew.py)
-    }
-    return g;
-}
+// The (E, P, U) a row width gets is the route's; the instantiations below are exactly the ones a call can reach: fp32 E = 4 with P = 1, 2, 4;
+// bf16 E = 8 with P = 1, 2 and E = 4, P = 1 (rows of 4 channels) -- bf16 (8, 4), (4, 2), (4, 4) would need more than 1024 channels.
 template <typename T, int MODE, bool BS = false>
-static void pixel_norm_launch_t(const void* a0, const void* a1, const void* a2, void* out, long p, int c, float eps, int act, int pre, const void* addend,
-                                void* out2, hipStream_t st, float* bsum = nullptr) {
+static void pixel_norm_launch_t(const EwRoute& r, const void* a0, const void* a1, const void* a2, void* out, long p, int c, float eps, int act, int pre,
+                                const void* addend, void* out2, hipStream_t st, float* bsum = nullptr) {
     constexpr int WN = Wide<T>::N;
-    const int E = c % WN == 0 ? WN : 4;
-    const int vecs = c / E, L = vecs < 64 ? vecs : 64, P = vecs / L;   // P in {1, 2, 4}
-    dim3 grid(pixel_norm_grid(p, c, WN, BS));
+    dim3 grid(r.grid_x);
 #define GS_PN(EE, PP, UU)                                                                                                          \
     hipLaunchKernelGGL((pixel_norm_kernel<T, MODE, EE, PP, UU, BS>), grid, dim3(256), 0, st, (const T*)a0, (const T*)a1, (const T*)a2, (T*)out, p, c, eps, \
                        act, pre, (const T*)addend, (T*)out2, bsum)
-    if (E == WN) {
-        if (P == 1) GS_PN(WN, 1, 2); else if (P == 2) GS_PN(WN, 2, 1); else GS_PN(WN, 4, 1);
-    } else {
-        if (P == 1) GS_PN(4, 1, 2); else if (P == 2) GS_PN(4, 2, 1); else GS_PN(4, 4, 1);
+    if (r.E == WN) {
+        if (r.P == 1) GS_PN(WN, 1, 2);
+        else if (r.P == 2) GS_PN(WN, 2, 1);
+        else if constexpr (WN == 4) GS_PN(4, 4, 1);
+    } else if constexpr (WN != 4) {
+        GS_PN(4, 1, 2);
     }
 #undef GS_PN
 }
 static int pixel_norm_launch(int mode, const void* a0, const void* a1, const void* a2, void* out, int64_t p, int c, float eps, int dtype, void* stream, int act = 0,
                              int pre = 0, const void* addend = nullptr, void* out2 = nullptr) {
-    GS_CHECK_ARG(p > 0 && c >= 4 && c <= 1024 && (c & (c - 1)) == 0, "pixel_norm: c=%d must be a power of two in [4,1024]", c);
+    EwRoute r;
+    if (int e = ew_plan("pixel_norm", mode == 0 ? GS_EW_OP_PIXEL_NORM_FWD : (mode == 1 ? GS_EW_OP_PIXEL_NORM_BWD : GS_EW_OP_PIXEL_NORM_BWD_BWD), dtype, p, c, 0, 0, &r))
+        return e;
     hipStream_t st = as_stream(stream);
     GS_DISPATCH_DTYPE(dtype, {
-        if (mode == 0) pixel_norm_launch_t<T, 0>(a0, a1, a2, out, (long)p, c, eps, act, pre, addend, out2, st);
-        else if (mode == 1) pixel_norm_launch_t<T, 1>(a0, a1, a2, out, (long)p, c, eps, act, pre, addend, out2, st);
-        else pixel_norm_launch_t<T, 2>(a0, a1, a2, out, (long)p, c, eps, act, pre, addend, out2, st);
+        if (mode == 0) pixel_norm_launch_t<T, 0>(r, a0, a1, a2, out, (long)p, c, eps, act, pre, addend, out2, st);
+        else if (mode == 1) pixel_norm_launch_t<T, 1>(r, a0, a1, a2, out, (long)p, c, eps, act, pre, addend, out2, st);
+        else pixel_norm_launch_t<T, 2>(r, a0, a1, a2, out, (long)p, c, eps, act, pre, addend, out2, st);
     });
     GS_CHECK_LAUNCH();
     return 0;
@@ -983,34 +1004,33 @@ extern "C" int gs_pixel_norm_bwd_fused(const void* g, const void* x, const void*
 }
 // ... and the per-channel sums of gx on the side (gb (+)= sum over pixels: the bias gradient of the conv block that produced x)
 extern "C" size_t gs_pixel_norm_bwd_bias_workspace_bytes(int64_t p, int c, int dtype) {
-    const int nb = pixel_norm_grid((long)p, c, dtype == GS_F32 ? 4 : 8, true);
-    return (size_t)(nb + cdiv(nb, CS_SLAB)) * c * sizeof(float);
+    EwRoute r;
+    const char* why = "";
+    return elementwise_route(EwCall{GS_EW_OP_PIXEL_NORM_BWD_BIAS, dtype == GS_F32 ? GS_F32 : GS_BF16, p, c, 0, 0}, ew_knobs_env(), &r, &why) ? 0 : r.ws_bytes;
 }
 extern "C" int gs_pixel_norm_bwd_fused_bias(const void* g, const void* x, const void* addend, void* gx, float* gb, int64_t p, int c, float eps, int pre_act,
                                             int post_act, int accumulate, int dtype, void* ws, size_t ws_bytes, void* stream) {
     GS_CHECK_ARG(pn_act_ok(pre_act) && pn_act_ok(post_act), "pixel_norm_bwd_fused_bias: bad activation %d / %d", pre_act, post_act);
-    GS_CHECK_ARG(p > 0 && c >= 4 && c <= 1024 && (c & (c - 1)) == 0 && gb && g && x && gx, "pixel_norm_bwd_fused_bias: bad args (c=%d)", c);
+    GS_CHECK_ARG(gb && g && x && gx, "pixel_norm_bwd_fused_bias: bad args (c=%d)", c);
+    EwRoute r;
+    if (int e = ew_plan("pixel_norm_bwd_fused_bias", GS_EW_OP_PIXEL_NORM_BWD_BIAS, dtype, p, c, 0, 0, &r)) return e;
     const bool partials_only = (accumulate & GS_SUM_PARTIALS) != 0;
     accumulate &= 1;
-    const int nb = pixel_norm_grid((long)p, c, dtype == GS_F32 ? 4 : 8, true);
-    if (ws_bytes < (partials_only ? (size_t)nb * c * sizeof(float) : gs_pixel_norm_bwd_bias_workspace_bytes(p, c, dtype)))
-        return fail(GS_ERR_WORKSPACE, "pixel_norm_bwd_fused_bias: workspace too small");
+    const int nb = r.nparts;
+    if (ws_bytes < (partials_only ? (size_t)nb * c * sizeof(float) : r.ws_bytes)) return fail(GS_ERR_WORKSPACE, "pixel_norm_bwd_fused_bias: workspace too small");
     hipStream_t st = as_stream(stream);
     float* part = (float*)ws;
-    GS_DISPATCH_DTYPE(dtype, (pixel_norm_launch_t<T, 1, true>(g, x, nullptr, gx, (long)p, c, eps, post_act, pre_act, addend, nullptr, st, part)));
+    GS_DISPATCH_DTYPE(dtype, (pixel_norm_launch_t<T, 1, true>(r, g, x, nullptr, gx, (long)p, c, eps, post_act, pre_act, addend, nullptr, st, part)));
     GS_CHECK_LAUNCH();
     if (partials_only) return 0;
     return channel_sum_finalize(part, gb, nb, c, accumulate, st);
 }
 extern "C" int gs_bias_partial_rows(int producer, int64_t p, int c, int dtype) {
-    if (p <= 0 || c <= 0) return 0;
-    const bool act_fast = !((c & 3) != 0 || c > 1024 || 256 % (c >> 2) != 0);   // gs_act_bwd_bias's one-pass shapes
-    switch (producer) {
-        case GS_BIAS_FROM_CHANNEL_SUM: return (p <= 64 && c >= 256) ? 0 : channel_sum_parts(p, c);
-        case GS_BIAS_FROM_ACT_BWD: return (!act_fast && p <= 64 && c >= 256) ? 0 : channel_sum_parts(p, c);
-        case GS_BIAS_FROM_PIXEL_NORM_BWD: return (c >= 4 && c <= 1024 && (c & (c - 1)) == 0) ? pixel_norm_grid((long)p, c, dtype == GS_F32 ? 4 : 8, true) : 0;
-        default: return 0;
-    }
+    const int op = producer == GS_BIAS_FROM_CHANNEL_SUM ? GS_EW_OP_CHANNEL_SUM
+                 : (producer == GS_BIAS_FROM_ACT_BWD ? GS_EW_OP_ACT_BWD_BIAS : (producer == GS_BIAS_FROM_PIXEL_NORM_BWD ? GS_EW_OP_PIXEL_NORM_BWD_BIAS : -1));
+    EwRoute r;
+    const char* why = "";   // (a shape the producer refuses leaves no rows)
+    return elementwise_route(EwCall{op, dtype == GS_F32 ? GS_F32 : GS_BF16, p, c, 0, 0}, ew_knobs_env(), &r, &why) ? 0 : r.nparts;
 }
 extern "C" int gs_pixel_norm_bwd_bwd_fused(const void* gg, const void* g, const void* x, void* out, void* out_g, int64_t p, int c, float eps, int pre_act,
                                            int dtype, void* stream) {
@@ -1021,7 +1041,9 @@ extern "C" int gs_pixel_norm_bwd_bwd_fused(const void* gg, const void* g, const 
 extern "C" int gs_upscale2d(const void* x, void* y, int n, int h, int w, int c, int fy, int fx, float scale, int dtype, void* stream) {
     GS_CHECK_ARG(n > 0 && h > 0 && w > 0 && c > 0 && fy > 0 && fx > 0, "upscale2d: bad args");
     const long total = (long)n * h * fy * w * fx * c;
-    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((upscale_kernel<T>), dim3(ew_grid(total)), dim3(256), 0, as_stream(stream),
+    EwRoute r;
+    if (int e = ew_plan("upscale2d", GS_EW_OP_UPSCALE, dtype, total, c, fy, fx, &r)) return e;
+    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((upscale_kernel<T>), dim3(r.grid_x), dim3(256), 0, as_stream(stream),
                                                 (const T*)x, (T*)y, n, h, w, c, fy, fx, scale));
     GS_CHECK_LAUNCH();
     return 0;
@@ -1030,11 +1052,13 @@ extern "C" int gs_upscale2d(const void* x, void* y, int n, int h, int w, int c, 
 extern "C" int gs_blocksum2d(const void* x, void* y, int n, int h, int w, int c, int fy, int fx, float scale, int dtype, void* stream) {
     GS_CHECK_ARG(n > 0 && c > 0 && fy > 0 && fx > 0 && h % fy == 0 && w % fx == 0, "blocksum2d: bad args");
     const long total = (long)n * (h / fy) * (w / fx) * c;
+    EwRoute r;
+    if (int e = ew_plan("blocksum2d", GS_EW_OP_BLOCKSUM, dtype, total, c, fy, fx, &r)) return e;
     hipStream_t st = as_stream(stream);
-    if (fy * fx >= 32) {
-        GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((blocksum_kernel<T>), dim3(ew_grid(total * 64)), dim3(256), 0, st, (const T*)x, (T*)y, n, h, w, c, fy, fx, scale));
+    if (r.kernel == GS_EW_BLOCKSUM) {
+        GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((blocksum_kernel<T>), dim3(r.grid_x), dim3(256), 0, st, (const T*)x, (T*)y, n, h, w, c, fy, fx, scale));
     } else {
-        GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((blocksum_small_kernel<T>), dim3(ew_grid(total)), dim3(256), 0, st, (const T*)x, (T*)y, n, h, w, c, fy, fx, scale));
+        GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((blocksum_small_kernel<T>), dim3(r.grid_x), dim3(256), 0, st, (const T*)x, (T*)y, n, h, w, c, fy, fx, scale));
     }
     GS_CHECK_LAUNCH();
     return 0;
@@ -1043,10 +1067,11 @@ extern "C" int gs_blocksum2d(const void* x, void* y, int n, int h, int w, int c,
 extern "C" size_t gs_sumsq_rows_workspace_bytes(int rows) { return (size_t)(rows > 0 ? rows : 0) * SSQ_CHUNKS * sizeof(float); }
 
 extern "C" int gs_sumsq_rows(const void* x, float* out, int rows, int64_t cols, int dtype, void* ws, size_t ws_bytes, void* stream) {
-    GS_CHECK_ARG(rows > 0 && cols > 0, "sumsq_rows: bad args");
-    if (ws_bytes < gs_sumsq_rows_workspace_bytes(rows)) return fail(GS_ERR_WORKSPACE, "sumsq_rows: workspace too small");
+    EwRoute r;
+    if (int e = ew_plan("sumsq_rows", GS_EW_OP_SUMSQ_ROWS, dtype, cols, 0, rows, 0, &r)) return e;
+    if (ws_bytes < r.ws_bytes) return fail(GS_ERR_WORKSPACE, "sumsq_rows: workspace too small");
     float* part = (float*)ws;
-    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((sumsq_rows_kernel<T>), dim3(SSQ_CHUNKS, rows), dim3(256), 0, as_stream(stream), (const T*)x, part, (long)cols));
+    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((sumsq_rows_kernel<T>), dim3(r.grid_x, r.grid_y), dim3(256), 0, as_stream(stream), (const T*)x, part, (long)cols));
     GS_CHECK_LAUNCH();
     hipLaunchKernelGGL(sumsq_rows_final_kernel, dim3(rows), dim3(64), 0, as_stream(stream), part, out);
     GS_CHECK_LAUNCH();
@@ -1054,9 +1079,9 @@ extern "C" int gs_sumsq_rows(const void* x, float* out, int rows, int64_t cols, 
 }
 
 extern "C" int gs_row_scale(const void* x, const float* s, float alpha, void* out, int rows, int64_t cols, int dtype, void* stream) {
-    GS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0, "row_scale: cols must be a multiple of 4");
-    const long nvec = ((long)rows * cols) >> 2;
-    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((row_scale_kernel<T>), dim3(ew_grid(nvec)), dim3(256), 0, as_stream(stream), (const T*)x, s, (T*)out, rows, (long)cols, alpha));
+    EwRoute r;
+    if (int e = ew_plan("row_scale", GS_EW_OP_ROW_SCALE, dtype, cols, 0, rows, 0, &r)) return e;
+    GS_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((row_scale_kernel<T>), dim3(r.grid_x), dim3(256), 0, as_stream(stream), (const T*)x, s, (T*)out, rows, (long)cols, alpha));
     GS_CHECK_LAUNCH();
     return 0;
 }
@@ -1145,5 +1170,20 @@ extern "C" int gs_swap_f32(float* a, float* b, int64_t numel, void* stream) {
     hipLaunchKernelGGL(swap_kernel, dim3(ew_grid((numel >> 2) + 4)), dim3(256), 0, as_stream(stream), reinterpret_cast<unsigned*>(a),
                        reinterpret_cast<unsigned*>(b), (long)numel);
     GS_CHECK_LAUNCH();
+    return 0;
+}
+
+// host-only: the route of a call, asked without running it (include/gansynth_hip.h)
+extern "C" int gs_elementwise_route(int op, int dtype, int64_t p, int c, int fy, int fx, int ew_grid_cap_or_minus1, int pn_bias_grid_cap_or_minus1, int* out) {
+    GS_CHECK_ARG(out, "elementwise_route: no output");
+    EwKnobs k = ew_knobs_env();
+    if (ew_grid_cap_or_minus1 != -1) k.ew_cap = ew_grid_cap_or_minus1;
+    if (pn_bias_grid_cap_or_minus1 != -1) k.pn_bias_cap = pn_bias_grid_cap_or_minus1;
+    GS_CHECK_ARG(k.ew_cap > 0 && k.pn_bias_cap > 0, "elementwise_route: a grid cap must be positive");
+    EwRoute r;
+    const char* why = "";
+    if (int e = elementwise_route(EwCall{op, dtype, (long)p, c, fy, fx}, k, &r, &why)) return fail(e, "elementwise_route: %s", why);
+    static_assert(sizeof(EwRoute) == GS_EW_ROUTE_INTS * sizeof(int), "EwRoute is the ints the query reports");
+    memcpy(out, &r, sizeof(r));
     return 0;
 }

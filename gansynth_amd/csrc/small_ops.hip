@@ -1,6 +1,7 @@
 // Small-tensor kernels of the PGGAN hot path: embedding (ops.py:204-218) and minibatch stddev (ops.py:336-348) with their first/second-order
 // gradients, and the GAN losses (models.py:39-65).  All tiny; none is MFMA work.  (The dense layers: dense.hip.)
-#include "gs_common.h"
+// (Which batch-stddev instantiation a shape runs -- VN -- and its blocks: elementwise_route.h, the route the elementwise kernels share.)
+#include "elementwise_route.h"
 
 namespace gs {
 
@@ -298,30 +299,33 @@ extern "C" int gs_embedding_bwd(const int64_t* idx, const void* gy, float* gw, i
 }
 
 extern "C" int gs_batch_stddev_fwd(const void* x, void* y, int b, int hw, int c, float eps, int dtype, void* stream) {
-    GS_CHECK_ARG(b > 0 && b % 4 == 0 && hw > 0 && c > 0, "batch_stddev: batch %d must be a positive multiple of 4 (ops.py:341)", b);
+    EwRoute r;
+    if (int e = ew_plan("batch_stddev_fwd", GS_EW_OP_BATCH_STDDEV_FWD, dtype, hw, c, b, 0, &r)) return e;
     GS_DISPATCH_DTYPE(dtype, {
-        if (((long)hw * c) % Wide<T>::N == 0) hipLaunchKernelGGL((batch_stddev_fwd_kernel<T, Wide<T>::N>), dim3(b / 4), dim3(BS_NT), 0, as_stream(stream), (const T*)x, (T*)y, b / 4, hw, c, eps);
-        else hipLaunchKernelGGL((batch_stddev_fwd_kernel<T, 1>), dim3(b / 4), dim3(BS_NT), 0, as_stream(stream), (const T*)x, (T*)y, b / 4, hw, c, eps);
+        if (r.E == Wide<T>::N) hipLaunchKernelGGL((batch_stddev_fwd_kernel<T, Wide<T>::N>), dim3(r.grid_x), dim3(BS_NT), 0, as_stream(stream), (const T*)x, (T*)y, b / 4, hw, c, eps);
+        else hipLaunchKernelGGL((batch_stddev_fwd_kernel<T, 1>), dim3(r.grid_x), dim3(BS_NT), 0, as_stream(stream), (const T*)x, (T*)y, b / 4, hw, c, eps);
     });
     GS_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int gs_batch_stddev_bwd(const void* gy, const void* x, const void* addend, void* gx, int b, int hw, int c, float eps, int dtype, void* stream) {
-    GS_CHECK_ARG(b > 0 && b % 4 == 0 && hw > 0 && c > 0, "batch_stddev_bwd: bad args");
+    EwRoute r;
+    if (int e = ew_plan("batch_stddev_bwd", GS_EW_OP_BATCH_STDDEV_BWD, dtype, hw, c, b, 0, &r)) return e;
     GS_DISPATCH_DTYPE(dtype, {
-        if (((long)hw * c) % Wide<T>::N == 0) hipLaunchKernelGGL((batch_stddev_bwd_kernel<T, Wide<T>::N>), dim3(b / 4), dim3(BS_NT), 0, as_stream(stream), (const T*)gy, (const T*)x, (const T*)addend, (T*)gx, b / 4, hw, c, eps);
-        else hipLaunchKernelGGL((batch_stddev_bwd_kernel<T, 1>), dim3(b / 4), dim3(BS_NT), 0, as_stream(stream), (const T*)gy, (const T*)x, (const T*)addend, (T*)gx, b / 4, hw, c, eps);
+        if (r.E == Wide<T>::N) hipLaunchKernelGGL((batch_stddev_bwd_kernel<T, Wide<T>::N>), dim3(r.grid_x), dim3(BS_NT), 0, as_stream(stream), (const T*)gy, (const T*)x, (const T*)addend, (T*)gx, b / 4, hw, c, eps);
+        else hipLaunchKernelGGL((batch_stddev_bwd_kernel<T, 1>), dim3(r.grid_x), dim3(BS_NT), 0, as_stream(stream), (const T*)gy, (const T*)x, (const T*)addend, (T*)gx, b / 4, hw, c, eps);
     });
     GS_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int gs_batch_stddev_bwd_bwd(const void* ggx, const void* gy, const void* x, void* ggy, void* gx2, int b, int hw, int c, float eps, int dtype, void* stream) {
-    GS_CHECK_ARG(b > 0 && b % 4 == 0 && hw > 0 && c > 0, "batch_stddev_bwd_bwd: bad args");
+    EwRoute r;
+    if (int e = ew_plan("batch_stddev_bwd_bwd", GS_EW_OP_BATCH_STDDEV_BWD_BWD, dtype, hw, c, b, 0, &r)) return e;
     GS_DISPATCH_DTYPE(dtype, {
-        if (((long)hw * c) % Wide<T>::N == 0) hipLaunchKernelGGL((batch_stddev_bwd_bwd_kernel<T, Wide<T>::N>), dim3(b / 4), dim3(BS_NT), 0, as_stream(stream), (const T*)ggx, (const T*)gy, (const T*)x, (T*)ggy, (T*)gx2, b / 4, hw, c, eps);
-        else hipLaunchKernelGGL((batch_stddev_bwd_bwd_kernel<T, 1>), dim3(b / 4), dim3(BS_NT), 0, as_stream(stream), (const T*)ggx, (const T*)gy, (const T*)x, (T*)ggy, (T*)gx2, b / 4, hw, c, eps);
+        if (r.E == Wide<T>::N) hipLaunchKernelGGL((batch_stddev_bwd_bwd_kernel<T, Wide<T>::N>), dim3(r.grid_x), dim3(BS_NT), 0, as_stream(stream), (const T*)ggx, (const T*)gy, (const T*)x, (T*)ggy, (T*)gx2, b / 4, hw, c, eps);
+        else hipLaunchKernelGGL((batch_stddev_bwd_bwd_kernel<T, 1>), dim3(r.grid_x), dim3(BS_NT), 0, as_stream(stream), (const T*)ggx, (const T*)gy, (const T*)x, (T*)ggy, (T*)gx2, b / 4, hw, c, eps);
     });
     GS_CHECK_LAUNCH();
     return 0;

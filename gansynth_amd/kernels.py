@@ -153,7 +153,22 @@ class HipKernels(object):
     # --------------------------------------------------------- prepared-weight workspaces
     def register_param_buffer(self, flat):
         """Weights living in `flat` may keep their kernel operand (re-laid, storage dtype) between calls."""
-        self._param_ranges.append([flat.data_ptr(), flat.numel() * flat.element_size(), 0])
+        lo, nbytes = flat.data_ptr(), flat.numel() * flat.element_size()
+        # A range that overlaps the new buffer belongs to a buffer that no longer exists (an earlier model of this process: the allocator has
+        # handed its memory out again).  Left in the list it would be the FIRST match of a weight of the new buffer that lies inside it, while
+        # invalidate_weights(flat) only reaches the ranges that hold the new buffer's first byte: after an optimizer step that weight's
+        # operand would pass for fresh and the layer would run one update behind its parameters.  The dead range goes, with the operands
+        # and slices that hang on it (kept alive, like the retired tables, for a captured graph that may still replay them).
+        dead = [r for r in self._param_ranges if r[0] < lo + nbytes and lo < r[0] + r[1]]
+        if dead:
+            self._param_ranges = [r for r in self._param_ranges if not any(r is d for d in dead)]
+            for key in [k for k, e in self._wcache.items() if any(e[4] is d for d in dead)]:
+                self._retired_tables.append(self._wcache.pop(key))
+            for key in [k for k in self._derived if lo <= k[0] < lo + nbytes]:
+                self._retired_tables.append(self._derived.pop(key))
+            self._retired_tables.extend(self._prep_tables.values())
+            self._prep_tables.clear()
+        self._param_ranges.append([lo, nbytes, 0])
 
     def invalidate_weights(self, flat=None):
         """Parameter values changed (all registered buffers, or only the one `flat` lives in)."""

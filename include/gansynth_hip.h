@@ -323,7 +323,8 @@ int gs_act_bwd(const void* g, const void* y, void* gx, int64_t numel, int act, i
 int gs_units_bias_act_to_nhwc(const void* y, const float* bias, const void* mask, void* z, int n, int c, int hw, int act, int dtype, void* stream);
 int gs_nhwc_act_bwd_to_units(const void* g, const void* z, void* gu, int n, int c, int hw, int act, int dtype, void* stream);
 
-/* act_bwd and the bias gradient in one pass: gx = g*act'(y), gb[c] = sum_p gx[p][c] (ws: gs_channel_sum_workspace_bytes) */
+/* act_bwd and the bias gradient in one pass: gx = g*act'(y), gb[c] = sum_p gx[p][c] (ws: gs_channel_sum_workspace_bytes).  The sums are taken
+ * over the fp32 values as computed, before a bf16 gx is rounded -- also for the shapes that take two passes (c % 4 != 0, c > 1024, 256 % (c/4) != 0). */
 int gs_act_bwd_bias(const void* g, const void* y, void* gx, float* gb, int64_t p, int c, int act, int accumulate, int dtype,
                     void* ws, size_t ws_bytes, void* stream);
 int gs_tanh_bwd_bwd(const void* gg, const void* g, const void* y, void* out, int64_t numel, int dtype, void* stream);
@@ -397,6 +398,39 @@ int gs_axpby_dev(const void* a, const void* b, void* out, int64_t numel, const f
 size_t gs_sumsq_rows_workspace_bytes(int rows);
 int gs_sumsq_rows(const void* x, float* out, int rows, int64_t cols, int dtype, void* ws, size_t ws_bytes, void* stream);
 int gs_row_scale(const void* x, const float* s, float alpha, void* out, int rows, int64_t cols, int dtype, void* stream);   /* out[r][:] = alpha s[r] x[r][:] */
+
+/* Which kernel an elementwise / row-reduction call above would run, asked without running it: host arithmetic on the very route the entry
+ * points, the two workspace functions and gs_bias_partial_rows read (csrc/elementwise_route.h), no launch, no device.  The shape words by op:
+ *    BIAS_ACT, CHANNEL_SUM, ACT_BWD_BIAS, PIXEL_NORM_*    p rows of c channels
+ *    ACT_BWD, TANH_BWD_BWD, AXPBY, AXPBY_DEV              p = numel
+ *    UPSCALE, BLOCKSUM                                    p = OUTPUT elements, fy x fx the factors
+ *    ROW_SCALE, SUMSQ_ROWS                                p = cols, fy = rows
+ *    BATCH_STDDEV_*                                       p = hw, c, fy = batch
+ * The two grid caps (GS_EW_GRID_CAP, GS_PN_BIAS_GRID_CAP) as positive values, -1 for the process's environment.  A call its entry point refuses
+ * is refused here with the same code.  out[GS_EW_ROUTE_INTS] =
+ *    0 kernel             GS_EW_* below, one per kernel template
+ *    1 path               GS_EW_PATH_*: the branch inside channel_sum_kernel (colour / quads / generic) and sumsq_rows_kernel (vector / scalar
+ *                         rows: rows > 1 with cols % 4 != 0 would break the alignment of the 4-element loads and are read element by element)
+ *    2 E                  elements per lane and access: 4, 8 (16 bytes of bf16: pixel norm, stddev VN), 1 scalar
+ *    3 P, 4 U, 5 L        pixel norm: passes per row, row groups per trip, lanes per row
+ *    6 rows               pixel norm: rows per wave; channel_sum / act_bwd_sum: row lanes per block
+ *    7 grid x, 8 grid y   blocks
+ *    9 trips              loop trips of the busiest thread (channel sums: rows a row lane visits)
+ *   10 tail               a sub-vector tail runs (act_bwd, axpby, sumsq_rows) / the last trip is partial (blocksum wave, stddev, channel_sum rows)
+ *   11 nparts             partial rows left for the fold = gs_bias_partial_rows; 12 levels: finalize launches that follow (0, 1, 2)
+ *   13 per                sumsq_rows: 4-element vectors per chunk
+ *   14 two_pass           ACT_BWD_BIAS: the channel sum this route describes, over g * act'(y) as computed, then a gs_act_bwd launch over p * c elements
+ *   15 reserved; 16, 17 ws_bytes: what the op's workspace function answers, low word first */
+enum { GS_EW_OP_BIAS_ACT = 0, GS_EW_OP_ACT_BWD = 1, GS_EW_OP_TANH_BWD_BWD = 2, GS_EW_OP_AXPBY = 3, GS_EW_OP_AXPBY_DEV = 4, GS_EW_OP_UPSCALE = 5,
+       GS_EW_OP_ROW_SCALE = 6, GS_EW_OP_CHANNEL_SUM = 7, GS_EW_OP_ACT_BWD_BIAS = 8, GS_EW_OP_PIXEL_NORM_FWD = 9, GS_EW_OP_PIXEL_NORM_BWD = 10,
+       GS_EW_OP_PIXEL_NORM_BWD_BIAS = 11, GS_EW_OP_PIXEL_NORM_BWD_BWD = 12, GS_EW_OP_BLOCKSUM = 13, GS_EW_OP_SUMSQ_ROWS = 14,
+       GS_EW_OP_BATCH_STDDEV_FWD = 15, GS_EW_OP_BATCH_STDDEV_BWD = 16, GS_EW_OP_BATCH_STDDEV_BWD_BWD = 17 };
+enum { GS_EW_BIAS_ACT = 0, GS_EW_BIAS_ACT_SCALAR = 1, GS_EW_ACT_BWD = 2, GS_EW_TANH_BWD_BWD = 3, GS_EW_AXPBY = 4, GS_EW_AXPBY_DEV = 5, GS_EW_UPSCALE = 6,
+       GS_EW_ROW_SCALE = 7, GS_EW_CHANNEL_SUM = 8, GS_EW_CHANNEL_SUM_ROWS = 9, GS_EW_ACT_BWD_SUM = 10, GS_EW_PIXEL_NORM = 11, GS_EW_BLOCKSUM = 12,
+       GS_EW_BLOCKSUM_SMALL = 13, GS_EW_SUMSQ_ROWS = 14, GS_EW_BATCH_STDDEV_FWD = 15, GS_EW_BATCH_STDDEV_BWD = 16, GS_EW_BATCH_STDDEV_BWD_BWD = 17 };
+enum { GS_EW_PATH_NONE = 0, GS_EW_PATH_COLOUR = 1, GS_EW_PATH_QUADS = 2, GS_EW_PATH_GENERIC = 3, GS_EW_PATH_VECTOR = 4, GS_EW_PATH_SCALAR = 5 };
+#define GS_EW_ROUTE_INTS 18
+int gs_elementwise_route(int op, int dtype, int64_t p, int c, int fy, int fx, int ew_grid_cap_or_minus1, int pn_bias_grid_cap_or_minus1, int* out);
 
 /* The two GAN losses (models.py:39-65) with their gradients, one launch each.  logits / labels [n][c] in the activation dtype,
  * labels one-hot (real_logit_i = sum_c logits[i][c] * labels[i][c] = tf.gather_nd(logits, tf.where(labels))):

@@ -48,7 +48,9 @@ def close(got, ref, rel=1e-3, name=""):
 # holds EVERY compiled kernel to a float64 reference at shapes it finds through that chooser.  The same for the weight gradients: which of the 28
 # kernels takes a shape is gs_conv_wgrad_plan's answer, and tests/test_wgrad_cover_gpu.py holds every one of them, every trip of the slice folds and
 # every kind of stream-K cut to a float64 reference.  The dense tests below are layer shapes as well: which of the 36 dense kernels a shape runs is
-# gs_dense_route's answer, and tests/test_dense_cover_gpu.py holds every one of them to a float64 reference.
+# gs_dense_route's answer, and tests/test_dense_cover_gpu.py holds every one of them to a float64 reference.  The elementwise, reduction and
+# batch-stddev tests below run a few fp32 shapes each: which kernel, path and template constants a shape gets is gs_elementwise_route's answer, and
+# tests/test_elementwise_cover_gpu.py (cases: tests/elementwise_cover.py) holds every instantiation and path, in both dtypes, to a float64 reference.
 CONV_CASES = [
     (2, 32, 32, 8, 128, 3, 1),    # 32 -> 32 at width >= 64: the resident 32-channel tile (top-level shape class)
     (2, 32, 32, 4, 32, 3, 1),
@@ -409,6 +411,25 @@ def test_prepared_weight_operand_cache(K, E):
     with torch.no_grad():
         w.mul_(0.5)
     close(K.conv2d_fwd(dev(x), w, 3, 1, 0.1), E.conv2d_fwd(x, w.cpu(), 3, 1, 0.1), name="after an in-place torch update")
+
+
+def test_prepared_weight_operand_behind_a_dead_overlapping_buffer(K, E):
+    """The memory of a registered buffer that no longer exists, handed out again to a new one that starts in front of it (a second model of
+    the process): a weight of the new buffer that lies inside the dead range still sees the new buffer's optimizer step -- its operand is
+    rebuilt, the layer does not run one update behind its parameters."""
+    pool = torch.randn(64 + 9 * 32 * 32 + 64, device="cuda")
+    K.register_param_buffer(pool[64:])            # the earlier buffer: it starts behind the new one's first byte
+    w = pool[64:64 + 9 * 32 * 32].view(3, 3, 32, 32)
+    x = rnd(2, 32, 8, 64, seed=1)
+    close(K.conv2d_fwd(dev(x), w, 3, 1, 0.1), E.conv2d_fwd(x, w.cpu(), 3, 1, 0.1), name="the earlier buffer's operand")
+    K.register_param_buffer(pool)                 # the new buffer over the same memory, then what models._build does
+    K.invalidate_weights()
+    ref1 = E.conv2d_fwd(x, w.cpu(), 3, 1, 0.1)
+    close(K.conv2d_fwd(dev(x), w, 3, 1, 0.1), ref1, name="the new buffer's operand")
+    K.adam_tf_step(pool, torch.ones_like(pool), torch.zeros_like(pool), torch.zeros_like(pool), 0.5, 0.0, 0.99, 1e-8, 1.0)
+    ref2 = E.conv2d_fwd(x, w.cpu(), 3, 1, 0.1)
+    assert float((ref2 - ref1).abs().max()) > 1e-3
+    close(K.conv2d_fwd(dev(x), w, 3, 1, 0.1), ref2, name="after the new buffer's optimizer step")
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
