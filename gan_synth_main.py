@@ -19,6 +19,10 @@ device (GANSynth.synthesize).  It needs no dataset:
 
     python gan_synth_main.py --synthesize score.mid --model_dir gan_synth_model --output score.wav
 
+`--output_rate HZ` (not in the reference; default: the model's 16000) writes the files of `--synthesize` and `--generate` at another
+sample rate, e.g. 44100 or 48000: resampled on the device, and for `--synthesize` peak-normalised and quantised THERE (GANSynth.synthesize
+with sample_rate, DESIGN.md "Output rates").
+
 `--pack_bank` / `--bank` (not in the reference): the notes packed once into one file (on any machine, no GPU needed), then held on the
 device and drawn there, batch for batch what `--filenames` yields (gansynth_amd/bank.py, DESIGN.md "Resident notes"):
 
@@ -53,6 +57,8 @@ parser.add_argument("--synthesize", type=str, default=None, metavar="PATH", help
 parser.add_argument("--output", type=str, default="synthesized.wav", help="the WAV file --synthesize writes")
 parser.add_argument("--seconds_per_instrument", type=float, default=6.0, help="--synthesize: seconds between two latent anchors")
 parser.add_argument("--release_seconds", type=float, default=1.0, help="--synthesize: length of a note's linear release")
+parser.add_argument("--output_rate", type=int, default=None, metavar="HZ",
+                    help="--synthesize, --generate: the sample rate of the files written (default: the model's rate), resampled on the device")
 parser.add_argument("--seed", type=int, default=0, help="--synthesize: seed of the latent anchors (a generator of their own)")
 parser.add_argument("--generator_ema_decay", type=float, default=0.0,
                     help="keep an exponential moving average of the generator's weights with this decay (0.0: off; progressive GAN uses 0.999)")
@@ -77,13 +83,14 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     info = {}
     _, pcm = model.synthesize(args.synthesize, model_dir=args.model_dir if restore else None, seed=args.seed,
                               seconds_per_instrument=args.seconds_per_instrument, release_seconds=args.release_seconds,
-                              want_pcm=True, info=info, pitches=pitches, batch_size=args.batch_size, weights=args.weights)
+                              want_pcm=True, info=info, pitches=pitches, batch_size=args.batch_size, weights=args.weights,
+                              sample_rate=getattr(args, "output_rate", None))
     if restore:
         log(f"restored {model.restored_from}")
     rate = int(model.spectral_params["sample_rate"])
-    wavfile.write(args.output, rate=rate, data=pcm.cpu().numpy())
+    wavfile.write(args.output, rate=info["sample_rate"], data=pcm.cpu().numpy())
     log(f"{len(info['notes'])} notes kept, {info['dropped']} dropped, {info['total_samples'] / rate:.3f} seconds, "
-        f"peak {info['peak']:.4f}: written to {args.output}")
+        f"peak {info['peak']:.4f}: written to {args.output}" + (f" at {info['sample_rate']} Hz" if info["sample_rate"] != rate else ""))
     return info
 
 
@@ -207,8 +214,8 @@ def main(args):
                 if path is None and from_file:
                     raise SystemExit(f"--weights average: {args.model_dir} holds no checkpoint to take the averaged generator from")
                 print(f"restored {path}" if path else "no checkpoint found: generating from the initial weights")
-            for waveform in model.generate(latents, labels, weights=args.weights).float().cpu().numpy():
-                wavfile.write(f"samples/{num_waveforms}.wav", rate=16000, data=waveform)
+            for waveform in model.generate(latents, labels, weights=args.weights, sample_rate=args.output_rate).float().cpu().numpy():
+                wavfile.write(f"samples/{num_waveforms}.wav", rate=args.output_rate or 16000, data=waveform)
                 num_waveforms += 1
             batches += 1
         print(f"{num_waveforms} waveforms are generated in `samples` directory")

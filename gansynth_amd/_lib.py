@@ -52,6 +52,15 @@ class GsSpectralRoute(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class GsResample(ctypes.Structure):
+    """include/gansynth_hip.h: the design of one rate conversion (gs_resample_design fills it)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("rate_in", "rate_out", "up", "down", "taps", "zeros")]
+
+
+R = POINTER(GsResample)
+RESAMPLE_TILE = 512   # GS_RESAMPLE_TILE: output samples per block of gs_resample's filter
+
+
 SPEC_FWD_GENERIC, SPEC_FWD_WAVE = 0, 1                                                                        # GS_SPEC_FWD_*
 SPEC_GEMM_NONE, SPEC_GEMM_F32_64, SPEC_GEMM_F32_128, SPEC_GEMM_SPLIT_ALL, SPEC_GEMM_SPLIT_TWO, SPEC_GEMM_WIDE_256 = range(6)   # GS_SPEC_GEMM_*
 SPEC_ISTFT_NONE, SPEC_ISTFT_WAVE_OLA, SPEC_ISTFT_WAVE_FRAMES, SPEC_ISTFT_BLOCK_FFT = range(4)                # GS_SPEC_ISTFT_*
@@ -177,6 +186,13 @@ SIGNATURES = {
     "gs_note_mix_workspace_bytes": (Z, [L]),
     "gs_note_mix": (I, [P, I, L, L, P, I, L, I, P, P, P, P, Z, P]),
     "gs_bank_gather": (I, [P, L, L, L, P, P, L, L, I, I, P, P, P]),
+    # R = POINTER(GsResample), the design of one (rate_in, rate_out)
+    "gs_resample_design": (I, [I, I, R]),
+    "gs_resample_out_len": (L, [R, L]),
+    "gs_resample_table_bytes": (Z, [R, I]),
+    "gs_resample_table": (I, [R, I, P]),
+    "gs_resample_workspace_bytes": (Z, [R, I, L]),
+    "gs_resample": (I, [R, P, P, I, L, L, I, P, P, P, P, Z, P]),
 }
 
 WGRAD_MAX_SOURCES = 4   # GS_WGRAD_MAX_SOURCES

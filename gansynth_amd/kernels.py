@@ -149,6 +149,7 @@ class HipKernels(object):
         self._complete = None     # (pred, callback, expected): see complete_rule
         self.ema_steps = 0        # calls of ema_step / ema_step_dev so far (tests: the averaged generator took the HIP path)
         self.ema_steps_dev = 0
+        self._resample = {}       # (rate_in, rate_out, device index) -> (GsResample, device table): resample_design
 
     # --------------------------------------------------------- prepared-weight workspaces
     def register_param_buffer(self, flat):
@@ -1407,6 +1408,43 @@ class HipKernels(object):
                                            None if waves is None else waves.data_ptr(), labels.data_ptr(), _stream()), "gs_bank_gather")
         return waves, labels
 
+    def resample_design(self, rate_in, rate_out, device):
+        """The design of rate_in -> rate_out and its table on `device` (in gs_resample's layout), built and uploaded once per
+        (rate_in, rate_out, device): -> (GsResample, table tensor)."""
+        device = torch.device(device)
+        key = (int(rate_in), int(rate_out), device.index if device.index is not None else torch.cuda.current_device())
+        if key not in self._resample:
+            design = _lib.GsResample()
+            _lib.check(self.lib.gs_resample_design(key[0], key[1], ctypes.byref(design)), "gs_resample_design")
+            host = np.empty(self.lib.gs_resample_table_bytes(ctypes.byref(design), 1) // 4, dtype=np.float32)
+            _lib.check(self.lib.gs_resample_table(ctypes.byref(design), 1, host.ctypes.data), "gs_resample_table")
+            self._resample[key] = (design, torch.from_numpy(host).to(device))
+        return self._resample[key]
+
+    def resample(self, x, rate_in, rate_out, normalize=False, want_pcm=False):
+        """gs_resample (include/gansynth_hip.h): the rows of x -- [rows, n] or [n] fp32 on the device, any row stride -- from rate_in to
+        rate_out.  -> (out [rows, n_out] fp32, pcm [rows, n_out] int16 or None, peak [rows] fp32 = max |y| per row before any scaling);
+        a row of out is divided by its peak when `normalize` and that peak > 1."""
+        if x.dim() not in (1, 2) or x.dtype != torch.float32 or not x.is_cuda:
+            raise ValueError(f"resample: x must be [rows, n] or [n] fp32 on the HIP device (got {tuple(x.shape)} {x.dtype} on {x.device})")
+        if x.dim() == 1:
+            x = x[None]
+        rows, n_in = int(x.shape[0]), int(x.shape[1])
+        if x.stride(1) != 1 or (rows > 1 and x.stride(0) < n_in):
+            x = x.contiguous()
+        design, table = self.resample_design(rate_in, rate_out, x.device)
+        n_out = int(self.lib.gs_resample_out_len(ctypes.byref(design), n_in))
+        if n_out <= 0:
+            _lib.check(n_out, "gs_resample_out_len")
+        out = torch.empty((rows, n_out), dtype=torch.float32, device=x.device)
+        pcm = torch.empty((rows, n_out), dtype=torch.int16, device=x.device) if want_pcm else None
+        peak = torch.empty((rows,), dtype=torch.float32, device=x.device)
+        ws = _ws(self.lib.gs_resample_workspace_bytes(ctypes.byref(design), rows, n_in), x.device)
+        _lib.check(self.lib.gs_resample(ctypes.byref(design), table.data_ptr(), x.data_ptr(), rows, n_in, int(x.stride(0)) if rows > 1 else n_in,
+                                        1 if normalize else 0, out.data_ptr(), None if pcm is None else pcm.data_ptr(), peak.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _stream()), "gs_resample")
+        return out, pcm, peak
+
     def account(self):
         """bench.py: `with K.account() as calls:` lists every kernel-layer call made inside as (method, argument dict, bytes read,
         bytes written) -- the algorithmic traffic of SURVEY.md 8(d): every tensor argument read once, every result written once
@@ -1442,7 +1480,7 @@ class HipKernels(object):
 class _Accounting(object):
     SKIP = ("account", "prof_enable", "prof_roofline", "prof_records", "prof_collect", "register_param_buffer", "invalidate_weights", "early_flush_rule",
             "derived_slice", "defer_wgrad_reductions", "wgrad_slice_target_ok", "drop_deferred", "dense_nhwc_ok", "norm_bwd_bias_ok",
-            "fwd_pnbwdbwd_is_fused", "bwd_data_pnbwd_is_fused", "conv2d_fwd_workspace")
+            "fwd_pnbwdbwd_is_fused", "bwd_data_pnbwd_is_fused", "conv2d_fwd_workspace", "resample_design")
 
     def __init__(self, K):
         self.K, self.calls, self.depth, self.names = K, [], 0, []

@@ -873,12 +873,15 @@ class GANSynth(Iterations, DataParallel, Capture):
         `weights` (keyword, both forms): "live" -- the weights as the last Adam step left them -- or "average": the averaged generator
         (averaged_generator(); the checkpoint is restored first, and a model built without generator_average_decay takes the averages
         from it: ValueError when there is nothing to take them from).  Data parallel: as every reader of the weights it joins the pending
-        update first -- a collective when `collective_pending()`."""
+        update first -- a collective when `collective_pending()`.
+        `sample_rate` (keyword, both forms): None or the model's own rate -- the waveforms as generated; another rate -- every row
+        resampled to it on the device (spectral_ops.resample: [B, ceil(waveform_length * sample_rate / model rate)]), not normalised:
+        the reference writes raw floats."""
         if "model_dir" in kwargs or (args and (args[0] is None or isinstance(args[0], (str, bytes)) or hasattr(args[0], "__fspath__"))):
             return self._generate_from(*args, **kwargs)
         return self._generate_batch(*args, **kwargs)
 
-    def _generate_from(self, model_dir, config=None, weights="live"):
+    def _generate_from(self, model_dir, config=None, weights="live", sample_rate=None):
         del config
         restored = False
         while True:
@@ -894,23 +897,26 @@ class GANSynth(Iterations, DataParallel, Capture):
                 restored = True
                 self.restored_from = self._restore_for(model_dir, weights)
             # (the swap there and back around EVERY batch: between two yields the caller finds the model as it always is)
-            yield self._generate_batch(latents, labels, weights=weights).float().cpu().numpy()
+            yield self._generate_batch(latents, labels, weights=weights, sample_rate=sample_rate).float().cpu().numpy()
 
-    def _generate_batch(self, latents, labels, weights="live"):
+    def _generate_batch(self, latents, labels, weights="live", sample_rate=None):
         """models.py:22-31 (`fake_waveforms`): fake waveforms for a batch."""
         if weights not in ("live", "average"):
             raise ValueError(f"weights must be 'live' or 'average' (got {weights!r})")
         if weights == "average" and not self._average_in:
             with self.averaged_generator():
-                return self._generate_batch(latents, labels)
+                return self._generate_batch(latents, labels, sample_rate=sample_rate)
         self._join_updates()
         with torch.no_grad():
             images = self.generator(latents.to(self.dtype), labels.to(self.dtype))
-        return spectral_ops.convert_images_to_waveform(images, **self.spectral_params)
+        waves = spectral_ops.convert_images_to_waveform(images, **self.spectral_params)
+        if sample_rate is None:
+            return waves
+        return spectral_ops.resample(waves, self.spectral_params["sample_rate"], sample_rate)
 
     # --------------------------------------------------------------------------------------- note sequences
     def synthesize(self, notes, model_dir=None, latents=None, seed=0, seconds_per_instrument=6.0, release_seconds=1.0, normalize=True,
-                   want_pcm=False, info=None, pitches=range(24, 85), batch_size=8, weights="live"):
+                   want_pcm=False, info=None, pitches=range(24, 85), batch_size=8, weights="live", sample_rate=None):
         """A score -> one mixed clip (not in the reference: the rules are this project's own, DESIGN.md "Note sequences").
 
         `notes`: notes.Note rows, or what notes.read_notes accepts (a .mid / .json file name or bytes).  Restores the latest checkpoint of
@@ -921,7 +927,12 @@ class GANSynth(Iterations, DataParallel, Capture):
         and all notes are mixed by ONE gs_note_mix call: held for their length, released linearly over `release_seconds`, scaled by
         velocity / 127, the clip divided by its peak when `normalize` and the peak exceeds 1.
         Returns the clip [T] fp32 on the device, or (clip, int16 clip) with `want_pcm`.  `info` (a dict) receives notes (the kept ones),
-        dropped, total_samples, latents ([N, 256] fp32, host) and peak.  `weights`: "live" or "average", as for `generate`.  One process only."""
+        dropped, total_samples, latents ([N, 256] fp32, host) and peak.  `weights`: "live" or "average", as for `generate`.  One process only.
+        `sample_rate`: None or the model's own rate -- the clip as mixed.  Another rate (DESIGN.md "Output rates"): the mix is left
+        unnormalised and without PCM, and ONE gs_resample call brings it to that rate, takes the peak THERE (a band-limited interpolation
+        overshoots the samples it passes through), normalises by it and quantises; the clip (and PCM) come back at the new rate.  `info`
+        also receives sample_rate and output_samples, and its peak is the resampled clip's; total_samples keeps its meaning at the
+        model's rate."""
         from . import notes as N
         if self.world > 1:
             raise RuntimeError("GANSynth.synthesize runs in one process: launch it without torch.distributed (world size 1)")
@@ -956,9 +967,15 @@ class GANSynth(Iterations, DataParallel, Capture):
                 rows = [min(i, count - 1) for i in range(lo, lo + batch)]   # the last chunk repeats its last row
                 wave = self._generate_batch(lat[rows].to(dev), labels[rows].to(dev))
                 waves[lo:lo + batch].copy_(wave[:min(batch, count - lo)])
-        clip, pcm, peak = kernels.get().note_mix(waves, table, total, normalize=normalize, want_pcm=want_pcm)
+        if sample_rate is None or int(sample_rate) == int(sr):
+            clip, pcm, peak = kernels.get().note_mix(waves, table, total, normalize=normalize, want_pcm=want_pcm)
+        else:
+            mix, _, _ = kernels.get().note_mix(waves, table, total, normalize=False, want_pcm=False)
+            clip, pcm, peak = kernels.get().resample(mix, int(sr), int(sample_rate), normalize=normalize, want_pcm=want_pcm)
+            clip, pcm = clip[0], (pcm[0] if want_pcm else None)
         if info is not None:
-            info.update(notes=kept, dropped=dropped, total_samples=total, latents=lat, peak=float(peak))
+            info.update(notes=kept, dropped=dropped, total_samples=total, latents=lat, peak=float(peak),
+                        sample_rate=int(sr if sample_rate is None else sample_rate), output_samples=int(clip.numel()))
         return (clip, pcm) if want_pcm else clip
 
     # ------------------------------------------------------------------------------------------- evaluation

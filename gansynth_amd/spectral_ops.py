@@ -161,6 +161,20 @@ def convert_images_to_waveform(images, waveform_length, sample_rate, spectrogram
     return wave
 
 
+def resample(waveforms, rate_in, rate_out):
+    """Waveforms [B, n] or [n] (fp32, on the device) from rate_in to rate_out samples per second: [B, ceil(n * rate_out / rate_in)], by
+    gs_resample's Kaiser-windowed-sinc rule (include/gansynth_hip.h, DESIGN.md "Output rates"), not normalised.  Equal rates: the
+    argument itself, no launch.  Not in the reference, whose samples stay at 16 kHz; also what brings a 44.1 kHz recording to the
+    model's rate before convert_to_spectrogram."""
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    if rate_in <= 0 or rate_out <= 0:
+        raise ValueError(f"resample: rates must be positive (got {rate_in} -> {rate_out})")
+    if rate_in == rate_out:
+        return waveforms
+    out, _, _ = kernels.get().resample(waveforms.float(), rate_in, rate_out)
+    return out[0] if waveforms.dim() == 1 else out
+
+
 def convert_to_waveform(log_mel_magnitude_spectrograms, mel_instantaneous_frequencies, waveform_length, sample_rate,
                         spectrogram_shape, overlap):
     """spectral_ops.py:97-149."""

@@ -675,6 +675,54 @@ int gs_note_mix(const float* waves, int rows, int64_t length, int64_t row_stride
 int gs_bank_gather(const int16_t* pcm, int64_t rows, int64_t length, int64_t row_stride, const int32_t* class_of_row, const int32_t* order,
                    int64_t n_order, int64_t first, int batch, int n_classes, float* waves, float* labels, void* stream);
 
+/* ---- Output rates: a rational-ratio polyphase resampler (GANSynth.synthesize / generate with sample_rate, spectral_ops.resample; this
+ * project's own rule, DESIGN.md "Output rates") -------------------------------------------------------------------------------------
+ * For rate_in != rate_out, both positive: g = gcd(rate_in, rate_out), up = rate_out / g, down = rate_in / g,
+ *     c = ROLLOFF * min(1, up / down),   taps = 2 * ceil(ZEROS / c),   n_out = ceil(n_in * up / down)
+ * with the fixed design constants below.  The continuous kernel is a Kaiser-windowed sinc,
+ *     h(u) = c * sinc(c u) * I0(BETA * sqrt(1 - a^2)) / I0(BETA),   a = c u / ZEROS,   for |a| < 1, else 0;   sinc(x) = sin(pi x) / (pi x)
+ * and the table is T[p][k] = h(p / up + taps/2 - 1 - k), p in [0, up), k in [0, taps), computed in double and rounded once to fp32.
+ * Output j of a row (all index arithmetic in 64 bits):
+ *     i0 = floor(j * down / up),   p = (j * down) mod up,   y[j] = sum over k of T[p][k] * x[i0 - taps/2 + 1 + k]
+ * where an x index outside [0, n_in) contributes 0 -- so a tap that falls into a row's stride padding or into the neighbouring row
+ * contributes 0 whatever lies there.  No per-phase renormalisation.  fp32 accumulation in a fixed order, FMA allowed; no atomics; two
+ * calls are bit-identical.
+ * Tail, per row, with gs_note_mix's semantics: peak[r] = max over j of |y[r][j]| (exact); out = y / peak[r] (correctly rounded) when
+ * `normalize` and peak[r] > 1, else y; pcm (or NULL): summary_audio_s16's rule applied to out.  x: [rows] rows of n_in fp32 samples,
+ * `row_stride` elements apart; out: [rows][n_out] fp32; pcm: [rows][n_out] int16 or NULL; peak: [rows] fp32 or NULL.
+ * Two launches: the filter -- a block owns GS_RESAMPLE_TILE consecutive outputs of one row, stages the input span they need in LDS
+ * (zero-filled beyond the row's ends) and leaves one |max| per block in ws (sized by the query) -- then every block folds its row's
+ * maxima, scales and quantises; the second is skipped when normalize == 0 and pcm == peak == NULL.  Capture-safe: no allocation, no
+ * synchronisation.
+ * The table is filled in HOST memory and uploaded by the caller once per (rate_in, rate_out).  device_layout == 0: the logical
+ * [up][taps] order above.  device_layout != 0: what gs_resample reads -- the same rows, each padded with zeros to
+ * GS_RESAMPLE_ROW(taps) floats so that every row starts on 16 bytes ([up][GS_RESAMPLE_ROW(taps)]; the base must be 16-byte aligned).
+ * gs_resample_design, _out_len, _table_bytes, _table and _workspace_bytes are host arithmetic and need no device.
+ * GS_ERR_ARG with a message and without a launch: non-positive rates, equal rates, up > GS_RESAMPLE_MAX_UP, taps > GS_RESAMPLE_MAX_TAPS
+ * (e.g. 16000 -> 44101, or a ratio beyond about 1/15), rows <= 0 (or > 65535), n_in <= 0 (or > GS_RESAMPLE_MAX_N), row_stride < n_in,
+ * x / out / table NULL, a misaligned pointer, a workspace that is too small, a descriptor whose up / down / taps / zeros do not follow
+ * from its rates.  (The queries answer a refusal with 0 bytes, gs_resample_out_len with the negative code.) */
+#define GS_RESAMPLE_ZEROS 32
+#define GS_RESAMPLE_ROLLOFF 0.95
+#define GS_RESAMPLE_BETA 12.0
+#define GS_RESAMPLE_MAX_UP 1024
+#define GS_RESAMPLE_MAX_TAPS 1024
+#define GS_RESAMPLE_MAX_N ((int64_t)1 << 40)
+#define GS_RESAMPLE_TILE 512                        /* outputs per block of the filter: 256 lanes x 2 */
+#define GS_RESAMPLE_ROW(taps) (((taps) + 3) & ~3)   /* floats per row of the device table */
+typedef struct GsResample {
+    int32_t rate_in, rate_out;
+    int32_t up, down, taps;   /* as defined above */
+    int32_t zeros;            /* GS_RESAMPLE_ZEROS */
+} GsResample;                 /* 24 bytes */
+int gs_resample_design(int rate_in, int rate_out, GsResample* out);
+int64_t gs_resample_out_len(const GsResample* r, int64_t n_in);
+size_t gs_resample_table_bytes(const GsResample* r, int device_layout);
+int gs_resample_table(const GsResample* r, int device_layout, float* table_host);
+size_t gs_resample_workspace_bytes(const GsResample* r, int rows, int64_t n_in);
+int gs_resample(const GsResample* r, const float* table_dev, const float* x, int rows, int64_t n_in, int64_t row_stride, int normalize,
+                float* out, int16_t* pcm, float* peak, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """What rendering a score costs ("Note sequences").
 
-    python scripts/bench_synthesize.py [--notes 200] [--seconds 60] [--repeats 5] [--mix_repeats 50] [--out FILE]
+    python scripts/bench_synthesize.py [--notes 200] [--seconds 60] [--repeats 5] [--mix_repeats 50] [--output_rate HZ] [--out FILE]
 
 A fixed generated score -- `--notes` notes over `--seconds` seconds, seeded, built here -- through GANSynth.synthesize at the headline
 model size (fully grown 128 x 1024 generator, batch 8, bf16, initial weights: the cost does not depend on them).  One warm-up call, then
@@ -8,6 +8,8 @@ model size (fully grown 128 x 1024 generator, batch 8, bf16, initial weights: th
 device ms of gs_note_mix alone (HIP events around `--mix_repeats` calls of the entry point on the call's own waves and table, with
 normalisation and PCM), notes per second end to end (host clock around synthesize, which ends in a device synchronise: info's peak is
 read), and the mix's algorithmic bytes -- 4 * sum(hold + release) read, 4 * T written, + 2 * T with pcm -- over its time.
+`--output_rate HZ`: the clip is rendered at that rate (synthesize's sample_rate: the mix unnormalised, then one gs_resample call with
+the normalisation and the PCM); the difference of `seconds_end_to_end` to a run without the flag is what the rate change adds.
 Needs a GPU; prints one JSON object.
 """
 import argparse
@@ -37,6 +39,7 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--mix_repeats", type=int, default=50)
+    ap.add_argument("--output_rate", type=int, default=None)
     ap.add_argument("--out", type=str, default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -78,7 +81,7 @@ def main():
             info = {}
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            model.synthesize(score, want_pcm=True, info=info, batch_size=args.batch)
+            model.synthesize(score, want_pcm=True, info=info, batch_size=args.batch, sample_rate=args.output_rate)
             torch.cuda.synchronize()
             seconds = time.perf_counter() - t0
             if i:   # (the first call builds the variables, prepares the weights and plans the inverse transform)
@@ -118,7 +121,7 @@ def main():
     median = mix_ms[len(mix_ms) // 2]
     best = min(calls, key=lambda c: c["seconds"])
     result = dict(config=dict(notes=len(kept), dropped=dropped, clip_seconds=total / 16000, batch=args.batch, dtype="bf16", resolution=[128, 1024],
-                              repeats=args.repeats, mix_repeats=args.mix_repeats),
+                              repeats=args.repeats, mix_repeats=args.mix_repeats, output_rate=args.output_rate or 16000),
                   calls=calls, generator_ms=best["generator_ms"], inverse_ms=best["inverse_ms"], seconds_end_to_end=best["seconds"],
                   notes_per_second=len(kept) / best["seconds"],
                   note_mix_ms=dict(median=median, min=mix_ms[0], max=mix_ms[-1]),
