@@ -19,6 +19,12 @@ device (GANSynth.synthesize).  It needs no dataset:
 
     python gan_synth_main.py --synthesize score.mid --model_dir gan_synth_model --output score.wav
 
+`--ensemble` gives every part of the score -- a MIDI channel under one program, a JSON "part" -- its own instrument and honours the channel
+volume; `--stereo` writes two channels placed by pan (CC 10, JSON "pan") and, for the parts without one, fanned out by `--spread` in [0, 1];
+both channels are normalised by ONE peak (GANSynth.synthesize with ensemble / stereo / spread, DESIGN.md "Parts and stereo"):
+
+    python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --spread 0.6 --output quartet.wav
+
 `--output_rate HZ` (not in the reference; default: the model's 16000) writes the files of `--synthesize` and `--generate` at another
 sample rate, e.g. 44100 or 48000: resampled on the device, and for `--synthesize` peak-normalised and quantised THERE (GANSynth.synthesize
 with sample_rate, DESIGN.md "Output rates").
@@ -60,6 +66,13 @@ parser.add_argument("--release_seconds", type=float, default=1.0, help="--synthe
 parser.add_argument("--output_rate", type=int, default=None, metavar="HZ",
                     help="--synthesize, --generate: the sample rate of the files written (default: the model's rate), resampled on the device")
 parser.add_argument("--seed", type=int, default=0, help="--synthesize: seed of the latent anchors (a generator of their own)")
+parser.add_argument("--ensemble", action="store_true",
+                    help="--synthesize: every part of the score (a MIDI channel under one program, a JSON \"part\") plays its own instrument, "
+                         "and the channel volume (CC 7) enters the gain")
+parser.add_argument("--stereo", action="store_true",
+                    help="--synthesize: a two-channel WAV: pan (CC 10, JSON \"pan\") and --spread place the notes, both channels share one peak")
+parser.add_argument("--spread", type=float, default=0.0, metavar="FLOAT",
+                    help="--synthesize --stereo: how far the parts without a pan fan out between left and right (0: all in the centre .. 1)")
 parser.add_argument("--generator_ema_decay", type=float, default=0.0,
                     help="keep an exponential moving average of the generator's weights with this decay (0.0: off; progressive GAN uses 0.999)")
 parser.add_argument("--pack_bank", type=str, default=None, metavar="PATH",
@@ -72,7 +85,8 @@ parser.add_argument("--weights", choices=["live", "average"], default="live",
 
 
 def synthesize_to_wav(model, args, pitches, restore=True, log=print):
-    """--synthesize: the score args.synthesize through GANSynth.synthesize into the 16-bit WAV args.output (the kernel's own PCM)."""
+    """--synthesize: the score args.synthesize through GANSynth.synthesize into the 16-bit WAV args.output (the kernel's own PCM: [T], or
+    the interleaved [T, 2] of --stereo, which is a two-channel WAV's layout)."""
     from scipy.io import wavfile
     from gansynth_amd import checkpoint
     if os.path.splitext(args.synthesize)[1].lower() not in (".mid", ".midi", ".json"):
@@ -84,7 +98,8 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     _, pcm = model.synthesize(args.synthesize, model_dir=args.model_dir if restore else None, seed=args.seed,
                               seconds_per_instrument=args.seconds_per_instrument, release_seconds=args.release_seconds,
                               want_pcm=True, info=info, pitches=pitches, batch_size=args.batch_size, weights=args.weights,
-                              sample_rate=getattr(args, "output_rate", None))
+                              sample_rate=getattr(args, "output_rate", None), ensemble=getattr(args, "ensemble", False),
+                              stereo=getattr(args, "stereo", False), spread=getattr(args, "spread", 0.0))
     if restore:
         log(f"restored {model.restored_from}")
     rate = int(model.spectral_params["sample_rate"])

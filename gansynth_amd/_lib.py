@@ -185,6 +185,10 @@ SIGNATURES = {
     "gs_summary_audio_s16": (I, [P, P, I, L, L, I, P]),
     "gs_note_mix_workspace_bytes": (Z, [L]),
     "gs_note_mix": (I, [P, I, L, L, P, I, L, I, P, P, P, P, Z, P]),
+    "gs_note_mix_stereo_workspace_bytes": (Z, [L]),
+    "gs_note_mix_stereo": (I, [P, I, L, L, P, I, L, I, P, L, P, P, P, Z, P]),
+    "gs_stereo_finish_workspace_bytes": (Z, [L]),
+    "gs_stereo_finish": (I, [P, L, L, I, P, P, P, Z, P]),
     "gs_bank_gather": (I, [P, L, L, L, P, P, L, L, I, I, P, P, P]),
     # R = POINTER(GsResample), the design of one (rate_in, rate_out)
     "gs_resample_design": (I, [I, I, R]),
@@ -246,6 +250,12 @@ MIX_TILE = 4096   # GS_MIX_TILE: output samples per block of gs_note_mix
 class GsMixNote(ctypes.Structure):
     """include/gansynth_hip.h: one note of gs_note_mix's table (24 bytes; the table lives in device memory, sorted by onset)."""
     _fields_ = [("onset", ctypes.c_int64), ("hold", ctypes.c_int32), ("release", ctypes.c_int32), ("row", ctypes.c_int32), ("gain", c_float)]
+
+
+class GsMixNoteStereo(ctypes.Structure):
+    """include/gansynth_hip.h: one note of gs_note_mix_stereo's table (32 bytes; device memory, sorted by onset; `reserved` is not read)."""
+    _fields_ = [("onset", ctypes.c_int64), ("hold", ctypes.c_int32), ("release", ctypes.c_int32), ("row", ctypes.c_int32),
+                ("gain_l", c_float), ("gain_r", c_float), ("reserved", ctypes.c_int32)]
 
 
 _lib = None

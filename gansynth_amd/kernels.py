@@ -100,31 +100,46 @@ def note_mix_table(table, rows, length, total):
     """The host side of note_mix: validates `table` -- (onset, hold, release, row, gain) per note -- against the waves' shape and the
     clip length, sorts it by (onset, position) and returns the rows as a ctypes array of GsMixNote.  ValueError by note index and
     field name.  (A note may run past `total`: it is clipped there.)"""
+    checked = _checked_notes("note_mix", table, rows, length, total, ("gain",))
+    return (_lib.GsMixNote * len(checked))(*[_lib.GsMixNote(*row) for row in checked])
+
+
+def note_mix_stereo_table(table, rows, length, total):
+    """The host side of note_mix_stereo: note_mix_table's checks and order for rows (onset, hold, release, row, gain_l, gain_r), as a
+    ctypes array of GsMixNoteStereo."""
+    checked = _checked_notes("note_mix_stereo", table, rows, length, total, ("gain_l", "gain_r"))
+    return (_lib.GsMixNoteStereo * len(checked))(*[_lib.GsMixNoteStereo(*row, 0) for row in checked])
+
+
+def _checked_notes(what, table, rows, length, total, gains):
+    """Rows (onset, hold, release, row, *gains) validated and sorted by (onset, position): what both note tables share."""
+    fields = ("onset", "hold", "release", "row") + gains
     if len(table) == 0:
-        raise ValueError("note_mix: the table is empty")
+        raise ValueError(f"{what}: the table is empty")
     if int(total) <= 0:
-        raise ValueError(f"note_mix: total must be positive (got {total})")
+        raise ValueError(f"{what}: total must be positive (got {total})")
     checked = []
     for i, entry in enumerate(table):
-        if len(entry) != 5:
-            raise ValueError(f"note_mix: note {i} has {len(entry)} fields, not (onset, hold, release, row, gain)")
-        onset, hold, release, row, gain = entry
+        if len(entry) != len(fields):
+            raise ValueError(f"{what}: note {i} has {len(entry)} fields, not ({', '.join(fields)})")
+        onset, hold, release, row = entry[:4]
         for name, v in (("onset", onset), ("hold", hold), ("release", release), ("row", row)):
             if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
-                raise ValueError(f"note_mix: note {i} field '{name}' must be an integer (got {v!r})")
+                raise ValueError(f"{what}: note {i} field '{name}' must be an integer (got {v!r})")
         if not 0 <= onset < total:
-            raise ValueError(f"note_mix: note {i} field 'onset' = {onset} is outside the clip [0, {total})")
+            raise ValueError(f"{what}: note {i} field 'onset' = {onset} is outside the clip [0, {total})")
         if not 1 <= hold <= length:
-            raise ValueError(f"note_mix: note {i} field 'hold' = {hold} is outside [1, {length}]")
+            raise ValueError(f"{what}: note {i} field 'hold' = {hold} is outside [1, {length}]")
         if not 0 <= release <= length - hold:
-            raise ValueError(f"note_mix: note {i} field 'release' = {release} is outside [0, {length} - hold = {length - hold}]")
+            raise ValueError(f"{what}: note {i} field 'release' = {release} is outside [0, {length} - hold = {length - hold}]")
         if not 0 <= row < rows:
-            raise ValueError(f"note_mix: note {i} field 'row' = {row} is outside [0, {rows})")
-        if isinstance(gain, bool) or not isinstance(gain, (int, float, np.floating, np.integer)) or not np.isfinite(gain):
-            raise ValueError(f"note_mix: note {i} field 'gain' must be a finite number (got {gain!r})")
-        checked.append((int(onset), int(hold), int(release), int(row), float(gain)))
+            raise ValueError(f"{what}: note {i} field 'row' = {row} is outside [0, {rows})")
+        for name, gain in zip(gains, entry[4:]):
+            if isinstance(gain, bool) or not isinstance(gain, (int, float, np.floating, np.integer)) or not np.isfinite(gain):
+                raise ValueError(f"{what}: note {i} field '{name}' must be a finite number (got {gain!r})")
+        checked.append((int(onset), int(hold), int(release), int(row)) + tuple(float(g) for g in entry[4:]))
     order = sorted(range(len(checked)), key=lambda i: (checked[i][0], i))
-    return (_lib.GsMixNote * len(checked))(*[_lib.GsMixNote(*checked[i]) for i in order])
+    return [checked[i] for i in order]
 
 
 class HipKernels(object):
@@ -1382,6 +1397,46 @@ class HipKernels(object):
                                         1 if normalize else 0, out.data_ptr(), None if pcm is None else pcm.data_ptr(), peak.data_ptr(),
                                         ws.data_ptr(), ws.numel(), _stream()), "gs_note_mix")
         return out, pcm, peak
+
+    def note_mix_stereo(self, waves, table, total, normalize=True, want_pcm=False):
+        """gs_note_mix_stereo (include/gansynth_hip.h): the notes of `table` -- host rows (onset, hold, release, row, gain_l, gain_r) -- mixed
+        from the rows of waves [rows, L] fp32 into two channels with ONE peak.  -> (out [2, total] fp32 -- a view of [2, S], S = total
+        rounded up to 4, so that both rows start on 16 bytes --, pcm [total, 2] int16 or None, peak [1] fp32 = max |mix| over both
+        channels); both channels are divided by peak when `normalize` and peak > 1."""
+        if waves.dim() != 2 or waves.dtype != torch.float32:
+            raise ValueError(f"note_mix_stereo: waves must be [rows, L] fp32 (got {tuple(waves.shape)} {waves.dtype})")
+        rows, length = int(waves.shape[0]), int(waves.shape[1])
+        total = int(total)
+        arr = note_mix_stereo_table(table, rows, length, total)
+        if waves.stride(1) != 1 or (rows > 1 and waves.stride(0) < length):
+            waves = waves.contiguous()
+        notes = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(waves.device)   # uploaded once
+        stride = (total + 3) // 4 * 4
+        out = torch.empty((2, stride), dtype=torch.float32, device=waves.device)
+        pcm = torch.empty((total, 2), dtype=torch.int16, device=waves.device) if want_pcm else None
+        peak = torch.empty((1,), dtype=torch.float32, device=waves.device)
+        ws = _ws(self.lib.gs_note_mix_stereo_workspace_bytes(total), waves.device)
+        _lib.check(self.lib.gs_note_mix_stereo(waves.data_ptr(), rows, length, int(waves.stride(0)) if rows > 1 else length, notes.data_ptr(),
+                                               len(arr), total, 1 if normalize else 0, out.data_ptr(), stride,
+                                               None if pcm is None else pcm.data_ptr(), peak.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                   "gs_note_mix_stereo")
+        return out[:, :total], pcm, peak
+
+    def stereo_finish(self, x, normalize=True, want_pcm=False):
+        """gs_stereo_finish (include/gansynth_hip.h): the second stage of note_mix_stereo on a clip x [2, n] fp32 that did not come from it
+        (any row stride >= n), IN PLACE.  -> (x, pcm [n, 2] int16 or None, peak [1] fp32 = max |x| over both rows before any scaling);
+        both rows are divided by peak when `normalize` and peak > 1."""
+        if x.dim() != 2 or x.shape[0] != 2 or x.dtype != torch.float32 or not x.is_cuda or x.shape[1] == 0:
+            raise ValueError(f"stereo_finish: x must be [2, n] fp32 on the HIP device (got {tuple(x.shape)} {x.dtype} on {x.device})")
+        n = int(x.shape[1])
+        if x.stride(1) != 1 or x.stride(0) < n:
+            raise ValueError(f"stereo_finish: the rows of x must be contiguous and apart (strides {tuple(x.stride())}): it works in place")
+        pcm = torch.empty((n, 2), dtype=torch.int16, device=x.device) if want_pcm else None
+        peak = torch.empty((1,), dtype=torch.float32, device=x.device)
+        ws = _ws(self.lib.gs_stereo_finish_workspace_bytes(n), x.device)
+        _lib.check(self.lib.gs_stereo_finish(x.data_ptr(), n, int(x.stride(0)), 1 if normalize else 0, None if pcm is None else pcm.data_ptr(),
+                                             peak.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_stereo_finish")
+        return x, pcm, peak
 
     def bank_gather(self, pcm, class_of_row, order, first, batch, n_classes, want_waves=True):
         """gs_bank_gather (include/gansynth_hip.h): the batch order[first : first + batch] of the resident bank pcm [rows, L] int16.

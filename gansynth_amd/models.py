@@ -916,7 +916,8 @@ class GANSynth(Iterations, DataParallel, Capture):
 
     # --------------------------------------------------------------------------------------- note sequences
     def synthesize(self, notes, model_dir=None, latents=None, seed=0, seconds_per_instrument=6.0, release_seconds=1.0, normalize=True,
-                   want_pcm=False, info=None, pitches=range(24, 85), batch_size=8, weights="live", sample_rate=None):
+                   want_pcm=False, info=None, pitches=range(24, 85), batch_size=8, weights="live", sample_rate=None, ensemble=False,
+                   stereo=False, spread=0.0):
         """A score -> one mixed clip (not in the reference: the rules are this project's own, DESIGN.md "Note sequences").
 
         `notes`: notes.Note rows, or what notes.read_notes accepts (a .mid / .json file name or bytes).  Restores the latest checkpoint of
@@ -932,19 +933,48 @@ class GANSynth(Iterations, DataParallel, Capture):
         unnormalised and without PCM, and ONE gs_resample call brings it to that rate, takes the peak THERE (a band-limited interpolation
         overshoots the samples it passes through), normalises by it and quantises; the clip (and PCM) come back at the new rate.  `info`
         also receives sample_rate and output_samples, and its peak is the resampled clip's; total_samples keeps its meaning at the
-        model's rate."""
+        model's rate.
+        `ensemble`, `stereo`, `spread` (DESIGN.md "Parts and stereo"; all off: the path above, untouched).  With either flag the score is
+        read by notes.read_score (a notes.Score is taken as it is, a list of Note is one part with the default volume and no pan).
+        `ensemble`: every part -- a MIDI channel under one program, a JSON "part" -- plays its own instrument
+        (notes.schedule_part_latents, unless `latents` is given) and the channel volume enters the gain, velocity * volume / 127^2.
+        `stereo`: pan and `spread` (in [0, 1]: how far the parts without a pan fan out) enter the two gains of notes.schedule_gains, ONE
+        gs_note_mix_stereo call mixes both channels and normalises them by their joint peak; the clip is [2, T] and the PCM [T, 2].  With
+        `sample_rate` at another rate: the stereo mix unnormalised, ONE gs_resample call on its two rows, ONE gs_stereo_finish at the new
+        rate.  `info` also receives parts, part_of_note (per kept note) and channels."""
         from . import notes as N
         if self.world > 1:
             raise RuntimeError("GANSynth.synthesize runs in one process: launch it without torch.distributed (world size 1)")
         if self.spectral_params is None:
             raise ValueError("synthesize: the model has no spectral_params (waveform_length, sample_rate, ...)")
-        if not (isinstance(notes, (list, tuple)) and all(isinstance(n, N.Note) for n in notes)):
+        score = None
+        if ensemble or stereo:
+            if isinstance(notes, N.Score):
+                score = notes
+            elif isinstance(notes, (list, tuple)) and all(isinstance(n, N.Note) for n in notes):
+                score = N.one_part_score(notes)
+            else:
+                score = N.read_score(notes)
+            notes = score.notes
+            N.part_positions(score, spread)   # (a spread outside [0, 1] is refused before anything is generated)
+        elif not (isinstance(notes, (list, tuple)) and all(isinstance(n, N.Note) for n in notes)):
             notes = N.read_notes(notes)
         pitches = sorted(pitches)
         sr, length = self.spectral_params["sample_rate"], int(self.spectral_params["waveform_length"])
         kept, table, total, dropped = N.schedule(notes, pitches, sr, length, release_seconds)
         count, batch = len(kept), int(batch_size)
-        if latents is None:
+        if score is not None:
+            index = N.kept_indices(notes, pitches)
+            part_of_note = [score.part[i] for i in index]
+            if not ensemble:   # one instrument, and the channel volume does not enter: 127 / 127 is an exact 1
+                score = score._replace(volume=[127] * len(score.notes))
+            if stereo:
+                table = [row[:4] + gains for row, gains in zip(table, N.schedule_gains(index, score, spread))]
+            else:
+                table = [row[:4] + (score.notes[i].velocity * score.volume[i] / 127.0 ** 2,) for row, i in zip(table, index)]
+        if latents is None and ensemble:
+            lat = N.schedule_part_latents(kept, part_of_note, len(score.parts), total, sr, seed, seconds_per_instrument)
+        elif latents is None:
             lat = N.schedule_latents(kept, total, sr, seed, seconds_per_instrument)
         else:
             lat = torch.as_tensor(latents).detach().float().cpu()
@@ -967,7 +997,13 @@ class GANSynth(Iterations, DataParallel, Capture):
                 rows = [min(i, count - 1) for i in range(lo, lo + batch)]   # the last chunk repeats its last row
                 wave = self._generate_batch(lat[rows].to(dev), labels[rows].to(dev))
                 waves[lo:lo + batch].copy_(wave[:min(batch, count - lo)])
-        if sample_rate is None or int(sample_rate) == int(sr):
+        if stereo and (sample_rate is None or int(sample_rate) == int(sr)):
+            clip, pcm, peak = kernels.get().note_mix_stereo(waves, table, total, normalize=normalize, want_pcm=want_pcm)
+        elif stereo:
+            mix, _, _ = kernels.get().note_mix_stereo(waves, table, total, normalize=False, want_pcm=False)
+            clip, _, _ = kernels.get().resample(mix, int(sr), int(sample_rate), normalize=False, want_pcm=False)
+            clip, pcm, peak = kernels.get().stereo_finish(clip, normalize=normalize, want_pcm=want_pcm)
+        elif sample_rate is None or int(sample_rate) == int(sr):
             clip, pcm, peak = kernels.get().note_mix(waves, table, total, normalize=normalize, want_pcm=want_pcm)
         else:
             mix, _, _ = kernels.get().note_mix(waves, table, total, normalize=False, want_pcm=False)
@@ -975,7 +1011,9 @@ class GANSynth(Iterations, DataParallel, Capture):
             clip, pcm = clip[0], (pcm[0] if want_pcm else None)
         if info is not None:
             info.update(notes=kept, dropped=dropped, total_samples=total, latents=lat, peak=float(peak),
-                        sample_rate=int(sr if sample_rate is None else sample_rate), output_samples=int(clip.numel()))
+                        sample_rate=int(sr if sample_rate is None else sample_rate), output_samples=int(clip.shape[-1]))
+            if score is not None:
+                info.update(parts=list(score.parts), part_of_note=part_of_note, channels=2 if stereo else 1)
         return (clip, pcm) if want_pcm else clip
 
     # ------------------------------------------------------------------------------------------- evaluation

@@ -4,7 +4,12 @@ The reference has no renderer: the rules here are this project's own.  A `Note` 
 and seconds with 0 <= start < end.  `read_notes` reads a JSON list or a Standard MIDI File (format 0 or 1); `schedule` turns notes into
 the sample-exact table that kernels.HipKernels.note_mix mixes; `schedule_latents` gives every note its latent by spherical
 interpolation between anchors drawn from a generator of their own (the global RNG, and with it a training run's stream, does not move).
+
+Parts and stereo (DESIGN.md "Parts and stereo"): `read_score` reads the same files into a `Score` -- the same notes, and per note its part
+(a MIDI channel under one program, or a JSON "part"), its channel volume and its pan; `schedule_gains` turns them into the two gains of
+kernels.HipKernels.note_mix_stereo, `schedule_part_latents` gives every part a latent trajectory of its own.
 """
+import bisect
 import collections
 import json
 import math
@@ -15,9 +20,13 @@ import numpy as np
 import torch
 
 Note = collections.namedtuple("Note", ["pitch", "velocity", "start", "end"])
+Part = collections.namedtuple("Part", ["channel", "program"])   # (None, None) for the parts of a JSON score
+# notes: what read_notes returns; part / volume / pan: one entry per note (pan: a float in [-1, 1], or None where the score sets none)
+Score = collections.namedtuple("Score", ["notes", "part", "volume", "pan", "parts"])
 
 DEFAULT_TEMPO = 500000   # microseconds per quarter note until a file says otherwise
 DRUM_CHANNEL = 9         # channel 10: percussion, no pitch
+DEFAULT_PROGRAM, DEFAULT_VOLUME = 0, 100   # until a program change / a channel volume (CC 7) says otherwise; pan (CC 10) stays unset
 
 
 class ScoreError(ValueError):
@@ -33,8 +42,8 @@ def _is_number(v):
     return isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)
 
 
-def notes_from_json(items):
-    """A list of {"pitch", "velocity", "start", "end"} objects -> [Note]; a missing or ill-typed field is refused by index and name."""
+def _json_notes(items):
+    """The note objects of a JSON score, validated -> [Note] in file order."""
     if not isinstance(items, list):
         raise ScoreError(f"JSON score: a list of note objects is expected (got {type(items).__name__})")
     out = []
@@ -56,8 +65,35 @@ def notes_from_json(items):
         if not item["start"] < item["end"]:
             raise ScoreError(f"JSON score: note {i} field 'end' must be later than 'start' (got {item['start']} .. {item['end']})")
         out.append(Note(item["pitch"], item["velocity"], float(item["start"]), float(item["end"])))
+    return out
+
+
+def notes_from_json(items):
+    """A list of {"pitch", "velocity", "start", "end"} objects -> [Note]; a missing or ill-typed field is refused by index and name."""
+    out = _json_notes(items)
     order = sorted(range(len(out)), key=lambda i: (out[i].start, i))
     return [out[i] for i in order]
+
+
+def score_from_json(items):
+    """notes_from_json's notes with the optional fields "part" (a non-negative integer, default 0), "volume" (0..127, default 100) and
+    "pan" (a number in [-1, 1], default unset) -> Score; an ill-typed or out-of-range one is refused by index and name.  The parts are the
+    distinct "part" values in ascending order."""
+    out = _json_notes(items)
+    part, volume, pan = [], [], []
+    for i, item in enumerate(items):
+        for field, ok, what, default in (("part", lambda v: _is_int(v) and v >= 0, "a non-negative integer", 0),
+                                         ("volume", lambda v: _is_int(v) and 0 <= v <= 127, "an integer 0..127", DEFAULT_VOLUME),
+                                         ("pan", lambda v: _is_number(v) and -1 <= v <= 1, "a number in [-1, 1]", None)):
+            if field in item and not ok(item[field]):
+                raise ScoreError(f"JSON score: note {i} field '{field}' must be {what} (got {item[field]!r})")
+        part.append(item.get("part", 0))
+        volume.append(item.get("volume", DEFAULT_VOLUME))
+        pan.append(float(item["pan"]) if "pan" in item else None)
+    values = sorted(set(part))
+    order = sorted(range(len(out)), key=lambda i: (out[i].start, i))
+    return Score([out[i] for i in order], [values.index(part[i]) for i in order], [volume[i] for i in order], [pan[i] for i in order],
+                 [Part(None, None) for _ in values])
 
 
 # ------------------------------------------------------------------------------------------------------------------ MIDI
@@ -75,8 +111,10 @@ def _vlq(data, pos, end, what):
     raise ScoreError(f"MIDI file: {what} is longer than four bytes")
 
 
-def _read_track(data, pos, end, track, counter):
-    """One MTrk chunk's events -> ([(pitch, velocity, start tick, end tick, appearance)], [(tick, tempo)])."""
+def _read_track(data, pos, end, track, counter, controls=None):
+    """One MTrk chunk's events -> ([(pitch, velocity, start tick, end tick, appearance, channel)], [(tick, tempo)]).  `controls` (a list)
+    also receives, in file order, (tick, channel, what, value) of every program change ("program"), CC 7 ("volume") and CC 10 ("pan")
+    outside channel 10."""
     notes, tempos = [], []
     sounding = {}   # (channel, pitch) -> (start tick, velocity, appearance)
     tick, status = 0, None
@@ -87,7 +125,7 @@ def _read_track(data, pos, end, track, counter):
 
     def stop(key, at):
         start, velocity, appearance = sounding.pop(key)
-        notes.append((key[1], velocity, start, at, appearance))
+        notes.append((key[1], velocity, start, at, appearance, key[0]))
 
     while pos < end:
         delta, pos = _vlq(data, pos, end, f"a delta time of track {track}")
@@ -125,6 +163,11 @@ def _read_track(data, pos, end, track, counter):
             first, second = data[pos], data[pos + size - 1]
             pos += size
             if kind not in (0x80, 0x90) or channel == DRUM_CHANNEL:
+                if controls is not None and channel != DRUM_CHANNEL:
+                    if kind == 0xC0:
+                        controls.append((tick, channel, "program", first & 0x7F))
+                    elif kind == 0xB0 and first in (7, 10):
+                        controls.append((tick, channel, "volume" if first == 7 else "pan", second & 0x7F))
                 continue
             key = (channel, first)
             if key in sounding:                              # a note-off, or a re-trigger: the earlier note ends here
@@ -137,10 +180,9 @@ def _read_track(data, pos, end, track, counter):
     return notes, tempos
 
 
-def notes_from_midi(data):
-    """A Standard MIDI File (bytes), format 0 or 1 -> [Note], times in seconds through one tempo map merged over all tracks.  Channel 10
-    is skipped; a note-on for a pitch that is sounding on its channel ends the earlier note; a note still sounding at the end of its
-    track ends at the track's last event.  (A note that ends at the tick it starts on has no length and is left out.)"""
+def _midi(data, controls=None):
+    """notes_from_midi's work -> [(Note, appearance, channel, start tick)] sorted by (start, appearance); `controls` as in _read_track, over
+    all tracks in (track, file) order."""
     data = bytes(data)
     if len(data) < 14 or data[:4] != b"MThd":
         raise ScoreError("MIDI file: truncated or missing MThd header chunk")
@@ -163,7 +205,7 @@ def notes_from_midi(data):
         if pos + length > len(data):
             raise ScoreError(f"MIDI file: truncated chunk {tag!r}: {length} bytes announced, {len(data) - pos} present")
         if tag == b"MTrk":
-            n, t = _read_track(data, pos, pos + length, track, counter)
+            n, t = _read_track(data, pos, pos + length, track, counter, controls)
             raw += n
             tempos += t
             track += 1
@@ -186,26 +228,74 @@ def notes_from_midi(data):
                 hi = mid
         return (elapsed[lo] + (tick - ticks[lo]) * values[lo]) / (division * 1e6)
 
-    out = [(Note(pitch, velocity, seconds(start), seconds(end)), appearance) for pitch, velocity, start, end, appearance in raw if end > start]
+    out = [(Note(pitch, velocity, seconds(start), seconds(end)), appearance, channel, start)
+           for pitch, velocity, start, end, appearance, channel in raw if end > start]
     out.sort(key=lambda e: (e[0].start, e[1]))
-    return [n for n, _ in out]
+    return out
+
+
+def notes_from_midi(data):
+    """A Standard MIDI File (bytes), format 0 or 1 -> [Note], times in seconds through one tempo map merged over all tracks.  Channel 10
+    is skipped; a note-on for a pitch that is sounding on its channel ends the earlier note; a note still sounding at the end of its
+    track ends at the track's last event.  (A note that ends at the tick it starts on has no length and is left out.)"""
+    return [e[0] for e in _midi(data)]
+
+
+def score_from_midi(data):
+    """notes_from_midi's notes with their parts -> Score.  Program changes, channel volume (CC 7) and pan (CC 10) are collected from all
+    tracks; for a note, the value in force is that of the last such event on its channel at a tick at or before the note-on's -- a
+    controller ON the note's tick applies wherever it stands; among several on one tick (track, file order) decides and the last one
+    holds.  Defaults: program 0, volume 100, no pan; pan = clamp((cc10 - 64) / 63, -1, 1).  A note keeps the values it starts with.  A part
+    is a distinct (channel, program in force at note-on), numbered in order of first appearance in the notes."""
+    controls = []
+    rows = _midi(data, controls)
+    lanes = {}   # (channel, what) -> ([tick], [value]) in (tick, track, file) order: the sort is stable and `controls` is in (track, file) order
+    for tick, channel, what, value in sorted(controls, key=lambda e: e[0]):
+        ticks, values = lanes.setdefault((channel, what), ([], []))
+        ticks.append(tick)
+        values.append(value)
+
+    def in_force(channel, what, tick, default):
+        ticks, values = lanes.get((channel, what), ((), ()))
+        i = bisect.bisect_right(ticks, tick)   # the events at or before `tick`
+        return values[i - 1] if i else default
+
+    part, volume, pan, parts = [], [], [], []
+    for _, _, channel, tick in rows:
+        key = Part(channel, in_force(channel, "program", tick, DEFAULT_PROGRAM))
+        if key not in parts:
+            parts.append(key)
+        part.append(parts.index(key))
+        volume.append(in_force(channel, "volume", tick, DEFAULT_VOLUME))
+        cc10 = in_force(channel, "pan", tick, None)
+        pan.append(None if cc10 is None else min(max((cc10 - 64) / 63.0, -1.0), 1.0))
+    return Score([e[0] for e in rows], part, volume, pan, parts)
 
 
 def read_notes(path_or_bytes):
     """A score -> [Note] sorted by (start, order of appearance).  `path_or_bytes`: a file name or the file's bytes; a Standard MIDI File is
     recognised by its MThd tag, anything else is read as JSON."""
+    return _read(path_or_bytes, notes_from_midi, notes_from_json)
+
+
+def read_score(path_or_bytes):
+    """The same files -> Score: `notes` is exactly read_notes' list, and every note has its part, volume and pan."""
+    return _read(path_or_bytes, score_from_midi, score_from_json)
+
+
+def _read(path_or_bytes, from_midi, from_json):
     if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
         data = bytes(path_or_bytes)
     else:
         with open(os.fspath(path_or_bytes), "rb") as f:
             data = f.read()
     if data[:4] == b"MThd":
-        return notes_from_midi(data)
+        return from_midi(data)
     try:
         items = json.loads(data.decode("utf-8"))
     except (UnicodeDecodeError, ValueError) as e:
         raise ScoreError(f"score: neither a Standard MIDI File (no MThd tag) nor JSON ({e})")
-    return notes_from_json(items)
+    return from_json(items)
 
 
 # -------------------------------------------------------------------------------------------------------------- schedule
@@ -273,4 +363,65 @@ def schedule_latents(kept, total, sample_rate, seed, seconds_per_instrument, lat
         x = note.start / seconds_per_instrument
         j = min(int(math.floor(x)), k - 1)
         out[n] = slerp(anchors[j], anchors[j + 1], min(x - j, 1.0))
+    return torch.from_numpy(out.astype(np.float32))
+
+
+# ------------------------------------------------------------------------------------------------------ parts and stereo
+def one_part_score(notes):
+    """[Note] -> the Score of one part with the default volume and no pan (the notes in the order given)."""
+    notes = list(notes)
+    return Score(notes, [0] * len(notes), [DEFAULT_VOLUME] * len(notes), [None] * len(notes), [Part(None, None)])
+
+
+def kept_indices(notes, pitches):
+    """The indices into `notes` of the notes `schedule` keeps, in its order (by start, stable)."""
+    known = set(pitches)
+    return [i for i in sorted(range(len(notes)), key=lambda i: notes[i].start) if notes[i].pitch in known]
+
+
+def part_positions(score, spread):
+    """One position in [-1, 1] per part for the notes WITHOUT a pan: spread * (2 p / (Q - 1) - 1) for the part of rank p among the Q parts
+    that have no pan anywhere in the score (0 when Q == 1), and 0 for a part that is panned elsewhere."""
+    if isinstance(spread, bool) or not isinstance(spread, (int, float)) or not 0.0 <= spread <= 1.0:   # (NaN fails the comparison)
+        raise ValueError(f"schedule_gains: spread must lie in [0, 1] (got {spread!r})")
+    panned = {p for p, pan in zip(score.part, score.pan) if pan is not None}
+    free = [p for p in range(len(score.parts)) if p not in panned]
+    positions = [0.0] * len(score.parts)
+    if len(free) > 1:
+        for rank, p in enumerate(free):
+            positions[p] = float(spread) * (2.0 * rank / (len(free) - 1) - 1.0)
+    return positions
+
+
+def schedule_gains(kept_index, score, spread=0.0):
+    """-> [(gain_l, gain_r)] of the notes score.notes[i], i in kept_index: constant-power panning,
+        g = (velocity / 127) * (volume / 127),  theta = (pan + 1) * pi / 4,  gain_l = g cos(theta),  gain_r = g sin(theta)
+    computed in float64 and rounded once to fp32 (returned as the Python floats of those fp32 values).  A note without a pan sits at
+    its part's position (part_positions).  ValueError for a spread outside [0, 1]."""
+    positions = part_positions(score, spread)
+    out = []
+    for i in kept_index:
+        g = (score.notes[i].velocity / 127.0) * (score.volume[i] / 127.0)
+        pan = score.pan[i] if score.pan[i] is not None else positions[score.part[i]]
+        theta = (pan + 1.0) * math.pi / 4.0
+        out.append((float(np.float32(g * math.cos(theta))), float(np.float32(g * math.sin(theta)))))
+    return out
+
+
+def schedule_part_latents(kept, part_of_kept, n_parts, total, sample_rate, seed, seconds_per_instrument, latent_size=256):
+    """[N, latent_size] fp32 (host): every part its own trajectory.  ONE CPU torch.Generator seeded with `seed` draws [K + 1, latent_size]
+    anchors for part 0, then for part 1 and so on (K as in schedule_latents); a note's latent is the slerp of ITS part's two anchors around
+    its start, by schedule_latents' rule -- so the rows of part 0 are schedule_latents' rows."""
+    if not seconds_per_instrument > 0:
+        raise ValueError(f"schedule_part_latents: seconds_per_instrument must be positive (got {seconds_per_instrument})")
+    if len(part_of_kept) != len(kept) or any(not 0 <= p < n_parts for p in part_of_kept):
+        raise ValueError(f"schedule_part_latents: part_of_kept must name one of the {n_parts} parts for each of the {len(kept)} notes")
+    k = int(math.floor(total / sample_rate / seconds_per_instrument)) + 1
+    generator = torch.Generator(device="cpu").manual_seed(int(seed))
+    anchors = [torch.randn(k + 1, latent_size, generator=generator, dtype=torch.float32).double().numpy() for _ in range(n_parts)]
+    out = np.empty((len(kept), latent_size), dtype=np.float64)
+    for n, (note, part) in enumerate(zip(kept, part_of_kept)):
+        x = note.start / seconds_per_instrument
+        j = min(int(math.floor(x)), k - 1)
+        out[n] = slerp(anchors[part][j], anchors[part][j + 1], min(x - j, 1.0))
     return torch.from_numpy(out.astype(np.float32))

@@ -661,6 +661,49 @@ size_t gs_note_mix_workspace_bytes(int64_t total);
 int gs_note_mix(const float* waves, int rows, int64_t length, int64_t row_stride, const GsMixNote* notes, int n_notes, int64_t total,
                 int normalize, float* out, int16_t* pcm, float* peak, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Parts and stereo: the same mixdown into two channels with ONE peak (GANSynth.synthesize with stereo; this project's own rules,
+ * DESIGN.md "Parts and stereo") ----------------------------------------------------------------------------------------------------
+ * waves, the table's order, onset / hold / release / row and env(k) are gs_note_mix's.  A note carries two gains, and for each channel c
+ *     mix_c[t] = sum over the covering notes, in ascending table order, of (gain_c * env(k)) * waves[row][k]
+ * with gs_note_mix's operation order and separate roundings (no FMA, env's quotient as a multiplication by fl(1 / (release + 1))); every
+ * waves[row][k] is loaded ONCE and enters both sums.  mix_l of a table with gain_l = g is therefore bit-identical to gs_note_mix's mix
+ * of the same table with gain = g, and likewise on the right.  out: [2] rows of `total` samples, `out_stride` elements apart (channel 0
+ * is the left one); a sample no note covers is 0, the elements between total and out_stride are not touched.
+ * peak = max over both channels and all t of |mix_c[t]| (exact): ONE peak, so that normalising cannot move the stereo image.  Both
+ * channels are divided by it (correctly rounded) when `normalize` and peak > 1.  pcm (or NULL): [total][2] interleaved,
+ * pcm[t][c] = summary_audio_s16's rule applied to out[c][t].  peak (or NULL): [1].
+ * Gather form, no atomics: a 256-thread block owns GS_MIX_TILE consecutive samples of BOTH channels (32 accumulators a lane) and finds
+ * the notes that reach into them by two binary searches on the onsets; the table's rows come through uniform loads.  The output leaves
+ * in 16-byte packs when both row bases are 16-byte aligned (and, in the second launch, pcm as well), sample by sample otherwise and at
+ * the tail.  Two launches: the mix with one |max| per block into ws (sized by the query), then every block folds the block maxima,
+ * scales and quantises its own tile of both channels; the second is skipped when normalize == 0 and pcm == peak == NULL.
+ * A bad table cannot make the kernel read outside waves or write outside the two rows' [0, total): a note with row outside [0, rows),
+ * hold < 1, release < 0, hold + release > length or onset < 0 is skipped IN the kernel before an address is formed from it, and every
+ * note is clipped at total.  `reserved` is not read.
+ * GS_ERR_ARG with a message and without a launch: n_notes, total, rows or length <= 0, row_stride < length, out_stride < total,
+ * waves / notes / out NULL, notes off 8 bytes, waves / out / peak off 4 bytes, pcm off 2 bytes, a workspace that is too small.
+ *
+ * gs_stereo_finish is that second stage on its own, for a [2]-row clip the mix did not leave (the resampled one): x: [2] rows of n
+ * samples, `row_stride` >= n elements apart (any such stride: a row 1 off 16 bytes takes the sample-by-sample path), IN PLACE.  A first
+ * launch leaves one |max| per GS_MIX_TILE samples of both rows in ws, then the SAME finish kernel runs: peak, the quotient and pcm are
+ * defined as above with x for the mix.  With normalize == 0 and pcm == NULL x is only read; with peak == NULL too nothing is launched.
+ * GS_ERR_ARG with a message and without a launch: n <= 0, row_stride < n, x NULL, x / peak off 4 bytes, pcm off 2 bytes, a workspace
+ * that is too small. */
+typedef struct GsMixNoteStereo {
+    int64_t onset;          /* as GsMixNote */
+    int32_t hold, release;
+    int32_t row;
+    float gain_l, gain_r;   /* the note's gain on channel 0 (left) and on channel 1 (right) */
+    int32_t reserved;       /* pads the row to 32 bytes; not read */
+} GsMixNoteStereo;          /* 32 bytes */
+size_t gs_note_mix_stereo_workspace_bytes(int64_t total);
+int gs_note_mix_stereo(const float* waves, int rows, int64_t length, int64_t row_stride, const GsMixNoteStereo* notes, int n_notes,
+                       int64_t total, int normalize, float* out, int64_t out_stride, int16_t* pcm, float* peak, void* ws, size_t ws_bytes,
+                       void* stream);
+size_t gs_stereo_finish_workspace_bytes(int64_t n);
+int gs_stereo_finish(float* x, int64_t n, int64_t row_stride, int normalize, int16_t* pcm, float* peak, void* ws, size_t ws_bytes,
+                     void* stream);
+
 /* ---- Resident notes: one batch drawn from the int16 bank on the device (gansynth_amd/bank.py, DESIGN.md "Resident notes") ----------
  * pcm: [rows] notes of `length` int16 samples, `row_stride` elements apart.  class_of_row: [rows] int32, the label index of a row or -1.
  * order: [n_order] int32 row numbers; the batch is order[first .. first + batch).  For b in [0, batch), r = order[first + b]:
