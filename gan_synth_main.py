@@ -29,6 +29,13 @@ both channels are normalised by ONE peak (GANSynth.synthesize with ensemble / st
 sample rate, e.g. 44100 or 48000: resampled on the device, and for `--synthesize` peak-normalised and quantised THERE (GANSynth.synthesize
 with sample_rate, DESIGN.md "Output rates").
 
+`--reverb SECONDS` (not in the reference) puts the rendered score into a designed room of that RT60, `--reverb_ir FILE.wav` into a recorded
+one (a mono or stereo impulse response; the two exclude each other); `--reverb_mix W` in [0, 1] is the share of the reverberated signal
+(default 0.25) and `--reverb_predelay SECONDS` delays it (default 0).  The stage runs on the device at the output rate, between the
+resampler and the ONE peak normalisation, and the file grows by the tail (gansynth_amd/reverb.py, DESIGN.md "Reverb"):
+
+    python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --output_rate 48000 --reverb 1.8 --reverb_mix 0.3 --output quartet.wav
+
 `--pack_bank` / `--bank` (not in the reference): the notes packed once into one file (on any machine, no GPU needed), then held on the
 device and drawn there, batch for batch what `--filenames` yields (gansynth_amd/bank.py, DESIGN.md "Resident notes"):
 
@@ -73,6 +80,13 @@ parser.add_argument("--stereo", action="store_true",
                     help="--synthesize: a two-channel WAV: pan (CC 10, JSON \"pan\") and --spread place the notes, both channels share one peak")
 parser.add_argument("--spread", type=float, default=0.0, metavar="FLOAT",
                     help="--synthesize --stereo: how far the parts without a pan fan out between left and right (0: all in the centre .. 1)")
+parser.add_argument("--reverb", type=float, default=None, metavar="SECONDS",
+                    help="--synthesize: reverberate the clip in a designed room with this RT60 (seeded by --seed; two channels with --stereo)")
+parser.add_argument("--reverb_ir", type=str, default=None, metavar="FILE.wav",
+                    help="--synthesize: reverberate the clip with this recorded impulse response (mono or stereo WAV) instead of --reverb")
+parser.add_argument("--reverb_mix", type=float, default=0.25, metavar="W",
+                    help="--reverb, --reverb_ir: the share of the reverberated signal in [0, 1]; the dry clip keeps 1 - W")
+parser.add_argument("--reverb_predelay", type=float, default=0.0, metavar="SECONDS", help="--reverb, --reverb_ir: silence in front of the room's response")
 parser.add_argument("--generator_ema_decay", type=float, default=0.0,
                     help="keep an exponential moving average of the generator's weights with this decay (0.0: off; progressive GAN uses 0.999)")
 parser.add_argument("--pack_bank", type=str, default=None, metavar="PATH",
@@ -84,28 +98,64 @@ parser.add_argument("--weights", choices=["live", "average"], default="live",
                          "(from --generator_ema_decay of this run, or from the checkpoint's averages)")
 
 
+def check_reverb_args(args):
+    """The four reverb flags against each other and against --synthesize: SystemExit with a message.  -> whether a reverb is asked for."""
+    room, recorded = getattr(args, "reverb", None), getattr(args, "reverb_ir", None)
+    mix, predelay = getattr(args, "reverb_mix", 0.25), getattr(args, "reverb_predelay", 0.0)
+    if room is not None and recorded is not None:
+        raise SystemExit("--reverb (a designed room) and --reverb_ir (a recorded one) exclude each other")
+    wanted = room is not None or recorded is not None
+    if not wanted and (mix != 0.25 or predelay != 0.0):
+        raise SystemExit("--reverb_mix and --reverb_predelay need --reverb or --reverb_ir")
+    if wanted and args.synthesize is None:
+        raise SystemExit("--reverb and --reverb_ir apply to --synthesize only")
+    if room is not None and not room > 0:
+        raise SystemExit(f"--reverb takes a positive RT60 in seconds (got {room})")
+    if wanted and not 0.0 <= mix <= 1.0:
+        raise SystemExit(f"--reverb_mix must be in [0, 1] (got {mix})")
+    if wanted and not predelay >= 0:
+        raise SystemExit(f"--reverb_predelay must not be negative (got {predelay})")
+    return wanted
+
+
 def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     """--synthesize: the score args.synthesize through GANSynth.synthesize into the 16-bit WAV args.output (the kernel's own PCM: [T], or
-    the interleaved [T, 2] of --stereo, which is a two-channel WAV's layout)."""
+    the interleaved [T, 2] of --stereo, which is a two-channel WAV's layout).  With --reverb / --reverb_ir: the unnormalised clip at the
+    output rate, then reverb.apply -- the room, ONE peak and the PCM there."""
     from scipy.io import wavfile
     from gansynth_amd import checkpoint
+    reverb_wanted = check_reverb_args(args)
     if os.path.splitext(args.synthesize)[1].lower() not in (".mid", ".midi", ".json"):
         raise SystemExit(f"--synthesize takes a .mid, .midi or .json score (got {args.synthesize})")
     if restore and checkpoint.latest(args.model_dir) is None:
         log("no checkpoint found: synthesizing from the initial weights")
         restore = False
     info = {}
-    _, pcm = model.synthesize(args.synthesize, model_dir=args.model_dir if restore else None, seed=args.seed,
-                              seconds_per_instrument=args.seconds_per_instrument, release_seconds=args.release_seconds,
-                              want_pcm=True, info=info, pitches=pitches, batch_size=args.batch_size, weights=args.weights,
-                              sample_rate=getattr(args, "output_rate", None), ensemble=getattr(args, "ensemble", False),
-                              stereo=getattr(args, "stereo", False), spread=getattr(args, "spread", 0.0))
+    how = dict(model_dir=args.model_dir if restore else None, seed=args.seed, seconds_per_instrument=args.seconds_per_instrument,
+               release_seconds=args.release_seconds, info=info, pitches=pitches, batch_size=args.batch_size, weights=args.weights,
+               sample_rate=getattr(args, "output_rate", None), ensemble=getattr(args, "ensemble", False),
+               stereo=getattr(args, "stereo", False), spread=getattr(args, "spread", 0.0))
+    if reverb_wanted:
+        from gansynth_amd import reverb
+        clip = model.synthesize(args.synthesize, normalize=False, want_pcm=False, **how)
+        try:   # the room AT the output rate: designed (one channel per channel of the clip, from the one seed) or read
+            if args.reverb is not None:
+                impulse = reverb.design_impulse(info["sample_rate"], args.reverb, channels=clip.dim(), seed=args.seed, predelay=args.reverb_predelay)
+            else:
+                impulse = reverb.read_impulse(args.reverb_ir, info["sample_rate"], predelay=args.reverb_predelay)
+            _, pcm, peak = reverb.apply(clip, impulse.to(clip.device), mix=args.reverb_mix, normalize=True, want_pcm=True)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        info.update(peak=float(peak), reverb_tail=int(impulse.shape[1]) - 1, output_samples=int(pcm.shape[0]))
+    else:
+        _, pcm = model.synthesize(args.synthesize, want_pcm=True, **how)
     if restore:
         log(f"restored {model.restored_from}")
     rate = int(model.spectral_params["sample_rate"])
     wavfile.write(args.output, rate=info["sample_rate"], data=pcm.cpu().numpy())
     log(f"{len(info['notes'])} notes kept, {info['dropped']} dropped, {info['total_samples'] / rate:.3f} seconds, "
-        f"peak {info['peak']:.4f}: written to {args.output}" + (f" at {info['sample_rate']} Hz" if info["sample_rate"] != rate else ""))
+        f"peak {info['peak']:.4f}: written to {args.output}" + (f" at {info['sample_rate']} Hz" if info["sample_rate"] != rate else "")
+        + (f", with a reverb tail of {info['reverb_tail']} samples ({info['reverb_tail'] / info['sample_rate']:.3f} seconds)" if reverb_wanted else ""))
     return info
 
 
@@ -121,6 +171,7 @@ def pack_bank(args, pitches, sources, log=print):
 
 
 def main(args):
+    check_reverb_args(args)
     if args.pack_bank is not None:
         pack_bank(args, range(24, 85), [0])
         return

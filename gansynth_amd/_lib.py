@@ -61,6 +61,17 @@ R = POINTER(GsResample)
 RESAMPLE_TILE = 512   # GS_RESAMPLE_TILE: output samples per block of gs_resample's filter
 
 
+class GsFftConv(ctypes.Structure):
+    """include/gansynth_hip.h: the design of one partitioned FFT convolution (gs_fftconv_design fills it)."""
+    _fields_ = [("n", ctypes.c_int64), ("m", ctypes.c_int64)] + [(n, ctypes.c_int32) for n in ("rows", "ir_rows", "block", "partitions", "blocks", "x_blocks")]
+
+
+V = POINTER(GsFftConv)
+FFTCONV_BLOCK = 2048                                              # GS_FFTCONV_BLOCK: new samples per block of gs_fftconv
+FFTCONV_MAX_TAPS = 1 << 20                                        # GS_FFTCONV_MAX_TAPS
+FFTCONV_HEADER_BYTES = (FFTCONV_BLOCK + FFTCONV_BLOCK // 2 + 8) * 8 + 16   # GS_FFTCONV_HEADER_BYTES
+
+
 SPEC_FWD_GENERIC, SPEC_FWD_WAVE = 0, 1                                                                        # GS_SPEC_FWD_*
 SPEC_GEMM_NONE, SPEC_GEMM_F32_64, SPEC_GEMM_F32_128, SPEC_GEMM_SPLIT_ALL, SPEC_GEMM_SPLIT_TWO, SPEC_GEMM_WIDE_256 = range(6)   # GS_SPEC_GEMM_*
 SPEC_ISTFT_NONE, SPEC_ISTFT_WAVE_OLA, SPEC_ISTFT_WAVE_FRAMES, SPEC_ISTFT_BLOCK_FFT = range(4)                # GS_SPEC_ISTFT_*
@@ -197,6 +208,13 @@ SIGNATURES = {
     "gs_resample_table": (I, [R, I, P]),
     "gs_resample_workspace_bytes": (Z, [R, I, L]),
     "gs_resample": (I, [R, P, P, I, L, L, I, P, P, P, P, Z, P]),
+    # V = POINTER(GsFftConv), the design of one (n, m, rows, ir_rows)
+    "gs_fftconv_design": (I, [L, L, I, I, V]),
+    "gs_fftconv_out_len": (L, [V]),
+    "gs_fftconv_spectrum_bytes": (Z, [V]),
+    "gs_fftconv_workspace_bytes": (Z, [V]),
+    "gs_fftconv_prepare": (I, [V, P, L, P, Z, P]),
+    "gs_fftconv": (I, [V, P, Z, P, L, F, F, I, P, L, P, P, P, Z, P]),
 }
 
 WGRAD_MAX_SOURCES = 4   # GS_WGRAD_MAX_SOURCES

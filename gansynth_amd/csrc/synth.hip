@@ -11,6 +11,7 @@
 // `note_mix_finish_kernel` folds the block maxima in one wave per block (a maximum is exact: the fold order does not show), then
 // scales and quantises its own tile.
 #include "gs_common.h"
+#include "clip_finish.h"
 
 namespace gs {
 
@@ -336,6 +337,15 @@ __global__ __launch_bounds__(MIX_NT) void stereo_finish_kernel(float* __restrict
             }
         }
     }
+}
+
+void launch_clip_finish(float* x, int rows, long n, long row_stride, short* pcm, float* peak, const float* block_max, int n_max, int normalize,
+                        hipStream_t st) {
+    const unsigned grid = (normalize != 0 || pcm != nullptr) ? (unsigned)mix_blocks(n) : 1u;
+    if (rows == 1)
+        hipLaunchKernelGGL(note_mix_finish_kernel, dim3(grid), dim3(MIX_NT), 0, st, x, pcm, peak, block_max, n_max, n, normalize);
+    else
+        hipLaunchKernelGGL(stereo_finish_kernel, dim3(grid), dim3(MIX_NT), 0, st, x, row_stride, pcm, peak, block_max, n_max, n, normalize);
 }
 
 }  // namespace gs

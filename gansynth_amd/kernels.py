@@ -10,6 +10,7 @@ an emulation to check the autograd algebra on CPU, the product never does.
 """
 import contextlib
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -111,6 +112,33 @@ def note_mix_stereo_table(table, rows, length, total):
     return (_lib.GsMixNoteStereo * len(checked))(*[_lib.GsMixNoteStereo(*row, 0) for row in checked])
 
 
+def fft_convolve_shapes(x, impulse, dry, wet):
+    """The host side of fft_convolve: -> (rows, n, ir_rows, m) of x ([n] or [rows, n], rows 1 or 2) and impulse ([m] or [ir_rows, m],
+    ir_rows 1 or rows), both fp32.  ValueError by argument name; needs no device."""
+    for name, t in (("x", x), ("impulse", impulse)):
+        if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.dtype != torch.float32 or t.numel() == 0:
+            got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"fft_convolve: {name} must be a non-empty fp32 vector or [rows, samples] matrix (got {got})")
+    rows, n = (1, int(x.shape[0])) if x.dim() == 1 else (int(x.shape[0]), int(x.shape[1]))
+    ir_rows, m = (1, int(impulse.shape[0])) if impulse.dim() == 1 else (int(impulse.shape[0]), int(impulse.shape[1]))
+    if rows > 2:
+        raise ValueError(f"fft_convolve: x must have 1 or 2 rows -- a clip is mono or stereo (got {rows})")
+    if ir_rows not in (1, rows):
+        raise ValueError(f"fft_convolve: impulse must have 1 row or as many as x, {rows} (got {ir_rows})")
+    if m > _lib.FFTCONV_MAX_TAPS:
+        raise ValueError(f"fft_convolve: impulse has {m} taps, more than {_lib.FFTCONV_MAX_TAPS}")
+    for name, v in (("dry", dry), ("wet", wet)):
+        if not isinstance(v, (int, float)) or isinstance(v, bool) or not math.isfinite(v):
+            raise ValueError(f"fft_convolve: {name} must be a finite number (got {v!r})")
+    return rows, n, ir_rows, m
+
+
+def fft_convolve(x, impulse, dry, wet, normalize=True, want_pcm=False):
+    """HipKernels.fft_convolve of the process-wide kernel object; the shapes are refused here, before a device is asked for."""
+    fft_convolve_shapes(x, impulse, dry, wet)
+    return get().fft_convolve(x, impulse, dry, wet, normalize=normalize, want_pcm=want_pcm)
+
+
 def _checked_notes(what, table, rows, length, total, gains):
     """Rows (onset, hold, release, row, *gains) validated and sorted by (onset, position): what both note tables share."""
     fields = ("onset", "hold", "release", "row") + gains
@@ -165,6 +193,8 @@ class HipKernels(object):
         self.ema_steps = 0        # calls of ema_step / ema_step_dev so far (tests: the averaged generator took the HIP path)
         self.ema_steps_dev = 0
         self._resample = {}       # (rate_in, rate_out, device index) -> (GsResample, device table): resample_design
+        self._fftconv = {}        # impulse tensor's identity -> (the tensor, its prepared spectrum): fft_convolve_spectrum
+        self.fftconv_prepares = 0   # gs_fftconv_prepare calls so far (tests: one per impulse tensor)
 
     # --------------------------------------------------------- prepared-weight workspaces
     def register_param_buffer(self, flat):
@@ -1499,6 +1529,56 @@ class HipKernels(object):
                                         1 if normalize else 0, out.data_ptr(), None if pcm is None else pcm.data_ptr(), peak.data_ptr(),
                                         ws.data_ptr(), ws.numel(), _stream()), "gs_resample")
         return out, pcm, peak
+
+    def fft_convolve_spectrum(self, design, impulse):
+        """The prepared spectrum of `impulse` ([ir_rows, m] fp32 on the device) for gs_fftconv: built by ONE gs_fftconv_prepare per impulse
+        tensor (keyed by its storage, shape, strides and version; the tensor is held, so that its address cannot be reused) and kept for
+        the last few."""
+        key = (impulse.data_ptr(), tuple(impulse.shape), tuple(impulse.stride()), impulse._version, impulse.device.index)
+        hit = self._fftconv.get(key)
+        if hit is None:
+            nbytes = self.lib.gs_fftconv_spectrum_bytes(ctypes.byref(design))
+            spectrum = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=impulse.device)
+            _lib.check(self.lib.gs_fftconv_prepare(ctypes.byref(design), impulse.data_ptr(), int(impulse.stride(0)) if impulse.shape[0] > 1 else
+                                                   int(impulse.shape[1]), spectrum.data_ptr(), spectrum.numel(), _stream()), "gs_fftconv_prepare")
+            while len(self._fftconv) >= 8:
+                self._fftconv.pop(next(iter(self._fftconv)))
+            hit = self._fftconv[key] = (impulse, spectrum)
+            self.fftconv_prepares += 1
+        return hit[1]
+
+    def fft_convolve(self, x, impulse, dry, wet, normalize=True, want_pcm=False):
+        """gs_fftconv (include/gansynth_hip.h): y = dry * x + wet * (impulse convolved with x), row by row.  x: [n] or [rows, n] fp32 on the
+        device, rows 1 or 2, any row stride; impulse: [m] or [ir_rows, m], ir_rows 1 (shared) or rows.  -> (out -- [n + m - 1] or
+        [rows, n + m - 1] fp32, a view of rows that start on 16 bytes --, pcm [n + m - 1] or [n + m - 1, rows] int16 or None, peak [1]
+        fp32 = max |y| over all rows before any scaling); every row is divided by that ONE peak when `normalize` and peak > 1."""
+        rows, n, ir_rows, m = fft_convolve_shapes(x, impulse, dry, wet)
+        for name, t in (("x", x), ("impulse", impulse)):
+            if not t.is_cuda:
+                raise ValueError(f"fft_convolve: {name} must be on the HIP device (it is on {t.device})")
+        if impulse.device != x.device:
+            raise ValueError(f"fft_convolve: impulse is on {impulse.device}, x on {x.device}")
+        mono = x.dim() == 1
+        x2 = x[None] if mono else x
+        if x2.stride(1) != 1 or (rows > 1 and x2.stride(0) < n):
+            x2 = x2.contiguous()
+        h2 = impulse[None] if impulse.dim() == 1 else impulse
+        if h2.stride(1) != 1 or (ir_rows > 1 and h2.stride(0) < m):
+            raise ValueError(f"fft_convolve: the rows of impulse must be contiguous and apart (strides {tuple(impulse.stride())}): its spectrum is "
+                             f"cached by its storage")
+        design = _lib.GsFftConv()
+        _lib.check(self.lib.gs_fftconv_design(n, m, rows, ir_rows, ctypes.byref(design)), "gs_fftconv_design")
+        n_out = n + m - 1
+        stride = (n_out + 3) // 4 * 4
+        out = torch.empty((rows, stride), dtype=torch.float32, device=x.device)[:, :n_out]
+        spectrum = self.fft_convolve_spectrum(design, h2)
+        pcm = torch.empty((n_out,) if mono else (n_out, rows), dtype=torch.int16, device=x.device) if want_pcm else None
+        peak = torch.empty((1,), dtype=torch.float32, device=x.device)
+        ws = _ws(self.lib.gs_fftconv_workspace_bytes(ctypes.byref(design)), x.device)
+        _lib.check(self.lib.gs_fftconv(ctypes.byref(design), spectrum.data_ptr(), spectrum.numel(), x2.data_ptr(), int(x2.stride(0)) if rows > 1 else n,
+                                       float(dry), float(wet), 1 if normalize else 0, out.data_ptr(), int(out.stride(0)) if rows > 1 else n_out,
+                                       None if pcm is None else pcm.data_ptr(), peak.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_fftconv")
+        return (out[0] if mono else out), pcm, peak
 
     def account(self):
         """bench.py: `with K.account() as calls:` lists every kernel-layer call made inside as (method, argument dict, bytes read,

@@ -766,6 +766,55 @@ size_t gs_resample_workspace_bytes(const GsResample* r, int rows, int64_t n_in);
 int gs_resample(const GsResample* r, const float* table_dev, const float* x, int rows, int64_t n_in, int64_t row_stride, int normalize,
                 float* out, int16_t* pcm, float* peak, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Reverb: convolution of a clip with an impulse response, partitioned FFT (gansynth_amd/reverb.py, kernels.fft_convolve; this
+ * project's own rule, DESIGN.md "Reverb") ---------------------------------------------------------------------------------------------
+ * x: [rows] rows of n fp32 samples, `row_stride` elements apart (rows is 1 or 2: a clip is mono or stereo).  h: [ir_rows] rows of m fp32
+ * taps, `ir_stride` apart, ir_rows == 1 (shared) or == rows.  n_out = n + m - 1, and for t in [0, n_out), rh = r when ir_rows == rows else 0:
+ *     y[r][t] = dry * x[r][t] + wet * sum over k in [0, m) of h[rh][k] * x[r][t - k]
+ * where an x index outside [0, n) contributes 0, whatever lies in the stride padding or in the next row.  With lead[rh] the index of the
+ * first non-zero tap of h[rh] (m when there is none), the sum is EXACTLY 0 for t < lead[rh]: a predelay is silent, not nearly silent.
+ * Tail with gs_note_mix_stereo's semantics: ONE peak = max over all rows and t of |y| (exact); out = y / peak (correctly rounded) when
+ * `normalize` and peak > 1, else y; pcm (or NULL): [n_out][rows] interleaved (plain [n_out] for rows == 1), summary_audio_s16's rule applied
+ * to out; peak (or NULL): [1].  out: [rows] rows of n_out samples, `out_stride` apart; the elements between n_out and out_stride are not
+ * touched.
+ * Form: uniform partitioned overlap-save, B = GS_FFTCONV_BLOCK new samples per block, P = ceil(m / B) partitions, J = ceil(n_out / B)
+ * blocks; a 2B-point real transform runs as a B-point complex one (even samples real, odd imaginary) in LDS, fp32, radix-2 Stockham
+ * (natural order in and out), twiddles computed in double and rounded once.  A spectrum is stored as B complex values: slot 0 holds the
+ * two real bins (0 and B) as (re, im), slot k the bin k.  The sum over partitions runs over p ascending, in registers, FMA allowed; the
+ * result is not bit-defined against another FFT, but no atomics: two calls are bit-identical.
+ * gs_fftconv_prepare, once per impulse response (3 launches): the twiddle tables, the transform of every partition of every IR row
+ * (zero-padded to 2B) and lead[] go into the caller's `spectrum` buffer (gs_fftconv_spectrum_bytes:
+ * GS_FFTCONV_HEADER_BYTES + ir_rows * P * B * 8; 16-byte aligned).
+ * gs_fftconv (3 launches; capture-safe: no allocation, no synchronisation): block j of row r covers the samples [(j - 1) B, (j + 1) B),
+ * zero outside [0, n) -- only the XB = min(J, floor((n - 1) / B) + 2) blocks that can hold a sample are transformed --; then one workgroup
+ * per (r, j) accumulates sum over p of X[r][j - p] * H[rh][p] (the p with j - p in [0, XB)), inverts, keeps the last B samples, applies dry
+ * and wet, writes 16 bytes per lane where the row bases are 16-byte aligned and leaves one |max| per block in ws; then the finish kernel
+ * of gs_note_mix (rows == 1) or gs_note_mix_stereo (rows == 2).  ws (gs_fftconv_workspace_bytes: rows * XB * B * 8 + rows * J * 4;
+ * 16-byte aligned).  Every bound the kernels use is recomputed from n and m.
+ * gs_fftconv_design, _out_len, _spectrum_bytes and _workspace_bytes are host arithmetic and need no device.
+ * GS_ERR_ARG with a message and without a launch: n, m or rows <= 0, rows > 2, n > GS_FFTCONV_MAX_N, m > GS_FFTCONV_MAX_TAPS, ir_rows
+ * outside {1, rows}, row_stride < n, ir_stride < m, out_stride < n_out, x / out / spectrum / ir NULL, x / out / ir / peak off 4 bytes, pcm
+ * off 2, spectrum / ws off 16, a workspace or spectrum buffer that is too small, a descriptor whose block / partitions / blocks /
+ * x_blocks do not follow from its n and m.  (The byte queries answer a refusal with 0, gs_fftconv_out_len with the negative code.) */
+#define GS_FFTCONV_BLOCK 2048
+#define GS_FFTCONV_MAX_TAPS (1 << 20)
+#define GS_FFTCONV_MAX_N ((int64_t)1 << 40)
+#define GS_FFTCONV_HEADER_BYTES ((GS_FFTCONV_BLOCK + GS_FFTCONV_BLOCK / 2 + 8) * 8 + 16)   /* stage twiddles, pack twiddles, lead[2] */
+typedef struct GsFftConv {
+    int64_t n, m;              /* samples per row, taps per IR row */
+    int32_t rows, ir_rows;
+    int32_t block;             /* GS_FFTCONV_BLOCK */
+    int32_t partitions;        /* P */
+    int32_t blocks, x_blocks;  /* J, XB */
+} GsFftConv;                   /* 40 bytes */
+int gs_fftconv_design(int64_t n, int64_t m, int rows, int ir_rows, GsFftConv* out);
+int64_t gs_fftconv_out_len(const GsFftConv* c);
+size_t gs_fftconv_spectrum_bytes(const GsFftConv* c);
+size_t gs_fftconv_workspace_bytes(const GsFftConv* c);
+int gs_fftconv_prepare(const GsFftConv* c, const float* ir, int64_t ir_stride, void* spectrum, size_t spectrum_bytes, void* stream);
+int gs_fftconv(const GsFftConv* c, const void* spectrum, size_t spectrum_bytes, const float* x, int64_t row_stride, float dry, float wet,
+               int normalize, float* out, int64_t out_stride, int16_t* pcm, float* peak, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
