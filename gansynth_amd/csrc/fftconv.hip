@@ -16,7 +16,7 @@
 //                        row), forward FFT, the unpacking to the real signal's spectrum.  The partitions of h (prepare) and the blocks of x.
 //   fc_mac_kernel        one block per (row, j): sum over p of X[j - p] * H[p] in registers (a lane owns 4 bin pairs (k, B - k): 16
 //                        accumulators), the packing, inverse FFT, the last B samples times wet plus dry * x, 16-byte stores, one |max| a block.
-// The finish (ONE peak, quotient, PCM) is synth.hip's kernel through launch_clip_finish.
+// The finish (ONE peak, quotient, PCM) is clip_finish.hip's, through launch_clip_finish: one clip of `rows` channels.
 #include <math.h>
 
 #include "clip_finish.h"
@@ -235,16 +235,7 @@ __global__ __launch_bounds__(FC_NT) void fc_mac_kernel(const float2* __restrict_
                 if (t0 + i < n_out) { mx = fmaxf(mx, fabsf(y[i])); o_row[t0 + i] = y[i]; }
         }
     }
-    mx = wave_extreme<true>(mx);
-    __shared__ float part[FC_NT / 64];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float m = part[0];
-#pragma unroll
-        for (int w = 1; w < FC_NT / 64; ++w) m = fmaxf(m, part[w]);
-        block_max[(size_t)r * gridDim.x + j] = m;
-    }
+    publish_block_max<FC_NT>(mx, block_max + (size_t)r * gridDim.x + j);
 }
 
 // ------------------------------------------------------------------------------------------------------------- host: the design
@@ -351,7 +342,7 @@ extern "C" int gs_fftconv(const GsFftConv* c, const void* spectrum, size_t spect
                        tables, (int)c->partitions, c->ir_rows == 1 ? 1 : 0, x, (long)c->n, (long)row_stride, dry, wet, n_out, out, (long)out_stride,
                        block_max);
     if (normalize != 0 || pcm != nullptr || peak != nullptr)
-        launch_clip_finish(out, c->rows, n_out, (long)out_stride, reinterpret_cast<short*>(pcm), peak, block_max, c->rows * c->blocks, normalize, st);
+        launch_clip_finish(out, c->rows, 1, n_out, (long)out_stride, reinterpret_cast<short*>(pcm), peak, block_max, c->rows * c->blocks, normalize, st);
     GS_CHECK_LAUNCH();
     return 0;
 }

@@ -9,9 +9,11 @@
 // first output); a lane's own offset and phase follow from r0 + l * down in 32 bits.  A lane reads its tap row from the table (rows
 // padded to 16 bytes: GS_RESAMPLE_ROW) as float4, the samples from LDS, and sums into four chains by k mod 4, folded at the end -- a
 // fixed order, so two calls agree bit for bit.  One |max| per block goes to the workspace.
-// `resample_finish_kernel`: every block folds its row's block maxima (a maximum is exact), then scales and quantises its own tile.
+// The finish of clip_finish.hip, one clip a row: every block folds its row's block maxima (a maximum is exact), then scales and quantises
+// its own tile.
 #include <math.h>
 
+#include "clip_finish.h"
 #include "gs_common.h"
 
 namespace gs {
@@ -19,12 +21,9 @@ namespace gs {
 constexpr int RS_NT = 256;        // threads per block
 constexpr int RS_PER_LANE = 2;    // outputs per lane of the filter (RS_NT apart: the stores of a wave stay contiguous)
 constexpr int RS_TILE = RS_NT * RS_PER_LANE;
-constexpr int RS_FIN_STEPS = 4;   // 4-sample packs per lane of the finish
-constexpr int RS_FIN_TILE = RS_NT * 4 * RS_FIN_STEPS;
 static_assert(RS_TILE == GS_RESAMPLE_TILE, "include/gansynth_hip.h states the tile");
 
 static inline long rs_tiles(long n_out) { return (n_out + RS_TILE - 1) / RS_TILE; }
-static inline long rs_fin_tiles(long n_out) { return (n_out + RS_FIN_TILE - 1) / RS_FIN_TILE; }
 static inline int rs_row(int taps) { return GS_RESAMPLE_ROW(taps); }
 // the largest span of input samples a tile needs: its last output starts at most ((up - 1) + (RS_TILE - 1) * down) / up behind its first
 static inline long rs_span(int up, int down, int taps) { return ((long)(up - 1) + (long)(RS_TILE - 1) * down) / up + taps; }
@@ -77,64 +76,7 @@ __global__ __launch_bounds__(RS_NT) void resample_kernel(const float* __restrict
         out[(size_t)row * n_out + j] = y;
         m = fmaxf(m, fabsf(y));
     }
-    m = wave_extreme<true>(m);
-    __shared__ float part[RS_NT / 64];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float r = part[0];
-#pragma unroll
-        for (int w = 1; w < RS_NT / 64; ++w) r = fmaxf(r, part[w]);
-        block_max[(size_t)row * tiles + blockIdx.x] = r;
-    }
-}
-
-// grid (finish tiles, or 1 when only the peaks are wanted; rows).  out = y / peak[row] when `normalize` and peak[row] > 1 (else untouched); pcm from out
-__global__ __launch_bounds__(RS_NT) void resample_finish_kernel(float* __restrict__ out, short* __restrict__ pcm, float* __restrict__ peak_out,
-                                                                const float* __restrict__ block_max, int tiles, long n_out, int normalize) {
-    const int row = blockIdx.y;
-    float m = 0.f;
-    for (int s = threadIdx.x; s < tiles; s += RS_NT) m = fmaxf(m, block_max[(size_t)row * tiles + s]);
-    m = wave_extreme<true>(m);
-    __shared__ float part[RS_NT / 64];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-    __syncthreads();
-    float peak = part[0];
-#pragma unroll
-    for (int w = 1; w < RS_NT / 64; ++w) peak = fmaxf(peak, part[w]);
-    if (blockIdx.x == 0 && threadIdx.x == 0 && peak_out != nullptr) peak_out[row] = peak;
-    const bool scale = normalize != 0 && peak > 1.f;
-    if (!scale && pcm == nullptr) return;
-    float* __restrict__ o = out + (size_t)row * n_out;
-    short* __restrict__ q = pcm != nullptr ? pcm + (size_t)row * n_out : nullptr;
-    const long tile_begin = (long)blockIdx.x * RS_FIN_TILE;
-    const long tile_end = tile_begin + RS_FIN_TILE < n_out ? tile_begin + RS_FIN_TILE : n_out;
-    const bool wide = (reinterpret_cast<uintptr_t>(o) & 15) == 0 && (reinterpret_cast<uintptr_t>(q) & 7) == 0;   // block-uniform
-#pragma unroll
-    for (int u = 0; u < RS_FIN_STEPS; ++u) {
-        const long t0 = tile_begin + ((long)u * RS_NT + threadIdx.x) * 4;
-        if (t0 + 4 <= tile_end && wide) {
-            float v[4];
-            ld4(o + t0, v);
-            if (scale) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = __fdiv_rn(v[j], peak);
-                st4(o + t0, v);
-            }
-            if (q != nullptr)
-                *reinterpret_cast<uint2*>(q + t0) =
-                    make_uint2(((unsigned int)quantise_s16(v[0]) & 0xffffu) | ((unsigned int)quantise_s16(v[1]) << 16),
-                               ((unsigned int)quantise_s16(v[2]) & 0xffffu) | ((unsigned int)quantise_s16(v[3]) << 16));
-        } else {
-            for (int j = 0; j < 4; ++j) {
-                const long t = t0 + j;
-                if (t >= tile_end) break;
-                float v = o[t];
-                if (scale) { v = __fdiv_rn(v, peak); o[t] = v; }
-                if (q != nullptr) q[t] = (short)quantise_s16(v);
-            }
-        }
-    }
+    publish_block_max<RS_NT>(m, block_max + (size_t)row * tiles + blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------------------- host: the design
@@ -244,7 +186,7 @@ extern "C" int gs_resample(const GsResample* r, const float* table_dev, const fl
     GS_CHECK_ARG(row_stride >= n_in, "resample: row_stride %lld is below n_in %lld", (long long)row_stride, (long long)n_in);
     GS_CHECK_ARG(x && out && table_dev, "resample: null pointer (x, out and table are required)");
     const long n_out = (long)((n_in * r->up + r->down - 1) / r->down);
-    const long tiles = rs_tiles(n_out), fin = rs_fin_tiles(n_out);
+    const long tiles = rs_tiles(n_out);
     GS_CHECK_ARG(tiles <= 0x7fffffffL, "resample: row too long (n_out %ld)", n_out);
     GS_CHECK_ARG((reinterpret_cast<uintptr_t>(table_dev) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 3) == 0 &&
                  (reinterpret_cast<uintptr_t>(out) & 3) == 0 && (reinterpret_cast<uintptr_t>(pcm) & 1) == 0 &&
@@ -258,8 +200,7 @@ extern "C" int gs_resample(const GsResample* r, const float* table_dev, const fl
     hipLaunchKernelGGL(resample_kernel, dim3((unsigned)tiles, (unsigned)rows), dim3(RS_NT), lds, st, x, (long)n_in, (long)row_stride, table_dev,
                        (int)r->up, (int)r->down, (int)r->taps, n_out, (int)tiles, out, block_max);
     if (normalize != 0 || pcm != nullptr || peak != nullptr)
-        hipLaunchKernelGGL(resample_finish_kernel, dim3((unsigned)((normalize != 0 || pcm != nullptr) ? fin : 1), (unsigned)rows), dim3(RS_NT), 0, st,
-                           out, reinterpret_cast<short*>(pcm), peak, static_cast<const float*>(block_max), (int)tiles, n_out, normalize);
+        launch_clip_finish(out, 1, rows, n_out, n_out, reinterpret_cast<short*>(pcm), peak, block_max, (int)tiles, normalize, st);
     GS_CHECK_LAUNCH();
     return 0;
 }

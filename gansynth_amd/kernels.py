@@ -97,19 +97,25 @@ def _rows_cols(x):
     return x.shape[0], x.shape[1]
 
 
+def _note_table(channels, table, rows, length, total):
+    """The checked, sorted rows of `table` as a ctypes array of the note struct of `channels` (1 or 2)."""
+    name, gains, note = (("note_mix", ("gain",), _lib.GsMixNote) if channels == 1 else
+                         ("note_mix_stereo", ("gain_l", "gain_r"), _lib.GsMixNoteStereo))   # (GsMixNoteStereo.reserved stays 0)
+    checked = _checked_notes(name, table, rows, length, total, gains)
+    return (note * len(checked))(*[note(*row) for row in checked])
+
+
 def note_mix_table(table, rows, length, total):
     """The host side of note_mix: validates `table` -- (onset, hold, release, row, gain) per note -- against the waves' shape and the
     clip length, sorts it by (onset, position) and returns the rows as a ctypes array of GsMixNote.  ValueError by note index and
     field name.  (A note may run past `total`: it is clipped there.)"""
-    checked = _checked_notes("note_mix", table, rows, length, total, ("gain",))
-    return (_lib.GsMixNote * len(checked))(*[_lib.GsMixNote(*row) for row in checked])
+    return _note_table(1, table, rows, length, total)
 
 
 def note_mix_stereo_table(table, rows, length, total):
     """The host side of note_mix_stereo: note_mix_table's checks and order for rows (onset, hold, release, row, gain_l, gain_r), as a
     ctypes array of GsMixNoteStereo."""
-    checked = _checked_notes("note_mix_stereo", table, rows, length, total, ("gain_l", "gain_r"))
-    return (_lib.GsMixNoteStereo * len(checked))(*[_lib.GsMixNoteStereo(*row, 0) for row in checked])
+    return _note_table(2, table, rows, length, total)
 
 
 def fft_convolve_shapes(x, impulse, dry, wet):
@@ -1407,50 +1413,40 @@ class HipKernels(object):
                    "gs_summary_audio_s16")
         return out
 
+    def _note_mix(self, channels, waves, table, total, normalize, want_pcm):
+        """note_mix (channels 1: out [total], pcm [total]) and note_mix_stereo (2: out [2, total] with rows on 16 bytes, pcm [total, 2])."""
+        name = "note_mix" if channels == 1 else "note_mix_stereo"
+        if waves.dim() != 2 or waves.dtype != torch.float32:
+            raise ValueError(f"{name}: waves must be [rows, L] fp32 (got {tuple(waves.shape)} {waves.dtype})")
+        rows, length = int(waves.shape[0]), int(waves.shape[1])
+        total = int(total)
+        arr = (note_mix_table if channels == 1 else note_mix_stereo_table)(table, rows, length, total)
+        if waves.stride(1) != 1 or (rows > 1 and waves.stride(0) < length):
+            waves = waves.contiguous()
+        notes = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(waves.device)   # uploaded once
+        stride = (total + 3) // 4 * 4
+        out = torch.empty((total,) if channels == 1 else (2, stride), dtype=torch.float32, device=waves.device)
+        pcm = torch.empty((total,) if channels == 1 else (total, 2), dtype=torch.int16, device=waves.device) if want_pcm else None
+        peak = torch.empty((1,), dtype=torch.float32, device=waves.device)
+        ws = _ws(getattr(self.lib, f"gs_{name}_workspace_bytes")(total), waves.device)
+        _lib.check(getattr(self.lib, f"gs_{name}")(waves.data_ptr(), rows, length, int(waves.stride(0)) if rows > 1 else length, notes.data_ptr(),
+                                                   len(arr), total, 1 if normalize else 0, out.data_ptr(), *(() if channels == 1 else (stride,)),
+                                                   None if pcm is None else pcm.data_ptr(), peak.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                   f"gs_{name}")
+        return (out if channels == 1 else out[:, :total]), pcm, peak
+
     def note_mix(self, waves, table, total, normalize=True, want_pcm=False):
         """gs_note_mix (include/gansynth_hip.h): the notes of `table` -- host rows (onset, hold, release, row, gain) -- mixed from the rows of
         waves [rows, L] fp32 into one clip.  -> (out [total] fp32, pcm [total] int16 or None, peak [1] fp32 = max |mix|); out is the mix
         divided by peak when `normalize` and peak > 1."""
-        if waves.dim() != 2 or waves.dtype != torch.float32:
-            raise ValueError(f"note_mix: waves must be [rows, L] fp32 (got {tuple(waves.shape)} {waves.dtype})")
-        rows, length = int(waves.shape[0]), int(waves.shape[1])
-        total = int(total)
-        arr = note_mix_table(table, rows, length, total)
-        if waves.stride(1) != 1 or (rows > 1 and waves.stride(0) < length):
-            waves = waves.contiguous()
-        notes = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(waves.device)   # uploaded once
-        out = torch.empty((total,), dtype=torch.float32, device=waves.device)
-        pcm = torch.empty((total,), dtype=torch.int16, device=waves.device) if want_pcm else None
-        peak = torch.empty((1,), dtype=torch.float32, device=waves.device)
-        ws = _ws(self.lib.gs_note_mix_workspace_bytes(total), waves.device)
-        _lib.check(self.lib.gs_note_mix(waves.data_ptr(), rows, length, int(waves.stride(0)) if rows > 1 else length, notes.data_ptr(), len(arr), total,
-                                        1 if normalize else 0, out.data_ptr(), None if pcm is None else pcm.data_ptr(), peak.data_ptr(),
-                                        ws.data_ptr(), ws.numel(), _stream()), "gs_note_mix")
-        return out, pcm, peak
+        return self._note_mix(1, waves, table, total, normalize, want_pcm)
 
     def note_mix_stereo(self, waves, table, total, normalize=True, want_pcm=False):
         """gs_note_mix_stereo (include/gansynth_hip.h): the notes of `table` -- host rows (onset, hold, release, row, gain_l, gain_r) -- mixed
         from the rows of waves [rows, L] fp32 into two channels with ONE peak.  -> (out [2, total] fp32 -- a view of [2, S], S = total
         rounded up to 4, so that both rows start on 16 bytes --, pcm [total, 2] int16 or None, peak [1] fp32 = max |mix| over both
         channels); both channels are divided by peak when `normalize` and peak > 1."""
-        if waves.dim() != 2 or waves.dtype != torch.float32:
-            raise ValueError(f"note_mix_stereo: waves must be [rows, L] fp32 (got {tuple(waves.shape)} {waves.dtype})")
-        rows, length = int(waves.shape[0]), int(waves.shape[1])
-        total = int(total)
-        arr = note_mix_stereo_table(table, rows, length, total)
-        if waves.stride(1) != 1 or (rows > 1 and waves.stride(0) < length):
-            waves = waves.contiguous()
-        notes = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(waves.device)   # uploaded once
-        stride = (total + 3) // 4 * 4
-        out = torch.empty((2, stride), dtype=torch.float32, device=waves.device)
-        pcm = torch.empty((total, 2), dtype=torch.int16, device=waves.device) if want_pcm else None
-        peak = torch.empty((1,), dtype=torch.float32, device=waves.device)
-        ws = _ws(self.lib.gs_note_mix_stereo_workspace_bytes(total), waves.device)
-        _lib.check(self.lib.gs_note_mix_stereo(waves.data_ptr(), rows, length, int(waves.stride(0)) if rows > 1 else length, notes.data_ptr(),
-                                               len(arr), total, 1 if normalize else 0, out.data_ptr(), stride,
-                                               None if pcm is None else pcm.data_ptr(), peak.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-                   "gs_note_mix_stereo")
-        return out[:, :total], pcm, peak
+        return self._note_mix(2, waves, table, total, normalize, want_pcm)
 
     def stereo_finish(self, x, normalize=True, want_pcm=False):
         """gs_stereo_finish (include/gansynth_hip.h): the second stage of note_mix_stereo on a clip x [2, n] fp32 that did not come from it

@@ -997,18 +997,17 @@ class GANSynth(Iterations, DataParallel, Capture):
                 rows = [min(i, count - 1) for i in range(lo, lo + batch)]   # the last chunk repeats its last row
                 wave = self._generate_batch(lat[rows].to(dev), labels[rows].to(dev))
                 waves[lo:lo + batch].copy_(wave[:min(batch, count - lo)])
-        if stereo and (sample_rate is None or int(sample_rate) == int(sr)):
-            clip, pcm, peak = kernels.get().note_mix_stereo(waves, table, total, normalize=normalize, want_pcm=want_pcm)
-        elif stereo:
-            mix, _, _ = kernels.get().note_mix_stereo(waves, table, total, normalize=False, want_pcm=False)
-            clip, _, _ = kernels.get().resample(mix, int(sr), int(sample_rate), normalize=False, want_pcm=False)
-            clip, pcm, peak = kernels.get().stereo_finish(clip, normalize=normalize, want_pcm=want_pcm)
-        elif sample_rate is None or int(sample_rate) == int(sr):
-            clip, pcm, peak = kernels.get().note_mix(waves, table, total, normalize=normalize, want_pcm=want_pcm)
-        else:
-            mix, _, _ = kernels.get().note_mix(waves, table, total, normalize=False, want_pcm=False)
-            clip, pcm, peak = kernels.get().resample(mix, int(sr), int(sample_rate), normalize=normalize, want_pcm=want_pcm)
-            clip, pcm = clip[0], (pcm[0] if want_pcm else None)
+        # mix, then resample if asked, then (two resampled channels) the joint finish: only the last stage normalises and quantises
+        K = kernels.get()
+        resampled = sample_rate is not None and int(sample_rate) != int(sr)
+        last, unfinished = dict(normalize=normalize, want_pcm=want_pcm), dict(normalize=False, want_pcm=False)
+        clip, pcm, peak = (K.note_mix_stereo if stereo else K.note_mix)(waves, table, total, **(unfinished if resampled else last))
+        if resampled:
+            clip, pcm, peak = K.resample(clip, int(sr), int(sample_rate), **(unfinished if stereo else last))
+            if stereo:
+                clip, pcm, peak = K.stereo_finish(clip, **last)
+            else:
+                clip, pcm = clip[0], (pcm[0] if want_pcm else None)
         if info is not None:
             info.update(notes=kept, dropped=dropped, total_samples=total, latents=lat, peak=float(peak),
                         sample_rate=int(sr if sample_rate is None else sample_rate), output_samples=int(clip.shape[-1]))

@@ -62,8 +62,9 @@ def mix(waves, table, total):
 
 def mix_f32(waves, table, total):
     """The same sum carried out in fp32 in the stated order, every operation rounded on its own: fl(1 / (release + 1)), the envelope's
-    product, gain * env, the product with the sample, the running sum.  (The kernel is NOT tested against this: it shows on the CPU how
-    far an honest fp32 evaluation sits inside the bound the kernel is held to.)"""
+    product, gain * env, the product with the sample, the running sum.  (The kernel computes exactly this: tests/test_notes_gpu.py and
+    tests/test_ensemble_gpu.py hold both channel counts to it bit for bit; on the CPU it shows how far an honest fp32 evaluation sits
+    inside the bound of the float64 comparison.)"""
     waves = np.asarray(waves, dtype=np.float32)
     out = np.zeros(total, dtype=np.float32)
     for onset, hold, release, row, gain in _sorted(table):

@@ -87,6 +87,15 @@ def test_each_channel_is_the_mono_mix(dense, case):
     assert none is None and torch.equal(only_mix, got)
 
 
+def test_each_side_is_the_stated_fp32_sum(dense):
+    """Bit for bit tests/stereo_ref.py's mix_f32 -- tests/synth_ref.py's fp32 sum in the stated order, side by side -- on three tiles and
+    on less than a tile with a 3-sample tail: both channels of the one kernel are held to the header's words themselves."""
+    d = dense[0.2]
+    assert np.array_equal(d["mix"].cpu().numpy(), STR.mix_f32(d["host"], d["table"], TOTAL))
+    got, _, _ = _raw(d["waves"], SMALL, 1003)
+    assert np.array_equal(got.cpu().numpy(), STR.mix_f32(d["host"], SMALL, 1003))
+
+
 @pytest.mark.parametrize("lean", [0.2, 0.8])
 def test_mix_against_the_reference(dense, lean):
     d = dense[lean]

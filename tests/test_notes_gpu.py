@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from oracle import torch_ref as R
+from tests import stereo_ref as STR
 from tests import synth_ref as SRF
 
 pytestmark = pytest.mark.gpu
@@ -83,6 +84,20 @@ def dense():
 
 def test_mix_against_the_reference(dense):
     _check(dense["mix"], dense["waves"], dense["table"], dense["total"], "dense case")
+
+
+SMALL = [(0, 900, 103, 0, 1.0), (3, 500, 0, 1, 0.5), (250, 64, 64, 2, 0.875), (990, 1, 400, 3, 0.7)]   # the last one cut at total = 1003
+
+
+def test_the_mix_is_the_stated_fp32_sum(dense):
+    """Bit for bit tests/synth_ref.py's mix_f32 -- fl(1 / (release + 1)), the envelope's product, gain * env, the product with the sample,
+    the running sum in table order, every operation rounded on its own, none contracted -- on the dense case and on less than a tile
+    with a 3-sample tail: the kernel's arithmetic is held to the header's words, not to a bound around them."""
+    waves, table, total = dense["waves"], dense["table"], dense["total"]
+    assert np.array_equal(dense["mix"].cpu().numpy(), SRF.mix_f32(waves.cpu().numpy(), table, total))
+    few = STR.dense_table()[0][:4, :L]                                                  # (the waves of tests/test_ensemble_gpu.py's like-named case)
+    out, _, _ = _K().note_mix(torch.from_numpy(few).cuda(), SMALL, 1003, normalize=False)
+    assert np.array_equal(out.cpu().numpy(), SRF.mix_f32(few, SMALL, 1003))
 
 
 def _waves(rows, length=L, seed=1):

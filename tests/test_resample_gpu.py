@@ -164,25 +164,32 @@ def _raw(pair, x, normalize, want_pcm, want_peak):
 
 
 def test_peak_normalisation_and_pcm():
-    """One call, two rows: a +-1 square wave, whose band-limited interpolation overshoots 1, and a quiet row.  (n_out = 12003 is odd, so
-    the second row starts off the 16-byte grid: both the wide and the sample-by-sample form of the second launch run.)"""
+    """One call, three rows, each finished by its OWN peak: a +-1 square wave, whose band-limited interpolation overshoots 1, a quiet row
+    that is left alone, and a loud sine with another peak above 1.  The input rows lie 4006 apart (a padded stride that 4 does not
+    divide) and n_out = 12003 (n_out % 4 == 3), so the second and third row of out and of pcm start off the 16-byte grid: the wide form
+    of the second launch runs on the first row and the sample-by-sample form on the others, a 3-sample tail behind each."""
     K = _K()
     pair = (16000, 48000)
     n_in = 4001
     t = np.arange(n_in)
-    x = np.stack([np.where((t // 25) % 2 == 0, 1.0, -1.0), 0.25 * np.sin(0.05 * t)]).astype(np.float32)
-    dev = torch.from_numpy(x).cuda()
+    x = np.stack([np.where((t // 25) % 2 == 0, 1.0, -1.0), 0.25 * np.sin(0.05 * t), 1.75 * np.sin(0.03 * t)]).astype(np.float32)
+    store = torch.full((3, 4006), float("nan"))
+    store[:, :n_in] = torch.from_numpy(x)
+    dev = store.cuda()[:, :n_in]
+    assert dev.stride(0) == 4006
     y, none, peak0 = K.resample(dev, *pair)
-    assert none is None and tuple(y.shape) == (2, 12003)
+    assert none is None and tuple(y.shape) == (3, 12003) and y.shape[1] % 4 == 3 and y[1].data_ptr() % 16 != 0 and y[2].data_ptr() % 16 != 0
     _check(y.cpu().numpy(), x, pair, "square wave")
     exact = y.abs().max(dim=1).values
     assert torch.equal(peak0, exact) and float(exact[0]) > 1.0 and float(exact[1]) <= 0.5     # a maximum is exact
+    assert float(exact[2]) > 1.5 and float(exact[2]) != float(exact[0])                      # (a row's peak is its own)
     out, pcm, peak = K.resample(dev, *pair, normalize=True, want_pcm=True)
     assert torch.equal(peak, exact)                                                             # the peak of y, not of out
     yn, on = y.cpu().numpy(), out.cpu().numpy()
     assert np.array_equal(on[0], yn[0] / np.float32(exact[0].item()))                            # IEEE division: correctly rounded
     assert np.array_equal(on[1], yn[1]) and float(np.abs(on[0]).max()) == 1.0                    # the quiet row is left alone
-    assert torch.equal(pcm, K.summary_audio_s16(out, count=2)) and np.array_equal(pcm.cpu().numpy(), RR.pcm16(on))
+    assert np.array_equal(on[2], yn[2] / np.float32(exact[2].item())) and float(np.abs(on[2]).max()) == 1.0
+    assert torch.equal(pcm, K.summary_audio_s16(out, count=3)) and np.array_equal(pcm.cpu().numpy(), RR.pcm16(on))
     # without normalisation the PCM clips, by the same rule
     plain, pcm, _ = K.resample(dev, *pair, normalize=False, want_pcm=True)
     assert torch.equal(plain, y) and np.array_equal(pcm.cpu().numpy(), RR.pcm16(yn)) and int(pcm[0].max()) == 32767
