@@ -36,6 +36,13 @@ resampler and the ONE peak normalisation, and the file grows by the tail (gansyn
 
     python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --output_rate 48000 --reverb 1.8 --reverb_mix 0.3 --output quartet.wav
 
+`--limit DB` (not in the reference) ends the chain of `--synthesize` with a look-ahead limiter instead of the division by the peak: the
+clip is scaled so that its peak would stand `--limit_drive DB` (default 6) above the ceiling of DB dBFS (<= 0), and a smooth gain, looking
+`--limit_lookahead SECONDS` ahead (default 0.005), pulls back only the peaks; no sample of the file exceeds the ceiling
+(gansynth_amd/limiter.py, DESIGN.md "Limiter"):
+
+    python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --output_rate 48000 --reverb 1.8 --limit -1 --limit_drive 9 --output quartet.wav
+
 `--pack_bank` / `--bank` (not in the reference): the notes packed once into one file (on any machine, no GPU needed), then held on the
 device and drawn there, batch for batch what `--filenames` yields (gansynth_amd/bank.py, DESIGN.md "Resident notes"):
 
@@ -44,6 +51,7 @@ device and drawn there, batch for batch what `--filenames` yields (gansynth_amd/
 """
 import argparse
 import glob
+import math
 import os
 
 import torch
@@ -87,6 +95,11 @@ parser.add_argument("--reverb_ir", type=str, default=None, metavar="FILE.wav",
 parser.add_argument("--reverb_mix", type=float, default=0.25, metavar="W",
                     help="--reverb, --reverb_ir: the share of the reverberated signal in [0, 1]; the dry clip keeps 1 - W")
 parser.add_argument("--reverb_predelay", type=float, default=0.0, metavar="SECONDS", help="--reverb, --reverb_ir: silence in front of the room's response")
+parser.add_argument("--limit", type=float, default=None, metavar="DB",
+                    help="--synthesize: end with a look-ahead limiter at this ceiling in dBFS (<= 0) instead of the division by the peak")
+parser.add_argument("--limit_drive", type=float, default=6.0, metavar="DB",
+                    help="--limit: how far above the ceiling the clip's peak is driven before the limiter brings it back (>= 0; 0: peak normalisation)")
+parser.add_argument("--limit_lookahead", type=float, default=0.005, metavar="SECONDS", help="--limit: the limiter's look-ahead (attack and release)")
 parser.add_argument("--generator_ema_decay", type=float, default=0.0,
                     help="keep an exponential moving average of the generator's weights with this decay (0.0: off; progressive GAN uses 0.999)")
 parser.add_argument("--pack_bank", type=str, default=None, metavar="PATH",
@@ -118,13 +131,35 @@ def check_reverb_args(args):
     return wanted
 
 
+def check_limit_args(args):
+    """The three limiter flags against each other and against --synthesize: SystemExit with a message.  -> whether a limiter is asked for."""
+    ceiling = getattr(args, "limit", None)
+    drive, lookahead = getattr(args, "limit_drive", 6.0), getattr(args, "limit_lookahead", 0.005)
+    wanted = ceiling is not None
+    if not wanted and (drive != 6.0 or lookahead != 0.005):
+        raise SystemExit("--limit_drive and --limit_lookahead need --limit")
+    if wanted and args.synthesize is None:
+        raise SystemExit("--limit applies to --synthesize only")
+    if wanted and not ceiling <= 0:
+        raise SystemExit(f"--limit takes a ceiling in dBFS, at most 0 (got {ceiling})")
+    if wanted and not 0 <= drive < float("inf"):
+        raise SystemExit(f"--limit_drive must be a non-negative number of dB (got {drive})")
+    if wanted and not 0 <= lookahead < float("inf"):
+        raise SystemExit(f"--limit_lookahead must be a non-negative number of seconds (got {lookahead})")
+    if wanted and ceiling == float("-inf"):
+        raise SystemExit(f"--limit takes a finite ceiling in dBFS (got {ceiling})")
+    return wanted
+
+
 def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     """--synthesize: the score args.synthesize through GANSynth.synthesize into the 16-bit WAV args.output (the kernel's own PCM: [T], or
     the interleaved [T, 2] of --stereo, which is a two-channel WAV's layout).  With --reverb / --reverb_ir: the unnormalised clip at the
-    output rate, then reverb.apply -- the room, ONE peak and the PCM there."""
+    output rate, then reverb.apply -- the room, ONE peak and the PCM there.  With --limit: whichever stage comes last hands over its
+    unnormalised clip and its peak, and limiter.apply writes the PCM."""
     from scipy.io import wavfile
     from gansynth_amd import checkpoint
     reverb_wanted = check_reverb_args(args)
+    limit_wanted = check_limit_args(args)
     if os.path.splitext(args.synthesize)[1].lower() not in (".mid", ".midi", ".json"):
         raise SystemExit(f"--synthesize takes a .mid, .midi or .json score (got {args.synthesize})")
     if restore and checkpoint.latest(args.model_dir) is None:
@@ -135,19 +170,29 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
                release_seconds=args.release_seconds, info=info, pitches=pitches, batch_size=args.batch_size, weights=args.weights,
                sample_rate=getattr(args, "output_rate", None), ensemble=getattr(args, "ensemble", False),
                stereo=getattr(args, "stereo", False), spread=getattr(args, "spread", 0.0))
+    if reverb_wanted or limit_wanted:   # only the last stage normalises (or limits) and quantises
+        clip = model.synthesize(args.synthesize, normalize=False, want_pcm=False, **how)
     if reverb_wanted:
         from gansynth_amd import reverb
-        clip = model.synthesize(args.synthesize, normalize=False, want_pcm=False, **how)
         try:   # the room AT the output rate: designed (one channel per channel of the clip, from the one seed) or read
             if args.reverb is not None:
                 impulse = reverb.design_impulse(info["sample_rate"], args.reverb, channels=clip.dim(), seed=args.seed, predelay=args.reverb_predelay)
             else:
                 impulse = reverb.read_impulse(args.reverb_ir, info["sample_rate"], predelay=args.reverb_predelay)
-            _, pcm, peak = reverb.apply(clip, impulse.to(clip.device), mix=args.reverb_mix, normalize=True, want_pcm=True)
+            clip, pcm, peak = reverb.apply(clip, impulse.to(clip.device), mix=args.reverb_mix, normalize=not limit_wanted, want_pcm=not limit_wanted)
         except ValueError as e:
             raise SystemExit(str(e))
-        info.update(peak=float(peak), reverb_tail=int(impulse.shape[1]) - 1, output_samples=int(pcm.shape[0]))
-    else:
+        info.update(peak=float(peak), reverb_tail=int(impulse.shape[1]) - 1, output_samples=int(clip.shape[-1]))
+    if limit_wanted:   # the clip as the stage before left it, and that stage's peak
+        from gansynth_amd import limiter
+        try:
+            _, pcm, out_peak, min_gain = limiter.apply(clip, info["sample_rate"], ceiling_db=args.limit, drive_db=args.limit_drive,
+                                                       lookahead_seconds=args.limit_lookahead, peak=info["peak"], want_pcm=True)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        info.update(limit_ceiling_db=float(args.limit), limit_drive_db=float(args.limit_drive), limit_peak=float(out_peak),
+                    limit_min_gain=float(min_gain))
+    elif not reverb_wanted:
         _, pcm = model.synthesize(args.synthesize, want_pcm=True, **how)
     if restore:
         log(f"restored {model.restored_from}")
@@ -155,7 +200,9 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     wavfile.write(args.output, rate=info["sample_rate"], data=pcm.cpu().numpy())
     log(f"{len(info['notes'])} notes kept, {info['dropped']} dropped, {info['total_samples'] / rate:.3f} seconds, "
         f"peak {info['peak']:.4f}: written to {args.output}" + (f" at {info['sample_rate']} Hz" if info["sample_rate"] != rate else "")
-        + (f", with a reverb tail of {info['reverb_tail']} samples ({info['reverb_tail'] / info['sample_rate']:.3f} seconds)" if reverb_wanted else ""))
+        + (f", with a reverb tail of {info['reverb_tail']} samples ({info['reverb_tail'] / info['sample_rate']:.3f} seconds)" if reverb_wanted else "")
+        + (f", limited to {args.limit:g} dBFS with {args.limit_drive:g} dB of drive, deepest gain reduction "
+           f"{-20.0 * math.log10(max(info['limit_min_gain'], 1e-10)):.2f} dB" if limit_wanted else ""))
     return info
 
 
@@ -172,6 +219,7 @@ def pack_bank(args, pitches, sources, log=print):
 
 def main(args):
     check_reverb_args(args)
+    check_limit_args(args)
     if args.pack_bank is not None:
         pack_bank(args, range(24, 85), [0])
         return

@@ -70,6 +70,8 @@ V = POINTER(GsFftConv)
 FFTCONV_BLOCK = 2048                                              # GS_FFTCONV_BLOCK: new samples per block of gs_fftconv
 FFTCONV_MAX_TAPS = 1 << 20                                        # GS_FFTCONV_MAX_TAPS
 FFTCONV_HEADER_BYTES = (FFTCONV_BLOCK + FFTCONV_BLOCK // 2 + 8) * 8 + 16   # GS_FFTCONV_HEADER_BYTES
+LIMIT_MAX_LOOKAHEAD = 2048                                        # GS_LIMIT_MAX_LOOKAHEAD: samples
+LIMIT_TILE = 4096                                                 # GS_LIMIT_TILE: samples per block of gs_limit
 
 
 SPEC_FWD_GENERIC, SPEC_FWD_WAVE = 0, 1                                                                        # GS_SPEC_FWD_*
@@ -215,6 +217,8 @@ SIGNATURES = {
     "gs_fftconv_workspace_bytes": (Z, [V]),
     "gs_fftconv_prepare": (I, [V, P, L, P, Z, P]),
     "gs_fftconv": (I, [V, P, Z, P, L, F, F, I, P, L, P, P, P, Z, P]),
+    "gs_limit_workspace_bytes": (Z, [I, L]),
+    "gs_limit": (I, [P, I, L, L, F, F, I, P, L, P, P, P, P, Z, P]),
 }
 
 WGRAD_MAX_SOURCES = 4   # GS_WGRAD_MAX_SOURCES

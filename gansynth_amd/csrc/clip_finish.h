@@ -30,6 +30,25 @@ __device__ inline void publish_block_max(float m, float* __restrict__ slot) {
     if (threadIdx.x == 0) *slot = r;
 }
 
+// the minimum counterparts (limiter.hip: the deepest gain; every thread's m a chain of fminf from +inf over values that are never NaN)
+template <int NT>
+__device__ inline float block_min_of(float m) {
+    m = wave_extreme<false>(m);
+    __shared__ float part[NT / 64];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+    __syncthreads();
+    float r = part[0];
+#pragma unroll
+    for (int w = 1; w < NT / 64; ++w) r = fminf(r, part[w]);
+    return r;
+}
+
+template <int NT>
+__device__ inline void publish_block_min(float m, float* __restrict__ slot) {
+    const float r = block_min_of<NT>(m);
+    if (threadIdx.x == 0) *slot = r;
+}
+
 // Finishes `rows` clips of `ch` channels (1 or 2) IN PLACE: channel c of clip r is the n samples at x + (r * ch + c) * row_stride.
 // block_max: n_max maxima per clip (over all its channels: ONE peak a clip), clip r's at block_max + r * n_max; peak[r] = their fold.
 // pcm: clip r's n * ch values at pcm + r * n * ch, the channels interleaved.  pcm / peak may be null; the caller skips the call when

@@ -1,0 +1,298 @@
+// Look-ahead limiter: the last stage of a rendered clip (gansynth_amd/limiter.py, kernels.limit; the rule is this project's own and is stated
+// in include/gansynth_hip.h and DESIGN.md "Limiter").  Purely FIR: every output is a function of the 2W + 1 inputs around it, so a block owns
+// a tile of LIM_TILE consecutive samples of BOTH rows (the gain is joint) and carries no state.
+//
+// In LDS lies r over [tile_begin - W, tile_begin + LIM_TILE + W) -- 1 outside [0, n): r <= 1 everywhere and no window of the rule is empty,
+// so the padding is exact --, then m over [tile_begin - W, tile_begin + LIM_TILE), then g over the tile, each in place of the one before.
+// A lane keeps the 16 samples of its own four packs of y in registers from the one global read to the store.
+// Both windows -- the minimum and the sum over W + 1 = L consecutive values -- come from ONE routine, lim_window: doubling, S_2w[i] = S_w[i] op
+// S_w[i + w] in place (a lane holds its elements i = k * 256 + lane in registers, reads the partner, barrier, writes, barrier), and on the way
+// every set bit w of L adds its S_w, the low bits at the window's tail.  floor(log2 L) passes, not L reads a sample; every fp32 sum is a tree
+// over exactly the window's L terms (no running prefix along the tile); L ones sum to L exactly.  Lanes i and i + 1 touch neighbouring
+// dwords in every pass: ds_read_b32 / ds_write_b32 of 32 consecutive banks, conflict-free whatever w.  r lies `pad` = (-W) & 3 floats into
+// the buffer, so that the tile's own part starts on 16 bytes and g is read back as one ds_read_b128 a pack.
+// The kernel is bound by the instructions a wave issues per element and pass (wave64 on a 16-lane SIMD: four cycles each), not by LDS or
+// HBM.  Hence lim_window has NO per-element bound: S_w[i] is meaningful where i + w <= count, a meaningful value is only ever formed from
+// meaningful ones, and what is formed past that is never used -- the buffer is long enough for every read (LIM_TILE + 3 * WMAX + 4 floats),
+// an address is the lane's base plus an immediate, an element costs one ds_read and one fmin / add.  And the elements a lane holds, EPT, is
+// a template parameter chosen by W (18: W <= 256, 24: W <= 1024, 32: W <= 2048), so that a short look-ahead does not pay for the longest.
+//
+//   limit_kernel<ROWS, EPT>   grid (tiles): stage, m, g, out, pcm, one |max| of out and one min of g a block
+//   limit_fold_kernel    grid (1): the folds of those slots (maxima of values that are never NaN, minima likewise: exact in any order)
+#include <math.h>
+
+#include "clip_finish.h"
+#include "gs_common.h"
+
+namespace gs {
+
+constexpr int LIM_NT = CLIP_NT;
+constexpr int LIM_STEPS = CLIP_STEPS;
+constexpr int LIM_TILE = CLIP_TILE;                                        // samples a block owns
+constexpr int LIM_MAXW = GS_LIMIT_MAX_LOOKAHEAD;
+constexpr int LIM_OWN = LIM_TILE / LIM_NT;                                 // elements per lane that cover the tile itself
+constexpr int lim_wmax(int ept) { return (ept - LIM_OWN) * LIM_NT / 2; }   // the longest look-ahead that EPT elements per lane cover
+static_assert(LIM_TILE == GS_LIMIT_TILE && LIM_TILE == LIM_NT * 4 * LIM_STEPS && lim_wmax(32) == LIM_MAXW, "the kernel is written for this tile");
+
+static inline long lim_tiles(long n) { return (n + LIM_TILE - 1) / LIM_TILE; }
+
+template <bool MIN> __device__ inline float lim_op(float a, float b) { return MIN ? fminf(a, b) : a + b; }
+
+// acc[k] = buf[i] op buf[i + 1] op ... op buf[i + L - 1] for i = k * LIM_NT + lane, meaningful where buf[i .. i + L) was (L >= 2).  Reads
+// buf[0 .. EPT * LIM_NT + L): all of it must lie inside the LDS array, whatever it holds.  buf (filled, barrier passed) is overwritten up to
+// EPT * LIM_NT; on return every read of it is done (barrier passed).
+template <bool MIN, int EPT>
+__device__ inline void lim_window(float* buf, int L, float (&acc)[EPT]) {
+    float* mine = buf + threadIdx.x;
+    float a[EPT];
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+        a[k] = mine[k * LIM_NT];
+        acc[k] = MIN ? __builtin_inff() : 0.f;
+    }
+    int off = L;
+    for (int w = 1;; w <<= 1) {          // buf holds S_w
+        if (L & w) {
+            off -= w;
+            const float* part = mine + off;
+#pragma unroll
+            for (int k = 0; k < EPT; ++k) acc[k] = lim_op<MIN>(acc[k], part[k * LIM_NT]);
+        }
+        if (2 * w > L) break;
+        const float* partner = mine + w;
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) a[k] = lim_op<MIN>(a[k], partner[k * LIM_NT]);
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < EPT; ++k) mine[k * LIM_NT] = a[k];
+        __syncthreads();
+    }
+    __syncthreads();
+}
+
+// r of one sample from its rows' y (steps 2 and 3 of the rule): fmaxf from 0 drops a NaN
+template <int ROWS>
+__device__ inline float lim_ratio(const float (&y)[ROWS], float c) {
+    float a = 0.f;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) a = fmaxf(a, fabsf(y[r]));
+    return a > c ? __fdiv_rn(c, a) : 1.f;
+}
+
+// step 6: the clamp that lets a NaN through
+__device__ inline float lim_clamp(float v, float c) { return v > c ? c : (v < -c ? -c : v); }
+
+// grid (tiles of n).  out / pcm of the tile's samples below n; block_max[b] = max |out|, block_min[b] = min g over them
+template <int ROWS, int EPT>
+__global__ __launch_bounds__(LIM_NT) void limit_kernel(const float* __restrict__ x, long n, long row_stride, float d, float c, int W,
+                                                       float* __restrict__ out, long out_stride, short* __restrict__ pcm,
+                                                       float* __restrict__ block_max, float* __restrict__ block_min) {
+    constexpr int HALO_STEPS = EPT - LIM_OWN;                                  // halo samples per lane: 2 * WMAX / LIM_NT
+    __shared__ __attribute__((aligned(16))) float lds[LIM_TILE + 3 * lim_wmax(EPT) + 4];   // W <= WMAX (the host's choice of EPT)
+    const int pad = (-W) & 3;
+    float* rl = lds + pad;                    // rl[i]: r of the sample tile_begin - W + i, i in [0, LIM_TILE + 2W)
+    const long tile_begin = (long)blockIdx.x * LIM_TILE;
+    const long tile_end = tile_begin + LIM_TILE < n ? tile_begin + LIM_TILE : n;
+    const float* xr[ROWS];
+    float* orow[ROWS];
+    uintptr_t bases = 0;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        xr[r] = x + (size_t)r * row_stride;
+        orow[r] = out + (size_t)r * out_stride;
+        bases |= reinterpret_cast<uintptr_t>(xr[r]) | reinterpret_cast<uintptr_t>(orow[r]);
+    }
+    const bool wide = (bases & 15) == 0 && (reinterpret_cast<uintptr_t>(pcm) & (8 * ROWS - 1)) == 0;   // block-uniform
+
+    // every global read first -- the tile's own samples into y (0 from n on), the halos' into hx --, then the arithmetic: the loads are in
+    // flight together instead of one round trip after the other
+    float y[LIM_STEPS][ROWS][4];
+#pragma unroll
+    for (int u = 0; u < LIM_STEPS; ++u) {
+        const long t0 = tile_begin + (u * LIM_NT + threadIdx.x) * 4;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+            if (wide && t0 + 4 <= tile_end) ld4(xr[r] + t0, v);
+            else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (t0 + j < tile_end) v[j] = xr[r][t0 + j];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) y[u][r][j] = v[j];
+        }
+    }
+    // the halos: W samples before the tile and W after its LIM_TILE, sample by sample; an index outside [0, n) is clamped into the row
+    // for the read and its value dropped (r = 1 there)
+    float hx[HALO_STEPS][ROWS];
+#pragma unroll
+    for (int it = 0; it < HALO_STEPS; ++it) {
+        if (it * LIM_NT < 2 * W) {            // block-uniform
+            const int i = it * LIM_NT + threadIdx.x;
+            const long t = i < W ? tile_begin - W + i : tile_begin + LIM_TILE + (i - W);
+            const long tc = t < 0 ? 0 : (t < n ? t : n - 1);
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) hx[it][r] = xr[r][tc];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < LIM_STEPS; ++u) {     // y = fl(d * x) stays in registers, r goes to rl[W + ..] (1 from n on: y is 0 there)
+        const int p = (u * LIM_NT + threadIdx.x) * 4;
+        float rr[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float ys[ROWS];
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) ys[r] = y[u][r][j] = __fmul_rn(d, y[u][r][j]);
+            rr[j] = lim_ratio<ROWS>(ys, c);
+        }
+        *reinterpret_cast<float4*>(rl + W + p) = make_float4(rr[0], rr[1], rr[2], rr[3]);   // (pad + W + p) % 4 == 0
+    }
+#pragma unroll
+    for (int it = 0; it < HALO_STEPS; ++it) {
+        if (it * LIM_NT < 2 * W) {
+            const int i = it * LIM_NT + threadIdx.x;
+            const long t = i < W ? tile_begin - W + i : tile_begin + LIM_TILE + (i - W);
+            float ys[ROWS];
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) ys[r] = __fmul_rn(d, hx[it][r]);
+            const float v = (t >= 0 && t < n) ? lim_ratio<ROWS>(ys, c) : 1.f;
+            if (i < 2 * W) rl[i < W ? i : LIM_TILE + i] = v;
+        }
+    }
+    __syncthreads();
+
+    const int L = W + 1;
+    float acc[EPT];
+    lim_window<true, EPT>(rl, L, acc);                   // acc: m of the sample tile_begin - W + i, meaningful for i < LIM_TILE + W (step 4)
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) rl[k * LIM_NT + threadIdx.x] = acc[k];
+    __syncthreads();
+    lim_window<false, EPT>(rl, L, acc);                  // acc: m[t - W] + ... + m[t] for t = tile_begin + i, meaningful for i < LIM_TILE
+    float gmin = __builtin_inff();
+    const float terms = (float)L;
+#pragma unroll
+    for (int k = 0; k < LIM_OWN; ++k) {
+        const int i = k * LIM_NT + threadIdx.x;
+        const float g = __fdiv_rn(acc[k], terms);        // step 5
+        lds[i] = g;
+        if (tile_begin + i < tile_end) gmin = fminf(gmin, g);
+    }
+    __syncthreads();
+
+    float mx = 0.f;
+#pragma unroll
+    for (int u = 0; u < LIM_STEPS; ++u) {
+        const int p = (u * LIM_NT + threadIdx.x) * 4;
+        const long t0 = tile_begin + p;
+        const float4 g4 = *reinterpret_cast<const float4*>(lds + p);
+        const float g[4] = {g4.x, g4.y, g4.z, g4.w};
+        float v[ROWS][4];
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[r][j] = lim_clamp(__fmul_rn(g[j], y[u][r][j]), c);
+        }
+        if (wide && t0 + 4 <= tile_end) {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) mx = fmaxf(mx, fabsf(v[r][j]));
+                st4(orow[r] + t0, v[r]);
+            }
+            if (pcm != nullptr) {   // 4 * ROWS interleaved values, two a dword, as clip_finish.hip packs them
+                unsigned int q[2 * ROWS];
+#pragma unroll
+                for (int i = 0; i < 2 * ROWS; ++i)
+                    q[i] = ((unsigned int)quantise_s16(v[(2 * i) % ROWS][(2 * i) / ROWS]) & 0xffffu) |
+                           ((unsigned int)quantise_s16(v[(2 * i + 1) % ROWS][(2 * i + 1) / ROWS]) << 16);
+                if constexpr (ROWS == 1) *reinterpret_cast<uint2*>(pcm + t0) = make_uint2(q[0], q[1]);
+                else *reinterpret_cast<uint4*>(pcm + 2 * t0) = make_uint4(q[0], q[1], q[2], q[3]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long t = t0 + j;
+                if (t < tile_end) {
+#pragma unroll
+                    for (int r = 0; r < ROWS; ++r) {
+                        mx = fmaxf(mx, fabsf(v[r][j]));
+                        orow[r][t] = v[r][j];
+                        if (pcm != nullptr) pcm[ROWS * t + r] = (short)quantise_s16(v[r][j]);
+                    }
+                }
+            }
+        }
+    }
+    publish_block_max<LIM_NT>(mx, block_max + blockIdx.x);
+    publish_block_min<LIM_NT>(gmin, block_min + blockIdx.x);
+}
+
+// grid (1).  peak = max of block_max[0 .. tiles), min_gain = min of block_min[0 .. tiles); either may be null
+__global__ __launch_bounds__(LIM_NT) void limit_fold_kernel(const float* __restrict__ block_max, const float* __restrict__ block_min, int tiles,
+                                                            float* __restrict__ peak, float* __restrict__ min_gain) {
+    float mx = 0.f, mn = __builtin_inff();
+    for (int s = threadIdx.x; s < tiles; s += LIM_NT) {
+        mx = fmaxf(mx, block_max[s]);
+        mn = fminf(mn, block_min[s]);
+    }
+    mx = block_max_of<LIM_NT>(mx);
+    mn = block_min_of<LIM_NT>(mn);
+    if (threadIdx.x == 0) {
+        if (peak != nullptr) *peak = mx;
+        if (min_gain != nullptr) *min_gain = mn;
+    }
+}
+
+static bool lim_shape_ok(int rows, int64_t n) { return (rows == 1 || rows == 2) && n > 0 && n <= GS_LIMIT_MAX_N; }
+static size_t lim_ws_bytes(int64_t n) { return ((size_t)lim_tiles((long)n) * 2 * sizeof(float) + 15) & ~(size_t)15; }
+
+}  // namespace gs
+
+using namespace gs;
+
+extern "C" size_t gs_limit_workspace_bytes(int rows, int64_t n) {
+    if (!lim_shape_ok(rows, n)) return 0;
+    return lim_ws_bytes(n);
+}
+
+extern "C" int gs_limit(const float* x, int rows, int64_t n, int64_t row_stride, float pre_gain, float ceiling, int lookahead, float* out,
+                        int64_t out_stride, int16_t* pcm, float* peak, float* min_gain, void* ws, size_t ws_bytes, void* stream) {
+    GS_CHECK_ARG(rows == 1 || rows == 2, "limit: rows must be 1 or 2 (got %d)", rows);
+    GS_CHECK_ARG(n > 0 && n <= GS_LIMIT_MAX_N, "limit: n must be in [1, 2^40] (got %lld)", (long long)n);
+    GS_CHECK_ARG(row_stride >= n, "limit: row_stride %lld is below n %lld", (long long)row_stride, (long long)n);
+    GS_CHECK_ARG(out_stride >= n, "limit: out_stride %lld is below n %lld", (long long)out_stride, (long long)n);
+    GS_CHECK_ARG(x && out, "limit: null pointer (x and out are required)");
+    GS_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0 && (reinterpret_cast<uintptr_t>(peak) & 3) == 0 &&
+                 (reinterpret_cast<uintptr_t>(min_gain) & 3) == 0 && (reinterpret_cast<uintptr_t>(pcm) & 1) == 0,
+                 "limit: misaligned pointer (x / out / peak / min_gain: 4 bytes, pcm: 2)");
+    const size_t need = lim_ws_bytes(n);
+    GS_CHECK_ARG(ws && ws_bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "limit: workspace too small or misaligned (%zu bytes, need %zu)",
+                 ws_bytes, need);
+    GS_CHECK_ARG(isfinite(pre_gain) && pre_gain > 0.f, "limit: pre_gain must be finite and positive (got %g)", (double)pre_gain);
+    GS_CHECK_ARG(ceiling > 0.f && ceiling <= 1.f, "limit: ceiling must be in (0, 1] (got %g)", (double)ceiling);
+    GS_CHECK_ARG(lookahead >= 1 && lookahead <= GS_LIMIT_MAX_LOOKAHEAD, "limit: lookahead must be in [1, %d] samples (got %d)", GS_LIMIT_MAX_LOOKAHEAD,
+                 lookahead);
+    // a tile reads its neighbours' input: in place would be a race
+    const uintptr_t x_lo = reinterpret_cast<uintptr_t>(x), x_hi = x_lo + ((size_t)(rows - 1) * (size_t)row_stride + (size_t)n) * sizeof(float);
+    const uintptr_t o_lo = reinterpret_cast<uintptr_t>(out), o_hi = o_lo + ((size_t)(rows - 1) * (size_t)out_stride + (size_t)n) * sizeof(float);
+    GS_CHECK_ARG(x_hi <= o_lo || o_hi <= x_lo, "limit: x and out overlap (the limiter does not work in place)");
+    hipStream_t st = as_stream(stream);
+    const int tiles = (int)lim_tiles((long)n);
+    float* block_max = static_cast<float*>(ws);
+    float* block_min = block_max + tiles;
+    const int ept = lookahead <= lim_wmax(18) ? 18 : (lookahead <= lim_wmax(24) ? 24 : 32);
+    with_constant<1, 2>(rows, [&](auto rows_c) {
+        return with_constant<18, 24, 32>(ept, [&](auto ept_c) {
+            hipLaunchKernelGGL((limit_kernel<decltype(rows_c)::value, decltype(ept_c)::value>), dim3((unsigned)tiles), dim3(LIM_NT), 0, st, x, (long)n,
+                               (long)row_stride, pre_gain, ceiling, lookahead, out, (long)out_stride, reinterpret_cast<short*>(pcm), block_max, block_min);
+            return true;
+        });
+    });
+    if (peak != nullptr || min_gain != nullptr)
+        hipLaunchKernelGGL(limit_fold_kernel, dim3(1), dim3(LIM_NT), 0, st, static_cast<const float*>(block_max), static_cast<const float*>(block_min), tiles,
+                           peak, min_gain);
+    GS_CHECK_LAUNCH();
+    return 0;
+}

@@ -145,6 +145,34 @@ def fft_convolve(x, impulse, dry, wet, normalize=True, want_pcm=False):
     return get().fft_convolve(x, impulse, dry, wet, normalize=normalize, want_pcm=want_pcm)
 
 
+def limit_shapes(x, pre_gain, ceiling, lookahead):
+    """The host side of limit: -> (rows, n) of x ([n] or [rows, n] fp32, rows 1 or 2); pre_gain finite and > 0, ceiling in (0, 1] -- both
+    as the fp32 values the kernel receives --, lookahead an integer number of samples in [1, LIMIT_MAX_LOOKAHEAD].  ValueError by argument
+    name; needs no device."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2) or x.dtype != torch.float32 or x.numel() == 0:
+        got = f"{tuple(x.shape)} {x.dtype}" if isinstance(x, torch.Tensor) else type(x).__name__
+        raise ValueError(f"limit: x must be a non-empty fp32 vector or [rows, samples] matrix (got {got})")
+    rows, n = (1, int(x.shape[0])) if x.dim() == 1 else (int(x.shape[0]), int(x.shape[1]))
+    if rows > 2:
+        raise ValueError(f"limit: x must have 1 or 2 rows -- a clip is mono or stereo (got {rows})")
+    for name, v in (("pre_gain", pre_gain), ("ceiling", ceiling)):
+        if not isinstance(v, (int, float)) or isinstance(v, bool) or not math.isfinite(v):
+            raise ValueError(f"limit: {name} must be a finite number (got {v!r})")
+    if not (pre_gain > 0 and math.isfinite(ctypes.c_float(pre_gain).value) and ctypes.c_float(pre_gain).value > 0):
+        raise ValueError(f"limit: pre_gain must be positive and finite in fp32 (got {pre_gain!r})")
+    if not 0 < ctypes.c_float(ceiling).value <= 1:
+        raise ValueError(f"limit: ceiling must be in (0, 1] (got {ceiling!r})")
+    if not isinstance(lookahead, (int, np.integer)) or isinstance(lookahead, bool) or not 1 <= lookahead <= _lib.LIMIT_MAX_LOOKAHEAD:
+        raise ValueError(f"limit: lookahead must be an integer number of samples in [1, {_lib.LIMIT_MAX_LOOKAHEAD}] (got {lookahead!r})")
+    return rows, n
+
+
+def limit(x, pre_gain, ceiling, lookahead, want_pcm=False):
+    """HipKernels.limit of the process-wide kernel object; the arguments are refused here, before a device is asked for."""
+    limit_shapes(x, pre_gain, ceiling, lookahead)
+    return get().limit(x, pre_gain, ceiling, lookahead, want_pcm=want_pcm)
+
+
 def _checked_notes(what, table, rows, length, total, gains):
     """Rows (onset, hold, release, row, *gains) validated and sorted by (onset, position): what both note tables share."""
     fields = ("onset", "hold", "release", "row") + gains
@@ -1575,6 +1603,29 @@ class HipKernels(object):
                                        float(dry), float(wet), 1 if normalize else 0, out.data_ptr(), int(out.stride(0)) if rows > 1 else n_out,
                                        None if pcm is None else pcm.data_ptr(), peak.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_fftconv")
         return (out[0] if mono else out), pcm, peak
+
+    def limit(self, x, pre_gain, ceiling, lookahead, want_pcm=False):
+        """gs_limit (include/gansynth_hip.h): the look-ahead limiter on x -- [n] or [rows, n] fp32 on the device, rows 1 or 2, any row
+        stride --: x times pre_gain, then ONE gain per sample for all rows that keeps every |sample| at or below ceiling, from the sliding
+        minimum and mean over `lookahead` samples.  -> (out -- [n] or [rows, n] fp32, a new tensor whose rows start on 16 bytes --, pcm [n] or
+        [n, rows] int16 or None, peak [1] fp32 = max |out|, min_gain [1] fp32 = the smallest gain applied)."""
+        rows, n = limit_shapes(x, pre_gain, ceiling, lookahead)
+        if not x.is_cuda:
+            raise ValueError(f"limit: x must be on the HIP device (it is on {x.device})")
+        mono = x.dim() == 1
+        x2 = x[None] if mono else x
+        if x2.stride(1) != 1 or (rows > 1 and x2.stride(0) < n):
+            x2 = x2.contiguous()
+        stride = (n + 3) // 4 * 4
+        out = torch.empty((rows, stride), dtype=torch.float32, device=x.device)[:, :n]
+        pcm = torch.empty((n,) if mono else (n, rows), dtype=torch.int16, device=x.device) if want_pcm else None
+        peak = torch.empty((1,), dtype=torch.float32, device=x.device)
+        min_gain = torch.empty((1,), dtype=torch.float32, device=x.device)
+        ws = _ws(self.lib.gs_limit_workspace_bytes(rows, n), x.device)
+        _lib.check(self.lib.gs_limit(x2.data_ptr(), rows, n, int(x2.stride(0)) if rows > 1 else n, float(pre_gain), float(ceiling), int(lookahead),
+                                     out.data_ptr(), stride, None if pcm is None else pcm.data_ptr(), peak.data_ptr(), min_gain.data_ptr(),
+                                     ws.data_ptr(), ws.numel(), _stream()), "gs_limit")
+        return (out[0] if mono else out), pcm, peak, min_gain
 
     def account(self):
         """bench.py: `with K.account() as calls:` lists every kernel-layer call made inside as (method, argument dict, bytes read,

@@ -815,6 +815,41 @@ int gs_fftconv_prepare(const GsFftConv* c, const float* ir, int64_t ir_stride, v
 int gs_fftconv(const GsFftConv* c, const void* spectrum, size_t spectrum_bytes, const float* x, int64_t row_stride, float dry, float wet,
                int normalize, float* out, int64_t out_stride, int16_t* pcm, float* peak, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Limiter: a look-ahead peak limiter as the last stage of a rendered clip (gansynth_amd/limiter.py, kernels.limit; this project's
+ * own rule, DESIGN.md "Limiter") -----------------------------------------------------------------------------------------------------
+ * x: [rows] rows of n fp32 samples, `row_stride` elements apart (rows is 1 or 2).  d = pre_gain (finite, > 0), c = ceiling (0 < c <= 1),
+ * W = lookahead in samples (1 <= W <= GS_LIMIT_MAX_LOOKAHEAD).  For t in [0, n):
+ *   1. y[r][t] = fl(d * x[r][t])                           one fp32 rounding, no FMA into a later step
+ *   2. a[t]    = max over the rows of |y[r][t]|            an fmaxf chain from 0: ONE gain for both channels, the stereo image cannot move; a
+ *                                                          NaN sample contributes nothing, passes to out as NaN, is PCM 0, disturbs no neighbour
+ *   3. r[t]    = c / a[t] if a[t] > c, else 1              a correctly rounded fp32 quotient
+ *   4. m[s]    = min of r over [max(s, 0), min(s + W, n - 1)]   for s in [-W, n); exact
+ *   5. g[t]    = (m[t - W] + ... + m[t]) / (W + 1)         W + 1 terms, a true division; every fp32 sum a tree over the window's own
+ *                                                          W + 1 terms (never a running sum along the clip)
+ *   6. out[r][t] = clamp(fl(g[t] * y[r][t]), -c, c)        (a NaN stays a NaN)
+ *   7. pcm     = summary_audio_s16's rule applied to out: [n] for one row, interleaved [n][2] for two
+ *   8. peak    = max |out| (exact)         9. min_gain = min g (exact): the deepest gain reduction
+ * Every window [s, s + W] with s in [t - W, t] contains t, so every term of the mean is <= r[t], g[t] <= r[t] and |g[t] y[t]| <= c in exact
+ * arithmetic: the clamp removes only a last ulp of rounding, and |out| <= c holds bit for bit.  Where no sample within W on either side
+ * exceeds c every term is exactly 1, W + 1 ones sum exactly in any order and (W + 1) / (W + 1) == 1: out == fl(d * x) bit for bit there.  The
+ * release is as long as the attack.  No atomics: two calls are bit-identical.
+ * pcm, peak ([1]) and min_gain ([1]) may be NULL.  out: [rows] rows of n samples, `out_stride` apart; the elements between n and out_stride
+ * are not touched.  out must not overlap x (a block reads its neighbours' input).
+ * One launch over tiles of GS_LIMIT_TILE samples of both rows (r with a halo of W on either side in LDS, the sliding minimum and the sliding
+ * sum by doubling, 16 bytes per lane where every row of x and out is 16-byte aligned -- and pcm 8 * rows --, sample by sample otherwise),
+ * which leaves one |max| and one min per block in ws (gs_limit_workspace_bytes: 2 * 4 * ceil(n / GS_LIMIT_TILE), rounded up to 16; 16-byte
+ * aligned), and one small fold launch when peak or min_gain is asked for.  Every bound is recomputed from n and W.  Capture-safe: no
+ * allocation, no synchronisation.  gs_limit_workspace_bytes is host arithmetic and answers 0 for a refused shape.
+ * GS_ERR_ARG with a message and without a launch: rows outside {1, 2}, n <= 0 (or > GS_LIMIT_MAX_N), a stride below n, x or out NULL,
+ * x / out / peak / min_gain off 4 bytes, pcm off 2, ws off 16 or too small, pre_gain not finite or <= 0, ceiling outside (0, 1], lookahead
+ * outside [1, GS_LIMIT_MAX_LOOKAHEAD], overlapping x and out. */
+#define GS_LIMIT_MAX_LOOKAHEAD 2048
+#define GS_LIMIT_TILE 4096
+#define GS_LIMIT_MAX_N ((int64_t)1 << 40)
+size_t gs_limit_workspace_bytes(int rows, int64_t n);
+int gs_limit(const float* x, int rows, int64_t n, int64_t row_stride, float pre_gain, float ceiling, int lookahead, float* out,
+             int64_t out_stride, int16_t* pcm, float* peak, float* min_gain, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
