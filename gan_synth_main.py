@@ -43,6 +43,13 @@ clip is scaled so that its peak would stand `--limit_drive DB` (default 6) above
 
     python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --output_rate 48000 --reverb 1.8 --limit -1 --limit_drive 9 --output quartet.wav
 
+`--loudness LUFS` (not in the reference) ends the chain of `--synthesize` at a target programme loudness instead of a peak level: the
+clip is measured (ITU-R BS.1770-4 integrated loudness, the K-weighted energies on the device), scaled to the target, and the limiter holds
+the peaks under `--limit DB` (default -1 dBFS) looking `--limit_lookahead` ahead; `--limit_drive` does not apply, the level is set by the
+target (gansynth_amd/loudness.py, DESIGN.md "Loudness"):
+
+    python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --output_rate 48000 --reverb 1.8 --loudness -16 --output quartet.wav
+
 `--pack_bank` / `--bank` (not in the reference): the notes packed once into one file (on any machine, no GPU needed), then held on the
 device and drawn there, batch for batch what `--filenames` yields (gansynth_amd/bank.py, DESIGN.md "Resident notes"):
 
@@ -100,6 +107,8 @@ parser.add_argument("--limit", type=float, default=None, metavar="DB",
 parser.add_argument("--limit_drive", type=float, default=6.0, metavar="DB",
                     help="--limit: how far above the ceiling the clip's peak is driven before the limiter brings it back (>= 0; 0: peak normalisation)")
 parser.add_argument("--limit_lookahead", type=float, default=0.005, metavar="SECONDS", help="--limit: the limiter's look-ahead (attack and release)")
+parser.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                    help="--synthesize: end at this integrated loudness (BS.1770, <= 0 LUFS); the limiter holds the peaks under --limit (default -1 dBFS)")
 parser.add_argument("--generator_ema_decay", type=float, default=0.0,
                     help="keep an exponential moving average of the generator's weights with this decay (0.0: off; progressive GAN uses 0.999)")
 parser.add_argument("--pack_bank", type=str, default=None, metavar="PATH",
@@ -136,7 +145,7 @@ def check_limit_args(args):
     ceiling = getattr(args, "limit", None)
     drive, lookahead = getattr(args, "limit_drive", 6.0), getattr(args, "limit_lookahead", 0.005)
     wanted = ceiling is not None
-    if not wanted and (drive != 6.0 or lookahead != 0.005):
+    if not wanted and (drive != 6.0 or lookahead != 0.005) and getattr(args, "loudness", None) is None:   # (--loudness has a limiter of its own)
         raise SystemExit("--limit_drive and --limit_lookahead need --limit")
     if wanted and args.synthesize is None:
         raise SystemExit("--limit applies to --synthesize only")
@@ -151,15 +160,37 @@ def check_limit_args(args):
     return wanted
 
 
+def check_loudness_args(args):
+    """--loudness against --synthesize and the limiter's flags: SystemExit with a message.  -> whether a loudness target is asked for."""
+    target = getattr(args, "loudness", None)
+    if target is None:
+        return False
+    if not math.isfinite(target):
+        raise SystemExit(f"--loudness takes a finite target in LUFS (got {target})")
+    if target > 0:
+        raise SystemExit(f"--loudness takes a target in LUFS, at most 0 (got {target})")
+    if args.synthesize is None:
+        raise SystemExit("--loudness applies to --synthesize only")
+    if getattr(args, "limit_drive", 6.0) != 6.0:
+        raise SystemExit("--limit_drive does not apply with --loudness: the level is set by --loudness")
+    lookahead = getattr(args, "limit_lookahead", 0.005)
+    if not 0 <= lookahead < float("inf"):   # (check_limit_args looks at it only with --limit)
+        raise SystemExit(f"--limit_lookahead must be a non-negative number of seconds (got {lookahead})")
+    return True
+
+
 def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     """--synthesize: the score args.synthesize through GANSynth.synthesize into the 16-bit WAV args.output (the kernel's own PCM: [T], or
     the interleaved [T, 2] of --stereo, which is a two-channel WAV's layout).  With --reverb / --reverb_ir: the unnormalised clip at the
     output rate, then reverb.apply -- the room, ONE peak and the PCM there.  With --limit: whichever stage comes last hands over its
-    unnormalised clip and its peak, and limiter.apply writes the PCM."""
+    unnormalised clip and its peak, and limiter.apply writes the PCM.  With --loudness: the same hand-over, and loudness.apply -- measure, scale to
+    the target, limit at the ceiling of --limit (or -1 dBFS) -- writes the PCM."""
     from scipy.io import wavfile
     from gansynth_amd import checkpoint
     reverb_wanted = check_reverb_args(args)
     limit_wanted = check_limit_args(args)
+    loudness_wanted = check_loudness_args(args)
+    last_wanted = limit_wanted or loudness_wanted   # a stage after the reverb that sets the level and quantises
     if os.path.splitext(args.synthesize)[1].lower() not in (".mid", ".midi", ".json"):
         raise SystemExit(f"--synthesize takes a .mid, .midi or .json score (got {args.synthesize})")
     if restore and checkpoint.latest(args.model_dir) is None:
@@ -170,7 +201,7 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
                release_seconds=args.release_seconds, info=info, pitches=pitches, batch_size=args.batch_size, weights=args.weights,
                sample_rate=getattr(args, "output_rate", None), ensemble=getattr(args, "ensemble", False),
                stereo=getattr(args, "stereo", False), spread=getattr(args, "spread", 0.0))
-    if reverb_wanted or limit_wanted:   # only the last stage normalises (or limits) and quantises
+    if reverb_wanted or last_wanted:   # only the last stage normalises (or limits) and quantises
         clip = model.synthesize(args.synthesize, normalize=False, want_pcm=False, **how)
     if reverb_wanted:
         from gansynth_amd import reverb
@@ -179,11 +210,21 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
                 impulse = reverb.design_impulse(info["sample_rate"], args.reverb, channels=clip.dim(), seed=args.seed, predelay=args.reverb_predelay)
             else:
                 impulse = reverb.read_impulse(args.reverb_ir, info["sample_rate"], predelay=args.reverb_predelay)
-            clip, pcm, peak = reverb.apply(clip, impulse.to(clip.device), mix=args.reverb_mix, normalize=not limit_wanted, want_pcm=not limit_wanted)
+            clip, pcm, peak = reverb.apply(clip, impulse.to(clip.device), mix=args.reverb_mix, normalize=not last_wanted, want_pcm=not last_wanted)
         except ValueError as e:
             raise SystemExit(str(e))
         info.update(peak=float(peak), reverb_tail=int(impulse.shape[1]) - 1, output_samples=int(clip.shape[-1]))
-    if limit_wanted:   # the clip as the stage before left it, and that stage's peak
+    if loudness_wanted:   # the clip as the stage before left it; its level comes from the meter, not from that stage's peak
+        from gansynth_amd import loudness
+        ceiling_db = args.limit if limit_wanted else -1.0
+        try:
+            _, pcm, heard = loudness.apply(clip, info["sample_rate"], args.loudness, ceiling_db=ceiling_db,
+                                           lookahead_seconds=args.limit_lookahead, want_pcm=True)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        info.update(loudness_target=float(args.loudness), loudness_measured=heard["measured_lufs"], loudness_output=heard["output_lufs"],
+                    limit_ceiling_db=float(ceiling_db), limit_peak=heard["peak"], limit_min_gain=heard["min_gain"])
+    elif limit_wanted:   # the clip as the stage before left it, and that stage's peak
         from gansynth_amd import limiter
         try:
             _, pcm, out_peak, min_gain = limiter.apply(clip, info["sample_rate"], ceiling_db=args.limit, drive_db=args.limit_drive,
@@ -202,7 +243,12 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
         f"peak {info['peak']:.4f}: written to {args.output}" + (f" at {info['sample_rate']} Hz" if info["sample_rate"] != rate else "")
         + (f", with a reverb tail of {info['reverb_tail']} samples ({info['reverb_tail'] / info['sample_rate']:.3f} seconds)" if reverb_wanted else "")
         + (f", limited to {args.limit:g} dBFS with {args.limit_drive:g} dB of drive, deepest gain reduction "
-           f"{-20.0 * math.log10(max(info['limit_min_gain'], 1e-10)):.2f} dB" if limit_wanted else ""))
+           f"{-20.0 * math.log10(max(info['limit_min_gain'], 1e-10)):.2f} dB" if limit_wanted and not loudness_wanted else "")
+        + (f", measured {info['loudness_measured']:.2f} LUFS, brought to {info['loudness_output']:.2f} LUFS for a target of {args.loudness:g} "
+           f"under a ceiling of {info['limit_ceiling_db']:g} dBFS"
+           + (f": the limiter had to work (least gain {info['limit_min_gain']:.4f}) and the output is "
+              f"{args.loudness - info['loudness_output']:.2f} LU short of the target" if info["limit_min_gain"] < 1 else "")
+           if loudness_wanted else ""))
     return info
 
 
@@ -220,6 +266,7 @@ def pack_bank(args, pitches, sources, log=print):
 def main(args):
     check_reverb_args(args)
     check_limit_args(args)
+    check_loudness_args(args)
     if args.pack_bank is not None:
         pack_bank(args, range(24, 85), [0])
         return

@@ -72,6 +72,18 @@ FFTCONV_MAX_TAPS = 1 << 20                                        # GS_FFTCONV_M
 FFTCONV_HEADER_BYTES = (FFTCONV_BLOCK + FFTCONV_BLOCK // 2 + 8) * 8 + 16   # GS_FFTCONV_HEADER_BYTES
 LIMIT_MAX_LOOKAHEAD = 2048                                        # GS_LIMIT_MAX_LOOKAHEAD: samples
 LIMIT_TILE = 4096                                                 # GS_LIMIT_TILE: samples per block of gs_limit
+LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 192000               # GS_LOUDNESS_MIN_RATE, GS_LOUDNESS_MAX_RATE
+LOUDNESS_STEPS = 8                                                # GS_LOUDNESS_STEPS: matrix powers per scan of gs_loudness
+
+
+class GsLoudness(ctypes.Structure):
+    """include/gansynth_hip.h: the K-weighting meter of one sample rate (gs_loudness_design fills it)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("rate", "hop", "chunk", "lanes", "rem", "reserved")] + \
+               [(n, c_double * 3) for n in ("b1", "a1", "b2", "a2")] + \
+               [("chunk_pow", c_double * 16 * LOUDNESS_STEPS), ("hop_pow", c_double * 16 * LOUDNESS_STEPS), ("rem_pow", c_double * 16)]
+
+
+W = POINTER(GsLoudness)
 
 
 SPEC_FWD_GENERIC, SPEC_FWD_WAVE = 0, 1                                                                        # GS_SPEC_FWD_*
@@ -219,6 +231,11 @@ SIGNATURES = {
     "gs_fftconv": (I, [V, P, Z, P, L, F, F, I, P, L, P, P, P, Z, P]),
     "gs_limit_workspace_bytes": (Z, [I, L]),
     "gs_limit": (I, [P, I, L, L, F, F, I, P, L, P, P, P, P, Z, P]),
+    # W = POINTER(GsLoudness), the meter of one rate
+    "gs_loudness_design": (I, [I, W]),
+    "gs_loudness_hops": (L, [W, L]),
+    "gs_loudness_workspace_bytes": (Z, [W, I, L]),
+    "gs_loudness": (I, [W, P, I, L, L, P, L, P, Z, P]),
 }
 
 WGRAD_MAX_SOURCES = 4   # GS_WGRAD_MAX_SOURCES

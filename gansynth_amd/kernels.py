@@ -173,6 +173,27 @@ def limit(x, pre_gain, ceiling, lookahead, want_pcm=False):
     return get().limit(x, pre_gain, ceiling, lookahead, want_pcm=want_pcm)
 
 
+def loudness_shapes(x, rate):
+    """The host side of loudness_energy: -> (rows, n) of x ([n] or [rows, n] fp32, rows 1 or 2); rate an integer number of samples per second
+    in [LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE].  ValueError by argument name; needs no device."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2) or x.dtype != torch.float32 or x.numel() == 0:
+        got = f"{tuple(x.shape)} {x.dtype}" if isinstance(x, torch.Tensor) else type(x).__name__
+        raise ValueError(f"loudness_energy: x must be a non-empty fp32 vector or [rows, samples] matrix (got {got})")
+    rows, n = (1, int(x.shape[0])) if x.dim() == 1 else (int(x.shape[0]), int(x.shape[1]))
+    if rows > 2:
+        raise ValueError(f"loudness_energy: x must have 1 or 2 rows -- a clip is mono or stereo (got {rows})")
+    if not isinstance(rate, (int, np.integer)) or isinstance(rate, bool) or not _lib.LOUDNESS_MIN_RATE <= rate <= _lib.LOUDNESS_MAX_RATE:
+        raise ValueError(f"loudness_energy: rate must be an integer number of samples per second in [{_lib.LOUDNESS_MIN_RATE}, "
+                         f"{_lib.LOUDNESS_MAX_RATE}] (got {rate!r})")
+    return rows, n
+
+
+def loudness_energy(x, rate):
+    """HipKernels.loudness_energy of the process-wide kernel object; the arguments are refused here, before a device is asked for."""
+    loudness_shapes(x, rate)
+    return get().loudness_energy(x, rate)
+
+
 def _checked_notes(what, table, rows, length, total, gains):
     """Rows (onset, hold, release, row, *gains) validated and sorted by (onset, position): what both note tables share."""
     fields = ("onset", "hold", "release", "row") + gains
@@ -229,6 +250,7 @@ class HipKernels(object):
         self._resample = {}       # (rate_in, rate_out, device index) -> (GsResample, device table): resample_design
         self._fftconv = {}        # impulse tensor's identity -> (the tensor, its prepared spectrum): fft_convolve_spectrum
         self.fftconv_prepares = 0   # gs_fftconv_prepare calls so far (tests: one per impulse tensor)
+        self._loudness = {}       # rate -> GsLoudness: loudness_design
 
     # --------------------------------------------------------- prepared-weight workspaces
     def register_param_buffer(self, flat):
@@ -1627,6 +1649,36 @@ class HipKernels(object):
                                      ws.data_ptr(), ws.numel(), _stream()), "gs_limit")
         return (out[0] if mono else out), pcm, peak, min_gain
 
+    def loudness_design(self, rate):
+        """The K-weighting meter of `rate` (gs_loudness_design: host arithmetic), built once per rate: -> GsLoudness."""
+        rate = int(rate)
+        if rate not in self._loudness:
+            design = _lib.GsLoudness()
+            _lib.check(self.lib.gs_loudness_design(rate, ctypes.byref(design)), "gs_loudness_design")
+            self._loudness[rate] = design
+        return self._loudness[rate]
+
+    def loudness_energy(self, x, rate):
+        """gs_loudness (include/gansynth_hip.h): the BS.1770 K-weighted energy of every complete hop of floor(0.1 * rate + 0.5) samples of x
+        -- [n] or [rows, n] fp32 on the device, rows 1 or 2, any row stride.  -> energy [rows, hops] fp32, hops = n // hop (possibly 0)."""
+        rows, n = loudness_shapes(x, rate)
+        if not x.is_cuda:
+            raise ValueError(f"loudness_energy: x must be on the HIP device (it is on {x.device})")
+        x2 = x[None] if x.dim() == 1 else x
+        if x2.stride(1) != 1 or (rows > 1 and x2.stride(0) < n):
+            x2 = x2.contiguous()
+        design = self.loudness_design(rate)
+        hops = int(self.lib.gs_loudness_hops(ctypes.byref(design), n))
+        if hops < 0:
+            _lib.check(hops, "gs_loudness_hops")
+        energy = torch.empty((rows, hops), dtype=torch.float32, device=x.device)
+        if hops == 0:   # no complete hop: nothing to measure (and an empty tensor has no address to hand over)
+            return energy
+        ws = _ws(self.lib.gs_loudness_workspace_bytes(ctypes.byref(design), rows, n), x.device)
+        _lib.check(self.lib.gs_loudness(ctypes.byref(design), x2.data_ptr(), rows, n, int(x2.stride(0)) if rows > 1 else n, energy.data_ptr(),
+                                        hops, ws.data_ptr(), ws.numel(), _stream()), "gs_loudness")
+        return energy
+
     def account(self):
         """bench.py: `with K.account() as calls:` lists every kernel-layer call made inside as (method, argument dict, bytes read,
         bytes written) -- the algorithmic traffic of SURVEY.md 8(d): every tensor argument read once, every result written once
@@ -1662,7 +1714,7 @@ class HipKernels(object):
 class _Accounting(object):
     SKIP = ("account", "prof_enable", "prof_roofline", "prof_records", "prof_collect", "register_param_buffer", "invalidate_weights", "early_flush_rule",
             "derived_slice", "defer_wgrad_reductions", "wgrad_slice_target_ok", "drop_deferred", "dense_nhwc_ok", "norm_bwd_bias_ok",
-            "fwd_pnbwdbwd_is_fused", "bwd_data_pnbwd_is_fused", "conv2d_fwd_workspace", "resample_design")
+            "fwd_pnbwdbwd_is_fused", "bwd_data_pnbwd_is_fused", "conv2d_fwd_workspace", "resample_design", "loudness_design")
 
     def __init__(self, K):
         self.K, self.calls, self.depth, self.names = K, [], 0, []

@@ -850,6 +850,56 @@ size_t gs_limit_workspace_bytes(int rows, int64_t n);
 int gs_limit(const float* x, int rows, int64_t n, int64_t row_stride, float pre_gain, float ceiling, int lookahead, float* out,
              int64_t out_stride, int16_t* pcm, float* peak, float* min_gain, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Loudness: the K-weighted hop energies of ITU-R BS.1770, from which the host gates the integrated loudness of a rendered clip
+ * (gansynth_amd/loudness.py, kernels.loudness_energy; DESIGN.md "Loudness") ------------------------------------------------------------
+ * gs_loudness_design(rate): host arithmetic in float64, no device.  hop = floor(0.1 * rate + 0.5) samples (a gating block is 4 hops: 400 ms
+ * with 75 % overlap; at a rate that is no multiple of 10 a hop departs from 100 ms by under half a sample).  The two K-weighting sections
+ * for any rate, by the bilinear forms whose 48 kHz values are the table of BS.1770 (a[0] = 1):
+ *   stage 1 (shelf):     f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196;
+ *                        K = tan(pi f0 / rate), Vh = 10^(G / 20), Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2,
+ *                        b = [Vh + Vb K / Q + K^2, 2 (K^2 - Vh), Vh - Vb K / Q + K^2] / a0,   a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0]
+ *   stage 2 (high-pass): f0 = 38.13547087602444, Q = 0.5003270373238773;   b = [1, -2, 1],   a as above
+ * and what the kernels' chunking needs: chunk = ceil(hop / 256) | 1 samples a lane (odd), lanes = ceil(hop / chunk), rem = hop - (lanes - 1) *
+ * chunk samples of the last lane, and with A the 4 x 4 matrix that one silent sample applies to the cascade's state (s1[0], s1[1], s2[0],
+ * s2[1]; transposed direct form II), row-major: chunk_pow[k] = A^(chunk * 2^k), hop_pow[k] = A^(hop * 2^k), k in [0, GS_LOUDNESS_STEPS),
+ * rem_pow = A^rem.
+ * gs_loudness: x is [rows] rows (1 or 2) of n fp32 samples, `row_stride` elements apart.  hops = floor(n / hop): an incomplete last hop is
+ * not measured.  Per row, starting at rest at sample 0 and running through the whole row,
+ *     y1[t] = b1[0] x[t] + b1[1] x[t-1] + b1[2] x[t-2] - a1[1] y1[t-1] - a1[2] y1[t-2],    y2 likewise from y1 with b2, a2
+ *     energy[r * energy_stride + j] = sum over t in [j hop, (j + 1) hop) of y2[t]^2,  j in [0, hops),  as fp32
+ * -- the EXACT recurrence: no block restarts at rest from a halo.  The recurrence is linear, so k samples from a state s end in A^k s plus
+ * their end from rest; everything after the fp32 load (filter, states, squares, sums) is float64, FMA allowed, rounded once at the store.
+ * Rows are independent: row 0 of a two-row call is bit-identical to the one-row call on it.  A non-finite sample propagates as IEEE
+ * arithmetic has it, to that row's energies from its hop on, and to nothing else.  Samples and hops before the first non-zero sample give
+ * exactly 0.  No atomics: two calls are bit-identical.  energy is written in [0, hops) of each row only; with hops == 0 nothing is launched.
+ * Three launches: (hops, rows) blocks, one hop in LDS each, leave the hop's end state from rest; one block per row carries the states
+ * across the hops (a scan with the powers of A^hop); (hops, rows) blocks run every chunk from its true state and reduce the squares in a
+ * fixed tree.  16-byte loads from the hop's first 16-byte boundary on whatever the row base, sample by sample before it and at the tail.
+ * Every bound is recomputed from n and the descriptor.  Capture-safe: no allocation, no synchronisation.  ws (gs_loudness_workspace_bytes:
+ * rows * max(hops, 1) * 64 -- two states of four doubles a hop; 16-byte aligned).
+ * gs_loudness_design, _hops and _workspace_bytes are host arithmetic and need no device.
+ * GS_ERR_ARG with a message and without a launch: a rate outside [GS_LOUDNESS_MIN_RATE, GS_LOUDNESS_MAX_RATE], rows outside {1, 2}, n <= 0
+ * (or > GS_LOUDNESS_MAX_N), row_stride < n, energy_stride < hops, x or energy NULL or off 4 bytes, ws NULL, off 16 or too small, a
+ * descriptor that differs in any byte from gs_loudness_design of its rate.  (The byte query answers a refusal with 0, gs_loudness_hops
+ * with the negative code.) */
+#define GS_LOUDNESS_MIN_RATE 8000
+#define GS_LOUDNESS_MAX_RATE 192000
+#define GS_LOUDNESS_MAX_N ((int64_t)1 << 40)
+#define GS_LOUDNESS_STEPS 8
+typedef struct GsLoudness {
+    int32_t rate, hop;
+    int32_t chunk, lanes, rem, reserved;
+    double b1[3], a1[3], b2[3], a2[3];
+    double chunk_pow[GS_LOUDNESS_STEPS][16];
+    double hop_pow[GS_LOUDNESS_STEPS][16];
+    double rem_pow[16];
+} GsLoudness;                  /* 2296 bytes */
+int gs_loudness_design(int rate, GsLoudness* out);
+int64_t gs_loudness_hops(const GsLoudness* d, int64_t n);
+size_t gs_loudness_workspace_bytes(const GsLoudness* d, int rows, int64_t n);
+int gs_loudness(const GsLoudness* d, const float* x, int rows, int64_t n, int64_t row_stride, float* energy, int64_t energy_stride, void* ws,
+                size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
