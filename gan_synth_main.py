@@ -50,6 +50,13 @@ target (gansynth_amd/loudness.py, DESIGN.md "Loudness"):
 
     python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --output_rate 48000 --reverb 1.8 --loudness -16 --output quartet.wav
 
+`--controllers` honours what a score says after a note has started (GANSynth.synthesize with controllers, DESIGN.md "Controllers"): channel
+volume (CC 7) and expression (CC 11) as they move, pan (CC 10) with `--stereo`, and the sustain pedal (CC 64), which holds notes past their
+key-up; every change takes effect over `--controller_ramp` seconds (default 0.01):
+
+    python gan_synth_main.py --synthesize sonata.mid --controllers --output sonata.wav
+    python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --controllers --controller_ramp 0.02 --output quartet.wav
+
 `--pack_bank` / `--bank` (not in the reference): the notes packed once into one file (on any machine, no GPU needed), then held on the
 device and drawn there, batch for batch what `--filenames` yields (gansynth_amd/bank.py, DESIGN.md "Resident notes"):
 
@@ -95,6 +102,11 @@ parser.add_argument("--stereo", action="store_true",
                     help="--synthesize: a two-channel WAV: pan (CC 10, JSON \"pan\") and --spread place the notes, both channels share one peak")
 parser.add_argument("--spread", type=float, default=0.0, metavar="FLOAT",
                     help="--synthesize --stereo: how far the parts without a pan fan out between left and right (0: all in the centre .. 1)")
+parser.add_argument("--controllers", action="store_true",
+                    help="--synthesize: honour what the score says after a note has started: channel volume (CC 7), expression (CC 11), "
+                         "pan (CC 10, with --stereo) and the sustain pedal (CC 64), as one gain curve per part")
+parser.add_argument("--controller_ramp", type=float, default=0.01, metavar="SECONDS",
+                    help="--controllers: the length of the linear ramp with which a controller change takes effect")
 parser.add_argument("--reverb", type=float, default=None, metavar="SECONDS",
                     help="--synthesize: reverberate the clip in a designed room with this RT60 (seeded by --seed; two channels with --stereo)")
 parser.add_argument("--reverb_ir", type=str, default=None, metavar="FILE.wav",
@@ -179,6 +191,19 @@ def check_loudness_args(args):
     return True
 
 
+def check_controller_args(args):
+    """--controllers and --controller_ramp against each other and against --synthesize: SystemExit with a message.  -> whether controllers
+    are asked for."""
+    wanted, ramp = getattr(args, "controllers", False), getattr(args, "controller_ramp", 0.01)
+    if not wanted and ramp != 0.01:   # (NaN differs from everything)
+        raise SystemExit("--controller_ramp needs --controllers")
+    if wanted and args.synthesize is None:
+        raise SystemExit("--controllers applies to --synthesize only")
+    if wanted and not 0 <= ramp < float("inf"):
+        raise SystemExit(f"--controller_ramp must be a finite, non-negative number of seconds (got {ramp})")
+    return wanted
+
+
 def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     """--synthesize: the score args.synthesize through GANSynth.synthesize into the 16-bit WAV args.output (the kernel's own PCM: [T], or
     the interleaved [T, 2] of --stereo, which is a two-channel WAV's layout).  With --reverb / --reverb_ir: the unnormalised clip at the
@@ -190,6 +215,7 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     reverb_wanted = check_reverb_args(args)
     limit_wanted = check_limit_args(args)
     loudness_wanted = check_loudness_args(args)
+    controllers_wanted = check_controller_args(args)
     last_wanted = limit_wanted or loudness_wanted   # a stage after the reverb that sets the level and quantises
     if os.path.splitext(args.synthesize)[1].lower() not in (".mid", ".midi", ".json"):
         raise SystemExit(f"--synthesize takes a .mid, .midi or .json score (got {args.synthesize})")
@@ -201,6 +227,8 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
                release_seconds=args.release_seconds, info=info, pitches=pitches, batch_size=args.batch_size, weights=args.weights,
                sample_rate=getattr(args, "output_rate", None), ensemble=getattr(args, "ensemble", False),
                stereo=getattr(args, "stereo", False), spread=getattr(args, "spread", 0.0))
+    if controllers_wanted:   # (without the flag the call is the one it was)
+        how.update(controllers=True, controller_ramp=args.controller_ramp)
     if reverb_wanted or last_wanted:   # only the last stage normalises (or limits) and quantises
         clip = model.synthesize(args.synthesize, normalize=False, want_pcm=False, **how)
     if reverb_wanted:
@@ -249,6 +277,10 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
            + (f": the limiter had to work (least gain {info['limit_min_gain']:.4f}) and the output is "
               f"{args.loudness - info['loudness_output']:.2f} LU short of the target" if info["limit_min_gain"] < 1 else "")
            if loudness_wanted else ""))
+    if controllers_wanted:
+        counts = info["controls"]
+        log(f"controllers: {counts['volume']} volume, {counts['expression']} expression and {counts['pan']} pan events in {info['curve_points']} "
+            f"curve points, {info['pedal_extended']} notes held by the pedal")
     return info
 
 
@@ -267,6 +299,7 @@ def main(args):
     check_reverb_args(args)
     check_limit_args(args)
     check_loudness_args(args)
+    check_controller_args(args)
     if args.pack_bank is not None:
         pack_bank(args, range(24, 85), [0])
         return

@@ -212,6 +212,8 @@ SIGNATURES = {
     "gs_note_mix": (I, [P, I, L, L, P, I, L, I, P, P, P, P, Z, P]),
     "gs_note_mix_stereo_workspace_bytes": (Z, [L]),
     "gs_note_mix_stereo": (I, [P, I, L, L, P, I, L, I, P, L, P, P, P, Z, P]),
+    "gs_note_mix_curves_workspace_bytes": (Z, [L]),
+    "gs_note_mix_curves": (I, [P, I, L, L, P, I, P, I, P, I, I, L, I, P, L, P, P, P, Z, P]),
     "gs_stereo_finish_workspace_bytes": (Z, [L]),
     "gs_stereo_finish": (I, [P, L, L, I, P, P, P, Z, P]),
     "gs_bank_gather": (I, [P, L, L, L, P, P, L, L, I, I, P, P, P]),
@@ -295,6 +297,17 @@ class GsMixNoteStereo(ctypes.Structure):
     """include/gansynth_hip.h: one note of gs_note_mix_stereo's table (32 bytes; device memory, sorted by onset; `reserved` is not read)."""
     _fields_ = [("onset", ctypes.c_int64), ("hold", ctypes.c_int32), ("release", ctypes.c_int32), ("row", ctypes.c_int32),
                 ("gain_l", c_float), ("gain_r", c_float), ("reserved", ctypes.c_int32)]
+
+
+class GsMixNoteCurve(ctypes.Structure):
+    """include/gansynth_hip.h: one note of gs_note_mix_curves' table (32 bytes; device memory, sorted by onset; `reserved` is not read)."""
+    _fields_ = [("onset", ctypes.c_int64), ("hold", ctypes.c_int32), ("release", ctypes.c_int32), ("row", ctypes.c_int32),
+                ("gain", c_float), ("curve", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class GsCurvePoint(ctypes.Structure):
+    """include/gansynth_hip.h: one point of a gain curve of gs_note_mix_curves (16 bytes; device memory, a curve's points by position)."""
+    _fields_ = [("pos", ctypes.c_int64), ("v_l", c_float), ("v_r", c_float)]
 
 
 _lib = None

@@ -118,6 +118,54 @@ def note_mix_stereo_table(table, rows, length, total):
     return _note_table(2, table, rows, length, total)
 
 
+def note_mix_curves_table(table, points, first, rows, length, total):
+    """The host side of note_mix_curves: note_mix_table's checks and order for rows (onset, hold, release, row, gain, curve), and the
+    curves -- `points`: rows (pos, v_l, v_r); `first`: len(curves) + 1 integers, curve p owning points[first[p]:first[p + 1]] -- checked:
+    `first` non-decreasing from 0 to len(points) with every range non-empty, positions integers strictly increasing within a curve, values
+    finite, every note's `curve` in range.  ValueError by index and field name.  -> (ctypes arrays of GsMixNoteCurve, GsCurvePoint and
+    int32).  Needs no device."""
+    what = "note_mix_curves"
+    fields = ("onset", "hold", "release", "row", "gain", "curve")
+    if len(table) == 0:
+        raise ValueError(f"{what}: the table is empty")
+    for i, entry in enumerate(table):
+        if len(entry) != len(fields):
+            raise ValueError(f"{what}: note {i} has {len(entry)} fields, not ({', '.join(fields)})")
+    first = list(first)
+    for p, v in enumerate(first):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise ValueError(f"{what}: first[{p}] must be an integer (got {v!r})")
+    if len(first) < 2 or first[0] != 0 or first[-1] != len(points):
+        raise ValueError(f"{what}: first must run from 0 to len(points) = {len(points)} over at least one curve (got {first})")
+    n_curves = len(first) - 1
+    for p in range(n_curves):
+        if not first[p] < first[p + 1]:
+            raise ValueError(f"{what}: curve {p} has no point (first[{p}] = {first[p]}, first[{p + 1}] = {first[p + 1]})")
+    curve_of = [p for p in range(n_curves) for _ in range(first[p], first[p + 1])]
+    for j, point in enumerate(points):
+        if len(point) != 3:
+            raise ValueError(f"{what}: point {j} has {len(point)} fields, not (pos, v_l, v_r)")
+        pos = point[0]
+        if not isinstance(pos, (int, np.integer)) or isinstance(pos, bool):
+            raise ValueError(f"{what}: point {j} field 'pos' must be an integer (got {pos!r})")
+        if j > first[curve_of[j]] and not points[j - 1][0] < pos:
+            raise ValueError(f"{what}: point {j} field 'pos' = {pos} does not come after point {j - 1}'s {points[j - 1][0]} in curve {curve_of[j]}")
+        for name, v in zip(("v_l", "v_r"), point[1:]):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(v):
+                raise ValueError(f"{what}: point {j} field '{name}' must be a finite number (got {v!r})")
+    for i, entry in enumerate(table):
+        curve = entry[5]
+        if not isinstance(curve, (int, np.integer)) or isinstance(curve, bool):
+            raise ValueError(f"{what}: note {i} field 'curve' must be an integer (got {curve!r})")
+        if not 0 <= curve < n_curves:
+            raise ValueError(f"{what}: note {i} field 'curve' = {curve} is outside [0, {n_curves})")
+    checked = _checked_notes(what, [tuple(entry[:5]) for entry in table], rows, length, total, ("gain",))
+    order = sorted(range(len(table)), key=lambda i: (int(table[i][0]), i))   # (_checked_notes' order)
+    notes = (_lib.GsMixNoteCurve * len(checked))(*[_lib.GsMixNoteCurve(*row, int(table[i][5]), 0) for row, i in zip(checked, order)])
+    pts = (_lib.GsCurvePoint * len(points))(*[_lib.GsCurvePoint(int(pos), float(v_l), float(v_r)) for pos, v_l, v_r in points])
+    return notes, pts, (ctypes.c_int32 * len(first))(*[int(v) for v in first])
+
+
 def fft_convolve_shapes(x, impulse, dry, wet):
     """The host side of fft_convolve: -> (rows, n, ir_rows, m) of x ([n] or [rows, n], rows 1 or 2) and impulse ([m] or [ir_rows, m],
     ir_rows 1 or rows), both fp32.  ValueError by argument name; needs no device."""
@@ -1497,6 +1545,31 @@ class HipKernels(object):
         rounded up to 4, so that both rows start on 16 bytes --, pcm [total, 2] int16 or None, peak [1] fp32 = max |mix| over both
         channels); both channels are divided by peak when `normalize` and peak > 1."""
         return self._note_mix(2, waves, table, total, normalize, want_pcm)
+
+    def note_mix_curves(self, waves, table, points, first, total, channels=2, normalize=True, want_pcm=False):
+        """gs_note_mix_curves (include/gansynth_hip.h): the notes of `table` -- host rows (onset, hold, release, row, gain, curve) -- mixed
+        from the rows of waves [rows, L] fp32 under the piecewise-linear gain curves `points` / `first` (note_mix_curves_table).
+        -> what note_mix returns with channels == 1 and what note_mix_stereo returns with channels == 2."""
+        if channels not in (1, 2):
+            raise ValueError(f"note_mix_curves: channels must be 1 or 2 (got {channels!r})")
+        if waves.dim() != 2 or waves.dtype != torch.float32:
+            raise ValueError(f"note_mix_curves: waves must be [rows, L] fp32 (got {tuple(waves.shape)} {waves.dtype})")
+        rows, length = int(waves.shape[0]), int(waves.shape[1])
+        total = int(total)
+        arr, pts, firsts = note_mix_curves_table(table, points, first, rows, length, total)
+        if waves.stride(1) != 1 or (rows > 1 and waves.stride(0) < length):
+            waves = waves.contiguous()
+        notes, pts_dev, first_dev = (torch.frombuffer(bytearray(bytes(a)), dtype=torch.uint8).to(waves.device) for a in (arr, pts, firsts))
+        stride = (total + 3) // 4 * 4
+        out = torch.empty((total,) if channels == 1 else (2, stride), dtype=torch.float32, device=waves.device)
+        pcm = torch.empty((total,) if channels == 1 else (total, 2), dtype=torch.int16, device=waves.device) if want_pcm else None
+        peak = torch.empty((1,), dtype=torch.float32, device=waves.device)
+        ws = _ws(self.lib.gs_note_mix_curves_workspace_bytes(total), waves.device)
+        _lib.check(self.lib.gs_note_mix_curves(waves.data_ptr(), rows, length, int(waves.stride(0)) if rows > 1 else length, notes.data_ptr(), len(arr),
+                                               pts_dev.data_ptr(), len(pts), first_dev.data_ptr(), len(firsts) - 1, channels, total,
+                                               1 if normalize else 0, out.data_ptr(), stride, None if pcm is None else pcm.data_ptr(),
+                                               peak.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_note_mix_curves")
+        return (out if channels == 1 else out[:, :total]), pcm, peak
 
     def stereo_finish(self, x, normalize=True, want_pcm=False):
         """gs_stereo_finish (include/gansynth_hip.h): the second stage of note_mix_stereo on a clip x [2, n] fp32 that did not come from it

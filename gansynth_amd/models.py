@@ -916,8 +916,8 @@ class GANSynth(Iterations, DataParallel, Capture):
 
     # --------------------------------------------------------------------------------------- note sequences
     def synthesize(self, notes, model_dir=None, latents=None, seed=0, seconds_per_instrument=6.0, release_seconds=1.0, normalize=True,
-                   want_pcm=False, info=None, pitches=range(24, 85), batch_size=8, weights="live", sample_rate=None, ensemble=False,
-                   stereo=False, spread=0.0):
+                   want_pcm=False, info=None, pitches=range(24, 85), batch_size=8, weights="live", sample_rate=None, controllers=False,
+                   controller_ramp=0.01, ensemble=False, stereo=False, spread=0.0):
         """A score -> one mixed clip (not in the reference: the rules are this project's own, DESIGN.md "Note sequences").
 
         `notes`: notes.Note rows, or what notes.read_notes accepts (a .mid / .json file name or bytes).  Restores the latest checkpoint of
@@ -941,14 +941,32 @@ class GANSynth(Iterations, DataParallel, Capture):
         `stereo`: pan and `spread` (in [0, 1]: how far the parts without a pan fan out) enter the two gains of notes.schedule_gains, ONE
         gs_note_mix_stereo call mixes both channels and normalises them by their joint peak; the clip is [2, T] and the PCM [T, 2].  With
         `sample_rate` at another rate: the stereo mix unnormalised, ONE gs_resample call on its two rows, ONE gs_stereo_finish at the new
-        rate.  `info` also receives parts, part_of_note (per kept note) and channels."""
+        rate.  `info` also receives parts, part_of_note (per kept note) and channels.
+        `controllers`, `controller_ramp` (DESIGN.md "Controllers"; off: the paths above, untouched).  The score is read by
+        notes.read_performance (a notes.Performance is taken as it is; a Score or a list of Note has no controls): the sustain pedal has
+        moved note ends, and channel volume, expression and -- with `stereo` -- pan form one gain curve per part (notes.schedule_curves,
+        every change a ramp of `controller_ramp` seconds).  A note's own gain is velocity / 127 and nothing else; ONE gs_note_mix_curves
+        call takes the place of the gs_note_mix / gs_note_mix_stereo call and everything behind it is as above.  `ensemble` still decides
+        the instruments only.  `info` also receives controls (counts by kind), pedal_extended and curve_points."""
         from . import notes as N
         if self.world > 1:
             raise RuntimeError("GANSynth.synthesize runs in one process: launch it without torch.distributed (world size 1)")
         if self.spectral_params is None:
             raise ValueError("synthesize: the model has no spectral_params (waveform_length, sample_rate, ...)")
-        score = None
-        if ensemble or stereo:
+        score = performance = None
+        if controllers:
+            if isinstance(notes, N.Performance):
+                performance = notes
+            elif isinstance(notes, N.Score):
+                performance = N.plain_performance(notes)
+            elif isinstance(notes, (list, tuple)) and all(isinstance(n, N.Note) for n in notes):
+                performance = N.plain_performance(N.one_part_score(notes))
+            else:
+                performance = N.read_performance(notes)
+            score = performance.score
+            notes = score.notes
+            N.schedule_curves(performance, [], self.spectral_params["sample_rate"], controller_ramp, stereo, spread)   # (refusals first)
+        elif ensemble or stereo:
             if isinstance(notes, N.Score):
                 score = notes
             elif isinstance(notes, (list, tuple)) and all(isinstance(n, N.Note) for n in notes):
@@ -966,6 +984,10 @@ class GANSynth(Iterations, DataParallel, Capture):
         if score is not None:
             index = N.kept_indices(notes, pitches)
             part_of_note = [score.part[i] for i in index]
+        if performance is not None:   # velocity / 127 and the part: volume, expression and pan reach the samples through the curves
+            table = [row + (part,) for row, part in zip(table, part_of_note)]
+            points, first = N.schedule_curves(performance, index, sr, controller_ramp, stereo, spread)
+        elif score is not None:
             if not ensemble:   # one instrument, and the channel volume does not enter: 127 / 127 is an exact 1
                 score = score._replace(volume=[127] * len(score.notes))
             if stereo:
@@ -1001,7 +1023,10 @@ class GANSynth(Iterations, DataParallel, Capture):
         K = kernels.get()
         resampled = sample_rate is not None and int(sample_rate) != int(sr)
         last, unfinished = dict(normalize=normalize, want_pcm=want_pcm), dict(normalize=False, want_pcm=False)
-        clip, pcm, peak = (K.note_mix_stereo if stereo else K.note_mix)(waves, table, total, **(unfinished if resampled else last))
+        if performance is not None:
+            clip, pcm, peak = K.note_mix_curves(waves, table, points, first, total, channels=2 if stereo else 1, **(unfinished if resampled else last))
+        else:
+            clip, pcm, peak = (K.note_mix_stereo if stereo else K.note_mix)(waves, table, total, **(unfinished if resampled else last))
         if resampled:
             clip, pcm, peak = K.resample(clip, int(sr), int(sample_rate), **(unfinished if stereo else last))
             if stereo:
@@ -1013,6 +1038,8 @@ class GANSynth(Iterations, DataParallel, Capture):
                         sample_rate=int(sr if sample_rate is None else sample_rate), output_samples=int(clip.shape[-1]))
             if score is not None:
                 info.update(parts=list(score.parts), part_of_note=part_of_note, channels=2 if stereo else 1)
+            if performance is not None:
+                info.update(controls=N.control_counts(performance), pedal_extended=performance.pedal_extended, curve_points=len(points))
         return (clip, pcm) if want_pcm else clip
 
     # ------------------------------------------------------------------------------------------- evaluation

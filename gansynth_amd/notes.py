@@ -8,6 +8,10 @@ interpolation between anchors drawn from a generator of their own (the global RN
 Parts and stereo (DESIGN.md "Parts and stereo"): `read_score` reads the same files into a `Score` -- the same notes, and per note its part
 (a MIDI channel under one program, or a JSON "part"), its channel volume and its pan; `schedule_gains` turns them into the two gains of
 kernels.HipKernels.note_mix_stereo, `schedule_part_latents` gives every part a latent trajectory of its own.
+
+Controllers (DESIGN.md "Controllers"): `read_performance` reads the same files into a `Performance` -- the Score with the sustain pedal
+applied to the note ends, and per part the channel volume, expression and pan events in time order; `schedule_curves` turns those into
+one piecewise-linear gain curve per part for kernels.HipKernels.note_mix_curves.
 """
 import bisect
 import collections
@@ -111,10 +115,13 @@ def _vlq(data, pos, end, what):
     raise ScoreError(f"MIDI file: {what} is longer than four bytes")
 
 
-def _read_track(data, pos, end, track, counter, controls=None):
+_CONTROLLERS = {7: "volume", 10: "pan", 11: "expression", 64: "pedal"}
+
+
+def _read_track(data, pos, end, track, counter, controls=None, ends=None):
     """One MTrk chunk's events -> ([(pitch, velocity, start tick, end tick, appearance, channel)], [(tick, tempo)]).  `controls` (a list)
-    also receives, in file order, (tick, channel, what, value) of every program change ("program"), CC 7 ("volume") and CC 10 ("pan")
-    outside channel 10."""
+    also receives, in file order, (tick, channel, what, value) of every program change ("program"), CC 7 ("volume"), CC 10 ("pan"),
+    CC 11 ("expression") and CC 64 ("pedal") outside channel 10; `ends` (a list) receives the tick of the track's last event."""
     notes, tempos = [], []
     sounding = {}   # (channel, pitch) -> (start tick, velocity, appearance)
     tick, status = 0, None
@@ -166,8 +173,8 @@ def _read_track(data, pos, end, track, counter, controls=None):
                 if controls is not None and channel != DRUM_CHANNEL:
                     if kind == 0xC0:
                         controls.append((tick, channel, "program", first & 0x7F))
-                    elif kind == 0xB0 and first in (7, 10):
-                        controls.append((tick, channel, "volume" if first == 7 else "pan", second & 0x7F))
+                    elif kind == 0xB0 and first in _CONTROLLERS:
+                        controls.append((tick, channel, _CONTROLLERS[first], second & 0x7F))
                 continue
             key = (channel, first)
             if key in sounding:                              # a note-off, or a re-trigger: the earlier note ends here
@@ -177,12 +184,15 @@ def _read_track(data, pos, end, track, counter, controls=None):
                 counter[0] += 1
     for key in sorted(sounding, key=lambda k: sounding[k][2]):   # still sounding: ends at the track's last event
         stop(key, tick)
+    if ends is not None:
+        ends.append(tick)
     return notes, tempos
 
 
-def _midi(data, controls=None):
+def _midi(data, controls=None, pedal=None):
     """notes_from_midi's work -> [(Note, appearance, channel, start tick)] sorted by (start, appearance); `controls` as in _read_track, over
-    all tracks in (track, file) order."""
+    all tracks in (track, file) order.  `pedal` (a dict, read_performance's): the sustain pedal moves the notes' end ticks before they
+    become seconds, and the dict receives `extended` (the notes made longer) and `seconds` (the tempo map, tick -> seconds)."""
     data = bytes(data)
     if len(data) < 14 or data[:4] != b"MThd":
         raise ScoreError("MIDI file: truncated or missing MThd header chunk")
@@ -196,7 +206,7 @@ def _midi(data, controls=None):
     if division == 0:
         raise ScoreError("MIDI file: division of 0 ticks per quarter note")
     pos, track, counter = 8 + header_len, 0, [0]
-    raw, tempos = [], []
+    raw, tempos, ends = [], [], []
     while track < ntracks:
         if pos + 8 > len(data):
             raise ScoreError(f"MIDI file: truncated: the header announces {ntracks} tracks, the file ends after {track}")
@@ -205,7 +215,7 @@ def _midi(data, controls=None):
         if pos + length > len(data):
             raise ScoreError(f"MIDI file: truncated chunk {tag!r}: {length} bytes announced, {len(data) - pos} present")
         if tag == b"MTrk":
-            n, t = _read_track(data, pos, pos + length, track, counter, controls)
+            n, t = _read_track(data, pos, pos + length, track, counter, controls, ends)
             raw += n
             tempos += t
             track += 1
@@ -228,8 +238,17 @@ def _midi(data, controls=None):
                 hi = mid
         return (elapsed[lo] + (tick - ticks[lo]) * values[lo]) / (division * 1e6)
 
+    raw = [e for e in raw if e[3] > e[2]]
+    if pedal is not None:
+        lanes = {}   # channel -> [(tick, down)] in (tick, track, file) order
+        for tick, channel, what, value in sorted(controls, key=lambda e: e[0]):
+            if what == "pedal":
+                lanes.setdefault(channel, []).append((tick, value >= 64))
+        new_ends, pedal["extended"] = _apply_pedal([(e[5], e[0], e[2], e[3]) for e in raw], lanes, max(ends, default=0))
+        raw = [e[:3] + (end,) + e[4:] for e, end in zip(raw, new_ends)]
+        pedal["seconds"] = seconds
     out = [(Note(pitch, velocity, seconds(start), seconds(end)), appearance, channel, start)
-           for pitch, velocity, start, end, appearance, channel in raw if end > start]
+           for pitch, velocity, start, end, appearance, channel in raw]
     out.sort(key=lambda e: (e[0].start, e[1]))
     return out
 
@@ -247,8 +266,13 @@ def score_from_midi(data):
     controller ON the note's tick applies wherever it stands; among several on one tick (track, file order) decides and the last one
     holds.  Defaults: program 0, volume 100, no pan; pan = clamp((cc10 - 64) / 63, -1, 1).  A note keeps the values it starts with.  A part
     is a distinct (channel, program in force at note-on), numbered in order of first appearance in the notes."""
+    return _score_from_midi(data)[0]
+
+
+def _score_from_midi(data, pedal=None):
+    """score_from_midi's work -> (Score, every controller event (tick, channel, what, value) in (track, file) order); `pedal` as in _midi."""
     controls = []
-    rows = _midi(data, controls)
+    rows = _midi(data, controls, pedal)
     lanes = {}   # (channel, what) -> ([tick], [value]) in (tick, track, file) order: the sort is stable and `controls` is in (track, file) order
     for tick, channel, what, value in sorted(controls, key=lambda e: e[0]):
         ticks, values = lanes.setdefault((channel, what), ([], []))
@@ -269,7 +293,7 @@ def score_from_midi(data):
         volume.append(in_force(channel, "volume", tick, DEFAULT_VOLUME))
         cc10 = in_force(channel, "pan", tick, None)
         pan.append(None if cc10 is None else min(max((cc10 - 64) / 63.0, -1.0), 1.0))
-    return Score([e[0] for e in rows], part, volume, pan, parts)
+    return Score([e[0] for e in rows], part, volume, pan, parts), controls
 
 
 def read_notes(path_or_bytes):
@@ -425,3 +449,198 @@ def schedule_part_latents(kept, part_of_kept, n_parts, total, sample_rate, seed,
         j = min(int(math.floor(x)), k - 1)
         out[n] = slerp(anchors[part][j], anchors[part][j + 1], min(x - j, 1.0))
     return torch.from_numpy(out.astype(np.float32))
+
+
+# ------------------------------------------------------------------------------------------------------------ controllers
+# DESIGN.md "Controllers": what a score says AFTER a note has started -- channel volume (CC 7), expression (CC 11), pan (CC 10) and the
+# sustain pedal (CC 64) -- read into a Performance and turned into one piecewise-linear gain curve per part for
+# kernels.HipKernels.note_mix_curves.  Nothing above reads any of it.
+# controls: per part the time-ordered (seconds, kind, value), kind "volume" / "expression" (0..127) or "pan" (a float in [-1, 1])
+Performance = collections.namedtuple("Performance", ["score", "controls", "pedal_extended"])
+CONTROL_KINDS = ("volume", "expression", "pan")
+DEFAULT_EXPRESSION = 127
+
+
+def _apply_pedal(notes, lanes, last):
+    """The sustain pedal, in whatever unit of time the caller counts (ticks, seconds).  notes: (lane, pitch, start, end) rows;
+    lanes: lane -> [(time, down)] in the order that decides (time, then the file's); last: the time of the file's last event.
+    The pedal's state at a time is the one after every event of the lane at or before that time.  A note whose end finds its lane's pedal
+    down ends at the first pedal-up after that (at the file's last event when none follows), but no later than the next start of a note of
+    the same (lane, pitch) after its own start, and no later than `last`.  -> ([end], how many notes became longer)."""
+    starts = {}
+    for lane, pitch, start, _ in notes:
+        starts.setdefault((lane, pitch), []).append(start)
+    for key in starts:
+        starts[key].sort()
+    ends, extended = [], 0
+    for lane, pitch, start, end in notes:
+        events = lanes.get(lane, [])
+        i = bisect.bisect_right([t for t, _ in events], end)   # the events at or before the note's end
+        new_end = end
+        if i and events[i - 1][1]:
+            ups = [t for t, down in events[i:] if not down]
+            new_end = ups[0] if ups else last
+            own = starts[(lane, pitch)]
+            j = bisect.bisect_right(own, start)
+            if j < len(own):
+                new_end = min(new_end, own[j])
+            new_end = max(min(new_end, last), end)
+        extended += new_end > end
+        ends.append(new_end)
+    return ends, extended
+
+
+def performance_from_midi(data):
+    """A Standard MIDI File -> Performance.  CC 7, CC 11, CC 10 and CC 64 are collected from all tracks outside channel 10 and ordered by
+    (tick, track, file order) -- score_from_midi's rule.  The pedal is applied in ticks, before the tempo map turns ticks into seconds.
+    A part, a (channel, program), receives the events of its channel; pan = clamp((cc10 - 64) / 63, -1, 1) as in score_from_midi."""
+    pedal = {}
+    score, events = _score_from_midi(data, pedal)
+    controls = [[] for _ in score.parts]
+    for tick, channel, what, value in sorted(events, key=lambda e: e[0]):   # (stable: (track, file) order inside a tick)
+        if what not in CONTROL_KINDS:
+            continue
+        if what == "pan":
+            value = min(max((value - 64) / 63.0, -1.0), 1.0)
+        for p, part in enumerate(score.parts):
+            if part.channel == channel:
+                controls[p].append((pedal["seconds"](tick), what, value))
+    return Performance(score, controls, pedal["extended"])
+
+
+def performance_from_json(obj):
+    """A JSON list of notes (score_from_json's; no controls), or {"notes": [...], "controls": [{"part", "time", "control", "value"}]}
+    -> Performance.  control: "volume" / "expression" (an integer 0..127), "pan" (a number in [-1, 1]) or "pedal" (a bool, or an integer
+    0..127 that is down from 64).  "part" names a "part" value of the notes.  With controls a note's own "volume" or "pan" is refused: the
+    controls say it.  The pedal is applied in seconds.  ScoreError by index and field name."""
+    if isinstance(obj, list):
+        score = score_from_json(obj)
+        return Performance(score, [[] for _ in score.parts], 0)
+    if not isinstance(obj, dict):
+        raise ScoreError(f"JSON score: a list of note objects or an object with \"notes\" and \"controls\" is expected (got {type(obj).__name__})")
+    for key in obj:
+        if key not in ("notes", "controls"):
+            raise ScoreError(f"JSON score: unknown field '{key}' (an object holds \"notes\" and \"controls\")")
+    if "notes" not in obj:
+        raise ScoreError("JSON score: the object has no field 'notes'")
+    items, entries = obj["notes"], obj.get("controls", [])
+    if isinstance(items, list):
+        for i, item in enumerate(items):
+            for field in ("volume", "pan"):
+                if isinstance(item, dict) and field in item:
+                    raise ScoreError(f"JSON score: note {i} field '{field}' is not allowed beside \"controls\": a control says it")
+    if not isinstance(entries, list):
+        raise ScoreError(f"JSON score: field 'controls' must be a list of control objects (got {type(entries).__name__})")
+    _json_notes(items)   # (refusals by note index before anything of the controls)
+    values = sorted({item.get("part", 0) for item in items if _is_int(item.get("part", 0))})
+    score = score_from_json(items)
+    checks = {"volume": (lambda v: _is_int(v) and 0 <= v <= 127, "an integer 0..127"),
+              "expression": (lambda v: _is_int(v) and 0 <= v <= 127, "an integer 0..127"),
+              "pan": (lambda v: _is_number(v) and -1 <= v <= 1, "a number in [-1, 1]"),
+              "pedal": (lambda v: isinstance(v, bool) or (_is_int(v) and 0 <= v <= 127), "a bool or an integer 0..127")}
+    timed = []
+    for i, entry in enumerate(entries):
+        if not isinstance(entry, dict):
+            raise ScoreError(f"JSON score: control {i} is not an object")
+        for field in ("part", "time", "control", "value"):
+            if field not in entry:
+                raise ScoreError(f"JSON score: control {i} has no field '{field}'")
+        if not _is_int(entry["part"]) or entry["part"] not in values:
+            raise ScoreError(f"JSON score: control {i} field 'part' must name a part of the notes, one of {values} (got {entry['part']!r})")
+        if not _is_number(entry["time"]) or entry["time"] < 0:
+            raise ScoreError(f"JSON score: control {i} field 'time' must be a non-negative number of seconds (got {entry['time']!r})")
+        if not isinstance(entry["control"], str) or entry["control"] not in checks:
+            raise ScoreError(f"JSON score: control {i} field 'control' must be one of {sorted(checks)} (got {entry['control']!r})")
+        ok, what = checks[entry["control"]]
+        if not ok(entry["value"]):
+            raise ScoreError(f"JSON score: control {i} field 'value' must be {what} for '{entry['control']}' (got {entry['value']!r})")
+        timed.append((float(entry["time"]), values.index(entry["part"]), entry["control"], entry["value"]))
+    timed.sort(key=lambda e: e[0])   # (stable: file order inside one time)
+    controls, lanes = [[] for _ in score.parts], {}
+    for time, part, kind, value in timed:
+        if kind == "pedal":
+            lanes.setdefault(part, []).append((time, value is True or (value is not False and value >= 64)))
+        else:
+            controls[part].append((time, kind, float(value) if kind == "pan" else value))
+    last = max([n.end for n in score.notes] + [e[0] for e in timed])
+    ends, extended = _apply_pedal([(p, n.pitch, n.start, n.end) for n, p in zip(score.notes, score.part)], lanes, last)
+    return Performance(score._replace(notes=[n._replace(end=end) for n, end in zip(score.notes, ends)]), controls, extended)
+
+
+def read_performance(path_or_bytes):
+    """The files of read_score -> Performance(score, controls, pedal_extended): `score` is read_score's, except that the sustain pedal has
+    moved note ends (_apply_pedal; `pedal_extended` counts the notes made longer); `controls` holds per part the time-ordered
+    (seconds, kind, value) of channel volume, expression and pan.  JSON may also be the object form of performance_from_json."""
+    return _read(path_or_bytes, performance_from_midi, performance_from_json)
+
+
+def plain_performance(score):
+    """A Score -> the Performance without a control or a pedal."""
+    return Performance(score, [[] for _ in score.parts], 0)
+
+
+def control_counts(performance):
+    """{"volume": n, "expression": n, "pan": n} over all parts."""
+    counts = dict.fromkeys(CONTROL_KINDS, 0)
+    for events in performance.controls:
+        for _, kind, _ in events:
+            counts[kind] += 1
+    return counts
+
+
+def schedule_curves(performance, kept_index, sample_rate, ramp_seconds=0.01, stereo=False, spread=0.0):
+    """-> (points, first): one piecewise-linear gain curve per part over clip samples at `sample_rate`, for kernels.note_mix_curves.
+    points: (pos, v_l, v_r) rows, pos strictly increasing inside a part; part p owns points[first[p]:first[p + 1]] and has at least one.
+    Per part the state (volume, expression, pan) starts at (100, 127, part_positions(score, spread)[p]); its target is
+        a = (volume / 127) (expression / 127);  stereo: (a cos(theta), a sin(theta)), theta = (pan + 1) pi / 4;  mono: (a, a), pan ignored.
+    An event stands at sample floor(seconds * sr + 0.5); the events of one sample collapse to the state after the last.  Events at sample
+    0 set the first value without a ramp.  A later sample s starts a linear ramp from the curve's value at s to the new target at s + R,
+    R = max(1, floor(ramp_seconds * sr + 0.5)); a ramp still in progress at s is cut there at its interpolated value.  Outside its points
+    a curve is constant.  Everything in float64, rounded once to fp32 (returned as the Python floats of those fp32 values).
+    `kept_index` (kept_indices'): the notes that sound; it must index the score's notes and does not change the curves, which describe
+    the parts.  ValueError for a ramp that is negative or not finite."""
+    score = performance.score
+    if isinstance(ramp_seconds, bool) or not isinstance(ramp_seconds, (int, float)) or not math.isfinite(ramp_seconds) or ramp_seconds < 0:
+        raise ValueError(f"schedule_curves: ramp_seconds must be a finite, non-negative number of seconds (got {ramp_seconds!r})")
+    if any(not 0 <= i < len(score.notes) for i in kept_index):
+        raise ValueError(f"schedule_curves: kept_index must index the {len(score.notes)} notes of the score")
+    positions = part_positions(score, spread)
+    ramp = max(1, _round(ramp_seconds * sample_rate))
+
+    def target(state):
+        a = (state["volume"] / 127.0) * (state["expression"] / 127.0)
+        if not stereo:
+            return (a, a)
+        theta = (state["pan"] + 1.0) * math.pi / 4.0
+        return (a * math.cos(theta), a * math.sin(theta))
+
+    points, first = [], [0]
+    for p, events in enumerate(performance.controls):
+        state = {"volume": DEFAULT_VOLUME, "expression": DEFAULT_EXPRESSION, "pan": positions[p]}
+        groups = []   # [sample, state after its last event] by sample
+        for seconds, kind, value in sorted(events, key=lambda e: e[0]):
+            if kind == "pan" and not stereo:
+                continue
+            state = dict(state, **{kind: value})
+            s = _round(seconds * sample_rate)
+            if groups and groups[-1][0] == s:
+                groups[-1][1] = state
+            else:
+                groups.append([s, state])
+        start = {"volume": DEFAULT_VOLUME, "expression": DEFAULT_EXPRESSION, "pan": positions[p]}
+        if groups and groups[0][0] == 0:
+            start = groups.pop(0)[1]
+        curve = [(0,) + target(start)]
+        for s, state in groups:
+            pos, v = curve[-1][0], curve[-1][1:]
+            if s < pos:                                   # a ramp in progress: cut at its interpolated value
+                (p0, *v0), (p1, *v1) = curve[-2], curve[-1]
+                x = (s - p0) / (p1 - p0)
+                v = tuple(a + x * (b - a) for a, b in zip(v0, v1))
+                curve.pop()
+            if s != curve[-1][0]:
+                curve.append((s,) + tuple(v))
+            curve.append((s + ramp,) + target(state))
+        points += [(pos, float(np.float32(v_l)), float(np.float32(v_r))) for pos, v_l, v_r in curve]
+        first.append(len(points))
+    return points, first

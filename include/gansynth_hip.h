@@ -704,6 +704,50 @@ size_t gs_stereo_finish_workspace_bytes(int64_t n);
 int gs_stereo_finish(float* x, int64_t n, int64_t row_stride, int normalize, int16_t* pcm, float* peak, void* ws, size_t ws_bytes,
                      void* stream);
 
+/* ---- Controllers: the same mixdown under gains that are functions of clip time (GANSynth.synthesize with controllers; this project's own
+ * rules, DESIGN.md "Controllers") ----------------------------------------------------------------------------------------------------------
+ * waves, the table's order, onset / hold / release / row and env(k) are gs_note_mix's.  A note carries ONE gain and names a curve; a
+ * curve is the piecewise-linear function through its points: curve p owns points[first[p] .. first[p + 1]) (first: a DEVICE array of
+ * n_curves + 1 int32, non-decreasing from 0 to n_points, every range non-empty), their pos strictly increasing.  With i the last point
+ * of the range whose pos is <= t, for each channel c (v = v_l for channel 0, v_r for channel 1; one channel reads v_l only)
+ *     curve_c(t) = v_first                       for t before the first point,
+ *                  v_last                        from the last point on (and for a one-point curve everywhere),
+ *                  fl(v_i + fl(fl((float)(t - pos_i) * fl(1 / (float)(pos_{i+1} - pos_i))) * fl(v_{i+1} - v_i)))   otherwise
+ * (so curve_c(pos_i) = v_i exactly), and
+ *     mix_c[t] = sum over the covering notes, in ascending table order, of fl(fl(fl(gain * env(k)) * curve_c(t)) * waves[row][k])
+ * in fp32, every operation rounded on its own (no FMA; both quotients correctly rounded reciprocals that are multiplied by; the two
+ * int64 differences converted to fp32 with one rounding).  A table whose curves are all the one point (0, 1, 1) therefore gives
+ * gs_note_mix's bits with one channel and gs_note_mix_stereo's with gain_l = gain_r = gain with two.
+ * out, peak, the quotient and pcm: gs_note_mix's for channels == 1 (out_stride is not read), gs_note_mix_stereo's for channels == 2.
+ * Gather form, no atomics: gs_note_mix_stereo's block and searches.  A curve's value does not depend on the note, so a lane keeps the
+ * values of its 16 samples (per channel) in registers and evaluates them again only when the next candidate names another curve: every
+ * wave finds the last point at or before the tile's first sample by a 64-way search of the curve's range, every thread brings one
+ * point from there on into LDS (256 points, 4 KB), and each of the lane's four packs searches that window and walks through its four
+ * samples; a tile that needs more than 256 points of one curve searches global memory instead, with the same result.  Two launches as for the other mixes, the second one clip_finish's, skipped when normalize == 0 and
+ * pcm == peak == NULL.
+ * A bad table cannot make the kernel read outside waves, points or first, or write outside the rows' [0, total): the judgements of
+ * gs_note_mix_stereo hold, a note whose curve is outside [0, n_curves) is skipped IN the kernel, first's entries are clamped so that
+ * every index into points lies in [0, n_points) before an address is formed, positions out of order give some value (finite or not)
+ * of the points in range, and a segment of length <= 0 is not divided by (the curve takes v_i there).  `reserved` is not read.
+ * GS_ERR_ARG with a message and without a launch: gs_note_mix_stereo's conditions (out_stride only with two channels), n_points or
+ * n_curves <= 0, channels outside {1, 2}, points / first NULL, points off 8 bytes, first off 4 bytes. */
+typedef struct GsMixNoteCurve {
+    int64_t onset;          /* as GsMixNote */
+    int32_t hold, release;
+    int32_t row;
+    float gain;             /* the note's own gain (velocity / 127); everything else comes through the curve */
+    int32_t curve;          /* which curve: 0 <= curve < n_curves */
+    int32_t reserved;       /* pads the row to 32 bytes; not read */
+} GsMixNoteCurve;           /* 32 bytes */
+typedef struct GsCurvePoint {
+    int64_t pos;            /* a clip sample */
+    float v_l, v_r;         /* the curve's value there on channel 0 and on channel 1 */
+} GsCurvePoint;             /* 16 bytes */
+size_t gs_note_mix_curves_workspace_bytes(int64_t total);
+int gs_note_mix_curves(const float* waves, int rows, int64_t length, int64_t row_stride, const GsMixNoteCurve* notes, int n_notes,
+                       const GsCurvePoint* points, int n_points, const int32_t* first, int n_curves, int channels, int64_t total,
+                       int normalize, float* out, int64_t out_stride, int16_t* pcm, float* peak, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Resident notes: one batch drawn from the int16 bank on the device (gansynth_amd/bank.py, DESIGN.md "Resident notes") ----------
  * pcm: [rows] notes of `length` int16 samples, `row_stride` elements apart.  class_of_row: [rows] int32, the label index of a row or -1.
  * order: [n_order] int32 row numbers; the batch is order[first .. first + batch).  For b in [0, batch), r = order[first + b]:
