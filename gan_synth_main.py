@@ -57,6 +57,13 @@ key-up; every change takes effect over `--controller_ramp` seconds (default 0.01
     python gan_synth_main.py --synthesize sonata.mid --controllers --output sonata.wav
     python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --controllers --controller_ramp 0.02 --output quartet.wav
 
+`--bend` honours pitch bend (GANSynth.synthesize with bend, DESIGN.md "Pitch bend"): the wheel's messages and the range set through RPN 0,0
+become one playback-rate curve per part, and the notes it touches are resampled along it on the device before the mix; the clip's length
+and every onset stay as they are.  A change takes effect over `--controller_ramp` seconds, which `--bend` shares with `--controllers`:
+
+    python gan_synth_main.py --synthesize lead.mid --bend --output lead.wav
+    python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --controllers --bend --controller_ramp 0.005 --output quartet.wav
+
 `--pack_bank` / `--bank` (not in the reference): the notes packed once into one file (on any machine, no GPU needed), then held on the
 device and drawn there, batch for batch what `--filenames` yields (gansynth_amd/bank.py, DESIGN.md "Resident notes"):
 
@@ -106,7 +113,10 @@ parser.add_argument("--controllers", action="store_true",
                     help="--synthesize: honour what the score says after a note has started: channel volume (CC 7), expression (CC 11), "
                          "pan (CC 10, with --stereo) and the sustain pedal (CC 64), as one gain curve per part")
 parser.add_argument("--controller_ramp", type=float, default=0.01, metavar="SECONDS",
-                    help="--controllers: the length of the linear ramp with which a controller change takes effect")
+                    help="--controllers, --bend: the length of the linear ramp with which a controller or bend change takes effect")
+parser.add_argument("--bend", action="store_true",
+                    help="--synthesize: honour pitch bend (and the range set through RPN 0,0): the notes it touches are resampled along "
+                         "their part's bend curve on the device before the mix")
 parser.add_argument("--reverb", type=float, default=None, metavar="SECONDS",
                     help="--synthesize: reverberate the clip in a designed room with this RT60 (seeded by --seed; two channels with --stereo)")
 parser.add_argument("--reverb_ir", type=str, default=None, metavar="FILE.wav",
@@ -195,11 +205,14 @@ def check_controller_args(args):
     """--controllers and --controller_ramp against each other and against --synthesize: SystemExit with a message.  -> whether controllers
     are asked for."""
     wanted, ramp = getattr(args, "controllers", False), getattr(args, "controller_ramp", 0.01)
-    if not wanted and ramp != 0.01:   # (NaN differs from everything)
+    bend = getattr(args, "bend", False)   # (--bend shares the ramp)
+    if not wanted and not bend and ramp != 0.01:   # (NaN differs from everything)
         raise SystemExit("--controller_ramp needs --controllers")
     if wanted and args.synthesize is None:
         raise SystemExit("--controllers applies to --synthesize only")
-    if wanted and not 0 <= ramp < float("inf"):
+    if bend and args.synthesize is None:
+        raise SystemExit("--bend applies to --synthesize only")
+    if (wanted or bend) and not 0 <= ramp < float("inf"):
         raise SystemExit(f"--controller_ramp must be a finite, non-negative number of seconds (got {ramp})")
     return wanted
 
@@ -229,6 +242,9 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
                stereo=getattr(args, "stereo", False), spread=getattr(args, "spread", 0.0))
     if controllers_wanted:   # (without the flag the call is the one it was)
         how.update(controllers=True, controller_ramp=args.controller_ramp)
+    bend_wanted = getattr(args, "bend", False)
+    if bend_wanted:
+        how.update(bend=True, controller_ramp=args.controller_ramp)
     if reverb_wanted or last_wanted:   # only the last stage normalises (or limits) and quantises
         clip = model.synthesize(args.synthesize, normalize=False, want_pcm=False, **how)
     if reverb_wanted:
@@ -281,6 +297,9 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
         counts = info["controls"]
         log(f"controllers: {counts['volume']} volume, {counts['expression']} expression and {counts['pan']} pan events in {info['curve_points']} "
             f"curve points, {info['pedal_extended']} notes held by the pedal")
+    if bend_wanted:
+        log(f"bend: {sum(info['bends'])} events on {sum(1 for n in info['bends'] if n)} parts in {info['bend_points']} curve points, "
+            f"{info['bent_notes']} notes bent")
     return info
 
 

@@ -214,6 +214,9 @@ SIGNATURES = {
     "gs_note_mix_stereo": (I, [P, I, L, L, P, I, L, I, P, L, P, P, P, Z, P]),
     "gs_note_mix_curves_workspace_bytes": (Z, [L]),
     "gs_note_mix_curves": (I, [P, I, L, L, P, I, P, I, P, I, I, L, I, P, L, P, P, P, Z, P]),
+    "gs_note_warp_table_bytes": (Z, []),
+    "gs_note_warp_table": (I, [P]),
+    "gs_note_warp": (I, [P, I, L, L, P, I, P, P, I, I, P, P]),
     "gs_stereo_finish_workspace_bytes": (Z, [L]),
     "gs_stereo_finish": (I, [P, L, L, I, P, P, P, Z, P]),
     "gs_bank_gather": (I, [P, L, L, L, P, P, L, L, I, I, P, P, P]),
@@ -308,6 +311,20 @@ class GsMixNoteCurve(ctypes.Structure):
 class GsCurvePoint(ctypes.Structure):
     """include/gansynth_hip.h: one point of a gain curve of gs_note_mix_curves (16 bytes; device memory, a curve's points by position)."""
     _fields_ = [("pos", ctypes.c_int64), ("v_l", c_float), ("v_r", c_float)]
+
+
+WARP_TILE, WARP_ZEROS, WARP_Q = 1024, 32, 256   # GS_WARP_TILE, GS_WARP_ZEROS, GS_WARP_Q
+
+
+class GsWarpNote(ctypes.Structure):
+    """include/gansynth_hip.h: one bent note of gs_note_warp (24 bytes; device memory)."""
+    _fields_ = [("src_row", ctypes.c_int32), ("dst_row", ctypes.c_int32), ("onset", ctypes.c_int64), ("count", ctypes.c_int32),
+                ("curve", ctypes.c_int32)]
+
+
+class GsWarpPoint(ctypes.Structure):
+    """include/gansynth_hip.h: one point of a ratio curve of gs_note_warp (24 bytes; device memory, a curve's points by position)."""
+    _fields_ = [("pos", c_double), ("ratio", c_double), ("cum", c_double)]
 
 
 _lib = None

@@ -166,6 +166,79 @@ def note_mix_curves_table(table, points, first, rows, length, total):
     return notes, pts, (ctypes.c_int32 * len(first))(*[int(v) for v in first])
 
 
+def note_warp_table(warp_notes, points, first, rows, length):
+    """The host side of note_warp: `warp_notes` -- rows (src_row, dst_row, onset, count, curve) -- and the ratio curves -- `points`: rows
+    (pos, ratio, cum); `first`: len(curves) + 1 integers, curve p owning points[first[p]:first[p + 1]] -- checked: rows inside [0, rows),
+    no dst_row that is a src_row or the dst_row of another note, count in [1, length], onset >= 0, curve in range; `first` non-decreasing
+    from 0 to len(points) with every range non-empty; positions integer-valued and strictly increasing within a curve, ratios in
+    [0.25, 4], cum finite.  ValueError by index and field name.  -> (ctypes arrays of GsWarpNote, GsWarpPoint and int32).  Needs no
+    device."""
+    what = "note_warp"
+    fields = ("src_row", "dst_row", "onset", "count", "curve")
+    if len(warp_notes) == 0:
+        raise ValueError(f"{what}: the table is empty")
+    first = list(first)
+    for p, v in enumerate(first):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise ValueError(f"{what}: first[{p}] must be an integer (got {v!r})")
+    if len(first) < 2 or first[0] != 0 or first[-1] != len(points):
+        raise ValueError(f"{what}: first must run from 0 to len(points) = {len(points)} over at least one curve (got {first})")
+    n_curves = len(first) - 1
+    for p in range(n_curves):
+        if not first[p] < first[p + 1]:
+            raise ValueError(f"{what}: curve {p} has no point (first[{p}] = {first[p]}, first[{p + 1}] = {first[p + 1]})")
+    for j, point in enumerate(points):
+        if len(point) != 3:
+            raise ValueError(f"{what}: point {j} has {len(point)} fields, not (pos, ratio, cum)")
+    try:   # (a sequenced file can hold thousands of points: checked as arrays, reported by the first offender)
+        values = np.array(points, dtype=np.float64).reshape(-1, 3)
+    except (TypeError, ValueError):
+        values = np.full((len(points), 3), np.nan)
+        for j, point in enumerate(points):
+            for k, v in enumerate(point):
+                if not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer)):
+                    values[j, k] = v
+    pos, ratio = values[:, 0], values[:, 1]
+    after = np.ones(len(points), dtype=bool)
+    after[1:] = pos[1:] > pos[:-1]
+    after[first[:-1]] = True                                   # a curve's first point follows nothing
+    problems = [(~np.isfinite(values[:, k]), name, "must be a finite number") for k, name in enumerate(("pos", "ratio", "cum"))] + \
+               [((pos != np.floor(pos)) | (np.abs(pos) > 2.0 ** 53), "pos", "must be a whole clip sample"),
+                (~after, "pos", "does not come after the point before it in its curve"), (~((ratio >= 0.25) & (ratio <= 4.0)), "ratio", "is outside [0.25, 4]")]
+    bad = [(int(np.argmax(mask)), name, why) for mask, name, why in problems if mask.any()]
+    if bad:
+        j, name, why = min(bad, key=lambda b: b[0])
+        raise ValueError(f"{what}: point {j} field '{name}' {why} (got {points[j][('pos', 'ratio', 'cum').index(name)]!r})")
+    sources = set()
+    for i, entry in enumerate(warp_notes):
+        if len(entry) != len(fields):
+            raise ValueError(f"{what}: note {i} has {len(entry)} fields, not ({', '.join(fields)})")
+        for name, v in zip(fields, entry):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+                raise ValueError(f"{what}: note {i} field '{name}' must be an integer (got {v!r})")
+        src, dst, onset, count, curve = entry
+        if not 0 <= src < rows:
+            raise ValueError(f"{what}: note {i} field 'src_row' = {src} is outside [0, {rows})")
+        if not 0 <= dst < rows:
+            raise ValueError(f"{what}: note {i} field 'dst_row' = {dst} is outside [0, {rows})")
+        if not 1 <= count <= length:
+            raise ValueError(f"{what}: note {i} field 'count' = {count} is outside [1, {length}]")
+        if not 0 <= onset < 2 ** 62:
+            raise ValueError(f"{what}: note {i} field 'onset' = {onset} is negative (or beyond 2^62)")
+        if not 0 <= curve < n_curves:
+            raise ValueError(f"{what}: note {i} field 'curve' = {curve} is outside [0, {n_curves})")
+        sources.add(int(src))
+    written = set()
+    for i, entry in enumerate(warp_notes):
+        dst = int(entry[1])
+        if dst in sources or dst in written:
+            raise ValueError(f"{what}: note {i} field 'dst_row' = {dst} is the src_row or the dst_row of another note")
+        written.add(dst)
+    notes = (_lib.GsWarpNote * len(warp_notes))(*[_lib.GsWarpNote(*[int(v) for v in entry]) for entry in warp_notes])
+    pts = (_lib.GsWarpPoint * len(points)).from_buffer_copy(np.ascontiguousarray(values).tobytes())
+    return notes, pts, (ctypes.c_int32 * len(first))(*[int(v) for v in first])
+
+
 def fft_convolve_shapes(x, impulse, dry, wet):
     """The host side of fft_convolve: -> (rows, n, ir_rows, m) of x ([n] or [rows, n], rows 1 or 2) and impulse ([m] or [ir_rows, m],
     ir_rows 1 or rows), both fp32.  ValueError by argument name; needs no device."""
@@ -299,6 +372,8 @@ class HipKernels(object):
         self._fftconv = {}        # impulse tensor's identity -> (the tensor, its prepared spectrum): fft_convolve_spectrum
         self.fftconv_prepares = 0   # gs_fftconv_prepare calls so far (tests: one per impulse tensor)
         self._loudness = {}       # rate -> GsLoudness: loudness_design
+        self._warp_table = {}     # device index -> gs_note_warp's coefficient table there: note_warp_table_dev
+        self.note_warps = 0       # gs_note_warp calls so far (tests: a score without a bent note launches none)
 
     # --------------------------------------------------------- prepared-weight workspaces
     def register_param_buffer(self, flat):
@@ -1570,6 +1645,36 @@ class HipKernels(object):
                                                1 if normalize else 0, out.data_ptr(), stride, None if pcm is None else pcm.data_ptr(),
                                                peak.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_note_mix_curves")
         return (out if channels == 1 else out[:, :total]), pcm, peak
+
+    def note_warp_table_dev(self, device):
+        """gs_note_warp's coefficient table on `device`, built on the host and uploaded once per device."""
+        device = torch.device(device)
+        key = device.index if device.index is not None else torch.cuda.current_device()
+        if key not in self._warp_table:
+            host = np.empty(self.lib.gs_note_warp_table_bytes() // 4, dtype=np.float32)
+            _lib.check(self.lib.gs_note_warp_table(host.ctypes.data), "gs_note_warp_table")
+            self._warp_table[key] = torch.from_numpy(host).to(device)
+        return self._warp_table[key]
+
+    def note_warp(self, waves, warp_notes, points, first):
+        """gs_note_warp (include/gansynth_hip.h): for every row (src_row, dst_row, onset, count, curve) of `warp_notes`, the first `count`
+        samples of waves[dst_row] become waves[src_row] played at the rate of its curve (`points` / `first`: note_warp_table), IN
+        PLACE; nothing else is written.  waves: [rows, L] fp32 on the device with contiguous rows.  -> waves."""
+        if waves.dim() != 2 or waves.dtype != torch.float32 or not waves.is_cuda:
+            raise ValueError(f"note_warp: waves must be [rows, L] fp32 on the HIP device (got {tuple(waves.shape)} {waves.dtype} on {waves.device})")
+        rows, length = int(waves.shape[0]), int(waves.shape[1])
+        if waves.stride(1) != 1 or (rows > 1 and waves.stride(0) < length):
+            raise ValueError(f"note_warp: the rows of waves must be contiguous and apart (strides {tuple(waves.stride())}): it works in place")
+        arr, pts, firsts = note_warp_table(warp_notes, points, first, rows, length)
+        if len(arr) > 65535:
+            raise ValueError(f"note_warp: {len(arr)} notes are more than the 65535 of one call")
+        table = self.note_warp_table_dev(waves.device)
+        notes, pts_dev, first_dev = (torch.frombuffer(bytearray(bytes(a)), dtype=torch.uint8).to(waves.device) for a in (arr, pts, firsts))
+        _lib.check(self.lib.gs_note_warp(waves.data_ptr(), rows, length, int(waves.stride(0)) if rows > 1 else length, notes.data_ptr(), len(arr),
+                                         pts_dev.data_ptr(), first_dev.data_ptr(), len(firsts) - 1, len(pts), table.data_ptr(), _stream()),
+                   "gs_note_warp")
+        self.note_warps += 1
+        return waves
 
     def stereo_finish(self, x, normalize=True, want_pcm=False):
         """gs_stereo_finish (include/gansynth_hip.h): the second stage of note_mix_stereo on a clip x [2, n] fp32 that did not come from it

@@ -917,7 +917,7 @@ class GANSynth(Iterations, DataParallel, Capture):
     # --------------------------------------------------------------------------------------- note sequences
     def synthesize(self, notes, model_dir=None, latents=None, seed=0, seconds_per_instrument=6.0, release_seconds=1.0, normalize=True,
                    want_pcm=False, info=None, pitches=range(24, 85), batch_size=8, weights="live", sample_rate=None, controllers=False,
-                   controller_ramp=0.01, ensemble=False, stereo=False, spread=0.0):
+                   controller_ramp=0.01, bend=False, ensemble=False, stereo=False, spread=0.0):
         """A score -> one mixed clip (not in the reference: the rules are this project's own, DESIGN.md "Note sequences").
 
         `notes`: notes.Note rows, or what notes.read_notes accepts (a .mid / .json file name or bytes).  Restores the latest checkpoint of
@@ -947,13 +947,39 @@ class GANSynth(Iterations, DataParallel, Capture):
         moved note ends, and channel volume, expression and -- with `stereo` -- pan form one gain curve per part (notes.schedule_curves,
         every change a ramp of `controller_ramp` seconds).  A note's own gain is velocity / 127 and nothing else; ONE gs_note_mix_curves
         call takes the place of the gs_note_mix / gs_note_mix_stereo call and everything behind it is as above.  `ensemble` still decides
-        the instruments only.  `info` also receives controls (counts by kind), pedal_extended and curve_points."""
+        the instruments only.  `info` also receives controls (counts by kind), pedal_extended and curve_points.
+        `bend` (DESIGN.md "Pitch bend"; off, or on with a score that bends no note: the paths above, not a launch changed).  True: the
+        score's pitch bend is read by notes.read_bends (a score given as notes.Note rows, a Score or a Performance carries none); or the
+        bends themselves, per part a list of (seconds, semitones).  Each note's part is read_score's, whatever `ensemble`, `stereo` and
+        `controllers` decide about instruments and gains.  Every part with a bend gets one playback-rate curve (notes.schedule_bends,
+        every change a ramp of `controller_ramp` seconds); `waves` is allocated [N + B, L] for the B notes whose curve leaves 1 while
+        they sound, the generator fills the first N rows, ONE gs_note_warp call writes the bent copies into the rest, the bent notes'
+        table rows name their copies, and the chosen mix call and everything behind it run unchanged.  The clip's length and every
+        onset stay as they are.  `info` also receives bends (events per part), bent_notes and bend_points."""
         from . import notes as N
         if self.world > 1:
             raise RuntimeError("GANSynth.synthesize runs in one process: launch it without torch.distributed (world size 1)")
         if self.spectral_params is None:
             raise ValueError("synthesize: the model has no spectral_params (waveform_length, sample_rate, ...)")
-        score = performance = None
+        score = performance = bends = None
+        if isinstance(bend, (list, tuple)):
+            bends, bend = [list(events) for events in bend], True
+        is_rows = isinstance(notes, (list, tuple)) and all(isinstance(n, N.Note) for n in notes)
+        if bend and bends is None and not is_rows and not isinstance(notes, (N.Score, N.Performance)):
+            if not isinstance(notes, (bytes, bytearray, memoryview)):
+                with open(os.fspath(notes), "rb") as f:   # (read once: the readers below take the bytes)
+                    notes = f.read()
+            bends = N.read_bends(notes)
+        if bends is not None:   # (refusals first)
+            bend_points, bend_first = N.schedule_bends(bends, self.spectral_params["sample_rate"], controller_ramp)
+        bend_counts = [len(events) for events in bends] if bends is not None else []
+        if bends is not None and not any(bends):
+            bends = None                                   # a score without a bend: the paths as they are
+        bend_score = None
+        if bends is not None and not (controllers or ensemble or stereo):   # the parts, for the plain path: read_score's
+            bend_score = notes if isinstance(notes, N.Score) else N.one_part_score(notes) if is_rows else \
+                notes.score if isinstance(notes, N.Performance) else N.read_score(notes)
+            notes = bend_score.notes
         if controllers:
             if isinstance(notes, N.Performance):
                 performance = notes
@@ -1005,6 +1031,17 @@ class GANSynth(Iterations, DataParallel, Capture):
             if lat.dim() != 2 or lat.shape[0] != count:
                 raise ValueError(f"synthesize: latents must be [{count}, Z] (one row per kept note) or [Z] (got {tuple(lat.shape)})")
             lat = lat.contiguous()
+        warp_notes = []
+        if bends is not None:   # the bent notes get rows of their own behind the generated ones
+            parts = score if score is not None else bend_score
+            if len(bends) != len(parts.parts):
+                raise ValueError(f"synthesize: bend must hold one list of events per part of the score, {len(parts.parts)} (got {len(bends)})")
+            bend_part = [parts.part[i] for i in N.kept_indices(notes, pitches)]
+            curved = [p for p in range(len(bends)) if bend_first[p] < bend_first[p + 1]]
+            for n in N.bent_notes(table, bend_part, bend_points, bend_first):
+                onset, hold, release, row = table[n][:4]
+                warp_notes.append((row, count + len(warp_notes), onset, hold + release, curved.index(bend_part[n])))
+                table[n] = table[n][:3] + (count + len(warp_notes) - 1,) + table[n][4:]
         labels = N.labels_for(kept, pitches)
         dev = self.store.device if hasattr(self.store, "device") else "cuda"
         if self.g_params is None:
@@ -1013,14 +1050,16 @@ class GANSynth(Iterations, DataParallel, Capture):
         if model_dir is not None:
             self.restored_from = restored
         self._join_updates()
-        waves = torch.empty((count, length), dtype=torch.float32, device=dev)
+        waves = torch.empty((count + len(warp_notes), length), dtype=torch.float32, device=dev)
         with self.averaged_generator() if weights == "average" else contextlib.nullcontext():
             for lo in range(0, count, batch):
                 rows = [min(i, count - 1) for i in range(lo, lo + batch)]   # the last chunk repeats its last row
                 wave = self._generate_batch(lat[rows].to(dev), labels[rows].to(dev))
-                waves[lo:lo + batch].copy_(wave[:min(batch, count - lo)])
+                waves[lo:min(lo + batch, count)].copy_(wave[:min(batch, count - lo)])   # (the rows behind `count` are the bent copies')
         # mix, then resample if asked, then (two resampled channels) the joint finish: only the last stage normalises and quantises
         K = kernels.get()
+        if warp_notes:
+            K.note_warp(waves, warp_notes, bend_points, [bend_first[p] for p in curved] + [len(bend_points)])
         resampled = sample_rate is not None and int(sample_rate) != int(sr)
         last, unfinished = dict(normalize=normalize, want_pcm=want_pcm), dict(normalize=False, want_pcm=False)
         if performance is not None:
@@ -1040,6 +1079,9 @@ class GANSynth(Iterations, DataParallel, Capture):
                 info.update(parts=list(score.parts), part_of_note=part_of_note, channels=2 if stereo else 1)
             if performance is not None:
                 info.update(controls=N.control_counts(performance), pedal_extended=performance.pedal_extended, curve_points=len(points))
+            if bend:
+                info.update(bends=bend_counts, bent_notes=len(warp_notes),
+                            bend_points=len(bend_points) if bends is not None else 0)
         return (clip, pcm) if want_pcm else clip
 
     # ------------------------------------------------------------------------------------------- evaluation

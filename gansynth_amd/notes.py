@@ -12,6 +12,10 @@ kernels.HipKernels.note_mix_stereo, `schedule_part_latents` gives every part a l
 Controllers (DESIGN.md "Controllers"): `read_performance` reads the same files into a `Performance` -- the Score with the sustain pedal
 applied to the note ends, and per part the channel volume, expression and pan events in time order; `schedule_curves` turns those into
 one piecewise-linear gain curve per part for kernels.HipKernels.note_mix_curves.
+
+Pitch bend (DESIGN.md "Pitch bend"): `read_bends` reads the same files into per-part (seconds, semitones) events -- the wheel under the
+range of RPN 0,0, or JSON "bend" controls; `schedule_bends` turns them into one playback-rate curve per part for
+kernels.HipKernels.note_warp, and `bent_notes` names the notes such a curve touches.
 """
 import bisect
 import collections
@@ -118,10 +122,15 @@ def _vlq(data, pos, end, what):
 _CONTROLLERS = {7: "volume", 10: "pan", 11: "expression", 64: "pedal"}
 
 
-def _read_track(data, pos, end, track, counter, controls=None, ends=None):
+_BEND_CONTROLLERS = {101: "rpn_msb", 100: "rpn_lsb", 6: "data_msb", 38: "data_lsb"}   # pitch-bend sensitivity is RPN 0,0 (read_bends)
+
+
+def _read_track(data, pos, end, track, counter, controls=None, ends=None, bends=None):
     """One MTrk chunk's events -> ([(pitch, velocity, start tick, end tick, appearance, channel)], [(tick, tempo)]).  `controls` (a list)
     also receives, in file order, (tick, channel, what, value) of every program change ("program"), CC 7 ("volume"), CC 10 ("pan"),
-    CC 11 ("expression") and CC 64 ("pedal") outside channel 10; `ends` (a list) receives the tick of the track's last event."""
+    CC 11 ("expression") and CC 64 ("pedal") outside channel 10; `ends` (a list) receives the tick of the track's last event; `bends` (a
+    list) receives, in file order, (tick, channel, what, value) of every pitch-bend message ("bend", value = (msb << 7 | lsb) - 8192)
+    and of CC 101 / 100 / 6 / 38 ("rpn_msb", "rpn_lsb", "data_msb", "data_lsb") outside channel 10."""
     notes, tempos = [], []
     sounding = {}   # (channel, pitch) -> (start tick, velocity, appearance)
     tick, status = 0, None
@@ -175,6 +184,11 @@ def _read_track(data, pos, end, track, counter, controls=None, ends=None):
                         controls.append((tick, channel, "program", first & 0x7F))
                     elif kind == 0xB0 and first in _CONTROLLERS:
                         controls.append((tick, channel, _CONTROLLERS[first], second & 0x7F))
+                if bends is not None and channel != DRUM_CHANNEL:
+                    if kind == 0xE0:
+                        bends.append((tick, channel, "bend", ((second & 0x7F) << 7 | (first & 0x7F)) - 8192))
+                    elif kind == 0xB0 and first in _BEND_CONTROLLERS:
+                        bends.append((tick, channel, _BEND_CONTROLLERS[first], second & 0x7F))
                 continue
             key = (channel, first)
             if key in sounding:                              # a note-off, or a re-trigger: the earlier note ends here
@@ -189,10 +203,11 @@ def _read_track(data, pos, end, track, counter, controls=None, ends=None):
     return notes, tempos
 
 
-def _midi(data, controls=None, pedal=None):
+def _midi(data, controls=None, pedal=None, bends=None):
     """notes_from_midi's work -> [(Note, appearance, channel, start tick)] sorted by (start, appearance); `controls` as in _read_track, over
     all tracks in (track, file) order.  `pedal` (a dict, read_performance's): the sustain pedal moves the notes' end ticks before they
-    become seconds, and the dict receives `extended` (the notes made longer) and `seconds` (the tempo map, tick -> seconds)."""
+    become seconds, and the dict receives `extended` (the notes made longer) and `seconds` (the tempo map, tick -> seconds).  `bends` (a
+    dict, read_bends'): receives `events` (_read_track's bends over all tracks in (track, file) order) and `seconds`."""
     data = bytes(data)
     if len(data) < 14 or data[:4] != b"MThd":
         raise ScoreError("MIDI file: truncated or missing MThd header chunk")
@@ -207,6 +222,7 @@ def _midi(data, controls=None, pedal=None):
         raise ScoreError("MIDI file: division of 0 ticks per quarter note")
     pos, track, counter = 8 + header_len, 0, [0]
     raw, tempos, ends = [], [], []
+    bend_events = None if bends is None else []
     while track < ntracks:
         if pos + 8 > len(data):
             raise ScoreError(f"MIDI file: truncated: the header announces {ntracks} tracks, the file ends after {track}")
@@ -215,7 +231,7 @@ def _midi(data, controls=None, pedal=None):
         if pos + length > len(data):
             raise ScoreError(f"MIDI file: truncated chunk {tag!r}: {length} bytes announced, {len(data) - pos} present")
         if tag == b"MTrk":
-            n, t = _read_track(data, pos, pos + length, track, counter, controls, ends)
+            n, t = _read_track(data, pos, pos + length, track, counter, controls, ends, bend_events)
             raw += n
             tempos += t
             track += 1
@@ -239,6 +255,8 @@ def _midi(data, controls=None, pedal=None):
         return (elapsed[lo] + (tick - ticks[lo]) * values[lo]) / (division * 1e6)
 
     raw = [e for e in raw if e[3] > e[2]]
+    if bends is not None:
+        bends["events"], bends["seconds"] = bend_events, seconds
     if pedal is not None:
         lanes = {}   # channel -> [(tick, down)] in (tick, track, file) order
         for tick, channel, what, value in sorted(controls, key=lambda e: e[0]):
@@ -269,10 +287,10 @@ def score_from_midi(data):
     return _score_from_midi(data)[0]
 
 
-def _score_from_midi(data, pedal=None):
-    """score_from_midi's work -> (Score, every controller event (tick, channel, what, value) in (track, file) order); `pedal` as in _midi."""
+def _score_from_midi(data, pedal=None, bends=None):
+    """score_from_midi's work -> (Score, every controller event (tick, channel, what, value) in (track, file) order); `pedal` and `bends` as in _midi."""
     controls = []
-    rows = _midi(data, controls, pedal)
+    rows = _midi(data, controls, pedal, bends)
     lanes = {}   # (channel, what) -> ([tick], [value]) in (tick, track, file) order: the sort is stable and `controls` is in (track, file) order
     for tick, channel, what, value in sorted(controls, key=lambda e: e[0]):
         ticks, values = lanes.setdefault((channel, what), ([], []))
@@ -457,6 +475,7 @@ def schedule_part_latents(kept, part_of_kept, n_parts, total, sample_rate, seed,
 # kernels.HipKernels.note_mix_curves.  Nothing above reads any of it.
 # controls: per part the time-ordered (seconds, kind, value), kind "volume" / "expression" (0..127) or "pan" (a float in [-1, 1])
 Performance = collections.namedtuple("Performance", ["score", "controls", "pedal_extended"])
+MAX_BEND_RANGE, DEFAULT_BEND_RANGE = 24, 2   # semitones: the clamp of a channel's pitch-bend sensitivity, and its value until RPN 0,0 sets one
 CONTROL_KINDS = ("volume", "expression", "pan")
 DEFAULT_EXPRESSION = 127
 
@@ -508,13 +527,17 @@ def performance_from_midi(data):
     return Performance(score, controls, pedal["extended"])
 
 
-def performance_from_json(obj):
+def performance_from_json(obj, bends=None):
     """A JSON list of notes (score_from_json's; no controls), or {"notes": [...], "controls": [{"part", "time", "control", "value"}]}
     -> Performance.  control: "volume" / "expression" (an integer 0..127), "pan" (a number in [-1, 1]) or "pedal" (a bool, or an integer
     0..127 that is down from 64).  "part" names a "part" value of the notes.  With controls a note's own "volume" or "pan" is refused: the
-    controls say it.  The pedal is applied in seconds.  ScoreError by index and field name."""
+    controls say it.  The pedal is applied in seconds.  ScoreError by index and field name.  A control may also be "bend" (a number of
+    semitones in [-24, 24]; DESIGN.md "Pitch bend"): it is checked like the others and does not enter the Performance; `bends` (a list,
+    read_bends') receives per part the time-ordered (seconds, semitones)."""
     if isinstance(obj, list):
         score = score_from_json(obj)
+        if bends is not None:
+            bends[:] = [[] for _ in score.parts]
         return Performance(score, [[] for _ in score.parts], 0)
     if not isinstance(obj, dict):
         raise ScoreError(f"JSON score: a list of note objects or an object with \"notes\" and \"controls\" is expected (got {type(obj).__name__})")
@@ -537,7 +560,8 @@ def performance_from_json(obj):
     checks = {"volume": (lambda v: _is_int(v) and 0 <= v <= 127, "an integer 0..127"),
               "expression": (lambda v: _is_int(v) and 0 <= v <= 127, "an integer 0..127"),
               "pan": (lambda v: _is_number(v) and -1 <= v <= 1, "a number in [-1, 1]"),
-              "pedal": (lambda v: isinstance(v, bool) or (_is_int(v) and 0 <= v <= 127), "a bool or an integer 0..127")}
+              "pedal": (lambda v: isinstance(v, bool) or (_is_int(v) and 0 <= v <= 127), "a bool or an integer 0..127"),
+              "bend": (lambda v: _is_number(v) and -MAX_BEND_RANGE <= v <= MAX_BEND_RANGE, "a number of semitones in [-24, 24]")}
     timed = []
     for i, entry in enumerate(entries):
         if not isinstance(entry, dict):
@@ -557,7 +581,11 @@ def performance_from_json(obj):
         timed.append((float(entry["time"]), values.index(entry["part"]), entry["control"], entry["value"]))
     timed.sort(key=lambda e: e[0])   # (stable: file order inside one time)
     controls, lanes = [[] for _ in score.parts], {}
+    if bends is not None:
+        bends[:] = [[(time, float(value)) for time, part, kind, value in timed if kind == "bend" and part == p] for p in range(len(score.parts))]
     for time, part, kind, value in timed:
+        if kind == "bend":
+            continue
         if kind == "pedal":
             lanes.setdefault(part, []).append((time, value is True or (value is not False and value >= 64)))
         else:
@@ -644,3 +672,139 @@ def schedule_curves(performance, kept_index, sample_rate, ramp_seconds=0.01, ste
         points += [(pos, float(np.float32(v_l)), float(np.float32(v_r))) for pos, v_l, v_r in curve]
         first.append(len(points))
     return points, first
+
+
+# ------------------------------------------------------------------------------------------------------------- pitch bend
+# DESIGN.md "Pitch bend": the one channel message that changes pitch.  read_bends reads it, schedule_bends turns it into one
+# playback-rate curve per part for kernels.HipKernels.note_warp, bent_notes says which notes that curve touches.  Nothing above reads any of it.
+BEND_PIECE = 160                       # a ramp is cut into pieces of at most this many samples
+BEND_RATIO_MIN, BEND_RATIO_MAX = 0.25, 4.0
+
+
+def bends_from_midi(data):
+    """A Standard MIDI File -> per part (score_from_midi's numbering) the time-ordered (seconds, semitones).  Outside channel 10:
+    0xEn lsb msb gives value = (msb << 7 | lsb) - 8192; the channel's range is set through RPN 0,0 -- CC 101 = 0 and CC 100 = 0 select it
+    (127, 127 or anything else deselects), CC 6 then sets its semitones and CC 38 its cents -- starts at 2 semitones and is clamped to
+    [0, 24]; semitones = value / 8192 * range, from the value and the range in force, and a bend as well as a change of the range sets a
+    new target.  Events are ordered by (tick, track, file order); a part, a (channel, program), receives the events of its channel."""
+    found = {}
+    score, _ = _score_from_midi(data, None, found)
+    state = {}   # channel -> [rpn msb, rpn lsb, range semitones, range cents, value]
+    out = [[] for _ in score.parts]
+    for tick, channel, what, value in sorted(found["events"], key=lambda e: e[0]):   # (stable: (track, file) order inside a tick)
+        st = state.setdefault(channel, [127, 127, DEFAULT_BEND_RANGE, 0, 0])
+        if what == "rpn_msb":
+            st[0] = value
+            continue
+        if what == "rpn_lsb":
+            st[1] = value
+            continue
+        if what == "bend":
+            st[4] = value
+        elif (st[0], st[1]) != (0, 0):
+            continue                                     # data entry for another parameter
+        elif what == "data_msb":
+            st[2] = value
+        else:
+            st[3] = value
+        span = min(max(st[2] + st[3] / 100.0, 0.0), float(MAX_BEND_RANGE))
+        for p, part in enumerate(score.parts):
+            if part.channel == channel:
+                out[p].append((found["seconds"](tick), st[4] / 8192.0 * span))
+    return out
+
+
+def bends_from_json(obj):
+    """performance_from_json's files -> per part the time-ordered (seconds, semitones) of their "bend" controls (a list of notes has none)."""
+    out = []
+    performance_from_json(obj, out)
+    return out
+
+
+def read_bends(path_or_bytes):
+    """The files of read_score -> per part, in read_score's numbering, the time-ordered [(seconds, semitones)] of its pitch bend."""
+    return _read(path_or_bytes, bends_from_midi, bends_from_json)
+
+
+def schedule_bends(bends, sample_rate, ramp_seconds=0.01):
+    """-> (points, first), all float64: one playback-rate curve per part over clip samples at `sample_rate`, for kernels.note_warp.
+    points: (pos, ratio, cum) rows, pos strictly increasing inside a part; part p owns points[first[p]:first[p + 1]], and a part without
+    a bend event owns none.  schedule_curves' conventions, in semitones: an event stands at floor(seconds * sr + 0.5), the events of one
+    sample collapse to the last, events at sample 0 set the value (0 otherwise) without a ramp, a later one starts a linear ramp of
+    R = max(1, floor(ramp_seconds * sr + 0.5)) samples from the curve's value there, and a ramp in progress is cut at its interpolated
+    value.  A ramp longer than 160 samples is cut into pieces of at most 160.  ratio = clamp(2 ** (semitones / 12), 0.25, 4); between
+    points the RATIO is linear in clip samples, outside them constant; cum = Phi(pos), Phi(t) the integral of the ratio from 0 to t, by
+        Phi(t) = cum_i + ratio_i * d + (ratio_{i+1} - ratio_i) * d * d / (2 * (pos_{i+1} - pos_i)),   d = t - pos_i
+    in float64 in this order.  ValueError for a ramp that is negative or not finite, and for an event that is not (seconds >= 0, finite
+    semitones)."""
+    if isinstance(ramp_seconds, bool) or not isinstance(ramp_seconds, (int, float)) or not math.isfinite(ramp_seconds) or ramp_seconds < 0:
+        raise ValueError(f"schedule_bends: ramp_seconds must be a finite, non-negative number of seconds (got {ramp_seconds!r})")
+    ramp = max(1, _round(ramp_seconds * sample_rate))
+    points, first = [], [0]
+    for p, events in enumerate(bends):
+        groups = []   # [sample, semitones after its last event] by sample
+        for e in events:
+            if len(e) != 2 or not all(_is_number(v) for v in e) or e[0] < 0:
+                raise ValueError(f"schedule_bends: part {p} holds {e!r}, not (seconds >= 0, semitones)")
+        for seconds, semitones in sorted(events, key=lambda e: e[0]):
+            s = _round(seconds * sample_rate)
+            if groups and groups[-1][0] == s:
+                groups[-1][1] = float(semitones)
+            else:
+                groups.append([s, float(semitones)])
+        if not groups:
+            first.append(len(points))
+            continue
+        start = groups.pop(0)[1] if groups[0][0] == 0 else 0.0
+        curve = [(0, start)]
+        for s, target in groups:
+            v = curve[-1][1]
+            if s < curve[-1][0]:                          # a ramp in progress: cut at its interpolated value
+                (p0, v0), (p1, v1) = curve[-2], curve[-1]
+                v = v0 + (s - p0) / (p1 - p0) * (v1 - v0)
+                curve.pop()
+            if s != curve[-1][0]:
+                curve.append((s, v))
+            curve.append((s + ramp, target))
+        fine = [curve[0]]
+        for (p0, v0), (p1, v1) in zip(curve, curve[1:]):
+            if v0 != v1:
+                fine += [(pos, v0 + (pos - p0) / (p1 - p0) * (v1 - v0)) for pos in range(p0 + BEND_PIECE, p1, BEND_PIECE)]
+            fine.append((p1, v1))
+        cum = 0.0
+        for i, (pos, semitones) in enumerate(fine):
+            ratio = min(max(2.0 ** (semitones / 12.0), BEND_RATIO_MIN), BEND_RATIO_MAX)
+            if i:
+                p0, r0, _ = points[-1]
+                d = float(pos) - p0
+                cum = cum + r0 * d + (ratio - r0) * d * d / (2.0 * d)
+            points.append((float(pos), ratio, cum))
+        first.append(len(points))
+    return points, first
+
+
+def bent_notes(table, part_of_note, points, first):
+    """The indices of the notes of `table` (schedule's rows; part_of_note: their parts) whose part's ratio differs from 1 anywhere in
+    [onset, onset + hold + release): the ratio is piecewise linear, so it does where it differs at an end of the span or at a point
+    inside it."""
+    out, curves = [], {}   # part -> (its points, their positions)
+    for n, (row, p) in enumerate(zip(table, part_of_note)):
+        if p not in curves:
+            pts = points[first[p]:first[p + 1]]
+            curves[p] = (pts, [q[0] for q in pts])
+        pts, pos = curves[p]
+        if not pts:
+            continue
+        lo, hi = row[0], row[0] + row[1] + row[2] - 1
+
+        def ratio(t):
+            k = bisect.bisect_right(pos, t)
+            if k == 0 or k == len(pts):
+                return pts[max(k - 1, 0)][1]
+            (p0, r0, _), (p1, r1, _) = pts[k - 1], pts[k]
+            return r0 + (r1 - r0) * (t - p0) / (p1 - p0)
+
+        i0, i1 = bisect.bisect_left(pos, lo), bisect.bisect_right(pos, hi)
+        if ratio(lo) != 1.0 or ratio(hi) != 1.0 or any(pts[i][1] != 1.0 for i in range(i0, i1)):
+            out.append(n)
+    return out

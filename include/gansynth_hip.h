@@ -748,6 +748,64 @@ int gs_note_mix_curves(const float* waves, int rows, int64_t length, int64_t row
                        const GsCurvePoint* points, int n_points, const int32_t* first, int n_curves, int channels, int64_t total,
                        int normalize, float* out, int64_t out_stride, int16_t* pcm, float* peak, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Pitch bend: bent copies of the affected notes' waveforms, written ahead of the mix (GANSynth.synthesize with bend; this project's
+ * own rule, DESIGN.md "Pitch bend") ---------------------------------------------------------------------------------------------------
+ * waves: gs_note_mix's buffer, [rows] rows of `length` fp32 samples, `row_stride` elements apart; it is read AND written.  A curve is a
+ * playback-rate ratio over clip samples: curve p owns points[first[p] .. first[p + 1]) (first: a DEVICE array of n_curves + 1 int32,
+ * non-decreasing from 0 to n_points, every range non-empty); a point is (pos, ratio, cum), all float64, pos an integer-valued clip
+ * sample, strictly increasing inside a curve, ratio in [0.25, 4].  Between two points the ratio is linear in t, before the first and
+ * from the last on it is constant, and cum = Phi(pos) with Phi(t) = integral from 0 to t of the ratio.  With i the last point of the
+ * curve whose pos is <= t (the first point for a t before it), d = t - pos_i, and -- inside a segment -- dp = pos_{i+1} - pos_i,
+ * dr = ratio_{i+1} - ratio_i, in float64, every operation rounded on its own (no FMA) and in this order:
+ *     Phi(t) = cum_i + ratio_i * d + dr * d * d / (2 * dp),   ratio(t) = ratio_i + dr * d / dp     inside a segment,
+ *     Phi(t) = cum_i + ratio_i * d,                           ratio(t) = ratio_i                   outside the points.
+ * A note (src_row, dst_row, onset, count, curve) gives, for k in [0, count):
+ *     q = Phi(onset + k) - Phi(onset),   n = floor(q),   f = (float)(q - n),   c = (float)min(1, 1 / ratio(onset + k))
+ *     waves[dst_row][k] = sum over integers i of h_i * x[i],   h_i = c * lerp(T, c * |(float)(i - n) - f| * Q),
+ * x = waves[src_row], and x[i] = 0 for an i outside [0, length) -- whatever lies in the stride padding or in the next row.  lerp(T, a),
+ * in fp32: a is first limited to Z Q, m = (int)a, T[m] + (a - m) * (T[m + 1] - T[m]); the table is
+ *     T[m] = sinc(m / Q) * I0(BETA * sqrt(1 - (m / (Q Z))^2)) / I0(BETA),   m = 0 .. Z Q,   sinc(x) = sin(pi x) / (pi x),
+ * computed in double and rounded once to fp32, with the exact values T[0] = 1 and T[j Q] = 0 for j >= 1 forced, and T[Z Q + 1] = 0.
+ * So h_i is an exact 0 wherever |c (n + f - i)| >= Z: 2 Z taps count at a ratio <= 1 and 8 Z at ratio 4, where the cutoff has followed
+ * the ratio down to a quarter of the band.  fp32 accumulation in a fixed order, FMA allowed; no atomics; two calls are bit-identical.
+ * With the ratio identically 1, q = k, f = 0 and c = 1: every coefficient but one is an exact 0 and the row comes back unchanged.
+ * gs_note_warp writes exactly `count` samples of each dst_row and nothing else.  The caller sees to it that no dst_row is the src_row or
+ * the dst_row of another note of the call.  One launch: a block owns GS_WARP_TILE consecutive outputs of one note (grid: tiles x
+ * notes) and stages the table (GS_WARP_TABLE_FLOATS floats) and the source span it can reach, at most 4 * GS_WARP_TILE + 8 Z + 4
+ * samples, in LDS.  Capture-safe: no allocation, no synchronisation.
+ * The table is filled in HOST memory by gs_note_warp_table (gs_note_warp_table_bytes bytes: T, the zero that follows, padding to 16
+ * bytes) and uploaded by the caller once; both are host arithmetic and need no device.
+ * A bad table cannot make the kernel read outside waves, points or first, or write outside the dst rows' [0, count): IN the kernel, and
+ * before an address is formed, a note whose src_row or dst_row is outside [0, rows), whose src_row == dst_row, whose count is outside
+ * [1, length], whose onset < 0 or whose curve is outside [0, n_curves) is skipped; first's entries are clamped so that every index
+ * into points lies in [0, n_points); a segment of length <= 0 is not divided by (the curve is constant there); a ratio that is NaN or
+ * outside [0.25, 4] is clamped into it; q is clamped into [0, length + 4 Z] (from there on every tap reads zeros, at every cutoff), and
+ * a lane's offset into the staged span into that span.
+ * GS_ERR_ARG with a message and without a launch: n_notes outside [1, 65535], rows / n_curves / n_points <= 0, length outside
+ * [1, GS_WARP_MAX_LENGTH], row_stride < length, waves / notes / points / first / table NULL, table off 16 bytes, notes / points off 8,
+ * waves / first off 4; gs_note_warp_table: a NULL table. */
+#define GS_WARP_ZEROS 32
+#define GS_WARP_Q 256
+#define GS_WARP_BETA 12.0
+#define GS_WARP_TILE 1024                           /* outputs per block: 256 lanes x 4 */
+#define GS_WARP_TABLE_FLOATS 8196                   /* Z Q + 1 entries, the zero that follows, padding to whole 16 bytes */
+#define GS_WARP_MAX_LENGTH ((int64_t)1 << 30)
+typedef struct GsWarpNote {
+    int32_t src_row, dst_row;   /* rows of waves: read [0, length) of the one, write [0, count) of the other */
+    int64_t onset;              /* the note's first clip sample: where its curve is read */
+    int32_t count;              /* samples to write: hold + release, 1 <= count <= length */
+    int32_t curve;              /* which curve: 0 <= curve < n_curves */
+} GsWarpNote;                   /* 24 bytes */
+typedef struct GsWarpPoint {
+    double pos;                 /* a clip sample (integer-valued) */
+    double ratio;               /* the playback-rate ratio there, in [0.25, 4] */
+    double cum;                 /* Phi(pos) */
+} GsWarpPoint;                  /* 24 bytes */
+size_t gs_note_warp_table_bytes(void);
+int gs_note_warp_table(float* table_host);
+int gs_note_warp(float* waves, int rows, int64_t length, int64_t row_stride, const GsWarpNote* notes, int n_notes,
+                 const GsWarpPoint* points, const int32_t* first, int n_curves, int n_points, const float* table_dev, void* stream);
+
 /* ---- Resident notes: one batch drawn from the int16 bank on the device (gansynth_amd/bank.py, DESIGN.md "Resident notes") ----------
  * pcm: [rows] notes of `length` int16 samples, `row_stride` elements apart.  class_of_row: [rows] int32, the label index of a row or -1.
  * order: [n_order] int32 row numbers; the batch is order[first .. first + batch).  For b in [0, batch), r = order[first + b]:
