@@ -64,6 +64,12 @@ and every onset stay as they are.  A change takes effect over `--controller_ramp
     python gan_synth_main.py --synthesize lead.mid --bend --output lead.wav
     python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --controllers --bend --controller_ramp 0.005 --output quartet.wav
 
+`--sustain` holds notes past the four seconds the generator makes (GANSynth.synthesize with sustain, DESIGN.md "Sustain"): a note the score
+holds longer -- an organ chord, a tied whole note, a pedalled piano with `--controllers` -- is looped on the device at a length found by
+correlation and keeps its whole release, and the clip is as long as the score says.  A held note that `--bend` bends is cut as before:
+
+    python gan_synth_main.py --synthesize organ.mid --sustain --output organ.wav
+
 `--pack_bank` / `--bank` (not in the reference): the notes packed once into one file (on any machine, no GPU needed), then held on the
 device and drawn there, batch for batch what `--filenames` yields (gansynth_amd/bank.py, DESIGN.md "Resident notes"):
 
@@ -117,6 +123,9 @@ parser.add_argument("--controller_ramp", type=float, default=0.01, metavar="SECO
 parser.add_argument("--bend", action="store_true",
                     help="--synthesize: honour pitch bend (and the range set through RPN 0,0): the notes it touches are resampled along "
                          "their part's bend curve on the device before the mix")
+parser.add_argument("--sustain", action="store_true",
+                    help="--synthesize: hold notes past the generated four seconds: a note the score holds longer is looped on the device "
+                         "and keeps its whole release")
 parser.add_argument("--reverb", type=float, default=None, metavar="SECONDS",
                     help="--synthesize: reverberate the clip in a designed room with this RT60 (seeded by --seed; two channels with --stereo)")
 parser.add_argument("--reverb_ir", type=str, default=None, metavar="FILE.wav",
@@ -202,8 +211,8 @@ def check_loudness_args(args):
 
 
 def check_controller_args(args):
-    """--controllers and --controller_ramp against each other and against --synthesize: SystemExit with a message.  -> whether controllers
-    are asked for."""
+    """--controllers, --controller_ramp, --bend and --sustain against each other and against --synthesize: SystemExit with a message.
+    -> whether controllers are asked for."""
     wanted, ramp = getattr(args, "controllers", False), getattr(args, "controller_ramp", 0.01)
     bend = getattr(args, "bend", False)   # (--bend shares the ramp)
     if not wanted and not bend and ramp != 0.01:   # (NaN differs from everything)
@@ -212,6 +221,8 @@ def check_controller_args(args):
         raise SystemExit("--controllers applies to --synthesize only")
     if bend and args.synthesize is None:
         raise SystemExit("--bend applies to --synthesize only")
+    if getattr(args, "sustain", False) and args.synthesize is None:
+        raise SystemExit("--sustain applies to --synthesize only")
     if (wanted or bend) and not 0 <= ramp < float("inf"):
         raise SystemExit(f"--controller_ramp must be a finite, non-negative number of seconds (got {ramp})")
     return wanted
@@ -245,6 +256,9 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     bend_wanted = getattr(args, "bend", False)
     if bend_wanted:
         how.update(bend=True, controller_ramp=args.controller_ramp)
+    sustain_wanted = getattr(args, "sustain", False)
+    if sustain_wanted:
+        how.update(sustain=True)
     if reverb_wanted or last_wanted:   # only the last stage normalises (or limits) and quantises
         clip = model.synthesize(args.synthesize, normalize=False, want_pcm=False, **how)
     if reverb_wanted:
@@ -300,6 +314,10 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     if bend_wanted:
         log(f"bend: {sum(info['bends'])} events on {sum(1 for n in info['bends'] if n)} parts in {info['bend_points']} curve points, "
             f"{info['bent_notes']} notes bent")
+    if sustain_wanted:
+        lags = [m for _, m, _ in info["loops"]]
+        log(f"sustain: {info['held_notes']} notes held in {info['sustain_rows']} pieces, loops of {min(lags, default=0)} to {max(lags, default=0)} "
+            f"samples, {info['sustain_cut_bent']} held notes cut because they bend")
     return info
 
 

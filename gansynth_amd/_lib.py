@@ -217,6 +217,8 @@ SIGNATURES = {
     "gs_note_warp_table_bytes": (Z, []),
     "gs_note_warp_table": (I, [P]),
     "gs_note_warp": (I, [P, I, L, L, P, I, P, P, I, I, P, P]),
+    "gs_loop_search": (I, [P, I, L, L, P, I, P, L, P]),
+    "gs_note_sustain": (I, [P, I, L, L, P, I, P]),
     "gs_stereo_finish_workspace_bytes": (Z, [L]),
     "gs_stereo_finish": (I, [P, L, L, I, P, P, P, Z, P]),
     "gs_bank_gather": (I, [P, L, L, L, P, P, L, L, I, I, P, P, P]),
@@ -325,6 +327,21 @@ class GsWarpNote(ctypes.Structure):
 class GsWarpPoint(ctypes.Structure):
     """include/gansynth_hip.h: one point of a ratio curve of gs_note_warp (24 bytes; device memory, a curve's points by position)."""
     _fields_ = [("pos", c_double), ("ratio", c_double), ("cum", c_double)]
+
+
+SUSTAIN_MAX_WINDOW, SUSTAIN_LAG_TILE, SUSTAIN_TILE = 4096, 256, 1024   # GS_SUSTAIN_MAX_WINDOW, GS_SUSTAIN_LAG_TILE, GS_SUSTAIN_TILE
+
+
+class GsLoopNote(ctypes.Structure):
+    """include/gansynth_hip.h: one note of gs_loop_search (24 bytes; device memory; `reserved` is not read)."""
+    _fields_ = [("row", ctypes.c_int32), ("a", ctypes.c_int32), ("m_min", ctypes.c_int32), ("m_max", ctypes.c_int32),
+                ("window", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class GsSustainJob(ctypes.Structure):
+    """include/gansynth_hip.h: one piece of a looped note of gs_note_sustain (32 bytes; device memory)."""
+    _fields_ = [("src_row", ctypes.c_int32), ("dst_row", ctypes.c_int32), ("offset", ctypes.c_int64), ("count", ctypes.c_int32),
+                ("a", ctypes.c_int32), ("m", ctypes.c_int32), ("xfade", ctypes.c_int32)]
 
 
 _lib = None

@@ -239,6 +239,80 @@ def note_warp_table(warp_notes, points, first, rows, length):
     return notes, pts, (ctypes.c_int32 * len(first))(*[int(v) for v in first])
 
 
+def _sustain_ints(what, kind, i, fields, entry):
+    if len(entry) != len(fields):
+        raise ValueError(f"{what}: {kind} {i} has {len(entry)} fields, not ({', '.join(fields)})")
+    for name, v in zip(fields, entry):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            raise ValueError(f"{what}: {kind} {i} field '{name}' must be an integer (got {v!r})")
+
+
+def loop_search_table(search_notes, rows, length, n_lags):
+    """The host side of loop_search: `search_notes` -- rows (row, a, m_min, m_max, window) -- checked: row inside [0, rows), a >= 0,
+    1 <= m_min <= m_max, window in [1, GS_SUSTAIN_MAX_WINDOW], a + m_max + window <= length and m_max - m_min + 1 <= n_lags (the
+    row length of the scores).  ValueError by index and field name.  -> a ctypes array of GsLoopNote.  Needs no device."""
+    what = "loop_search"
+    fields = ("row", "a", "m_min", "m_max", "window")
+    if len(search_notes) == 0:
+        raise ValueError(f"{what}: the table is empty")
+    for i, entry in enumerate(search_notes):
+        _sustain_ints(what, "note", i, fields, entry)
+        row, a, m_min, m_max, window = entry
+        if not 0 <= row < rows:
+            raise ValueError(f"{what}: note {i} field 'row' = {row} is outside [0, {rows})")
+        if a < 0:
+            raise ValueError(f"{what}: note {i} field 'a' = {a} is negative")
+        if m_min < 1:
+            raise ValueError(f"{what}: note {i} field 'm_min' = {m_min} is below 1")
+        if m_max < m_min:
+            raise ValueError(f"{what}: note {i} field 'm_max' = {m_max} is below m_min = {m_min}")
+        if not 1 <= window <= _lib.SUSTAIN_MAX_WINDOW:
+            raise ValueError(f"{what}: note {i} field 'window' = {window} is outside [1, {_lib.SUSTAIN_MAX_WINDOW}]")
+        if a + m_max + window > length:
+            raise ValueError(f"{what}: note {i} field 'm_max': a + m_max + window = {a + m_max + window} is beyond the length {length}")
+        if m_max - m_min + 1 > n_lags:
+            raise ValueError(f"{what}: note {i} field 'm_max': {m_max - m_min + 1} lags are more than the {n_lags} of a row of scores")
+    return (_lib.GsLoopNote * len(search_notes))(*[_lib.GsLoopNote(*[int(v) for v in entry], 0) for entry in search_notes])
+
+
+def note_sustain_table(jobs, rows, length):
+    """The host side of note_sustain: `jobs` -- rows (src_row, dst_row, offset, count, a, m, xfade) -- checked: rows inside [0, rows), no
+    dst_row that is a src_row or the dst_row of another job, count in [1, length], offset in [0, 2^62), a >= 0, m >= 1, xfade >= 0 and
+    a + m + xfade <= length.  ValueError by index and field name.  -> a ctypes array of GsSustainJob.  Needs no device."""
+    what = "note_sustain"
+    fields = ("src_row", "dst_row", "offset", "count", "a", "m", "xfade")
+    if len(jobs) == 0:
+        raise ValueError(f"{what}: the table is empty")
+    sources = set()
+    for i, entry in enumerate(jobs):
+        _sustain_ints(what, "job", i, fields, entry)
+        src, dst, offset, count, a, m, xfade = entry
+        if not 0 <= src < rows:
+            raise ValueError(f"{what}: job {i} field 'src_row' = {src} is outside [0, {rows})")
+        if not 0 <= dst < rows:
+            raise ValueError(f"{what}: job {i} field 'dst_row' = {dst} is outside [0, {rows})")
+        if not 0 <= offset < 2 ** 62:
+            raise ValueError(f"{what}: job {i} field 'offset' = {offset} is negative (or beyond 2^62)")
+        if not 1 <= count <= length:
+            raise ValueError(f"{what}: job {i} field 'count' = {count} is outside [1, {length}]")
+        if a < 0:
+            raise ValueError(f"{what}: job {i} field 'a' = {a} is negative")
+        if m < 1:
+            raise ValueError(f"{what}: job {i} field 'm' = {m} is below 1")
+        if xfade < 0:
+            raise ValueError(f"{what}: job {i} field 'xfade' = {xfade} is negative")
+        if a + m + xfade > length:
+            raise ValueError(f"{what}: job {i} field 'xfade': a + m + xfade = {a + m + xfade} is beyond the length {length}")
+        sources.add(int(src))
+    written = set()
+    for i, entry in enumerate(jobs):
+        dst = int(entry[1])
+        if dst in sources or dst in written:
+            raise ValueError(f"{what}: job {i} field 'dst_row' = {dst} is the src_row or the dst_row of another job")
+        written.add(dst)
+    return (_lib.GsSustainJob * len(jobs))(*[_lib.GsSustainJob(*[int(v) for v in entry]) for entry in jobs])
+
+
 def fft_convolve_shapes(x, impulse, dry, wet):
     """The host side of fft_convolve: -> (rows, n, ir_rows, m) of x ([n] or [rows, n], rows 1 or 2) and impulse ([m] or [ir_rows, m],
     ir_rows 1 or rows), both fp32.  ValueError by argument name; needs no device."""
@@ -374,6 +448,7 @@ class HipKernels(object):
         self._loudness = {}       # rate -> GsLoudness: loudness_design
         self._warp_table = {}     # device index -> gs_note_warp's coefficient table there: note_warp_table_dev
         self.note_warps = 0       # gs_note_warp calls so far (tests: a score without a bent note launches none)
+        self.loop_searches = self.note_sustains = 0   # gs_loop_search / gs_note_sustain calls so far (tests: no held note, no launch)
 
     # --------------------------------------------------------- prepared-weight workspaces
     def register_param_buffer(self, flat):
@@ -1674,6 +1749,47 @@ class HipKernels(object):
                                          pts_dev.data_ptr(), first_dev.data_ptr(), len(firsts) - 1, len(pts), table.data_ptr(), _stream()),
                    "gs_note_warp")
         self.note_warps += 1
+        return waves
+
+    @staticmethod
+    def _sustain_waves(what, waves):
+        if waves.dim() != 2 or waves.dtype != torch.float32 or not waves.is_cuda:
+            raise ValueError(f"{what}: waves must be [rows, L] fp32 on the HIP device (got {tuple(waves.shape)} {waves.dtype} on {waves.device})")
+        rows, length = int(waves.shape[0]), int(waves.shape[1])
+        if waves.stride(1) != 1 or (rows > 1 and waves.stride(0) < length):
+            raise ValueError(f"{what}: the rows of waves must be contiguous and apart (strides {tuple(waves.stride())})")
+        return rows, length, int(waves.stride(0)) if rows > 1 else length
+
+    def loop_search(self, waves, rows_of_notes, plan):
+        """gs_loop_search (include/gansynth_hip.h): for every row of `rows_of_notes` the normalised correlation of waves[row][a : a + W]
+        with waves[row][a + m : a + m + W] for every lag m in [m_min, m_max]; `plan` = (a, m_min, m_max, W) or notes.sustain_plan's
+        (a, m_min, m_max, W, X).  waves: [rows, L] fp32 on the device with contiguous rows; only read.
+        -> scores [len(rows_of_notes), m_max - m_min + 1] fp32 on the device (notes.pick_loop picks from them on the host)."""
+        rows, length, stride = self._sustain_waves("loop_search", waves)
+        a, m_min, m_max, window = (plan[i] for i in range(4))
+        n_lags = m_max - m_min + 1 if all(isinstance(v, (int, np.integer)) for v in (m_min, m_max)) else 1
+        arr = loop_search_table([(row, a, m_min, m_max, window) for row in rows_of_notes], rows, length, n_lags)
+        if len(arr) > 65535:
+            raise ValueError(f"loop_search: {len(arr)} notes are more than the 65535 of one call")
+        notes = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(waves.device)
+        scores = torch.empty((len(arr), n_lags), dtype=torch.float32, device=waves.device)
+        _lib.check(self.lib.gs_loop_search(waves.data_ptr(), rows, length, stride, notes.data_ptr(), len(arr), scores.data_ptr(), n_lags,
+                                           _stream()), "gs_loop_search")
+        self.loop_searches += 1
+        return scores
+
+    def note_sustain(self, waves, jobs):
+        """gs_note_sustain (include/gansynth_hip.h): for every row (src_row, dst_row, offset, count, a, m, xfade) of `jobs`, the first
+        `count` samples of waves[dst_row] become the samples offset .. offset + count of waves[src_row] looped over [a, a + m) with a
+        crossfade of `xfade` samples, IN PLACE; nothing else is written.  waves: [rows, L] fp32 on the device with contiguous rows.
+        -> waves."""
+        rows, length, stride = self._sustain_waves("note_sustain", waves)
+        arr = note_sustain_table(jobs, rows, length)
+        if len(arr) > 65535:
+            raise ValueError(f"note_sustain: {len(arr)} jobs are more than the 65535 of one call")
+        table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(waves.device)
+        _lib.check(self.lib.gs_note_sustain(waves.data_ptr(), rows, length, stride, table.data_ptr(), len(arr), _stream()), "gs_note_sustain")
+        self.note_sustains += 1
         return waves
 
     def stereo_finish(self, x, normalize=True, want_pcm=False):

@@ -917,7 +917,7 @@ class GANSynth(Iterations, DataParallel, Capture):
     # --------------------------------------------------------------------------------------- note sequences
     def synthesize(self, notes, model_dir=None, latents=None, seed=0, seconds_per_instrument=6.0, release_seconds=1.0, normalize=True,
                    want_pcm=False, info=None, pitches=range(24, 85), batch_size=8, weights="live", sample_rate=None, controllers=False,
-                   controller_ramp=0.01, bend=False, ensemble=False, stereo=False, spread=0.0):
+                   controller_ramp=0.01, bend=False, sustain=False, ensemble=False, stereo=False, spread=0.0):
         """A score -> one mixed clip (not in the reference: the rules are this project's own, DESIGN.md "Note sequences").
 
         `notes`: notes.Note rows, or what notes.read_notes accepts (a .mid / .json file name or bytes).  Restores the latest checkpoint of
@@ -955,7 +955,17 @@ class GANSynth(Iterations, DataParallel, Capture):
         every change a ramp of `controller_ramp` seconds); `waves` is allocated [N + B, L] for the B notes whose curve leaves 1 while
         they sound, the generator fills the first N rows, ONE gs_note_warp call writes the bent copies into the rest, the bent notes'
         table rows name their copies, and the chosen mix call and everything behind it run unchanged.  The clip's length and every
-        onset stay as they are.  `info` also receives bends (events per part), bent_notes and bend_points."""
+        onset stay as they are.  `info` also receives bends (events per part), bent_notes and bend_points.
+        `sustain` (DESIGN.md "Sustain"; off, or on with a score whose every note fits the waveform with its release: the paths above,
+        not a launch, a table row or an output bit changed).  True: a note with hold + R > L (notes.schedule_sustain: the hold unclamped,
+        R the full release) is HELD -- it sounds for its whole length and keeps its whole release.  `waves` is allocated with one more
+        row per piece of a held note (pieces of at most L samples), ONE gs_loop_search call scores the loop lengths of the held notes'
+        generated rows under notes.sustain_plan(L), notes.pick_loop picks one per note on the host, ONE gs_note_sustain call writes the
+        pieces of the looped waveform into the extra rows, and the chosen mix call and everything behind it run unchanged on a table
+        that holds one entry per piece; the clip grows to the score's length.  Bend and sustain do not compose -- a bent piece would
+        have to start reading where the earlier pieces stopped, and gs_note_warp has no such start: a held note whose part bends while
+        it sounds is cut at L as before and counted.  `info` also receives held_notes, sustain_rows, loops (per held note
+        (a, m, score)) and sustain_cut_bent."""
         from . import notes as N
         if self.world > 1:
             raise RuntimeError("GANSynth.synthesize runs in one process: launch it without torch.distributed (world size 1)")
@@ -1007,6 +1017,26 @@ class GANSynth(Iterations, DataParallel, Capture):
         sr, length = self.spectral_params["sample_rate"], int(self.spectral_params["waveform_length"])
         kept, table, total, dropped = N.schedule(notes, pitches, sr, length, release_seconds)
         count, batch = len(kept), int(batch_size)
+        held, cut_bent = [], 0
+        if sustain:   # which notes are held, and how long the clip becomes; the pieces enter the table once it has its gains
+            _, piece_table, piece_total, _, owner, offsets = N.schedule_sustain(notes, pitches, sr, length, release_seconds)
+            held = sorted({n for n, offset in zip(owner, offsets) if offset is not None})
+            parts = score if score is not None else bend_score
+            if held and bends is not None and len(bends) == len(parts.parts):   # (another count is refused below)
+                index = N.kept_indices(notes, pitches)
+                spans = {n: [table[n][0], 0, N._round(release_seconds * sr)] for n in held}   # the whole span of a held note
+                for row, n, offset in zip(piece_table, owner, offsets):
+                    if offset is not None:
+                        spans[n][1] += row[1]
+                bent = N.bent_notes([spans[n] for n in held], [parts.part[index[n]] for n in held], bend_points, bend_first)
+                if bent:   # bend and sustain do not compose: these are cut at L, as without the flag
+                    cut_bent = len(bent)
+                    _, piece_table, piece_total, _, owner, offsets = N.schedule_sustain(notes, pitches, sr, length, release_seconds,
+                                                                                        cut=[held[i] for i in bent])
+                    held = [n for i, n in enumerate(held) if i not in set(bent)]
+            if held:
+                total = piece_total
+                sustain_plan = N.sustain_plan(length)   # (a waveform too short to loop is refused before anything is generated)
         if score is not None:
             index = N.kept_indices(notes, pitches)
             part_of_note = [score.part[i] for i in index]
@@ -1042,6 +1072,15 @@ class GANSynth(Iterations, DataParallel, Capture):
                 onset, hold, release, row = table[n][:4]
                 warp_notes.append((row, count + len(warp_notes), onset, hold + release, curved.index(bend_part[n])))
                 table[n] = table[n][:3] + (count + len(warp_notes) - 1,) + table[n][4:]
+        pieces = []   # (held note, its row behind the generated and the bent ones, offset into the note, samples)
+        if held:      # a held note's entry becomes one entry per piece, with the note's gains (and curve)
+            per_note, table = table, []
+            for row, n, offset in zip(piece_table, owner, offsets):
+                if offset is None:
+                    table.append(per_note[n])
+                    continue
+                table.append(row[:3] + (count + len(warp_notes) + len(pieces),) + per_note[n][4:])
+                pieces.append((n, count + len(warp_notes) + len(pieces), offset, row[1] + row[2]))
         labels = N.labels_for(kept, pitches)
         dev = self.store.device if hasattr(self.store, "device") else "cuda"
         if self.g_params is None:
@@ -1050,7 +1089,7 @@ class GANSynth(Iterations, DataParallel, Capture):
         if model_dir is not None:
             self.restored_from = restored
         self._join_updates()
-        waves = torch.empty((count + len(warp_notes), length), dtype=torch.float32, device=dev)
+        waves = torch.empty((count + len(warp_notes) + len(pieces), length), dtype=torch.float32, device=dev)
         with self.averaged_generator() if weights == "average" else contextlib.nullcontext():
             for lo in range(0, count, batch):
                 rows = [min(i, count - 1) for i in range(lo, lo + batch)]   # the last chunk repeats its last row
@@ -1060,6 +1099,13 @@ class GANSynth(Iterations, DataParallel, Capture):
         K = kernels.get()
         if warp_notes:
             K.note_warp(waves, warp_notes, bend_points, [bend_first[p] for p in curved] + [len(bend_points)])
+        loops = []
+        if held:   # score the loop lengths on the device, pick on the host, write the pieces of the looped notes
+            loop_a, m_min, _, _, xfade = sustain_plan
+            scores = K.loop_search(waves, held, sustain_plan).cpu().numpy()
+            picked = {n: N.pick_loop(scores[i], m_min) for i, n in enumerate(held)}
+            loops = [(loop_a, picked[n], float(scores[i, picked[n] - m_min])) for i, n in enumerate(held)]
+            K.note_sustain(waves, [(n, row, offset, samples, loop_a, picked[n], xfade) for n, row, offset, samples in pieces])
         resampled = sample_rate is not None and int(sample_rate) != int(sr)
         last, unfinished = dict(normalize=normalize, want_pcm=want_pcm), dict(normalize=False, want_pcm=False)
         if performance is not None:
@@ -1082,6 +1128,8 @@ class GANSynth(Iterations, DataParallel, Capture):
             if bend:
                 info.update(bends=bend_counts, bent_notes=len(warp_notes),
                             bend_points=len(bend_points) if bends is not None else 0)
+            if sustain:
+                info.update(held_notes=len(held), sustain_rows=len(pieces), loops=loops, sustain_cut_bent=cut_bent)
         return (clip, pcm) if want_pcm else clip
 
     # ------------------------------------------------------------------------------------------- evaluation

@@ -808,3 +808,78 @@ def bent_notes(table, part_of_note, points, first):
         if ratio(lo) != 1.0 or ratio(hi) != 1.0 or any(pts[i][1] != 1.0 for i in range(i0, i1)):
             out.append(n)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- sustain
+# DESIGN.md "Sustain": notes the score holds longer than the generated waveform.  sustain_plan says where a note's loop is searched,
+# pick_loop picks its length from the scores of kernels.HipKernels.loop_search, schedule_sustain cuts a held note into pieces the mix
+# accepts, each a row that kernels.HipKernels.note_sustain writes.  Nothing above reads any of it.
+def sustain_plan(waveform_length):
+    """-> (a, m_min, m_max, W, X) for notes of L = waveform_length samples: the loop starts at a = 3 L // 8, its length lies in
+    [L // 8, L // 4], a lag is scored over a window of W = max(16, L // 32) samples and a wrap is crossfaded over X = max(1, L // 64).
+    a + m_max + max(W, X) <= L for every L >= 64; a smaller L is a ValueError."""
+    length = int(waveform_length)
+    if length < 64:
+        raise ValueError(f"sustain_plan: the waveform must have at least 64 samples (got {waveform_length})")
+    return 3 * length // 8, length // 8, length // 4, max(16, length // 32), max(1, length // 64)
+
+
+def pick_loop(scores, m_min, tie=1e-3):
+    """The loop length from the scores of the lags m_min, m_min + 1, ...: the LARGEST lag whose score is at least max - tie (every
+    multiple of the period scores near 1 and a longer loop repeats less audibly, so the margin, not rounding, decides between them).
+    Non-finite scores count as -inf; where every score is -inf or 0 the note is silent and the largest lag is taken."""
+    s = np.asarray(scores, dtype=np.float64).reshape(-1)
+    if s.size == 0:
+        raise ValueError("pick_loop: no scores")
+    s = np.where(np.isfinite(s), s, -np.inf)
+    if np.all((s == 0.0) | np.isneginf(s)):
+        return int(m_min) + s.size - 1
+    return int(m_min) + int(np.nonzero(s >= s.max() - tie)[0][-1])
+
+
+def sustain_pieces(hold, full_release, waveform_length):
+    """A hold of `hold` samples followed by the full release R (hold + R > L, R <= L - 1) -> [(offset, hold_s, release_s)], pieces that
+    tile [0, hold) and that the mix accepts (hold_s >= 1, hold_s + release_s <= L), only the last with a release: pieces of L while more
+    than L remains; a remainder r <= L - R is the last piece, a longer one is split into r - (L - R) and L - R."""
+    length, out, offset = int(waveform_length), [], 0
+    while hold - offset > length:
+        out.append((offset, length, 0))
+        offset += length
+    r = hold - offset
+    if r > length - full_release:
+        out.append((offset, r - (length - full_release), 0))
+        offset, r = offset + r - (length - full_release), length - full_release
+    out.append((offset, r, full_release))
+    return out
+
+
+def schedule_sustain(notes, pitches, sample_rate, waveform_length, release_seconds, cut=()):
+    """`schedule` for notes that may be held past the waveform -> (kept notes, table, total samples, dropped, owner, offset).
+    hold = max(1, floor((end - start) * sr + 0.5)), unclamped; a note is HELD iff hold + R > L.  Every other note -- and every kept
+    note whose index is in `cut` -- gets exactly schedule's row.  A held note keeps its full release R and becomes one table entry per
+    piece of sustain_pieces: (onset + offset_s, hold_s, release_s, a row of its own, the note's gain); the rows of the pieces count on
+    from N = len(kept) in table order, and under the mix's envelope -- 1 over a hold -- the pieces butt together sample-exactly.
+    owner[e] is the kept note of table entry e; offset[e] is the piece's offset into the held note, None for an ordinary row.
+    R <= L - 1 is required (ValueError): a piece with a release needs a hold of at least one sample."""
+    sr, length = sample_rate, int(waveform_length)
+    kept, table, total, dropped = schedule(notes, pitches, sr, length, release_seconds)
+    full_release = _round(release_seconds * sr)
+    if full_release > length - 1:
+        raise ValueError(f"schedule_sustain: the release of {full_release} samples must be at most {length - 1}, the waveform's "
+                         f"length less one (release_seconds {release_seconds})")
+    cut = set(cut)
+    out, owner, offset, next_row = [], [], [], len(kept)
+    for n, (note, row) in enumerate(zip(kept, table)):
+        hold = max(_round((note.end - note.start) * sr), 1)
+        if hold + full_release <= length or n in cut:
+            out.append(row)
+            owner.append(n)
+            offset.append(None)
+            continue
+        for piece_offset, piece_hold, piece_release in sustain_pieces(hold, full_release, length):
+            out.append((row[0] + piece_offset, piece_hold, piece_release, next_row, row[4]))
+            owner.append(n)
+            offset.append(piece_offset)
+            total = max(total, row[0] + piece_offset + piece_hold + piece_release)
+            next_row += 1
+    return kept, out, total, dropped, owner, offset

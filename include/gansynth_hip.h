@@ -806,6 +806,59 @@ int gs_note_warp_table(float* table_host);
 int gs_note_warp(float* waves, int rows, int64_t length, int64_t row_stride, const GsWarpNote* notes, int n_notes,
                  const GsWarpPoint* points, const int32_t* first, int n_curves, int n_points, const float* table_dev, void* stream);
 
+/* ---- Sustain: notes held past the generated length, as looped copies written ahead of the mix (GANSynth.synthesize with sustain; this
+ * project's own rule, DESIGN.md "Sustain") -------------------------------------------------------------------------------------------
+ * waves: gs_note_mix's buffer, [rows] rows of `length` fp32 samples, `row_stride` elements apart.
+ *
+ * gs_loop_search scores every candidate loop length of every note.  A note (row, a, m_min, m_max, window), x = waves[row], W = window:
+ *     S_aa = sum_{i<W} x[a+i]^2,   S_ab(m) = sum_{i<W} x[a+i] x[a+m+i],   S_bb(m) = sum_{i<W} x[a+m+i]^2,
+ *     scores[n * scores_stride + (m - m_min)] = S_ab / sqrt(S_aa * S_bb),  or 0 where S_aa * S_bb == 0,     m in [m_min, m_max].
+ * fp32 accumulation in a fixed order (S_ab and S_bb: four chains by tap index mod 4, folded (0 + 1) + (2 + 3); S_aa: one chain per lane,
+ * folded over the block in a fixed tree), FMA allowed, no atomics: two calls are bit-identical.  One launch: a 256-lane block owns
+ * GS_SUSTAIN_LAG_TILE consecutive lags of one note (grid: lag tiles x notes), stages x[a .. a+W) and the span of its lags in LDS
+ * (zero-filled past the row's end; with W <= GS_SUSTAIN_MAX_WINDOW under 34 KB) and computes S_aa itself -- no second launch and no
+ * workspace.  Which lag to take is host work on the returned scores.  waves is only read.
+ * A bad table cannot fault: IN the kernel, and before an address is formed, a note whose row is outside [0, rows), whose a < 0,
+ * m_min < 1, m_max < m_min, window < 1 or window > GS_SUSTAIN_MAX_WINDOW, whose a + m_max + window > length (in 64 bits) or whose
+ * m_max - m_min + 1 > scores_stride is skipped, and its scores are left untouched.
+ *
+ * gs_note_sustain writes pieces of the endless waveform of a looped note.  For a source row x, a loop (a, m), b = a + m and a crossfade
+ * of X = xfade samples (b + X <= length):
+ *     y[k] = x[k]                                          k < b
+ *     y[k] = (1 - w) * x[b + p] + w * x[a + p]             k >= b,  p = (k - b) mod m < X,   w = (float)(p + 1) * fl(1 / (X + 1))
+ *     y[k] = x[a + p]                                      k >= b,  p >= X
+ * in fp32, every operation rounded on its own and in the order written (no FMA): at every wrap the outgoing signal is the waveform's
+ * own continuation past b, fading out under the loop's start.  A job (src_row, dst_row, offset, count, a, m, xfade) makes
+ * waves[dst_row][j] = y[offset + j] for j in [0, count), x = waves[src_row], and writes nothing else; (k - b) mod m is taken in 64 bits.
+ * The caller sees to it that no dst_row is the src_row or the dst_row of another job.  One launch: a 256-lane block owns
+ * GS_SUSTAIN_TILE consecutive outputs of one job (grid: tiles x jobs), 16 bytes per lane on the store side where the row allows it.
+ * A bad table cannot fault: IN the kernel, and before an address is formed, a job whose src_row or dst_row is outside [0, rows), whose
+ * src_row == dst_row, whose count is outside [1, length], whose offset < 0, a < 0, m < 1 or xfade < 0, or whose a + m + xfade > length
+ * (in 64 bits) is skipped.
+ * Both are capture-safe: no allocation, no synchronisation.  GS_ERR_ARG with a message and without a launch: n_notes / n_jobs outside
+ * [1, 65535], rows <= 0, length outside [1, GS_SUSTAIN_MAX_LENGTH], row_stride < length, scores_stride outside [1, 2^24], a NULL
+ * pointer, waves / scores off 4 bytes, notes off 4, jobs off 8. */
+#define GS_SUSTAIN_MAX_WINDOW 4096
+#define GS_SUSTAIN_LAG_TILE 256                     /* lags per block of gs_loop_search: one per lane */
+#define GS_SUSTAIN_TILE 1024                        /* outputs per block of gs_note_sustain: 256 lanes x 4 */
+#define GS_SUSTAIN_MAX_LENGTH ((int64_t)1 << 30)
+typedef struct GsLoopNote {
+    int32_t row;                /* the row of waves that is searched */
+    int32_t a;                  /* the loop's start */
+    int32_t m_min, m_max;       /* the lags that are scored: 1 <= m_min <= m_max */
+    int32_t window;             /* W: taps per correlation, 1 <= W <= GS_SUSTAIN_MAX_WINDOW */
+    int32_t reserved;           /* not read */
+} GsLoopNote;                   /* 24 bytes */
+typedef struct GsSustainJob {
+    int32_t src_row, dst_row;   /* rows of waves: read [0, a + m + xfade) of the one, write [0, count) of the other */
+    int64_t offset;             /* the index into y of the first sample written */
+    int32_t count;              /* samples to write, 1 <= count <= length */
+    int32_t a, m, xfade;        /* the loop's start, its length and the crossfade: a + m + xfade <= length */
+} GsSustainJob;                 /* 32 bytes */
+int gs_loop_search(const float* waves, int rows, int64_t length, int64_t row_stride, const GsLoopNote* notes, int n_notes, float* scores,
+                   int64_t scores_stride, void* stream);
+int gs_note_sustain(float* waves, int rows, int64_t length, int64_t row_stride, const GsSustainJob* jobs, int n_jobs, void* stream);
+
 /* ---- Resident notes: one batch drawn from the int16 bank on the device (gansynth_amd/bank.py, DESIGN.md "Resident notes") ----------
  * pcm: [rows] notes of `length` int16 samples, `row_stride` elements apart.  class_of_row: [rows] int32, the label index of a row or -1.
  * order: [n_order] int32 row numbers; the batch is order[first .. first + batch).  For b in [0, batch), r = order[first + b]:
