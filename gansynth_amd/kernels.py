@@ -1624,7 +1624,8 @@ class HipKernels(object):
 
     def momentum_tf_step(self, p, g, accum, lr, momentum, use_nesterov, weight_decay=0.0, decay_range=(0, 0), zero_grad=True, want_l2=True):
         """tf.train.MomentumOptimizer over a flat buffer, the L2 term's gradient (weight_decay * p on decay_range) folded in; returns
-        sum p^2 / 2 of that range at the pre-update values ([1] fp32) or None."""
+        sum p^2 / 2 of that range at the pre-update values ([1] fp32) or None.  zero_grad=False leaves g as it came: the kernel adds the
+        L2 term in registers and stores nothing back to g."""
         for t in (p, g, accum):
             assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()
         l2 = torch.empty((1,), dtype=torch.float32, device=p.device) if want_l2 else None
