@@ -50,6 +50,13 @@ target (gansynth_amd/loudness.py, DESIGN.md "Loudness"):
 
     python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --output_rate 48000 --reverb 1.8 --loudness -16 --output quartet.wav
 
+`--true_peak` (not in the reference) reads the ceiling of `--limit` -- alone or under `--loudness` -- in dBTP: the peak of the reconstructed
+waveform, measured on the 4x oversampled signal (ITU-R BS.1770-4 Annex 2; EBU R128 asks for -1 dBTP), which a file limited by its samples
+alone exceeds by 2-3 dB.  The limiter then follows the detector's envelope, and the summary states the file's true peak
+(gansynth_amd/true_peak.py, DESIGN.md "True peak"):
+
+    python gan_synth_main.py --synthesize quartet.mid --ensemble --stereo --output_rate 48000 --reverb 1.8 --loudness -16 --limit -1 --true_peak --output quartet.wav
+
 `--controllers` honours what a score says after a note has started (GANSynth.synthesize with controllers, DESIGN.md "Controllers"): channel
 volume (CC 7) and expression (CC 11) as they move, pan (CC 10) with `--stereo`, and the sustain pedal (CC 64), which holds notes past their
 key-up; every change takes effect over `--controller_ramp` seconds (default 0.01):
@@ -138,6 +145,8 @@ parser.add_argument("--limit", type=float, default=None, metavar="DB",
 parser.add_argument("--limit_drive", type=float, default=6.0, metavar="DB",
                     help="--limit: how far above the ceiling the clip's peak is driven before the limiter brings it back (>= 0; 0: peak normalisation)")
 parser.add_argument("--limit_lookahead", type=float, default=0.005, metavar="SECONDS", help="--limit: the limiter's look-ahead (attack and release)")
+parser.add_argument("--true_peak", action="store_true",
+                    help="--limit / --loudness: read the ceiling in dBTP -- the limiter holds the 4x oversampled (reconstructed) waveform under it")
 parser.add_argument("--loudness", type=float, default=None, metavar="LUFS",
                     help="--synthesize: end at this integrated loudness (BS.1770, <= 0 LUFS); the limiter holds the peaks under --limit (default -1 dBFS)")
 parser.add_argument("--generator_ema_decay", type=float, default=0.0,
@@ -210,6 +219,15 @@ def check_loudness_args(args):
     return True
 
 
+def check_true_peak_args(args):
+    """--true_peak against --limit / --loudness: SystemExit with a message.  -> whether the ceiling is read in dBTP."""
+    if not getattr(args, "true_peak", False):
+        return False
+    if getattr(args, "limit", None) is None and getattr(args, "loudness", None) is None:
+        raise SystemExit("--true_peak needs --limit or --loudness: it says how their ceiling is read")
+    return True
+
+
 def check_controller_args(args):
     """--controllers, --controller_ramp, --bend and --sustain against each other and against --synthesize: SystemExit with a message.
     -> whether controllers are asked for."""
@@ -240,6 +258,8 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     limit_wanted = check_limit_args(args)
     loudness_wanted = check_loudness_args(args)
     controllers_wanted = check_controller_args(args)
+    true_peak_wanted = check_true_peak_args(args)
+    extra = dict(true_peak=True) if true_peak_wanted else {}   # (without the flag the calls are the ones they were)
     last_wanted = limit_wanted or loudness_wanted   # a stage after the reverb that sets the level and quantises
     if os.path.splitext(args.synthesize)[1].lower() not in (".mid", ".midi", ".json"):
         raise SystemExit(f"--synthesize takes a .mid, .midi or .json score (got {args.synthesize})")
@@ -276,8 +296,8 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
         from gansynth_amd import loudness
         ceiling_db = args.limit if limit_wanted else -1.0
         try:
-            _, pcm, heard = loudness.apply(clip, info["sample_rate"], args.loudness, ceiling_db=ceiling_db,
-                                           lookahead_seconds=args.limit_lookahead, want_pcm=True)
+            limited, pcm, heard = loudness.apply(clip, info["sample_rate"], args.loudness, ceiling_db=ceiling_db,
+                                                 lookahead_seconds=args.limit_lookahead, want_pcm=True, **extra)
         except ValueError as e:
             raise SystemExit(str(e))
         info.update(loudness_target=float(args.loudness), loudness_measured=heard["measured_lufs"], loudness_output=heard["output_lufs"],
@@ -285,14 +305,17 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     elif limit_wanted:   # the clip as the stage before left it, and that stage's peak
         from gansynth_amd import limiter
         try:
-            _, pcm, out_peak, min_gain = limiter.apply(clip, info["sample_rate"], ceiling_db=args.limit, drive_db=args.limit_drive,
-                                                       lookahead_seconds=args.limit_lookahead, peak=info["peak"], want_pcm=True)
+            limited, pcm, out_peak, min_gain = limiter.apply(clip, info["sample_rate"], ceiling_db=args.limit, drive_db=args.limit_drive,
+                                                             lookahead_seconds=args.limit_lookahead, peak=info["peak"], want_pcm=True, **extra)
         except ValueError as e:
             raise SystemExit(str(e))
         info.update(limit_ceiling_db=float(args.limit), limit_drive_db=float(args.limit_drive), limit_peak=float(out_peak),
                     limit_min_gain=float(min_gain))
     elif not reverb_wanted:
         _, pcm = model.synthesize(args.synthesize, want_pcm=True, **how)
+    if true_peak_wanted:   # what the file reconstructs to: one more detector call, on the limiter's float output
+        from gansynth_amd import true_peak
+        info.update(true_peak_db=true_peak.measure(limited))
     if restore:
         log(f"restored {model.restored_from}")
     rate = int(model.spectral_params["sample_rate"])
@@ -306,7 +329,8 @@ def synthesize_to_wav(model, args, pitches, restore=True, log=print):
            f"under a ceiling of {info['limit_ceiling_db']:g} dBFS"
            + (f": the limiter had to work (least gain {info['limit_min_gain']:.4f}) and the output is "
               f"{args.loudness - info['loudness_output']:.2f} LU short of the target" if info["limit_min_gain"] < 1 else "")
-           if loudness_wanted else ""))
+           if loudness_wanted else "")
+        + (f", true peak {info['true_peak_db']:.2f} dBTP (the ceiling is read in dBTP)" if true_peak_wanted else ""))
     if controllers_wanted:
         counts = info["controls"]
         log(f"controllers: {counts['volume']} volume, {counts['expression']} expression and {counts['pan']} pan events in {info['curve_points']} "
@@ -337,6 +361,7 @@ def main(args):
     check_limit_args(args)
     check_loudness_args(args)
     check_controller_args(args)
+    check_true_peak_args(args)
     if args.pack_bank is not None:
         pack_bank(args, range(24, 85), [0])
         return

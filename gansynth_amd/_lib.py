@@ -72,6 +72,7 @@ FFTCONV_MAX_TAPS = 1 << 20                                        # GS_FFTCONV_M
 FFTCONV_HEADER_BYTES = (FFTCONV_BLOCK + FFTCONV_BLOCK // 2 + 8) * 8 + 16   # GS_FFTCONV_HEADER_BYTES
 LIMIT_MAX_LOOKAHEAD = 2048                                        # GS_LIMIT_MAX_LOOKAHEAD: samples
 LIMIT_TILE = 4096                                                 # GS_LIMIT_TILE: samples per block of gs_limit
+TRUE_PEAK_TILE, TRUE_PEAK_TAPS, TRUE_PEAK_OVERSAMPLE = 2048, 68, 4   # GS_TRUE_PEAK_TILE, GS_TRUE_PEAK_TAPS, GS_TRUE_PEAK_OVERSAMPLE
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 192000               # GS_LOUDNESS_MIN_RATE, GS_LOUDNESS_MAX_RATE
 LOUDNESS_STEPS = 8                                                # GS_LOUDNESS_STEPS: matrix powers per scan of gs_loudness
 
@@ -238,6 +239,9 @@ SIGNATURES = {
     "gs_fftconv": (I, [V, P, Z, P, L, F, F, I, P, L, P, P, P, Z, P]),
     "gs_limit_workspace_bytes": (Z, [I, L]),
     "gs_limit": (I, [P, I, L, L, F, F, I, P, L, P, P, P, P, Z, P]),
+    "gs_limit_env": (I, [P, P, I, L, L, F, F, I, P, L, P, P, P, P, Z, P]),
+    "gs_true_peak_workspace_bytes": (Z, [I, L]),
+    "gs_true_peak": (I, [P, P, I, L, L, P, P, P, Z, P]),
     # W = POINTER(GsLoudness), the meter of one rate
     "gs_loudness_design": (I, [I, W]),
     "gs_loudness_hops": (L, [W, L]),

@@ -17,7 +17,8 @@
 // an address is the lane's base plus an immediate, an element costs one ds_read and one fmin / add.  And the elements a lane holds, EPT, is
 // a template parameter chosen by W (18: W <= 256, 24: W <= 1024, 32: W <= 2048), so that a short look-ahead does not pay for the longest.
 //
-//   limit_kernel<ROWS, EPT>   grid (tiles): stage, m, g, out, pcm, one |max| of out and one min of g a block
+//   limit_kernel<ROWS, EPT, ENV>   grid (tiles): stage, m, g, out, pcm, one |max| of out and one min of g a block; ENV: gs_limit_env, whose
+//                                  step 2 also takes fl(d * env[t]) -- a true-peak envelope from true_peak.hip -- into the maximum
 //   limit_fold_kernel    grid (1): the folds of those slots (maxima of values that are never NaN, minima likewise: exact in any order)
 #include <math.h>
 
@@ -78,13 +79,22 @@ __device__ inline float lim_ratio(const float (&y)[ROWS], float c) {
     for (int r = 0; r < ROWS; ++r) a = fmaxf(a, fabsf(y[r]));
     return a > c ? __fdiv_rn(c, a) : 1.f;
 }
+// step 2' of gs_limit_env: the scaled envelope fl(d * env[t]) joins the maximum (a NaN there contributes nothing)
+template <int ROWS>
+__device__ inline float lim_ratio(const float (&y)[ROWS], float c, float scaled_env) {
+    float a = fmaxf(0.f, scaled_env);
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) a = fmaxf(a, fabsf(y[r]));
+    return a > c ? __fdiv_rn(c, a) : 1.f;
+}
 
 // step 6: the clamp that lets a NaN through
 __device__ inline float lim_clamp(float v, float c) { return v > c ? c : (v < -c ? -c : v); }
 
-// grid (tiles of n).  out / pcm of the tile's samples below n; block_max[b] = max |out|, block_min[b] = min g over them
-template <int ROWS, int EPT>
-__global__ __launch_bounds__(LIM_NT) void limit_kernel(const float* __restrict__ x, long n, long row_stride, float d, float c, int W,
+// grid (tiles of n).  out / pcm of the tile's samples below n; block_max[b] = max |out|, block_min[b] = min g over them.  ENV: gs_limit_env,
+// env [n] enters step 2 (it is not read otherwise)
+template <int ROWS, int EPT, bool ENV>
+__global__ __launch_bounds__(LIM_NT) void limit_kernel(const float* __restrict__ x, const float* __restrict__ env, long n, long row_stride, float d, float c, int W,
                                                        float* __restrict__ out, long out_stride, short* __restrict__ pcm,
                                                        float* __restrict__ block_max, float* __restrict__ block_min) {
     constexpr int HALO_STEPS = EPT - LIM_OWN;                                  // halo samples per lane: 2 * WMAX / LIM_NT
@@ -102,6 +112,7 @@ __global__ __launch_bounds__(LIM_NT) void limit_kernel(const float* __restrict__
         orow[r] = out + (size_t)r * out_stride;
         bases |= reinterpret_cast<uintptr_t>(xr[r]) | reinterpret_cast<uintptr_t>(orow[r]);
     }
+    if constexpr (ENV) bases |= reinterpret_cast<uintptr_t>(env);
     const bool wide = (bases & 15) == 0 && (reinterpret_cast<uintptr_t>(pcm) & (8 * ROWS - 1)) == 0;   // block-uniform
 
     // every global read first -- the tile's own samples into y (0 from n on), the halos' into hx --, then the arithmetic: the loads are in
@@ -123,9 +134,26 @@ __global__ __launch_bounds__(LIM_NT) void limit_kernel(const float* __restrict__
             for (int j = 0; j < 4; ++j) y[u][r][j] = v[j];
         }
     }
+    float ev[ENV ? LIM_STEPS : 1][4];        // the envelope of the tile's own samples (0 from n on, like y)
+    if constexpr (ENV) {
+#pragma unroll
+        for (int u = 0; u < LIM_STEPS; ++u) {
+            const long t0 = tile_begin + (u * LIM_NT + threadIdx.x) * 4;
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+            if (wide && t0 + 4 <= tile_end) ld4(env + t0, v);
+            else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (t0 + j < tile_end) v[j] = env[t0 + j];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ev[u][j] = v[j];
+        }
+    }
     // the halos: W samples before the tile and W after its LIM_TILE, sample by sample; an index outside [0, n) is clamped into the row
     // for the read and its value dropped (r = 1 there)
     float hx[HALO_STEPS][ROWS];
+    float he[ENV ? HALO_STEPS : 1];
 #pragma unroll
     for (int it = 0; it < HALO_STEPS; ++it) {
         if (it * LIM_NT < 2 * W) {            // block-uniform
@@ -134,6 +162,7 @@ __global__ __launch_bounds__(LIM_NT) void limit_kernel(const float* __restrict__
             const long tc = t < 0 ? 0 : (t < n ? t : n - 1);
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) hx[it][r] = xr[r][tc];
+            if constexpr (ENV) he[it] = env[tc];
         }
     }
 #pragma unroll
@@ -145,7 +174,8 @@ __global__ __launch_bounds__(LIM_NT) void limit_kernel(const float* __restrict__
             float ys[ROWS];
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) ys[r] = y[u][r][j] = __fmul_rn(d, y[u][r][j]);
-            rr[j] = lim_ratio<ROWS>(ys, c);
+            if constexpr (ENV) rr[j] = lim_ratio<ROWS>(ys, c, __fmul_rn(d, ev[u][j]));
+            else rr[j] = lim_ratio<ROWS>(ys, c);
         }
         *reinterpret_cast<float4*>(rl + W + p) = make_float4(rr[0], rr[1], rr[2], rr[3]);   // (pad + W + p) % 4 == 0
     }
@@ -157,7 +187,11 @@ __global__ __launch_bounds__(LIM_NT) void limit_kernel(const float* __restrict__
             float ys[ROWS];
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) ys[r] = __fmul_rn(d, hx[it][r]);
-            const float v = (t >= 0 && t < n) ? lim_ratio<ROWS>(ys, c) : 1.f;
+            float v = 1.f;
+            if (t >= 0 && t < n) {
+                if constexpr (ENV) v = lim_ratio<ROWS>(ys, c, __fmul_rn(d, he[it]));
+                else v = lim_ratio<ROWS>(ys, c);
+            }
             if (i < 2 * W) rl[i < W ? i : LIM_TILE + i] = v;
         }
     }
@@ -257,13 +291,16 @@ extern "C" size_t gs_limit_workspace_bytes(int rows, int64_t n) {
     return lim_ws_bytes(n);
 }
 
-extern "C" int gs_limit(const float* x, int rows, int64_t n, int64_t row_stride, float pre_gain, float ceiling, int lookahead, float* out,
-                        int64_t out_stride, int16_t* pcm, float* peak, float* min_gain, void* ws, size_t ws_bytes, void* stream) {
+// gs_limit (env == nullptr, ENV false) and gs_limit_env (ENV true): one set of checks, one launch
+template <bool ENV>
+static int lim_launch(const float* x, const float* env, int rows, int64_t n, int64_t row_stride, float pre_gain, float ceiling, int lookahead, float* out,
+                      int64_t out_stride, int16_t* pcm, float* peak, float* min_gain, void* ws, size_t ws_bytes, void* stream) {
     GS_CHECK_ARG(rows == 1 || rows == 2, "limit: rows must be 1 or 2 (got %d)", rows);
     GS_CHECK_ARG(n > 0 && n <= GS_LIMIT_MAX_N, "limit: n must be in [1, 2^40] (got %lld)", (long long)n);
     GS_CHECK_ARG(row_stride >= n, "limit: row_stride %lld is below n %lld", (long long)row_stride, (long long)n);
     GS_CHECK_ARG(out_stride >= n, "limit: out_stride %lld is below n %lld", (long long)out_stride, (long long)n);
     GS_CHECK_ARG(x && out, "limit: null pointer (x and out are required)");
+    if (ENV) GS_CHECK_ARG(env != nullptr && (reinterpret_cast<uintptr_t>(env) & 3) == 0, "limit: env is required and 4-byte aligned");
     GS_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0 && (reinterpret_cast<uintptr_t>(peak) & 3) == 0 &&
                  (reinterpret_cast<uintptr_t>(min_gain) & 3) == 0 && (reinterpret_cast<uintptr_t>(pcm) & 1) == 0,
                  "limit: misaligned pointer (x / out / peak / min_gain: 4 bytes, pcm: 2)");
@@ -285,8 +322,8 @@ extern "C" int gs_limit(const float* x, int rows, int64_t n, int64_t row_stride,
     const int ept = lookahead <= lim_wmax(18) ? 18 : (lookahead <= lim_wmax(24) ? 24 : 32);
     with_constant<1, 2>(rows, [&](auto rows_c) {
         return with_constant<18, 24, 32>(ept, [&](auto ept_c) {
-            hipLaunchKernelGGL((limit_kernel<decltype(rows_c)::value, decltype(ept_c)::value>), dim3((unsigned)tiles), dim3(LIM_NT), 0, st, x, (long)n,
-                               (long)row_stride, pre_gain, ceiling, lookahead, out, (long)out_stride, reinterpret_cast<short*>(pcm), block_max, block_min);
+            hipLaunchKernelGGL((limit_kernel<decltype(rows_c)::value, decltype(ept_c)::value, ENV>), dim3((unsigned)tiles), dim3(LIM_NT), 0, st, x, env,
+                               (long)n, (long)row_stride, pre_gain, ceiling, lookahead, out, (long)out_stride, reinterpret_cast<short*>(pcm), block_max, block_min);
             return true;
         });
     });
@@ -295,4 +332,14 @@ extern "C" int gs_limit(const float* x, int rows, int64_t n, int64_t row_stride,
                            peak, min_gain);
     GS_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int gs_limit(const float* x, int rows, int64_t n, int64_t row_stride, float pre_gain, float ceiling, int lookahead, float* out,
+                        int64_t out_stride, int16_t* pcm, float* peak, float* min_gain, void* ws, size_t ws_bytes, void* stream) {
+    return lim_launch<false>(x, nullptr, rows, n, row_stride, pre_gain, ceiling, lookahead, out, out_stride, pcm, peak, min_gain, ws, ws_bytes, stream);
+}
+
+extern "C" int gs_limit_env(const float* x, const float* env, int rows, int64_t n, int64_t row_stride, float pre_gain, float ceiling, int lookahead,
+                            float* out, int64_t out_stride, int16_t* pcm, float* peak, float* min_gain, void* ws, size_t ws_bytes, void* stream) {
+    return lim_launch<true>(x, env, rows, n, row_stride, pre_gain, ceiling, lookahead, out, out_stride, pcm, peak, min_gain, ws, ws_bytes, stream);
 }

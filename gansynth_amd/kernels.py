@@ -362,10 +362,37 @@ def limit_shapes(x, pre_gain, ceiling, lookahead):
     return rows, n
 
 
-def limit(x, pre_gain, ceiling, lookahead, want_pcm=False):
+def limit(x, pre_gain, ceiling, lookahead, want_pcm=False, envelope=None):
     """HipKernels.limit of the process-wide kernel object; the arguments are refused here, before a device is asked for."""
-    limit_shapes(x, pre_gain, ceiling, lookahead)
-    return get().limit(x, pre_gain, ceiling, lookahead, want_pcm=want_pcm)
+    rows, n = limit_shapes(x, pre_gain, ceiling, lookahead)
+    if envelope is None:   # (the call it was)
+        return get().limit(x, pre_gain, ceiling, lookahead, want_pcm=want_pcm)
+    envelope_shape(envelope, n)
+    return get().limit(x, pre_gain, ceiling, lookahead, want_pcm=want_pcm, envelope=envelope)
+
+
+def envelope_shape(envelope, n):
+    """limit's envelope: an fp32 vector of the clip's n samples (true_peak's first result).  ValueError; needs no device."""
+    if not isinstance(envelope, torch.Tensor) or envelope.dtype != torch.float32 or tuple(envelope.shape) != (n,):
+        got = f"{tuple(envelope.shape)} {envelope.dtype}" if isinstance(envelope, torch.Tensor) else type(envelope).__name__
+        raise ValueError(f"limit: envelope must be an fp32 vector of the clip's {n} samples (got {got})")
+
+
+def true_peak_shapes(x):
+    """The host side of true_peak: -> (rows, n) of x ([n] or [rows, n] fp32, rows 1 or 2).  ValueError; needs no device."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2) or x.dtype != torch.float32 or x.numel() == 0:
+        got = f"{tuple(x.shape)} {x.dtype}" if isinstance(x, torch.Tensor) else type(x).__name__
+        raise ValueError(f"true_peak: x must be a non-empty fp32 vector or [rows, samples] matrix (got {got})")
+    rows, n = (1, int(x.shape[0])) if x.dim() == 1 else (int(x.shape[0]), int(x.shape[1]))
+    if rows > 2:
+        raise ValueError(f"true_peak: x must have 1 or 2 rows -- a clip is mono or stereo (got {rows})")
+    return rows, n
+
+
+def true_peak(x, want_envelope=True):
+    """HipKernels.true_peak of the process-wide kernel object; the shape is refused here, before a device is asked for."""
+    true_peak_shapes(x)
+    return get().true_peak(x, want_envelope=want_envelope)
 
 
 def loudness_shapes(x, rate):
@@ -1921,14 +1948,38 @@ class HipKernels(object):
                                        None if pcm is None else pcm.data_ptr(), peak.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_fftconv")
         return (out[0] if mono else out), pcm, peak
 
-    def limit(self, x, pre_gain, ceiling, lookahead, want_pcm=False):
+    def true_peak(self, x, want_envelope=True):
+        """gs_true_peak (include/gansynth_hip.h): the 4x oversampled peak detector on x -- [n] or [rows, n] fp32 on the device, rows 1 or 2,
+        any row stride.  -> (env [n] fp32 -- e[t] = the largest |value| of the reconstructed waveform of any row on [t, t + 1) -- or None,
+        peak [1] fp32 = max e, the clip's true peak as a linear value).  The 1 -> 4 table is resample_design's, built once a device."""
+        rows, n = true_peak_shapes(x)
+        if not x.is_cuda:
+            raise ValueError(f"true_peak: x must be on the HIP device (it is on {x.device})")
+        x2 = x[None] if x.dim() == 1 else x
+        if x2.stride(1) != 1 or (rows > 1 and x2.stride(0) < n):
+            x2 = x2.contiguous()
+        _, table = self.resample_design(1, _lib.TRUE_PEAK_OVERSAMPLE, x.device)
+        env = torch.empty((n,), dtype=torch.float32, device=x.device) if want_envelope else None
+        peak = torch.empty((1,), dtype=torch.float32, device=x.device)
+        ws = _ws(self.lib.gs_true_peak_workspace_bytes(rows, n), x.device)
+        _lib.check(self.lib.gs_true_peak(table.data_ptr(), x2.data_ptr(), rows, n, int(x2.stride(0)) if rows > 1 else n,
+                                         None if env is None else env.data_ptr(), peak.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_true_peak")
+        return env, peak
+
+    def limit(self, x, pre_gain, ceiling, lookahead, want_pcm=False, envelope=None):
         """gs_limit (include/gansynth_hip.h): the look-ahead limiter on x -- [n] or [rows, n] fp32 on the device, rows 1 or 2, any row
         stride --: x times pre_gain, then ONE gain per sample for all rows that keeps every |sample| at or below ceiling, from the sliding
         minimum and mean over `lookahead` samples.  -> (out -- [n] or [rows, n] fp32, a new tensor whose rows start on 16 bytes --, pcm [n] or
-        [n, rows] int16 or None, peak [1] fp32 = max |out|, min_gain [1] fp32 = the smallest gain applied)."""
+        [n, rows] int16 or None, peak [1] fp32 = max |out|, min_gain [1] fp32 = the smallest gain applied).  `envelope` ([n] fp32 on the device,
+        true_peak's of the same x): gs_limit_env -- the gain also keeps pre_gain * envelope at or below ceiling, i.e. the reconstructed waveform."""
         rows, n = limit_shapes(x, pre_gain, ceiling, lookahead)
         if not x.is_cuda:
             raise ValueError(f"limit: x must be on the HIP device (it is on {x.device})")
+        if envelope is not None:
+            envelope_shape(envelope, n)
+            if envelope.device != x.device:
+                raise ValueError(f"limit: envelope is on {envelope.device}, x on {x.device}")
+            envelope = envelope.contiguous()
         mono = x.dim() == 1
         x2 = x[None] if mono else x
         if x2.stride(1) != 1 or (rows > 1 and x2.stride(0) < n):
@@ -1939,9 +1990,12 @@ class HipKernels(object):
         peak = torch.empty((1,), dtype=torch.float32, device=x.device)
         min_gain = torch.empty((1,), dtype=torch.float32, device=x.device)
         ws = _ws(self.lib.gs_limit_workspace_bytes(rows, n), x.device)
-        _lib.check(self.lib.gs_limit(x2.data_ptr(), rows, n, int(x2.stride(0)) if rows > 1 else n, float(pre_gain), float(ceiling), int(lookahead),
-                                     out.data_ptr(), stride, None if pcm is None else pcm.data_ptr(), peak.data_ptr(), min_gain.data_ptr(),
-                                     ws.data_ptr(), ws.numel(), _stream()), "gs_limit")
+        tail = (rows, n, int(x2.stride(0)) if rows > 1 else n, float(pre_gain), float(ceiling), int(lookahead), out.data_ptr(), stride,
+                None if pcm is None else pcm.data_ptr(), peak.data_ptr(), min_gain.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        if envelope is None:
+            _lib.check(self.lib.gs_limit(x2.data_ptr(), *tail), "gs_limit")
+        else:
+            _lib.check(self.lib.gs_limit_env(x2.data_ptr(), envelope.data_ptr(), *tail), "gs_limit_env")
         return (out[0] if mono else out), pcm, peak, min_gain
 
     def loudness_design(self, rate):

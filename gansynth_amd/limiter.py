@@ -8,6 +8,9 @@ Host code, except `apply`'s call into kernels.limit (gs_limit on the device).
 
     design(rate, ceiling_db, drive_db, lookahead_seconds, peak)   -> (pre_gain, ceiling, lookahead in samples): host arithmetic
     apply(clip, rate, ...)                                         -> (out, pcm or None, peak, min_gain) of kernels.limit
+
+`apply(..., true_peak=True)` reads the ceiling in dBTP: the clip's 4x oversampled envelope (kernels.true_peak, DESIGN.md "True peak") sets the
+pre-gain and goes to the kernel, which then holds the reconstructed waveform, not only the samples, under the ceiling.
 """
 import math
 
@@ -62,15 +65,19 @@ def design(rate, ceiling_db=-1.0, drive_db=6.0, lookahead_seconds=0.005, peak=1.
     return pre_gain, c, w
 
 
-def apply(clip, rate, ceiling_db=-1.0, drive_db=6.0, lookahead_seconds=0.005, peak=None, want_pcm=False):
+def apply(clip, rate, ceiling_db=-1.0, drive_db=6.0, lookahead_seconds=0.005, peak=None, want_pcm=False, true_peak=False):
     """The limiter on clip ([n] or [2, n] fp32 on the device) at `rate` samples per second: -> (out, pcm or None, peak [1], min_gain [1]) of
     kernels.limit with design()'s numbers.  `peak`: the unnormalised clip's max |sample| as the stage before returned it (a number or a
-    one-element tensor); None: taken here.  Both channels share ONE gain."""
+    one-element tensor); None: taken here.  Both channels share ONE gain.  `true_peak`: the ceiling is in dBTP -- the pre-gain is designed
+    from the clip's true peak (measured here; `peak` is not used) and the detector's envelope goes to the kernel with the clip."""
     from . import kernels
     if not isinstance(clip, torch.Tensor) or clip.dim() not in (1, 2) or clip.dtype != torch.float32 or clip.numel() == 0 or \
             (clip.dim() == 2 and clip.shape[0] != 2):
         got = f"{tuple(clip.shape)} {clip.dtype}" if isinstance(clip, torch.Tensor) else type(clip).__name__
         raise ValueError(f"limiter.apply: clip must be [n] or [2, n] fp32 (got {got})")
+    envelope = None
+    if true_peak:
+        envelope, peak = kernels.true_peak(clip, want_envelope=True)
     if peak is None:
         peak = clip.abs().max()
     if isinstance(peak, torch.Tensor):
@@ -78,4 +85,6 @@ def apply(clip, rate, ceiling_db=-1.0, drive_db=6.0, lookahead_seconds=0.005, pe
             raise ValueError(f"limiter.apply: peak must be one number (got a tensor of {tuple(peak.shape)})")
         peak = float(peak)
     pre_gain, c, w = design(rate, ceiling_db, drive_db, lookahead_seconds, peak)
-    return kernels.limit(clip, pre_gain, c, w, want_pcm=want_pcm)
+    if envelope is None:   # (the call it was)
+        return kernels.limit(clip, pre_gain, c, w, want_pcm=want_pcm)
+    return kernels.limit(clip, pre_gain, c, w, want_pcm=want_pcm, envelope=envelope)

@@ -91,11 +91,12 @@ def measure(clip, rate):
     return integrated(kernels.loudness_energy(clip, int(rate)).cpu().numpy(), hop)
 
 
-def apply(clip, rate, target_lufs, ceiling_db=-1.0, lookahead_seconds=0.005, want_pcm=False):
+def apply(clip, rate, target_lufs, ceiling_db=-1.0, lookahead_seconds=0.005, want_pcm=False, true_peak=False):
     """clip ([n] or [2, n] fp32 on the device) brought to `target_lufs`: measured, scaled by pre_gain = 10 ** ((target - measured) / 20) (1
     for a clip that measures -inf) and finished by kernels.limit at the ceiling -- where the scaled clip stays under it the limiter's gain is
     exactly 1 and the target is met; where not, the peaks are pulled back and the output falls short of it.  The output is measured once
-    more.  -> (out, pcm or None, info) with info = dict(measured_lufs, pre_gain, output_lufs, peak, min_gain)."""
+    more.  -> (out, pcm or None, info) with info = dict(measured_lufs, pre_gain, output_lufs, peak, min_gain).  `true_peak`: the ceiling is in
+    dBTP -- the clip's 4x oversampled envelope (kernels.true_peak) goes to the limiter with it."""
     from . import kernels
     _checked_clip("apply", clip)
     if not isinstance(target_lufs, (int, float, np.integer, np.floating)) or isinstance(target_lufs, bool) or not math.isfinite(target_lufs):
@@ -103,6 +104,9 @@ def apply(clip, rate, target_lufs, ceiling_db=-1.0, lookahead_seconds=0.005, wan
     _, c, w = limiter.design(rate, ceiling_db, 0.0, lookahead_seconds, 0.0)   # the ceiling and the look-ahead; the level is not the limiter's
     measured = measure(clip, rate)
     pre_gain = 10.0 ** ((float(target_lufs) - measured) / 20.0) if math.isfinite(measured) else 1.0
-    out, pcm, peak, min_gain = kernels.limit(clip, pre_gain, c, w, want_pcm=want_pcm)
+    if true_peak:
+        out, pcm, peak, min_gain = kernels.limit(clip, pre_gain, c, w, want_pcm=want_pcm, envelope=kernels.true_peak(clip, want_envelope=True)[0])
+    else:
+        out, pcm, peak, min_gain = kernels.limit(clip, pre_gain, c, w, want_pcm=want_pcm)
     info = dict(measured_lufs=measured, pre_gain=pre_gain, output_lufs=measure(out, rate), peak=float(peak), min_gain=float(min_gain))
     return out, pcm, info

@@ -1005,6 +1005,43 @@ size_t gs_limit_workspace_bytes(int rows, int64_t n);
 int gs_limit(const float* x, int rows, int64_t n, int64_t row_stride, float pre_gain, float ceiling, int lookahead, float* out,
              int64_t out_stride, int16_t* pcm, float* peak, float* min_gain, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- True peak: a 4x oversampled peak detector and the limiter that listens to it (gansynth_amd/true_peak.py, kernels.true_peak,
+ * kernels.limit(envelope=...); this project's own rule, DESIGN.md "True peak") ----------------------------------------------------------
+ * Detector.  T is the [4][68] fp32 table that gs_resample_table gives for the design 1 -> 4 (up 4, down 1, taps 68): the same Kaiser design
+ * and the same single rounding to fp32 as the resampler's; it does not depend on the clip's rate.  For x of [rows] rows (1 or 2) of n
+ * samples, `row_stride` elements apart, with x outside [0, n) taken as 0:
+ *     z[r][4t + p] = sum over k in [0, 68) of T[p][k] * x[r][t - 33 + k]      p = 0..3   (what gs_resample 1:4 would write)
+ *     e[t]         = max over rows r of max(|x[r][t]|, |z[r][4t + 0]|, ..., |z[r][4t + 3]|)        an fmaxf chain from 0
+ *     true_peak    = max over t in [0, n) of e[t]                              the exact fold of the computed e
+ * e[t] covers the reconstructed waveform on [t, t + 1).  |x| is in the maximum because phase 0 of a 0.95-rolloff design is not the identity
+ * and a true peak below the sample peak would be absurd.  fp32 accumulation in any order, with or without FMA: the contract is the
+ * resampler's, |z - z64| <= (taps + 3) * 2^-24 * B with B = sum |T||x|, and e inherits the largest bound among its five terms.  No atomics:
+ * two calls are bit-identical.  The 4x signal is never written to memory.
+ * gs_true_peak: table_dev is the device-layout table of the 1 -> 4 design, as gs_resample takes it (16-byte aligned).  env ([n]) and peak
+ * ([1]) may each be NULL, not both.  One launch over tiles of GS_TRUE_PEAK_TILE samples of all rows (the tile with a halo of 33 before and 34
+ * after in LDS, a lane register-blocks 8 samples x 4 phases, the coefficients come through scalar registers), which leaves one |max| per block
+ * in ws (gs_true_peak_workspace_bytes: 4 * ceil(n / GS_TRUE_PEAK_TILE), rounded up to 16; 16-byte aligned), and one small fold launch when
+ * peak is asked for.  Capture-safe: no allocation, no synchronisation.  gs_true_peak_workspace_bytes is host arithmetic and answers 0 for a
+ * refused shape.
+ * GS_ERR_ARG with a message and without a launch: rows outside {1, 2}, n <= 0 (or > GS_TRUE_PEAK_MAX_N), row_stride < n, table or x NULL, env
+ * and peak both NULL, table off 16 bytes, x / env / peak off 4, ws NULL, off 16 or too small.
+ * True-peak limiter.  gs_limit_env is gs_limit's rule, steps 1-9, with one change in step 2:
+ *   2'. a[t] = max( max over the rows of |y[r][t]| ,  fl(d * env[t]) )         env: the detector's e of the unscaled x ([n], required)
+ * Everything else is character for character gs_limit's: the correctly rounded quotient, the exact minimum, the tree sums over exactly W + 1
+ * terms, the clamp, |out| <= c bit for bit per sample, out == fl(d * x) bit for bit where no a within W exceeds c.  What it adds: every
+ * reconstructed point between t and t + 1 sees gains <= c / (d e[t]); the remaining overshoot comes only from the gain moving under the
+ * 68-tap kernel and is second order.  A NaN in env contributes nothing.  With env[t] = max over the rows of |x[r][t]| it is gs_limit bit for
+ * bit.  Same launches, workspace and refusals as gs_limit, and env NULL or off 4 bytes. */
+#define GS_TRUE_PEAK_TILE 2048
+#define GS_TRUE_PEAK_TAPS 68
+#define GS_TRUE_PEAK_OVERSAMPLE 4
+#define GS_TRUE_PEAK_MAX_N ((int64_t)1 << 40)
+size_t gs_true_peak_workspace_bytes(int rows, int64_t n);
+int gs_true_peak(const float* table_dev, const float* x, int rows, int64_t n, int64_t row_stride, float* env, float* peak, void* ws,
+                 size_t ws_bytes, void* stream);
+int gs_limit_env(const float* x, const float* env, int rows, int64_t n, int64_t row_stride, float pre_gain, float ceiling, int lookahead, float* out,
+                 int64_t out_stride, int16_t* pcm, float* peak, float* min_gain, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Loudness: the K-weighted hop energies of ITU-R BS.1770, from which the host gates the integrated loudness of a rendered clip
  * (gansynth_amd/loudness.py, kernels.loudness_energy; DESIGN.md "Loudness") ------------------------------------------------------------
  * gs_loudness_design(rate): host arithmetic in float64, no device.  hop = floor(0.1 * rate + 0.5) samples (a gating block is 4 hops: 400 ms
