@@ -13,6 +13,11 @@ TensorFlow GraphDef, read without TensorFlow) or the same weights as a .safetens
 
     python gan_synth_main.py --evaluate --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
 
+`--ndb` (not in the reference's driver) adds the other figures of its metrics.py to that dict: inception_score, pitch_accuracy,
+num_different_bins and bin_jsd, the k-means of NDB on HIP kernels (gansynth_amd/kmeans.py, DESIGN.md "NDB on the device"):
+
+    python gan_synth_main.py --evaluate --ndb --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
+
 `--synthesize` (not in the reference) renders a score -- a Standard MIDI File or a JSON list of {"pitch", "velocity", "start", "end"}
 notes -- into one 16 kHz 16-bit WAV: every note generated at its pitch, the timbre gliding between latent anchors, the mixdown on the
 device (GANSynth.synthesize).  It needs no dataset:
@@ -103,6 +108,9 @@ parser.add_argument("--evaluate", action="store_true")
 parser.add_argument("--generate", action="store_true")
 # not in the reference
 parser.add_argument("--synthetic", action="store_true", help="generated notes instead of --filenames")
+parser.add_argument("--ndb", action="store_true",
+                    help="--evaluate: also the inception score, the pitch accuracy and the number of statistically different bins (NDB) with the "
+                         "Jensen-Shannon divergence of the bin proportions, the k-means on the device (no scikit-learn)")
 parser.add_argument("--dtype", choices=["f32", "bf16"], default="bf16", help="activation storage (master weights / Adam stay fp32)")
 parser.add_argument("--save_checkpoint_steps", type=int, default=1000)
 parser.add_argument("--log_tensor_steps", type=int, default=100)
@@ -446,7 +454,8 @@ def main(args):
                 classifier=args.classifier,    # the frozen pitch-classifier GraphDef (.pb), or its weights as .safetensors
                 input_name="images:0",
                 output_names=["features:0", "logits:0"],
-                weights=args.weights))
+                weights=args.weights,
+                **(dict(extra_metrics=True, ndb="device") if args.ndb else {})))   # (without the flag the call is the one it was)
         finally:
             model.real_input_fn = kept
 

@@ -73,6 +73,7 @@ FFTCONV_HEADER_BYTES = (FFTCONV_BLOCK + FFTCONV_BLOCK // 2 + 8) * 8 + 16   # GS_
 LIMIT_MAX_LOOKAHEAD = 2048                                        # GS_LIMIT_MAX_LOOKAHEAD: samples
 LIMIT_TILE = 4096                                                 # GS_LIMIT_TILE: samples per block of gs_limit
 TRUE_PEAK_TILE, TRUE_PEAK_TAPS, TRUE_PEAK_OVERSAMPLE = 2048, 68, 4   # GS_TRUE_PEAK_TILE, GS_TRUE_PEAK_TAPS, GS_TRUE_PEAK_OVERSAMPLE
+KMEANS_MAX_K, KMEANS_TILE, KMEANS_MAX_SLICES, KMEANS_MAX_N, KMEANS_MAX_D = 256, 256, 512, 2 ** 31 - 1, 1 << 20   # GS_KMEANS_MAX_K, _TILE, _MAX_SLICES, _MAX_N, _MAX_D
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 192000               # GS_LOUDNESS_MIN_RATE, GS_LOUDNESS_MAX_RATE
 LOUDNESS_STEPS = 8                                                # GS_LOUDNESS_STEPS: matrix powers per scan of gs_loudness
 
@@ -242,6 +243,11 @@ SIGNATURES = {
     "gs_limit_env": (I, [P, P, I, L, L, F, F, I, P, L, P, P, P, P, Z, P]),
     "gs_true_peak_workspace_bytes": (Z, [I, L]),
     "gs_true_peak": (I, [P, P, I, L, L, P, P, P, Z, P]),
+    "gs_kmeans_workspace_bytes": (Z, [L, I, I]),
+    "gs_kmeans_assign": (I, [P, L, L, I, P, I, P, P, P, P, P, Z, P]),
+    "gs_kmeans_inertia": (I, [P, L, L, I, P, I, P, P, P, Z, P]),
+    "gs_kmeans_update": (I, [P, L, L, I, P, I, P, P, P, Z, P]),
+    "gs_kmeans_mindist": (I, [P, L, L, I, P, P, I, P]),
     # W = POINTER(GsLoudness), the meter of one rate
     "gs_loudness_design": (I, [I, W]),
     "gs_loudness_hops": (L, [W, L]),

@@ -395,6 +395,98 @@ def true_peak(x, want_envelope=True):
     return get().true_peak(x, want_envelope=want_envelope)
 
 
+def _kmeans_matrix(what, name, t, cols=None):
+    """x / centres of the k-means entries: a non-empty fp32 matrix (with `cols` columns); -> (rows, columns).  ValueError by argument name."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or t.numel() == 0 or (cols is not None and t.shape[1] != cols):
+        got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+        want = "[rows, columns]" if cols is None else f"[rows, {cols}]"
+        raise ValueError(f"{what}: {name} must be a non-empty fp32 {want} matrix (got {got})")
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def _kmeans_vector(what, name, t, n, dtype):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n,) or not t.is_contiguous():
+        got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{what}: {name} must be a contiguous {str(dtype).replace('torch.', '')} vector of {n} (got {got})")
+
+
+def _kmeans_nk(what, n, k, d=1):
+    if n > _lib.KMEANS_MAX_N:
+        raise ValueError(f"{what}: x must have at most {_lib.KMEANS_MAX_N} rows (got {n})")
+    if d > _lib.KMEANS_MAX_D:
+        raise ValueError(f"{what}: x must have at most {_lib.KMEANS_MAX_D} columns (got {d})")
+    if k > _lib.KMEANS_MAX_K:
+        raise ValueError(f"{what}: centres must have at most {_lib.KMEANS_MAX_K} rows (got {k})")
+
+
+def kmeans_assign_shapes(x, centres, labels=None):
+    """The host side of kmeans_assign: -> (n, d, k) of x [n, d] and centres [k, d] (fp32, k <= KMEANS_MAX_K); labels, when given, a contiguous
+    int32 vector of n.  ValueError by argument name; needs no device."""
+    n, d = _kmeans_matrix("kmeans_assign", "x", x)
+    k, _ = _kmeans_matrix("kmeans_assign", "centres", centres, d)
+    _kmeans_nk("kmeans_assign", n, k, d)
+    if labels is not None:
+        _kmeans_vector("kmeans_assign", "labels", labels, n, torch.int32)
+    return n, d, k
+
+
+def kmeans_assign(x, centres, labels=None, want_dist=True, want_inertia=False):
+    """HipKernels.kmeans_assign of the process-wide kernel object; the shapes are refused here, before a device is asked for."""
+    kmeans_assign_shapes(x, centres, labels)
+    return get().kmeans_assign(x, centres, labels=labels, want_dist=want_dist, want_inertia=want_inertia)
+
+
+def kmeans_inertia_shapes(x, centres, labels):
+    """The host side of kmeans_inertia: -> (n, d, k) of x [n, d], centres [k, d] (fp32) and labels (a contiguous int32 vector of n).  ValueError by
+    argument name; needs no device."""
+    n, d = _kmeans_matrix("kmeans_inertia", "x", x)
+    k, _ = _kmeans_matrix("kmeans_inertia", "centres", centres, d)
+    _kmeans_nk("kmeans_inertia", n, k, d)
+    _kmeans_vector("kmeans_inertia", "labels", labels, n, torch.int32)
+    return n, d, k
+
+
+def kmeans_inertia(x, centres, labels):
+    """HipKernels.kmeans_inertia of the process-wide kernel object; the shapes are refused here, before a device is asked for."""
+    kmeans_inertia_shapes(x, centres, labels)
+    return get().kmeans_inertia(x, centres, labels)
+
+
+def kmeans_update_shapes(x, labels, centres):
+    """The host side of kmeans_update: -> (n, d, k) of x [n, d], labels (a contiguous int32 vector of n) and centres [k, d] (fp32, contiguous:
+    written in place).  ValueError by argument name; needs no device."""
+    n, d = _kmeans_matrix("kmeans_update", "x", x)
+    _kmeans_vector("kmeans_update", "labels", labels, n, torch.int32)
+    k, _ = _kmeans_matrix("kmeans_update", "centres", centres, d)
+    if not centres.is_contiguous():
+        raise ValueError("kmeans_update: centres must be contiguous (it is written in place)")
+    _kmeans_nk("kmeans_update", n, k, d)
+    return n, d, k
+
+
+def kmeans_update(x, labels, centres):
+    """HipKernels.kmeans_update of the process-wide kernel object; the shapes are refused here, before a device is asked for."""
+    kmeans_update_shapes(x, labels, centres)
+    return get().kmeans_update(x, labels, centres)
+
+
+def kmeans_mindist_shapes(x, centre, dist=None):
+    """The host side of kmeans_mindist: -> (n, d) of x [n, d] and centre (a contiguous fp32 vector of d); dist, when given (the running minimum),
+    a contiguous fp32 vector of n.  ValueError by argument name; needs no device."""
+    n, d = _kmeans_matrix("kmeans_mindist", "x", x)
+    _kmeans_vector("kmeans_mindist", "centre", centre, d, torch.float32)
+    _kmeans_nk("kmeans_mindist", n, 1, d)
+    if dist is not None:
+        _kmeans_vector("kmeans_mindist", "dist", dist, n, torch.float32)
+    return n, d
+
+
+def kmeans_mindist(x, centre, dist=None):
+    """HipKernels.kmeans_mindist of the process-wide kernel object; the shapes are refused here, before a device is asked for."""
+    kmeans_mindist_shapes(x, centre, dist)
+    return get().kmeans_mindist(x, centre, dist=dist)
+
+
 def loudness_shapes(x, rate):
     """The host side of loudness_energy: -> (rows, n) of x ([n] or [rows, n] fp32, rows 1 or 2); rate an integer number of samples per second
     in [LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE].  ValueError by argument name; needs no device."""
@@ -1965,6 +2057,71 @@ class HipKernels(object):
         _lib.check(self.lib.gs_true_peak(table.data_ptr(), x2.data_ptr(), rows, n, int(x2.stride(0)) if rows > 1 else n,
                                          None if env is None else env.data_ptr(), peak.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_true_peak")
         return env, peak
+
+    @staticmethod
+    def _kmeans_rows(what, x, *others):
+        """x as the k-means entries read it (unit column stride, rows at least d apart: a view with row slack is taken as it stands)."""
+        if not x.is_cuda:
+            raise ValueError(f"{what}: x must be on the HIP device (it is on {x.device})")
+        for name, t in others:
+            if t is not None and t.device != x.device:
+                raise ValueError(f"{what}: {name} is on {t.device}, x on {x.device}")
+        if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+            x = x.contiguous()
+        return x, (int(x.stride(0)) if x.shape[0] > 1 else int(x.shape[1]))
+
+    def kmeans_assign(self, x, centres, labels=None, want_dist=True, want_inertia=False):
+        """gs_kmeans_assign (include/gansynth_hip.h): the nearest of centres [k, d] for every row of x [n, d] (fp32 on the device, any row stride)
+        in the squared Euclidean distance, ties to the lowest index.  -> (labels [n] int32, dist [n] fp32 or None, changed [1] int32 or None,
+        inertia [1] float64 or None: the sum of dist, accumulated in double).  `labels` given: it is read, overwritten and returned, and changed
+        counts the rows whose label moved."""
+        n, d, k = kmeans_assign_shapes(x, centres, labels)
+        x2, ldx = self._kmeans_rows("kmeans_assign", x, ("centres", centres), ("labels", labels))
+        centres = centres.contiguous()
+        changed = torch.empty((1,), dtype=torch.int32, device=x.device) if labels is not None else None
+        if labels is None:
+            labels = torch.empty((n,), dtype=torch.int32, device=x.device)
+        dist = torch.empty((n,), dtype=torch.float32, device=x.device) if want_dist else None
+        inertia = torch.empty((1,), dtype=torch.float64, device=x.device) if want_inertia else None
+        ws = _ws(self.lib.gs_kmeans_workspace_bytes(n, d, k), x.device)
+        _lib.check(self.lib.gs_kmeans_assign(x2.data_ptr(), ldx, n, d, centres.data_ptr(), k, labels.data_ptr(), None if dist is None else dist.data_ptr(),
+                                             None if changed is None else changed.data_ptr(), None if inertia is None else inertia.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), _stream()), "gs_kmeans_assign")
+        return labels, dist, changed, inertia
+
+    def kmeans_inertia(self, x, centres, labels):
+        """gs_kmeans_inertia (include/gansynth_hip.h): -> [1] float64, the sum over the rows of x [n, d] of the squared distance to the row of
+        centres [k, d] that labels [n] (int32) names, every term and every sum in double, in a fixed order."""
+        n, d, k = kmeans_inertia_shapes(x, centres, labels)
+        x2, ldx = self._kmeans_rows("kmeans_inertia", x, ("centres", centres), ("labels", labels))
+        centres = centres.contiguous()
+        inertia = torch.empty((1,), dtype=torch.float64, device=x.device)
+        ws = _ws(self.lib.gs_kmeans_workspace_bytes(n, d, k), x.device)
+        _lib.check(self.lib.gs_kmeans_inertia(x2.data_ptr(), ldx, n, d, centres.data_ptr(), k, labels.data_ptr(), inertia.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              _stream()), "gs_kmeans_inertia")
+        return inertia
+
+    def kmeans_update(self, x, labels, centres):
+        """gs_kmeans_update (include/gansynth_hip.h): centres [k, d] (fp32, contiguous, on the device) receives, in place, the mean of the rows
+        of x [n, d] of every label that has rows; an empty label's centre is left as it is.  -> counts [k] int32."""
+        n, d, k = kmeans_update_shapes(x, labels, centres)
+        x2, ldx = self._kmeans_rows("kmeans_update", x, ("labels", labels), ("centres", centres))
+        counts = torch.empty((k,), dtype=torch.int32, device=x.device)
+        ws = _ws(self.lib.gs_kmeans_workspace_bytes(n, d, k), x.device)
+        _lib.check(self.lib.gs_kmeans_update(x2.data_ptr(), ldx, n, d, labels.data_ptr(), k, centres.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             _stream()), "gs_kmeans_update")
+        return counts
+
+    def kmeans_mindist(self, x, centre, dist=None):
+        """gs_kmeans_mindist (include/gansynth_hip.h), the k-means++ step: -> dist [n] fp32, |x_i - centre|^2 in a new vector, or, with `dist`
+        given, the smaller of it and dist[i], in place."""
+        n, d = kmeans_mindist_shapes(x, centre, dist)
+        x2, ldx = self._kmeans_rows("kmeans_mindist", x, ("centre", centre), ("dist", dist))
+        first = dist is None
+        if first:
+            dist = torch.empty((n,), dtype=torch.float32, device=x.device)
+        _lib.check(self.lib.gs_kmeans_mindist(x2.data_ptr(), ldx, n, d, centre.data_ptr(), dist.data_ptr(), 1 if first else 0, _stream()), "gs_kmeans_mindist")
+        return dist
 
     def limit(self, x, pre_gain, ceiling, lookahead, want_pcm=False, envelope=None):
         """gs_limit (include/gansynth_hip.h): the look-ahead limiter on x -- [n] or [rows, n] fp32 on the device, rows 1 or 2, any row

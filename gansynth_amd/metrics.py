@@ -1,6 +1,7 @@
 """GANSynth's sample-quality metrics on host arrays (float64), with the reference's semantics (metrics.py:6-63):
 softmax, KL divergence, inception score, Frechet distance between two feature sets, the two-proportion z-test and the number of
-statistically different bins (NDB) of a k-means partition of the real features."""
+statistically different bins (NDB) of a k-means partition of the real features.  num_different_bins_device is NDB with the partition made on
+the device (kmeans.py: this project's own clustering rules, no scikit-learn), beside the Jensen-Shannon divergence of the bin proportions."""
 import numpy as np
 import scipy.linalg
 import scipy.stats
@@ -63,4 +64,30 @@ def num_different_bins(real_features, fake_features, num_bins=50, significance_l
     d = (fake ** 2).sum(axis=1, keepdims=True) - 2.0 * fake @ c.T + (c ** 2).sum(axis=1)[None, :]
     fake_counts = np.bincount(np.argmin(d, axis=1), minlength=num_bins)
     fake_prop = fake_counts / fake_counts.sum()
+    return int(np.count_nonzero(binomial_proportion_test(real_prop, len(real), fake_prop, len(fake), significance_level)))
+
+
+def jensen_shannon_divergence(p, q, axis=-1):
+    """(KL(p || m) + KL(q || m)) / 2 with m = (p + q) / 2, in nats and float64: 0 for identical, ln 2 for disjoint distributions.  A bin that is
+    zero in p (or q) contributes nothing to its term, as in kl_divergence; m is zero only where both are."""
+    p, q = np.asarray(p, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    m = 0.5 * (p + q)
+    return 0.5 * kl_divergence(p, m, axis=axis) + 0.5 * kl_divergence(q, m, axis=axis)
+
+
+def num_different_bins_device(real_features, fake_features, num_bins=50, significance_level=0.05, seed=0, n_init=10, details=None):
+    """NDB without scikit-learn: kmeans.kmeans (this project's own, stated rules; HIP kernels) on the real features, whose labels give the real
+    counts; one kmeans_assign of the fake features to its centres gives the fake counts; then binomial_proportion_test as in num_different_bins.
+    `details` (a dict) receives real_counts, fake_counts, inertia and jsd, the Jensen-Shannon divergence of the two bin proportions."""
+    from . import kernels, kmeans
+    real, fake = kmeans.to_device(real_features, "real_features"), kmeans.to_device(fake_features, "fake_features")
+    if real.shape[1] != fake.shape[1]:
+        raise ValueError(f"num_different_bins_device: real and fake features differ in width ({real.shape[1]} and {fake.shape[1]})")
+    result = kmeans.kmeans(real, num_bins, seed=seed, n_init=n_init)
+    real_counts = np.asarray(result.counts, dtype=np.int64)
+    fake_labels = kernels.kmeans_assign(fake.to(real.device), result.centres, want_dist=False)[0]
+    fake_counts = np.bincount(fake_labels.cpu().numpy(), minlength=num_bins).astype(np.int64)
+    real_prop, fake_prop = real_counts / real_counts.sum(), fake_counts / fake_counts.sum()
+    if details is not None:
+        details.update(real_counts=real_counts, fake_counts=fake_counts, inertia=result.inertia, jsd=float(jensen_shannon_divergence(real_prop, fake_prop)))
     return int(np.count_nonzero(binomial_proportion_test(real_prop, len(real), fake_prop, len(fake), significance_level)))

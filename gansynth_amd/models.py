@@ -1134,7 +1134,7 @@ class GANSynth(Iterations, DataParallel, Capture):
 
     # ------------------------------------------------------------------------------------------- evaluation
     def evaluate(self, model_dir, config, classifier, input_name="images:0", output_names=("features:0", "logits:0"), batch_size=64,
-                 extra_metrics=False, classifier_dtype=torch.float32, features_out=None, weights="live"):
+                 extra_metrics=False, classifier_dtype=torch.float32, features_out=None, weights="live", ndb="sklearn"):
         """models.py:196-230: the Frechet distance between the pitch classifier's features of real and generated spectrograms.
 
         Restores the latest checkpoint of `model_dir` as `generate` does, then for every batch of `real_input_fn()` until it runs dry:
@@ -1146,10 +1146,14 @@ class GANSynth(Iterations, DataParallel, Capture):
         `extra_metrics` also the inception score of the fake logits, the pitch accuracy of their argmax against the conditioning labels
         and, when scikit-learn imports, the number of statistically different bins.  `features_out` (a dict): receives the host arrays
         real_features, fake_features, real_logits, fake_logits, labels.  `weights`: "live" or "average", as for `generate` -- the fake side
-        comes from the averaged generator, swapped in behind the restore and out again at the end.  One process only."""
+        comes from the averaged generator, swapped in behind the restore and out again at the end.  `ndb` (read with `extra_metrics`):
+        "sklearn" as above; "device": num_different_bins and bin_jsd (the Jensen-Shannon divergence of the bin proportions) from
+        metrics.num_different_bins_device -- k-means on HIP kernels, no scikit-learn.  One process only."""
         import numpy as np
         from . import metrics, networks
         del config
+        if ndb not in ("sklearn", "device"):
+            raise ValueError(f"evaluate: ndb must be 'sklearn' or 'device' (got {ndb!r})")
         if self.world > 1:
             raise RuntimeError("GANSynth.evaluate runs in one process: launch it without torch.distributed (world size 1)")
         if input_name != "images:0" or list(output_names) != ["features:0", "logits:0"]:
@@ -1208,10 +1212,15 @@ class GANSynth(Iterations, DataParallel, Capture):
         if extra_metrics:
             out["inception_score"] = metrics.inception_score(fake_l)
             out["pitch_accuracy"] = float(np.mean(np.argmax(fake_l, axis=1) == np.argmax(labs, axis=1)))
-            try:
-                out["num_different_bins"] = metrics.num_different_bins(real_f, fake_f, random_state=0)
-            except ImportError:
-                pass
+            if ndb == "device":
+                details = {}
+                out["num_different_bins"] = metrics.num_different_bins_device(real_f, fake_f, details=details)
+                out["bin_jsd"] = details["jsd"]
+            else:
+                try:
+                    out["num_different_bins"] = metrics.num_different_bins(real_f, fake_f, random_state=0)
+                except ImportError:
+                    pass
         return out
 
 

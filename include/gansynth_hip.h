@@ -1092,6 +1092,49 @@ size_t gs_loudness_workspace_bytes(const GsLoudness* d, int rows, int64_t n);
 int gs_loudness(const GsLoudness* d, const float* x, int rows, int64_t n, int64_t row_stride, float* energy, int64_t energy_stride, void* ws,
                 size_t ws_bytes, void* stream);
 
+/* ---- k-means for the NDB metric (gansynth_amd/kmeans.py, metrics.num_different_bins_device; DESIGN.md "NDB on the device") ----
+ * fp32, deterministic (fixed-order sums, no float atomics): two calls with the same arguments write the same bits.  x is [n, d] with its rows
+ * ldx >= d floats apart, 4-byte aligned; centres is [k, d] dense.  Inputs are finite.
+ *
+ * gs_kmeans_assign: labels[i] = the centre nearest to row i in the squared Euclidean distance, sum over the columns in ascending order of
+ * (x - c)^2 on the vector ALU (never |x|^2 - 2 x.c + |c|^2: that form cancels on features with a common offset); ties to the lowest centre
+ * index.  dist ([n], the minimum), changed ([1] int32: labels is read before it is written, and the rows whose label moved are counted) and
+ * inertia ([1] double: the sum of those fp32 minima, accumulated in double in a fixed order) may each be NULL.  One launch over tiles of GS_KMEANS_TILE rows, and
+ * a one-block fold of the tiles' partial sums when changed or inertia is asked for.
+ *
+ * gs_kmeans_inertia: inertia ([1] double) = the sum over the rows of |x_i - centres[labels[i]]|^2 with every term and every sum in double, in
+ * a fixed order: the figure kmeans.py chooses between runs by (two runs that end within fp32 rounding of each other are not told apart by the
+ * sum of fp32 minima).  One read of x: a launch over the same tiles and the same one-block fold.  A row whose label is outside [0, k) adds
+ * nothing.
+ *
+ * gs_kmeans_update: counts[k] (int32) = the rows of every label, and for every label with rows the mean of them into its row of centres; the
+ * centre of an empty label is not written.  A row whose label is outside [0, k) is ignored.  A block of one wave owns a slice of rows and 64
+ * columns and adds row after row, in order, into its own [k, 64] slab; the slabs go to ws and a second launch folds them in slice order.
+ *
+ * gs_kmeans_mindist (the k-means++ step): dist[i] = |x_i - centre|^2 when first != 0, else min(dist[i], |x_i - centre|^2); centre is d floats
+ * on the device (it may be a row of x).
+ *
+ * gs_kmeans_workspace_bytes (host arithmetic; 0 for a shape the entries refuse) covers both launches:
+ *   max(12 * ceil(n / GS_KMEANS_TILE),  4 * slices * k * (d + 1)),  rounded up to 16, with
+ *   slices = ceil(n / ceil(n / s0)),  s0 = max(1, min(GS_KMEANS_MAX_SLICES, 2048 / ceil(d / 64), ceil(n / 64))).
+ * ws is 16-byte aligned.  Capture-safe: no allocation, no synchronisation.
+ * GS_ERR_ARG with a message that names the argument and without a launch: k outside [1, GS_KMEANS_MAX_K], d outside [1, GS_KMEANS_MAX_D] (update
+ * puts ceil(d / 64) into a grid dimension), n < 1 (or > GS_KMEANS_MAX_N),
+ * ldx < d, a NULL or misaligned pointer, a workspace that is too small. */
+#define GS_KMEANS_MAX_K 256
+#define GS_KMEANS_MAX_D (1 << 20)
+#define GS_KMEANS_TILE 256
+#define GS_KMEANS_MAX_SLICES 512
+#define GS_KMEANS_MAX_N ((int64_t)0x7fffffff)
+size_t gs_kmeans_workspace_bytes(int64_t n, int d, int k);
+int gs_kmeans_assign(const float* x, int64_t ldx, int64_t n, int d, const float* centres, int k, int32_t* labels, float* dist, int32_t* changed,
+                     double* inertia, void* ws, size_t ws_bytes, void* stream);
+int gs_kmeans_inertia(const float* x, int64_t ldx, int64_t n, int d, const float* centres, int k, const int32_t* labels, double* inertia, void* ws,
+                      size_t ws_bytes, void* stream);
+int gs_kmeans_update(const float* x, int64_t ldx, int64_t n, int d, const int32_t* labels, int k, float* centres, int32_t* counts, void* ws,
+                     size_t ws_bytes, void* stream);
+int gs_kmeans_mindist(const float* x, int64_t ldx, int64_t n, int d, const float* centre, float* dist, int first, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
