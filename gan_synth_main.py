@@ -18,6 +18,13 @@ num_different_bins and bin_jsd, the k-means of NDB on HIP kernels (gansynth_amd/
 
     python gan_synth_main.py --evaluate --ndb --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
 
+`--swd` (not in the reference's driver) adds sliced_wasserstein_distance and sliced_wasserstein_distance_levels, the metric of the
+progressive-GAN paper on HIP kernels (gansynth_amd/swd.py, DESIGN.md "SWD on the device"); it needs no classifier, and with
+`--classifier none` none is loaded and these are the only figures:
+
+    python gan_synth_main.py --evaluate --swd --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
+    python gan_synth_main.py --evaluate --swd --classifier none --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord'
+
 `--synthesize` (not in the reference) renders a score -- a Standard MIDI File or a JSON list of {"pitch", "velocity", "start", "end"}
 notes -- into one 16 kHz 16-bit WAV: every note generated at its pitch, the timbre gliding between latent anchors, the mixdown on the
 device (GANSynth.synthesize).  It needs no dataset:
@@ -111,6 +118,9 @@ parser.add_argument("--synthetic", action="store_true", help="generated notes in
 parser.add_argument("--ndb", action="store_true",
                     help="--evaluate: also the inception score, the pitch accuracy and the number of statistically different bins (NDB) with the "
                          "Jensen-Shannon divergence of the bin proportions, the k-means on the device (no scikit-learn)")
+parser.add_argument("--swd", action="store_true",
+                    help="--evaluate: also the sliced Wasserstein distance between Laplacian-pyramid patches of the real and generated images, one "
+                         "figure a pyramid level and their mean, on the device; with --classifier none these are the only figures")
 parser.add_argument("--dtype", choices=["f32", "bf16"], default="bf16", help="activation storage (master weights / Adam stay fp32)")
 parser.add_argument("--save_checkpoint_steps", type=int, default=1000)
 parser.add_argument("--log_tensor_steps", type=int, default=100)
@@ -445,17 +455,21 @@ def main(args):
             raise SystemExit("--evaluate runs in one process: launch it without torch.distributed")
         if args.synthetic and args.num_generate_batches is None:
             raise SystemExit("--evaluate --synthetic needs --num_generate_batches (synthetic input never ends)")
+        no_classifier = args.classifier.lower() == "none"
+        if no_classifier and not args.swd:
+            raise SystemExit("--evaluate --classifier none needs --swd (every other figure comes from the pitch classifier)")
         kept = model.real_input_fn   # evaluate runs over an input of its own: --generate after it still has its batches
         model.real_input_fn = real_input_fn_factory(False)
         try:
             print(model.evaluate(
                 model_dir=args.model_dir,
                 config=None,
-                classifier=args.classifier,    # the frozen pitch-classifier GraphDef (.pb), or its weights as .safetensors
+                classifier=None if no_classifier else args.classifier,    # the frozen pitch-classifier GraphDef (.pb), or its weights as .safetensors
                 input_name="images:0",
                 output_names=["features:0", "logits:0"],
                 weights=args.weights,
-                **(dict(extra_metrics=True, ndb="device") if args.ndb else {})))   # (without the flag the call is the one it was)
+                **(dict(extra_metrics=True, ndb="device") if args.ndb else {}),     # (without the flags the call is the one it was)
+                **(dict(swd=True) if args.swd else {})))
         finally:
             model.real_input_fn = kept
 

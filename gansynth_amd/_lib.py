@@ -74,7 +74,9 @@ LIMIT_MAX_LOOKAHEAD = 2048                                        # GS_LIMIT_MAX
 LIMIT_TILE = 4096                                                 # GS_LIMIT_TILE: samples per block of gs_limit
 TRUE_PEAK_TILE, TRUE_PEAK_TAPS, TRUE_PEAK_OVERSAMPLE = 2048, 68, 4   # GS_TRUE_PEAK_TILE, GS_TRUE_PEAK_TAPS, GS_TRUE_PEAK_OVERSAMPLE
 KMEANS_MAX_K, KMEANS_TILE, KMEANS_MAX_SLICES, KMEANS_MAX_N, KMEANS_MAX_D = 256, 256, 512, 2 ** 31 - 1, 1 << 20   # GS_KMEANS_MAX_K, _TILE, _MAX_SLICES, _MAX_N, _MAX_D
-LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 192000               # GS_LOUDNESS_MIN_RATE, GS_LOUDNESS_MAX_RATE
+SWD_DESC, SWD_PATCHES, SWD_SORT_TILE, SWD_MAX_N, SWD_MAX_ROWS, SWD_MAX_SIDE, SWD_MAX_BATCH = 98, 128, 4096, 1 << 21, 65535, 16384, 65536   # GS_SWD_*
+SWD_STAGE_PYRAMID, SWD_STAGE_MOMENTS, SWD_STAGE_SORT, SWD_STAGE_L1 = range(4)   # GS_SWD_STAGE_*
+LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 192000              # GS_LOUDNESS_MIN_RATE, GS_LOUDNESS_MAX_RATE
 LOUDNESS_STEPS = 8                                                # GS_LOUDNESS_STEPS: matrix powers per scan of gs_loudness
 
 
@@ -248,6 +250,14 @@ SIGNATURES = {
     "gs_kmeans_inertia": (I, [P, L, L, I, P, I, P, P, P, Z, P]),
     "gs_kmeans_update": (I, [P, L, L, I, P, I, P, P, P, Z, P]),
     "gs_kmeans_mindist": (I, [P, L, L, I, P, P, I, P]),
+    "gs_swd_levels": (I, [I, I]),
+    "gs_swd_workspace_bytes": (Z, [I, L, L, L]),
+    "gs_swd_pyramid": (I, [P, I, L, I, I, P, P, Z, P]),
+    "gs_swd_patches": (I, [P, L, I, I, P, P, P, L, L, P]),
+    "gs_swd_moments": (I, [P, L, P, P, Z, P]),
+    "gs_swd_project": (I, [P, L, P, P, I, P, P]),
+    "gs_swd_sort": (I, [P, L, L, P, Z, P]),
+    "gs_swd_l1": (I, [P, P, L, L, P, P, Z, P]),
     # W = POINTER(GsLoudness), the meter of one rate
     "gs_loudness_design": (I, [I, W]),
     "gs_loudness_hops": (L, [W, L]),

@@ -487,6 +487,111 @@ def kmeans_mindist(x, centre, dist=None):
     return get().kmeans_mindist(x, centre, dist=dist)
 
 
+def swd_levels(h, w):
+    """gs_swd_levels restated on the host: the number of l >= 0 with min(h, w) >> l >= 16; 0 when there is none, when a size that is halved on
+    the way down is odd or when a side exceeds SWD_MAX_SIDE."""
+    h, w = int(h), int(w)
+    if min(h, w) < 16 or max(h, w) > _lib.SWD_MAX_SIDE:
+        return 0
+    levels = 0
+    while min(h, w) >= 16:
+        levels += 1
+        if min(h, w) // 2 < 16:
+            break
+        if (h | w) & 1:
+            return 0
+        h, w = h // 2, w // 2
+    return levels if h >= 7 and w >= 7 else 0
+
+
+def _swd_tensor(what, name, t, dims, dtypes=(torch.float32,)):
+    if not isinstance(t, torch.Tensor) or t.dim() != dims or t.dtype not in dtypes or t.numel() == 0:
+        got = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+        names = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise ValueError(f"{what}: {name} must be a non-empty {names} tensor of {dims} dimensions (got {got})")
+
+
+def swd_pyramid_shapes(images):
+    """The host side of swd_pyramid: -> (b, h, w, levels) of images [b, 2, h, w] (fp32 or bf16).  ValueError; needs no device."""
+    _swd_tensor("swd_pyramid", "images", images, 4, (torch.float32, torch.bfloat16))
+    b, c, h, w = (int(s) for s in images.shape)
+    if c != 2:
+        raise ValueError(f"swd_pyramid: images must have 2 channels (got {c})")
+    if b > _lib.SWD_MAX_BATCH:
+        raise ValueError(f"swd_pyramid: images must hold at most {_lib.SWD_MAX_BATCH} images a call (got {b})")
+    levels = swd_levels(h, w)
+    if levels == 0:
+        raise ValueError(f"swd_pyramid: images of {h} x {w} have no level (both sides at least 16 and at most {_lib.SWD_MAX_SIDE}, every halved size even)")
+    return b, h, w, levels
+
+
+def swd_pyramid(images):
+    """HipKernels.swd_pyramid of the process-wide kernel object; the shape is refused here, before a device is asked for."""
+    swd_pyramid_shapes(images)
+    return get().swd_pyramid(images)
+
+
+def swd_patches_shapes(level, ys, xs, desc, row_offset):
+    """The host side of swd_patches: -> (b, h, w) of level [b, h, w, 2] (fp32, contiguous); ys, xs contiguous int32 vectors of b * 128; desc a
+    contiguous fp32 [rows, 98] matrix that holds rows row_offset .. row_offset + b * 128.  ValueError; needs no device."""
+    _swd_tensor("swd_patches", "level", level, 4)
+    b, h, w, c = (int(s) for s in level.shape)
+    if c != 2 or not level.is_contiguous() or h < 7 or w < 7:
+        raise ValueError(f"swd_patches: level must be a contiguous [b, h, w, 2] tensor of at least 7 x 7 (got {tuple(level.shape)})")
+    for name, t in (("ys", ys), ("xs", xs)):
+        _kmeans_vector("swd_patches", name, t, b * _lib.SWD_PATCHES, torch.int32)
+    _swd_tensor("swd_patches", "desc", desc, 2)
+    if desc.shape[1] != _lib.SWD_DESC or not desc.is_contiguous() or desc.shape[0] > _lib.SWD_MAX_N:
+        raise ValueError(f"swd_patches: desc must be a contiguous [rows, {_lib.SWD_DESC}] matrix of at most {_lib.SWD_MAX_N} rows (got {tuple(desc.shape)})")
+    if not 0 <= row_offset <= desc.shape[0] - b * _lib.SWD_PATCHES:
+        raise ValueError(f"swd_patches: rows {row_offset} .. {row_offset + b * _lib.SWD_PATCHES} do not lie inside desc of {desc.shape[0]} rows")
+    return b, h, w
+
+
+def swd_desc_shapes(what, desc):
+    """desc of swd_moments / swd_project: -> its rows; a contiguous fp32 [rows, 98] matrix of at most SWD_MAX_N rows.  ValueError; needs no device."""
+    _swd_tensor(what, "desc", desc, 2)
+    if desc.shape[1] != _lib.SWD_DESC or not desc.is_contiguous() or desc.shape[0] > _lib.SWD_MAX_N:
+        raise ValueError(f"{what}: desc must be a contiguous [rows, {_lib.SWD_DESC}] matrix of at most {_lib.SWD_MAX_N} rows (got {tuple(desc.shape)})")
+    return int(desc.shape[0])
+
+
+def swd_project_shapes(desc, moments, dirs):
+    """The host side of swd_project: -> (n, ndir) of desc [n, 98], moments (float64 [8], swd_moments's result) and dirs [98, ndir] (fp32,
+    contiguous, ndir <= SWD_MAX_ROWS).  ValueError; needs no device."""
+    n = swd_desc_shapes("swd_project", desc)
+    if not isinstance(moments, torch.Tensor) or moments.dtype != torch.float64 or tuple(moments.shape) != (8,) or not moments.is_contiguous():
+        raise ValueError("swd_project: moments must be the contiguous float64 vector of 8 that swd_moments returns")
+    _swd_tensor("swd_project", "dirs", dirs, 2)
+    if dirs.shape[0] != _lib.SWD_DESC or not dirs.is_contiguous() or dirs.shape[1] > _lib.SWD_MAX_ROWS:
+        raise ValueError(f"swd_project: dirs must be a contiguous [{_lib.SWD_DESC}, directions] matrix of at most {_lib.SWD_MAX_ROWS} directions (got {tuple(dirs.shape)})")
+    return n, int(dirs.shape[1])
+
+
+def swd_rows_shapes(what, name, t):
+    """data of swd_sort, a and b of swd_l1: -> (rows, n) of a contiguous fp32 [rows, n] matrix, rows <= SWD_MAX_ROWS, n <= SWD_MAX_N."""
+    _swd_tensor(what, name, t, 2)
+    rows, n = int(t.shape[0]), int(t.shape[1])
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous (it is read and written as dense rows)")
+    if rows > _lib.SWD_MAX_ROWS or n > _lib.SWD_MAX_N:
+        raise ValueError(f"{what}: {name} must have at most {_lib.SWD_MAX_ROWS} rows of at most {_lib.SWD_MAX_N} values (got {rows} x {n})")
+    return rows, n
+
+
+def swd_sort(data):
+    """HipKernels.swd_sort of the process-wide kernel object; the shape is refused here, before a device is asked for."""
+    swd_rows_shapes("swd_sort", "data", data)
+    return get().swd_sort(data)
+
+
+def swd_l1(a, b):
+    """HipKernels.swd_l1 of the process-wide kernel object; the shapes are refused here, before a device is asked for."""
+    if swd_rows_shapes("swd_l1", "a", a) != swd_rows_shapes("swd_l1", "b", b):
+        raise ValueError(f"swd_l1: a and b differ in shape ({tuple(a.shape)} and {tuple(b.shape)})")
+    return get().swd_l1(a, b)
+
+
 def loudness_shapes(x, rate):
     """The host side of loudness_energy: -> (rows, n) of x ([n] or [rows, n] fp32, rows 1 or 2); rate an integer number of samples per second
     in [LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE].  ValueError by argument name; needs no device."""
@@ -2122,6 +2227,77 @@ class HipKernels(object):
             dist = torch.empty((n,), dtype=torch.float32, device=x.device)
         _lib.check(self.lib.gs_kmeans_mindist(x2.data_ptr(), ldx, n, d, centre.data_ptr(), dist.data_ptr(), 1 if first else 0, _stream()), "gs_kmeans_mindist")
         return dist
+
+    @staticmethod
+    def _swd_device(what, first, *others):
+        if not first[1].is_cuda:
+            raise ValueError(f"{what}: {first[0]} must be on the HIP device (it is on {first[1].device})")
+        for name, t in others:
+            if t.device != first[1].device:
+                raise ValueError(f"{what}: {name} is on {t.device}, {first[0]} on {first[1].device}")
+
+    def swd_pyramid(self, images):
+        """gs_swd_pyramid (include/gansynth_hip.h): the Laplacian pyramid of images [b, 2, h, w] (fp32 or bf16 on the device; made channels-last
+        when they are not) -> a list of its L levels, finest first, as fp32 [b, h >> l, w >> l, 2] views of one buffer."""
+        b, h, w, levels = swd_pyramid_shapes(images)
+        self._swd_device("swd_pyramid", ("images", images))
+        x = _act(images)
+        sizes = [b * (h >> l) * (w >> l) * 2 for l in range(levels)]
+        lap = torch.empty((sum(sizes),), dtype=torch.float32, device=x.device)
+        ws = _ws(self.lib.gs_swd_workspace_bytes(_lib.SWD_STAGE_PYRAMID, b, h, w), x.device)
+        _lib.check(self.lib.gs_swd_pyramid(x.data_ptr(), _dt(x), b, h, w, lap.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_swd_pyramid")
+        out, at = [], 0
+        for l, size in enumerate(sizes):
+            out.append(lap[at:at + size].view(b, h >> l, w >> l, 2))
+            at += size
+        return out
+
+    def swd_patches(self, level, ys, xs, desc, row_offset=0):
+        """gs_swd_patches (include/gansynth_hip.h): the 128 7 x 7 patches an image of level [b, h, w, 2] at the corners ys, xs (int32 [b * 128] on
+        the device) into the rows row_offset .. of desc [rows, 98], in place.  -> desc."""
+        b, h, w = swd_patches_shapes(level, ys, xs, desc, row_offset)
+        self._swd_device("swd_patches", ("level", level), ("ys", ys), ("xs", xs), ("desc", desc))
+        _lib.check(self.lib.gs_swd_patches(level.data_ptr(), b, h, w, ys.data_ptr(), xs.data_ptr(), desc.data_ptr(), int(desc.shape[0]), int(row_offset),
+                                           _stream()), "gs_swd_patches")
+        return desc
+
+    def swd_moments(self, desc):
+        """gs_swd_moments (include/gansynth_hip.h): -> float64 [8]: the sum, the sum of squares, the mean and the population standard deviation
+        of channel 0 (columns 0 .. 48 of desc [rows, 98]), then of channel 1."""
+        rows = swd_desc_shapes("swd_moments", desc)
+        self._swd_device("swd_moments", ("desc", desc))
+        out = torch.empty((8,), dtype=torch.float64, device=desc.device)
+        ws = _ws(self.lib.gs_swd_workspace_bytes(_lib.SWD_STAGE_MOMENTS, rows, 0, 0), desc.device)
+        _lib.check(self.lib.gs_swd_moments(desc.data_ptr(), rows, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_swd_moments")
+        return out
+
+    def swd_project(self, desc, moments, dirs):
+        """gs_swd_project (include/gansynth_hip.h): desc [n, 98] normalised by `moments` (swd_moments's result) times dirs [98, ndir] -> fp32
+        [ndir, n]: every direction's n values are contiguous."""
+        n, ndir = swd_project_shapes(desc, moments, dirs)
+        self._swd_device("swd_project", ("desc", desc), ("moments", moments), ("dirs", dirs))
+        out = torch.empty((ndir, n), dtype=torch.float32, device=desc.device)
+        _lib.check(self.lib.gs_swd_project(desc.data_ptr(), n, moments.data_ptr(), dirs.data_ptr(), ndir, out.data_ptr(), _stream()), "gs_swd_project")
+        return out
+
+    def swd_sort(self, data):
+        """gs_swd_sort (include/gansynth_hip.h): every row of data [rows, n] (fp32, contiguous, on the device) ascending, in place.  -> data."""
+        rows, n = swd_rows_shapes("swd_sort", "data", data)
+        self._swd_device("swd_sort", ("data", data))
+        ws = _ws(self.lib.gs_swd_workspace_bytes(_lib.SWD_STAGE_SORT, rows, n, 0), data.device)
+        _lib.check(self.lib.gs_swd_sort(data.data_ptr(), rows, n, ws.data_ptr(), ws.numel(), _stream()), "gs_swd_sort")
+        return data
+
+    def swd_l1(self, a, b):
+        """gs_swd_l1 (include/gansynth_hip.h): -> float64 [1], the sum of |a - b| over two [rows, n] buffers, in double and in a fixed order."""
+        rows, n = swd_rows_shapes("swd_l1", "a", a)
+        if (rows, n) != swd_rows_shapes("swd_l1", "b", b):
+            raise ValueError(f"swd_l1: a and b differ in shape ({tuple(a.shape)} and {tuple(b.shape)})")
+        self._swd_device("swd_l1", ("a", a), ("b", b))
+        out = torch.empty((1,), dtype=torch.float64, device=a.device)
+        ws = _ws(self.lib.gs_swd_workspace_bytes(_lib.SWD_STAGE_L1, rows, n, 0), a.device)
+        _lib.check(self.lib.gs_swd_l1(a.data_ptr(), b.data_ptr(), rows, n, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_swd_l1")
+        return out
 
     def limit(self, x, pre_gain, ceiling, lookahead, want_pcm=False, envelope=None):
         """gs_limit (include/gansynth_hip.h): the look-ahead limiter on x -- [n] or [rows, n] fp32 on the device, rows 1 or 2, any row

@@ -91,3 +91,34 @@ def num_different_bins_device(real_features, fake_features, num_bins=50, signifi
     if details is not None:
         details.update(real_counts=real_counts, fake_counts=fake_counts, inertia=result.inertia, jsd=float(jensen_shannon_divergence(real_prop, fake_prop)))
     return int(np.count_nonzero(binomial_proportion_test(real_prop, len(real), fake_prop, len(fake), significance_level)))
+
+
+def sliced_wasserstein_distance_device(real_images, fake_images, seed=0, details=None, batch_size=None):
+    """The sliced Wasserstein distance between Laplacian-pyramid patches of two image sets [n, 2, h, w] (tensors or arrays, fp32 or bf16; the
+    same n): swd.SlicedWasserstein (this project's own, stated rules; HIP kernels, no classifier) -> the mean over the levels of
+    1e3 * mean |sort(A) - sort(B)|.  `details` (a dict) receives levels (one float a level, finest first), sizes ("HxW" a level) and n.
+    `batch_size`: the sets are added that many images at a time, in order -- the corner draws follow the batches, so this reproduces an
+    accumulator that was fed the same batches; None: all at once."""
+    import torch
+    from . import kernels, swd
+    sets = []
+    for name, images in (("real_images", real_images), ("fake_images", fake_images)):
+        t = images if isinstance(images, torch.Tensor) else torch.from_numpy(np.array(images))   # (a copy: torch does not wrap a read-only array quietly)
+        if t.dim() != 4 or t.shape[0] == 0:
+            raise ValueError(f"sliced_wasserstein_distance_device: {name} must be a non-empty [n, 2, h, w] set (got {tuple(t.shape)})")
+        sets.append(t)
+    if sets[0].shape != sets[1].shape:
+        raise ValueError(f"sliced_wasserstein_distance_device: the sets differ in shape ({tuple(sets[0].shape)} and {tuple(sets[1].shape)})")
+    acc = swd.SlicedWasserstein(sets[0].shape, seed=seed)
+    n = sets[0].shape[0]
+    step = n if batch_size is None else int(batch_size)
+    if step < 1:
+        raise ValueError(f"sliced_wasserstein_distance_device: batch_size must be positive (got {batch_size})")
+    on_hip = isinstance(kernels.get(), kernels.HipKernels)   # (a host without a device fails here, with the library's message)
+    device = torch.device("cuda") if on_hip and not sets[0].is_cuda else sets[0].device
+    for at in range(0, n, step):
+        acc.add(*(t[at:at + step].to(device) for t in sets))
+    out = acc.result()
+    if details is not None:
+        details.update(levels=out["levels"], sizes=out["sizes"], n=out["n"])
+    return out["mean"]

@@ -1134,7 +1134,7 @@ class GANSynth(Iterations, DataParallel, Capture):
 
     # ------------------------------------------------------------------------------------------- evaluation
     def evaluate(self, model_dir, config, classifier, input_name="images:0", output_names=("features:0", "logits:0"), batch_size=64,
-                 extra_metrics=False, classifier_dtype=torch.float32, features_out=None, weights="live", ndb="sklearn"):
+                 extra_metrics=False, classifier_dtype=torch.float32, features_out=None, weights="live", ndb="sklearn", swd=False, swd_seed=0):
         """models.py:196-230: the Frechet distance between the pitch classifier's features of real and generated spectrograms.
 
         Restores the latest checkpoint of `model_dir` as `generate` does, then for every batch of `real_input_fn()` until it runs dry:
@@ -1148,7 +1148,11 @@ class GANSynth(Iterations, DataParallel, Capture):
         real_features, fake_features, real_logits, fake_logits, labels.  `weights`: "live" or "average", as for `generate` -- the fake side
         comes from the averaged generator, swapped in behind the restore and out again at the end.  `ndb` (read with `extra_metrics`):
         "sklearn" as above; "device": num_different_bins and bin_jsd (the Jensen-Shannon divergence of the bin proportions) from
-        metrics.num_different_bins_device -- k-means on HIP kernels, no scikit-learn.  One process only."""
+        metrics.num_different_bins_device -- k-means on HIP kernels, no scikit-learn.  `swd`: the dict gains sliced_wasserstein_distance (the
+        mean over the levels) and sliced_wasserstein_distance_levels (a list, finest first; features_out receives their sizes as swd_sizes,
+        "HxW" a level): the sliced Wasserstein distance between Laplacian-pyramid patches of the same real and fake images (swd.py: HIP
+        kernels, corners and directions seeded by `swd_seed`), every batch added as it arrives -- the images are not kept.  `classifier` may
+        be None together with `swd`: no classifier is loaded or run and only the two SWD keys come back.  One process only."""
         import numpy as np
         from . import metrics, networks
         del config
@@ -1159,10 +1163,15 @@ class GANSynth(Iterations, DataParallel, Capture):
         if input_name != "images:0" or list(output_names) != ["features:0", "logits:0"]:
             raise ValueError(f"evaluate: the classifier graph's tensors are 'images:0' -> ['features:0', 'logits:0'] "
                              f"(got {input_name!r} -> {list(output_names)!r})")
-        if isinstance(classifier, networks.ResNet):
+        if classifier is None:
+            if not swd:
+                raise ValueError("evaluate: classifier=None needs swd=True (every other figure comes from the pitch classifier)")
+            resnet = None
+        elif isinstance(classifier, networks.ResNet):
             resnet = classifier
         else:
             resnet = networks.ResNet.pitch_classifier().load(classifier)
+        sliced = None
         real_f, fake_f, real_l, fake_l, labs = [], [], [], [], []
         pending = {"real": [], "fake": []}
 
@@ -1195,15 +1204,30 @@ class GANSynth(Iterations, DataParallel, Capture):
                 with torch.no_grad():
                     real = spectral_ops.convert_to_images(data, **self.spectral_params, dtype=self.dtype) if data.dim() == 2 else data
                     fake = self.generator(latents.to(self.dtype), labels.to(self.dtype))
+                if swd:
+                    if sliced is None:
+                        from . import swd as swd_module
+                        sliced = swd_module.SlicedWasserstein(real.shape, seed=swd_seed)
+                    sliced.add(real, fake)
+                if resnet is None:
+                    continue
                 pending["real"].append(real)
                 pending["fake"].append(fake)
                 labs.append(labels.float().cpu().numpy())
                 flush("real")
                 flush("fake")
+        if not restored:
+            raise ValueError("evaluate: real_input_fn() gave no batch")
+        sliced_out = {}
+        if swd:
+            result = sliced.result()
+            sliced_out = dict(sliced_wasserstein_distance=result["mean"], sliced_wasserstein_distance_levels=result["levels"])
+            if features_out is not None:
+                features_out.update(swd_sizes=result["sizes"])
+        if resnet is None:
+            return sliced_out
         flush("real", True)
         flush("fake", True)
-        if not real_f:
-            raise ValueError("evaluate: real_input_fn() gave no batch")
         real_f, fake_f = np.concatenate(real_f), np.concatenate(fake_f)
         real_l, fake_l, labs = np.concatenate(real_l), np.concatenate(fake_l), np.concatenate(labs)
         if features_out is not None:
@@ -1221,6 +1245,7 @@ class GANSynth(Iterations, DataParallel, Capture):
                     out["num_different_bins"] = metrics.num_different_bins(real_f, fake_f, random_state=0)
                 except ImportError:
                     pass
+        out.update(sliced_out)
         return out
 
 

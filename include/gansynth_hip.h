@@ -1135,6 +1135,61 @@ int gs_kmeans_update(const float* x, int64_t ldx, int64_t n, int d, const int32_
                      size_t ws_bytes, void* stream);
 int gs_kmeans_mindist(const float* x, int64_t ldx, int64_t n, int d, const float* centre, float* dist, int first, void* stream);
 
+/* ---- sliced Wasserstein distance of Laplacian-pyramid patches (gansynth_amd/swd.py, metrics.sliced_wasserstein_distance_device; DESIGN.md
+ * "SWD on the device") ----
+ * fp32 values, sums in double, fixed orders, no float atomics: two calls with the same arguments write the same bits.  No sort library.
+ * Images are channels-last [b][h][w][2], fp32 or bf16 (widened exactly at the first read).  Inputs are finite.
+ *
+ * gs_swd_levels (host arithmetic): the number L of l >= 0 with min(h, w) >> l >= 16; 0 (refused) when there is none, when a size that is halved
+ * on the way down is odd, or when a side exceeds GS_SWD_MAX_SIDE.
+ *
+ * gs_swd_pyramid: lap receives the L Laplacian levels of x one after the other, level l as [b][h >> l][w >> l][2] fp32.  G_0 = x; G_{l+1} =
+ * G_l filtered by outer(k, k) / 256, k = [1, 4, 6, 4, 1], at the even rows and columns, the border mirrored without the edge sample;
+ * Lap_l = G_l - up(G_{l+1}) with up = zero stuffing to twice the size and 4 x the same filter under the same border rule; Lap_{L-1} = G_{L-1}.
+ * Every product is exact (dyadic weights); a row of taps is summed left to right, then the row sums top to bottom.  ws holds G_1 .. G_{L-1}.
+ *
+ * gs_swd_patches: desc[row_offset + i * 128 + p][(c * 7 + dy) * 7 + dx] = level[i][ys[i * 128 + p] + dy][xs[i * 128 + p] + dx][c] for the b
+ * images of one level ([b][h][w][2] fp32); ys, xs are int32 on the device, desc is [desc_rows][GS_SWD_DESC].  A corner outside
+ * [0, h - 7] x [0, w - 7] is moved to the nearest one inside.
+ *
+ * gs_swd_moments: out[8] (double) = for channel 0 then channel 1 of desc [rows][GS_SWD_DESC]: the sum, the sum of squares, the mean and the
+ * population standard deviation sqrt(max(0, sumsq / m - mean^2)) of its m = rows * 49 values.  Two launches: the blocks' shares, then their fold
+ * in block order.
+ *
+ * gs_swd_project: out[j][i] = sum over k ascending (fp32 FMA) of a_ik * dirs[k][j], a_ik = (desc[i][k] - mean_c) / std_c with mean and std the
+ * fp32 roundings of moments[2], [3] (k < 49) and moments[6], [7] (k >= 49); dirs is [GS_SWD_DESC][ndir], out [ndir][n]: a direction's n values
+ * are contiguous.
+ *
+ * gs_swd_sort: every one of the `rows` rows of n floats of data (dense) ascending, in place (-0 before +0).  Tiles of GS_SWD_SORT_TILE values
+ * are sorted in LDS, then ceil(log2(ceil(n / GS_SWD_SORT_TILE))) merge passes alternate between data and ws (rows * n floats when
+ * n > GS_SWD_SORT_TILE).  n <= GS_SWD_MAX_N.  NaN is not ordered.
+ *
+ * gs_swd_l1: out[1] (double) = the sum of |a - b| over two dense [rows][n] buffers, differences and sums in double; a == b gives 0.
+ *
+ * gs_swd_workspace_bytes(stage, a, b, c) (host arithmetic; 0 for arguments the entry refuses): GS_SWD_STAGE_PYRAMID (b, h, w),
+ * GS_SWD_STAGE_MOMENTS (rows), GS_SWD_STAGE_SORT (rows, n), GS_SWD_STAGE_L1 (rows, n).  ws is 16-byte aligned.  Capture-safe.
+ * GS_ERR_ARG with a message and without a launch: a shape outside the stated limits, a NULL or misaligned pointer, a workspace that is too small. */
+#define GS_SWD_DESC 98
+#define GS_SWD_PATCHES 128
+#define GS_SWD_SORT_TILE 4096
+#define GS_SWD_MAX_N (1 << 21)
+#define GS_SWD_MAX_ROWS 65535
+#define GS_SWD_MAX_SIDE 16384
+#define GS_SWD_MAX_BATCH 65536
+#define GS_SWD_STAGE_PYRAMID 0
+#define GS_SWD_STAGE_MOMENTS 1
+#define GS_SWD_STAGE_SORT 2
+#define GS_SWD_STAGE_L1 3
+int gs_swd_levels(int h, int w);
+size_t gs_swd_workspace_bytes(int stage, int64_t a, int64_t b, int64_t c);
+int gs_swd_pyramid(const void* x, int dtype, int64_t b, int h, int w, float* lap, void* ws, size_t ws_bytes, void* stream);
+int gs_swd_patches(const float* level, int64_t b, int h, int w, const int32_t* ys, const int32_t* xs, float* desc, int64_t desc_rows, int64_t row_offset,
+                   void* stream);
+int gs_swd_moments(const float* desc, int64_t rows, double* out, void* ws, size_t ws_bytes, void* stream);
+int gs_swd_project(const float* desc, int64_t n, const double* moments, const float* dirs, int ndir, float* out, void* stream);
+int gs_swd_sort(float* data, int64_t rows, int64_t n, void* ws, size_t ws_bytes, void* stream);
+int gs_swd_l1(const float* a, const float* b, int64_t rows, int64_t n, double* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
