@@ -25,6 +25,14 @@ progressive-GAN paper on HIP kernels (gansynth_amd/swd.py, DESIGN.md "SWD on the
     python gan_synth_main.py --evaluate --swd --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
     python gan_synth_main.py --evaluate --swd --classifier none --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord'
 
+`--prd` (not in the reference's driver) adds precision, recall, density and coverage of the generated features against the real ones, which
+tell a generator that makes bad notes (precision, density) from one that makes too few kinds (recall, coverage); `--prd_k` is the neighbour
+that sets a row's radius (default 3).  k-nearest-neighbour radii on HIP kernels (gansynth_amd/manifold.py, DESIGN.md "Precision and recall on
+the device"); the figures come from the classifier's features, so `--classifier none` is refused:
+
+    python gan_synth_main.py --evaluate --prd --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
+    python gan_synth_main.py --evaluate --ndb --prd --prd_k 5 --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
+
 `--synthesize` (not in the reference) renders a score -- a Standard MIDI File or a JSON list of {"pitch", "velocity", "start", "end"}
 notes -- into one 16 kHz 16-bit WAV: every note generated at its pitch, the timbre gliding between latent anchors, the mixdown on the
 device (GANSynth.synthesize).  It needs no dataset:
@@ -121,6 +129,10 @@ parser.add_argument("--ndb", action="store_true",
 parser.add_argument("--swd", action="store_true",
                     help="--evaluate: also the sliced Wasserstein distance between Laplacian-pyramid patches of the real and generated images, one "
                          "figure a pyramid level and their mean, on the device; with --classifier none these are the only figures")
+parser.add_argument("--prd", action="store_true",
+                    help="--evaluate: also precision, recall, density and coverage of the generated features against the real ones, from "
+                         "k-nearest-neighbour radii on the device; needs the classifier")
+parser.add_argument("--prd_k", type=int, default=3, help="--prd: the neighbour whose distance is a row's radius")
 parser.add_argument("--dtype", choices=["f32", "bf16"], default="bf16", help="activation storage (master weights / Adam stay fp32)")
 parser.add_argument("--save_checkpoint_steps", type=int, default=1000)
 parser.add_argument("--log_tensor_steps", type=int, default=100)
@@ -264,6 +276,20 @@ def check_controller_args(args):
     return wanted
 
 
+def check_prd_args(args):
+    """--prd and --prd_k against --evaluate and --classifier: SystemExit with a message.  -> whether the four figures are asked for."""
+    wanted, k = getattr(args, "prd", False), getattr(args, "prd_k", 3)
+    if not wanted and k != 3:
+        raise SystemExit("--prd_k needs --prd")
+    if wanted and not getattr(args, "evaluate", False):
+        raise SystemExit("--prd applies to --evaluate only")
+    if wanted and str(getattr(args, "classifier", "")).lower() == "none":
+        raise SystemExit("--prd needs the pitch classifier (precision, recall, density and coverage come from its features): not --classifier none")
+    if wanted and not 1 <= k <= 8:
+        raise SystemExit(f"--prd_k must be in [1, 8] (got {k})")
+    return wanted
+
+
 def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     """--synthesize: the score args.synthesize through GANSynth.synthesize into the 16-bit WAV args.output (the kernel's own PCM: [T], or
     the interleaved [T, 2] of --stereo, which is a two-channel WAV's layout).  With --reverb / --reverb_ir: the unnormalised clip at the
@@ -380,6 +406,7 @@ def main(args):
     check_loudness_args(args)
     check_controller_args(args)
     check_true_peak_args(args)
+    check_prd_args(args)
     if args.pack_bank is not None:
         pack_bank(args, range(24, 85), [0])
         return
@@ -469,7 +496,8 @@ def main(args):
                 output_names=["features:0", "logits:0"],
                 weights=args.weights,
                 **(dict(extra_metrics=True, ndb="device") if args.ndb else {}),     # (without the flags the call is the one it was)
-                **(dict(swd=True) if args.swd else {})))
+                **(dict(swd=True) if args.swd else {}),
+                **(dict(prd=True, prd_k=args.prd_k) if args.prd else {})))
         finally:
             model.real_input_fn = kept
 

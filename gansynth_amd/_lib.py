@@ -76,6 +76,7 @@ TRUE_PEAK_TILE, TRUE_PEAK_TAPS, TRUE_PEAK_OVERSAMPLE = 2048, 68, 4   # GS_TRUE_P
 KMEANS_MAX_K, KMEANS_TILE, KMEANS_MAX_SLICES, KMEANS_MAX_N, KMEANS_MAX_D = 256, 256, 512, 2 ** 31 - 1, 1 << 20   # GS_KMEANS_MAX_K, _TILE, _MAX_SLICES, _MAX_N, _MAX_D
 SWD_DESC, SWD_PATCHES, SWD_SORT_TILE, SWD_MAX_N, SWD_MAX_ROWS, SWD_MAX_SIDE, SWD_MAX_BATCH = 98, 128, 4096, 1 << 21, 65535, 16384, 65536   # GS_SWD_*
 SWD_STAGE_PYRAMID, SWD_STAGE_MOMENTS, SWD_STAGE_SORT, SWD_STAGE_L1 = range(4)   # GS_SWD_STAGE_*
+KNN_MAX_K, KNN_BLOCKS, KNN_MIN_SLICE_ROWS = 8, 3072, 256   # GS_KNN_MAX_K, _BLOCKS, _MIN_SLICE_ROWS
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 192000              # GS_LOUDNESS_MIN_RATE, GS_LOUDNESS_MAX_RATE
 LOUDNESS_STEPS = 8                                                # GS_LOUDNESS_STEPS: matrix powers per scan of gs_loudness
 
@@ -258,6 +259,10 @@ SIGNATURES = {
     "gs_swd_project": (I, [P, L, P, P, I, P, P]),
     "gs_swd_sort": (I, [P, L, L, P, Z, P]),
     "gs_swd_l1": (I, [P, P, L, L, P, P, Z, P]),
+    "gs_knn_workspace_bytes": (Z, [L, L, I, I]),
+    "gs_knn_slices": (I, [L, L, I]),
+    "gs_knn_kth": (I, [P, L, L, P, L, L, I, I, I, P, P, Z, P]),
+    "gs_knn_within": (I, [P, L, L, P, L, L, I, P, P, P, Z, P]),
     # W = POINTER(GsLoudness), the meter of one rate
     "gs_loudness_design": (I, [I, W]),
     "gs_loudness_hops": (L, [W, L]),

@@ -487,6 +487,47 @@ def kmeans_mindist(x, centre, dist=None):
     return get().kmeans_mindist(x, centre, dist=dist)
 
 
+def _knn_nm(what, names, n, m, d):
+    for name, rows in zip(names, (n, m)):
+        if rows > _lib.KMEANS_MAX_N:
+            raise ValueError(f"{what}: {name} must have at most {_lib.KMEANS_MAX_N} rows (got {rows})")
+    if d > _lib.KMEANS_MAX_D:
+        raise ValueError(f"{what}: {names[0]} must have at most {_lib.KMEANS_MAX_D} columns (got {d})")
+
+
+def knn_kth_shapes(a, b, k):
+    """The host side of knn_kth: -> (n, m, d) of a [n, d] and b [m, d] (fp32; b may be a itself) and k in [1, KNN_MAX_K].  ValueError by argument
+    name; needs no device."""
+    n, d = _kmeans_matrix("knn_kth", "a", a)
+    m, _ = _kmeans_matrix("knn_kth", "b", b, d)
+    _knn_nm("knn_kth", ("a", "b"), n, m, d)
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or not 1 <= k <= _lib.KNN_MAX_K:
+        raise ValueError(f"knn_kth: k must be an integer in [1, {_lib.KNN_MAX_K}] (got {k!r})")
+    return n, m, d
+
+
+def knn_kth(a, b, k, exclude_diagonal=False):
+    """HipKernels.knn_kth of the process-wide kernel object; the shapes are refused here, before a device is asked for."""
+    knn_kth_shapes(a, b, k)
+    return get().knn_kth(a, b, k, exclude_diagonal=exclude_diagonal)
+
+
+def knn_within_shapes(q, ref, radius2):
+    """The host side of knn_within: -> (n, m, d) of q [n, d], ref [m, d] (fp32) and radius2 (a contiguous fp32 vector of m).  ValueError by
+    argument name; needs no device."""
+    n, d = _kmeans_matrix("knn_within", "q", q)
+    m, _ = _kmeans_matrix("knn_within", "ref", ref, d)
+    _knn_nm("knn_within", ("q", "ref"), n, m, d)
+    _kmeans_vector("knn_within", "radius2", radius2, m, torch.float32)
+    return n, m, d
+
+
+def knn_within(q, ref, radius2):
+    """HipKernels.knn_within of the process-wide kernel object; the shapes are refused here, before a device is asked for."""
+    knn_within_shapes(q, ref, radius2)
+    return get().knn_within(q, ref, radius2)
+
+
 def swd_levels(h, w):
     """gs_swd_levels restated on the host: the number of l >= 0 with min(h, w) >> l >= 16; 0 when there is none, when a size that is halved on
     the way down is odd or when a side exceeds SWD_MAX_SIDE."""
@@ -2227,6 +2268,31 @@ class HipKernels(object):
             dist = torch.empty((n,), dtype=torch.float32, device=x.device)
         _lib.check(self.lib.gs_kmeans_mindist(x2.data_ptr(), ldx, n, d, centre.data_ptr(), dist.data_ptr(), 1 if first else 0, _stream()), "gs_kmeans_mindist")
         return dist
+
+    def knn_kth(self, a, b, k, exclude_diagonal=False):
+        """gs_knn_kth (include/gansynth_hip.h): -> [n, k] fp32, for every row of a [n, d] the k smallest squared distances to the rows of b [m, d]
+        (fp32 on the device, any row stride), ascending; with `exclude_diagonal` row i of b is no candidate of row i of a (a set against itself).
+        Where the candidates run out the rest is +inf."""
+        n, m, d = knn_kth_shapes(a, b, k)
+        a2, lda = self._kmeans_rows("knn_kth", a, ("b", b))
+        b2, ldb = (a2, lda) if b is a else self._kmeans_rows("knn_kth", b)
+        out = torch.empty((n, int(k)), dtype=torch.float32, device=a.device)
+        ws = _ws(self.lib.gs_knn_workspace_bytes(n, m, d, int(k)), a.device)
+        _lib.check(self.lib.gs_knn_kth(a2.data_ptr(), lda, n, b2.data_ptr(), ldb, m, d, int(k), 1 if exclude_diagonal else 0, out.data_ptr(), ws.data_ptr(),
+                                       ws.numel(), _stream()), "gs_knn_kth")
+        return out
+
+    def knn_within(self, q, ref, radius2):
+        """gs_knn_within (include/gansynth_hip.h): -> [n] int32, for every row of q [n, d] the number of rows j of ref [m, d] (fp32 on the device,
+        any row stride) whose squared distance to it is at most radius2[j]."""
+        n, m, d = knn_within_shapes(q, ref, radius2)
+        q2, ldq = self._kmeans_rows("knn_within", q, ("ref", ref), ("radius2", radius2))
+        r2, ldr = self._kmeans_rows("knn_within", ref)
+        count = torch.empty((n,), dtype=torch.int32, device=q.device)
+        ws = _ws(self.lib.gs_knn_workspace_bytes(n, m, d, 1), q.device)
+        _lib.check(self.lib.gs_knn_within(q2.data_ptr(), ldq, n, r2.data_ptr(), ldr, m, d, radius2.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          _stream()), "gs_knn_within")
+        return count
 
     @staticmethod
     def _swd_device(what, first, *others):

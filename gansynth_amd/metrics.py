@@ -1,7 +1,8 @@
 """GANSynth's sample-quality metrics on host arrays (float64), with the reference's semantics (metrics.py:6-63):
 softmax, KL divergence, inception score, Frechet distance between two feature sets, the two-proportion z-test and the number of
 statistically different bins (NDB) of a k-means partition of the real features.  num_different_bins_device is NDB with the partition made on
-the device (kmeans.py: this project's own clustering rules, no scikit-learn), beside the Jensen-Shannon divergence of the bin proportions."""
+the device (kmeans.py: this project's own clustering rules, no scikit-learn), beside the Jensen-Shannon divergence of the bin proportions.
+precision_recall_device is precision, recall, density and coverage from k-nearest-neighbour radii on the device (manifold.py)."""
 import numpy as np
 import scipy.linalg
 import scipy.stats
@@ -91,6 +92,25 @@ def num_different_bins_device(real_features, fake_features, num_bins=50, signifi
     if details is not None:
         details.update(real_counts=real_counts, fake_counts=fake_counts, inertia=result.inertia, jsd=float(jensen_shannon_divergence(real_prop, fake_prop)))
     return int(np.count_nonzero(binomial_proportion_test(real_prop, len(real), fake_prop, len(fake), significance_level)))
+
+
+def precision_recall_device(real_features, fake_features, k=3, details=None):
+    """Improved precision and recall (Kynkaanniemi et al. 2019) and density and coverage (Naeem et al. 2020) of two feature sets [rows, columns]
+    (numpy or torch): manifold.figures (this project's own, stated rules; HIP kernels, no distance matrix) -> dict(precision=, recall=, density=,
+    coverage=).  `details` (a dict) receives real_radii and fake_radii (the squared k-NN radii, fp32), fake_counts and real_counts (int32: the balls
+    of the other set every row lies in) and coverage_minima (fp32: every real row's squared distance to its nearest fake row)."""
+    from . import kmeans, manifold
+    for name, t in (("real_features", real_features), ("fake_features", fake_features)):
+        if not hasattr(t, "shape"):
+            raise ValueError(f"precision_recall_device: {name} must be a [rows, columns] array or tensor (got {type(t).__name__})")
+    manifold.check_sets(real_features, fake_features, k, "precision_recall_device")   # (before a device is asked for)
+    real = kmeans.to_device(real_features, "real_features")
+    fake = kmeans.to_device(fake_features, "fake_features").to(real.device)
+    result = manifold.figures(real, fake, k)
+    if details is not None:
+        details.update(real_radii=result.real_radii, fake_radii=result.fake_radii, fake_counts=result.fake_counts, real_counts=result.real_counts,
+                       coverage_minima=result.coverage_minima)
+    return dict(precision=result.precision, recall=result.recall, density=result.density, coverage=result.coverage)
 
 
 def sliced_wasserstein_distance_device(real_images, fake_images, seed=0, details=None, batch_size=None):

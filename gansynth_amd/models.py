@@ -1134,7 +1134,7 @@ class GANSynth(Iterations, DataParallel, Capture):
 
     # ------------------------------------------------------------------------------------------- evaluation
     def evaluate(self, model_dir, config, classifier, input_name="images:0", output_names=("features:0", "logits:0"), batch_size=64,
-                 extra_metrics=False, classifier_dtype=torch.float32, features_out=None, weights="live", ndb="sklearn", swd=False, swd_seed=0):
+                 extra_metrics=False, classifier_dtype=torch.float32, features_out=None, weights="live", ndb="sklearn", swd=False, swd_seed=0, prd=False, prd_k=3):
         """models.py:196-230: the Frechet distance between the pitch classifier's features of real and generated spectrograms.
 
         Restores the latest checkpoint of `model_dir` as `generate` does, then for every batch of `real_input_fn()` until it runs dry:
@@ -1152,7 +1152,10 @@ class GANSynth(Iterations, DataParallel, Capture):
         mean over the levels) and sliced_wasserstein_distance_levels (a list, finest first; features_out receives their sizes as swd_sizes,
         "HxW" a level): the sliced Wasserstein distance between Laplacian-pyramid patches of the same real and fake images (swd.py: HIP
         kernels, corners and directions seeded by `swd_seed`), every batch added as it arrives -- the images are not kept.  `classifier` may
-        be None together with `swd`: no classifier is loaded or run and only the two SWD keys come back.  One process only."""
+        be None together with `swd`: no classifier is loaded or run and only the two SWD keys come back.  `prd`: the dict gains precision,
+        recall, density and coverage of the fake features against the real ones -- the features of the FID -- from
+        metrics.precision_recall_device (manifold.py: `prd_k`-nearest-neighbour radii on HIP kernels); it needs the classifier.  One process
+        only."""
         import numpy as np
         from . import metrics, networks
         del config
@@ -1163,6 +1166,10 @@ class GANSynth(Iterations, DataParallel, Capture):
         if input_name != "images:0" or list(output_names) != ["features:0", "logits:0"]:
             raise ValueError(f"evaluate: the classifier graph's tensors are 'images:0' -> ['features:0', 'logits:0'] "
                              f"(got {input_name!r} -> {list(output_names)!r})")
+        if classifier is None and prd:
+            raise ValueError("evaluate: prd=True needs a classifier (precision, recall, density and coverage come from its features)")
+        if prd and (not isinstance(prd_k, int) or isinstance(prd_k, bool) or not 1 <= prd_k <= 8):   # (before the first batch, not after the last)
+            raise ValueError(f"evaluate: prd_k must be an integer in [1, 8] (got {prd_k!r})")
         if classifier is None:
             if not swd:
                 raise ValueError("evaluate: classifier=None needs swd=True (every other figure comes from the pitch classifier)")
@@ -1245,6 +1252,8 @@ class GANSynth(Iterations, DataParallel, Capture):
                     out["num_different_bins"] = metrics.num_different_bins(real_f, fake_f, random_state=0)
                 except ImportError:
                     pass
+        if prd:
+            out.update(metrics.precision_recall_device(real_f, fake_f, k=prd_k))
         out.update(sliced_out)
         return out
 

@@ -1190,6 +1190,42 @@ int gs_swd_project(const float* desc, int64_t n, const double* moments, const fl
 int gs_swd_sort(float* data, int64_t rows, int64_t n, void* ws, size_t ws_bytes, void* stream);
 int gs_swd_l1(const float* a, const float* b, int64_t rows, int64_t n, double* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- k-nearest-neighbour radii and cover, for precision / recall / density / coverage (gansynth_amd/manifold.py,
+ * metrics.precision_recall_device; DESIGN.md "Precision and recall on the device") ----
+ * fp32, deterministic (no float atomics; a result is a multiset of values or an integer sum, so it depends neither on the slicing nor on any
+ * merge order): two calls with the same arguments write the same bits.  Both sides are matrices of d columns with their rows lda / ldb (ldq /
+ * ldr) >= d floats apart, 4-byte aligned.  Inputs are finite.  No distance is ever written to memory.
+ *
+ * The distance, in both entries: |x - y|^2 in fp32 as ONE chain over the columns in ascending order, t = x - y; acc = fmaf(t, t, acc), from
+ * acc = 0 (never |x|^2 - 2 x.y + |y|^2: that form cancels on features with a common offset).  (x - y)^2 and (y - x)^2 have the same bits, so
+ * d(i, j) has the same bits in either entry and from either side: a radius that gs_knn_kth returned admits, in gs_knn_within, exactly the
+ * pairs that defined it.
+ *
+ * gs_knn_kth: out[i][0 .. k) = the k smallest values of |a_i - b_j|^2 over j in [0, m), ascending; with exclude_diagonal != 0 over j != i (the
+ * index alone excludes: a duplicate of row i elsewhere is a candidate like any other and gives an exact 0).  Where fewer than k candidates
+ * exist the rest is +inf.  out is [n][k] dense.
+ *
+ * gs_knn_within: count[i] (int32) = the number of j in [0, m) with |q_i - ref_j|^2 <= radius2[j].  A NaN radius admits nothing, a +inf radius
+ * every row.
+ *
+ * One launch over a grid of (tiles of GS_KMEANS_TILE rows of the first side) x (slices of the second side), every block leaving its rows'
+ * partial list or count in ws as [slices][n][k] floats or [slices][n] int32, and a fold over the slices; with one slice the block writes the
+ * result itself and ws is not touched.  gs_knn_slices (host arithmetic; 0 for a shape the entries refuse; d does not enter today):
+ *   slices = ceil(m / rows),  rows = max(GS_KNN_MIN_SLICE_ROWS, 64 * ceil(ceil(m / want) / 64)),  want = ceil(GS_KNN_BLOCKS / ceil(n / GS_KMEANS_TILE)).
+ * gs_knn_workspace_bytes (host arithmetic; 0 for a shape the entries refuse): 16 with one slice, else 4 * slices * n * k rounded up to 16;
+ * gs_knn_within needs that of k = 1.  ws is 16-byte aligned.  Capture-safe: no allocation, no synchronisation.
+ * GS_ERR_ARG with a message that names the argument and without a launch: k outside [1, GS_KNN_MAX_K], d, n or m below 1, n or m above
+ * GS_KMEANS_MAX_N, d above GS_KMEANS_MAX_D, a row stride below d, a NULL or misaligned pointer, a workspace that is too small. */
+#define GS_KNN_MAX_K 8
+#define GS_KNN_BLOCKS 3072
+#define GS_KNN_MIN_SLICE_ROWS 256
+size_t gs_knn_workspace_bytes(int64_t n, int64_t m, int d, int k);
+int gs_knn_slices(int64_t n, int64_t m, int d);
+int gs_knn_kth(const float* a, int64_t lda, int64_t n, const float* b, int64_t ldb, int64_t m, int d, int k, int exclude_diagonal, float* out, void* ws,
+               size_t ws_bytes, void* stream);
+int gs_knn_within(const float* q, int64_t ldq, int64_t n, const float* ref, int64_t ldr, int64_t m, int d, const float* radius2, int32_t* count, void* ws,
+                  size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
