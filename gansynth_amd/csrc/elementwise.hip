@@ -759,6 +759,15 @@ static inline const char* pair_refusal(const void* a, const void* b, int64_t num
     return nullptr;
 }
 
+// the checks the three Adam entry points share: the four buffers present and 16-byte aligned (float4 accesses)
+static inline const char* adam_refusal(const void* p, const void* g, const void* m, const void* v, int64_t numel) {
+    if (numel <= 0) return "numel must be positive";
+    if (p == nullptr || g == nullptr || m == nullptr || v == nullptr) return "null pointer";
+    if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15)
+        return "pointers must be 16-byte aligned";
+    return nullptr;
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -1114,7 +1123,8 @@ extern "C" int gs_pack_act_bits(void* z, int64_t p, int c, int dtype, void* stre
 
 extern "C" int gs_adam_tf_step(float* p, const float* g, float* m, float* v, int64_t numel, float lr_t, float beta1, float beta2,
                                float eps, float grad_scale, void* stream) {
-    GS_CHECK_ARG(numel > 0, "adam: bad args");
+    const char* why = adam_refusal(p, g, m, v, numel);
+    GS_CHECK_ARG(why == nullptr, "adam: %s", why);
     hipLaunchKernelGGL((adam_tf_kernel<false, false>), dim3(ew_grid((numel >> 2) + 4)), dim3(256), 0, as_stream(stream), p, const_cast<float*>(g), m, v,
                        (long)numel, lr_t, (const float*)nullptr, beta1, beta2, eps, grad_scale);
     GS_CHECK_LAUNCH();
@@ -1123,7 +1133,8 @@ extern "C" int gs_adam_tf_step(float* p, const float* g, float* m, float* v, int
 
 extern "C" int gs_adam_tf_step_zero_grad(float* p, float* g, float* m, float* v, int64_t numel, float lr_t, float beta1, float beta2,
                                          float eps, float grad_scale, void* stream) {
-    GS_CHECK_ARG(numel > 0, "adam: bad args");
+    const char* why = adam_refusal(p, g, m, v, numel);
+    GS_CHECK_ARG(why == nullptr, "adam: %s", why);
     hipLaunchKernelGGL((adam_tf_kernel<true, false>), dim3(ew_grid((numel >> 2) + 4)), dim3(256), 0, as_stream(stream), p, g, m, v, (long)numel, lr_t,
                        (const float*)nullptr, beta1, beta2, eps, grad_scale);
     GS_CHECK_LAUNCH();
@@ -1132,7 +1143,9 @@ extern "C" int gs_adam_tf_step_zero_grad(float* p, float* g, float* m, float* v,
 
 extern "C" int gs_adam_tf_step_dev(float* p, float* g, float* m, float* v, int64_t numel, const float* lr_t_dev, float beta1, float beta2,
                                    float eps, float grad_scale, int zero_grad, void* stream) {
-    GS_CHECK_ARG(numel > 0 && lr_t_dev != nullptr, "adam: bad args");
+    const char* why = adam_refusal(p, g, m, v, numel);
+    GS_CHECK_ARG(why == nullptr, "adam: %s", why);
+    GS_CHECK_ARG(lr_t_dev != nullptr, "adam: null pointer (lr_t_dev)");
     const dim3 grid(ew_grid((numel >> 2) + 4));
     if (zero_grad)
         hipLaunchKernelGGL((adam_tf_kernel<true, true>), grid, dim3(256), 0, as_stream(stream), p, g, m, v, (long)numel, 0.f, lr_t_dev, beta1, beta2, eps,

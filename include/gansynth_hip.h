@@ -301,7 +301,9 @@ enum { GS_DENSE_FWD = 0, GS_DENSE_FWD_SMALL = 1, GS_DENSE_FWD_FAST = 2, GS_DENSE
 int gs_dense_route(const GsDense* d, int map, int no_mfma_or_minus1, int* out);
 
 /* tf.nn.embedding_lookup(w*alpha, argmax(labels,1)) (ops.py:217): idx[b] are the argmax indices.
- * fwd: y[b][units] = alpha * w[idx[b]][:]  ; bwd: gw[rows][units] = alpha * scatter_add(gy) (gw zero-filled here). */
+ * fwd: y[b][units] = alpha * w[idx[b]][:]  ; bwd: gw[rows][units] = alpha * scatter_add(gy) (gw zero-filled here).
+ * gs_embedding_fwd clamps an index outside [0, rows) to the nearest valid row (idx < 0 reads row 0, idx >= rows reads row rows - 1);
+ * gs_embedding_bwd adds nothing for such an index. */
 int gs_embedding_fwd(const int64_t* idx, const float* w, void* y, int b, int rows, int units, float alpha, int dtype, void* stream);
 /* ... with the row index taken from the one-hot input itself (ops.py:207: tf.argmax of the inputs; first maximum), written to idx_out[b]
  * for gs_embedding_bwd: labels [b][rows] of `dtype`, y [b][units] of `dtype` */
@@ -447,7 +449,10 @@ int gs_gan_g_loss(const void* fake_logits, const void* labels, const float* sums
 
 /* tf.train.AdamOptimizer step (models.py:67-89), TF form, fused over one flat fp32 buffer:
  *   m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g*g ; p -= lr_t * m / (sqrt(v) + eps),
- *   lr_t = lr*sqrt(1-b2^t)/(1-b1^t) computed by the caller; grad_scale multiplies g first (1/world). */
+ *   lr_t = lr*sqrt(1-b2^t)/(1-b1^t) computed by the caller; grad_scale multiplies g first (1/world).
+ * All-zero elements (p = g = m = v = +0.0: the padding between the tensors of a flat buffer) stay +0.0.
+ * Refused by the three entry points (GS_ERR_ARG, nothing launched): numel <= 0, a null p, g, m or v, one of them off a 16-byte
+ * boundary (the kernel reads and writes them as float4), and for gs_adam_tf_step_dev a null lr_t_dev. */
 int gs_adam_tf_step(float* p, const float* g, float* m, float* v, int64_t numel, float lr_t, float beta1,
                     float beta2, float eps, float grad_scale, void* stream);
 /* the same step, and g is cleared behind it: tf.gradients starts every run from zero (models.py:81-89 builds the sums anew), the
