@@ -6,11 +6,21 @@
 
 namespace gs {
 
+// Bias and activation behind the kernels that take the activation as a run-time argument (direct, single): the arithmetic of gs_bias_act_fwd
+// (elementwise.hip), on the fp32 sum.  As a pass behind the kernel the same two steps read a bf16 result back: the sum was rounded to bf16
+// BEFORE the bias went in, and where sum and bias cancel that rounding is many times the size of the result's own.
+__device__ inline float bias_act_rt(float v, const float* __restrict__ bias, int oc, int act) {
+    if (bias) v += bias[oc];
+    if (act == GS_ACT_LRELU) v = v > 0.f ? v : 0.2f * v;
+    if (act == GS_ACT_TANH) v = tanhf(v);
+    return v;
+}
+
 // ------------------------------------------------------------------------- direct gather conv
-// y[n][oy][ox][oc0..oc0+OCV) = alpha * sum_{tap,ic} x[n][iy][ix][ic] * wp[tap][oc][ic]   (wp fp32)
+// y[n][oy][ox][oc0..oc0+OCV) = act(alpha * sum_{tap,ic} x[n][iy][ix][ic] * wp[tap][oc][ic] + bias[oc])   (wp fp32; bias optional, OC floats)
 template <typename T, int OCV, int VEC>
 __global__ void conv_direct_kernel(const T* __restrict__ x, const float* __restrict__ wp, T* __restrict__ y, int mode,
-                                   int ks, int N, int Hi, int Wi, int IC, int OC, int Ho, int Wo, float alpha) {
+                                   int ks, int N, int Hi, int Wi, int IC, int OC, int Ho, int Wo, float alpha, const float* __restrict__ bias, int act) {
     const int ngrp = OC / OCV;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long total = (long)N * Ho * Wo * ngrp;
@@ -56,11 +66,11 @@ __global__ void conv_direct_kernel(const T* __restrict__ x, const float* __restr
     if (OCV == 4) {
         float o[4];
 #pragma unroll
-        for (int v = 0; v < 4; ++v) o[v] = acc[v < OCV ? v : 0] * alpha;
+        for (int v = 0; v < 4; ++v) o[v] = bias_act_rt(acc[v < OCV ? v : 0] * alpha, bias, oc + (v < OCV ? v : 0), act);
         st4(yp, o);
     } else {
 #pragma unroll
-        for (int v = 0; v < OCV; ++v) DT<T>::st(yp + v, acc[v] * alpha);
+        for (int v = 0; v < OCV; ++v) DT<T>::st(yp + v, bias_act_rt(acc[v] * alpha, bias, oc + v, act));
     }
 }
 
@@ -352,7 +362,8 @@ __global__ __launch_bounds__(256) void thin_reduce_kernel(const T* __restrict__ 
 // discriminator block): a wave per output pixel, lanes over the input channels.
 template <typename T>
 __global__ __launch_bounds__(256) void thin_single_kernel(const T* __restrict__ x, const float* __restrict__ wp, T* __restrict__ y, int mode,
-                                                          int ks, int N, int Hi, int Wi, int IC, int Ho, int Wo, float alpha) {
+                                                          int ks, int N, int Hi, int Wi, int IC, int Ho, int Wo, float alpha,
+                                                          const float* __restrict__ bias, int act) {
     const long pix = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (pix >= (long)N * Ho * Wo) return;
@@ -372,7 +383,7 @@ __global__ __launch_bounds__(256) void thin_single_kernel(const T* __restrict__ 
         }
     }
     a = wave_sum(a);
-    if (lane == 0) DT<T>::st(y + pix, a * alpha);
+    if (lane == 0) DT<T>::st(y + pix, bias_act_rt(a * alpha, bias, 0, act));
 }
 
 // the same for 3x3 kernels with IC a multiple of 256: a lane owns 4 consecutive channels per 256-channel block and ALL its loads (9 taps x
@@ -380,7 +391,7 @@ __global__ __launch_bounds__(256) void thin_single_kernel(const T* __restrict__ 
 // load pairs (11.6 us for the 256-channel stddev-plane gradient at 2 x 16: a pure latency chain)
 template <typename T, int NB>
 __global__ __launch_bounds__(256) void thin_single3_kernel(const T* __restrict__ x, const float* __restrict__ wp, T* __restrict__ y, int mode,
-                                                           int N, int Hi, int Wi, int Ho, int Wo, float alpha) {
+                                                           int N, int Hi, int Wi, int Ho, int Wo, float alpha, const float* __restrict__ bias, int act) {
     constexpr int IC = 256 * NB;
     const long pix = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -409,7 +420,7 @@ __global__ __launch_bounds__(256) void thin_single3_kernel(const T* __restrict__
 #pragma unroll
         for (int b = 0; b < NB; ++b) a += xv[t][b][0] * wv[t][b].x + xv[t][b][1] * wv[t][b].y + xv[t][b][2] * wv[t][b].z + xv[t][b][3] * wv[t][b].w;
     a = wave_sum(a);
-    if (lane == 0) DT<T>::st(y + pix, a * alpha);
+    if (lane == 0) DT<T>::st(y + pix, bias_act_rt(a * alpha, bias, 0, act));
 }
 
 // ------------------------------------------------------------------------------- the launcher
@@ -420,6 +431,8 @@ static bool launch_thin(const ThinRoute& r, const ThinArgs& a, hipStream_t st) {
     const dim3 grid((unsigned)r.grid), block(256);
     const T* x = reinterpret_cast<const T*>(a.x);
     T* y = reinterpret_cast<T*>(a.y);
+    const float* rt_bias = r.epilogue_fused ? a.bias : nullptr;   // (direct, single: a.act is the norm's activation where the epilogue is not theirs)
+    const int rt_act = r.epilogue_fused ? a.act : GS_ACT_NONE;
     switch (r.kernel) {
     case GS_THIN_EXPAND:
         return with_constant<1, 2, 3, 4>(r.C, [&](auto ic) {
@@ -448,16 +461,16 @@ static bool launch_thin(const ThinRoute& r, const ThinArgs& a, hipStream_t st) {
             return true;
         });
     case GS_THIN_SINGLE3:
-        hipLaunchKernelGGL((thin_single3_kernel<T, 1>), grid, block, 0, st, x, a.wp, y, a.mode, a.N, a.Hi, a.Wi, a.Ho, a.Wo, a.alpha);
+        hipLaunchKernelGGL((thin_single3_kernel<T, 1>), grid, block, 0, st, x, a.wp, y, a.mode, a.N, a.Hi, a.Wi, a.Ho, a.Wo, a.alpha, rt_bias, rt_act);
         return true;
     case GS_THIN_SINGLE:
-        hipLaunchKernelGGL((thin_single_kernel<T>), grid, block, 0, st, x, a.wp, y, a.mode, a.ks, a.N, a.Hi, a.Wi, a.ICk, a.Ho, a.Wo, a.alpha);
+        hipLaunchKernelGGL((thin_single_kernel<T>), grid, block, 0, st, x, a.wp, y, a.mode, a.ks, a.N, a.Hi, a.Wi, a.ICk, a.Ho, a.Wo, a.alpha, rt_bias, rt_act);
         return true;
     case GS_THIN_DIRECT:
         return with_constant<4, 2, 1>(r.OCV, [&](auto ocv) {
             return with_constant<4, 1>(r.VEC, [&](auto vec) {
                 hipLaunchKernelGGL((conv_direct_kernel<T, decltype(ocv)::value, decltype(vec)::value>), grid, block, 0, st, x, a.wp, y, a.mode, a.ks, a.N, a.Hi, a.Wi, a.ICk, a.OCk,
-                                   a.Ho, a.Wo, a.alpha);
+                                   a.Ho, a.Wo, a.alpha, rt_bias, rt_act);
                 return true;
             });
         });

@@ -107,6 +107,7 @@ inline ThinRoute thin_route(const ThinCall& c, const ThinKnobs& k) {
         r.grid = cdiv(c.P, 4);
         r.ppb = 4;
         r.tails = 1;
+        r.epilogue_fused = epilogue;
         return r;
     }
     r.kernel = GS_THIN_DIRECT;
@@ -114,6 +115,7 @@ inline ThinRoute thin_route(const ThinCall& c, const ThinKnobs& k) {
     r.VEC = c.ICk % 4 == 0 ? 4 : 1;
     r.grid = cdiv(c.P * (c.OCk / r.OCV), 256);
     r.tails = 1;
+    r.epilogue_fused = epilogue;   // (on the fp32 sum: a pass behind the kernel would add the bias to a sum already rounded to bf16)
     return r;
 }
 

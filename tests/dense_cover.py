@@ -7,12 +7,35 @@ and, where a finalize launch follows, the ksplit that launch folds.  Which kerne
 (gs_dense_route, host arithmetic on the route the entry points read) and hold the answer against the case's key.  `route_py` is a restatement of
 csrc/dense_route.h for the CPU test's sweep; `reference` is float64 on the operands as stored (activations rounded to bf16 for bf16, weights and
 bias fp32).
+
+Every result is held element by element to the bound of tests/cover_bounds.py (`bound`): K = in (forward), out (data gradient) or b (weight
+gradient), e = 3 (+ 1 for a leaky-relu slope), u = 2^-24 throughout (dense.hip runs the f32 MFMA, a k-ordered fmaf chain, for bf16 as well); a bf16
+result is rounded once, the weight gradients are fp32 results in both dtypes and take the fp32 rule.
+
+Worst max error over max |ref| of the fp32 results measured on the MI355X over seeds 0 .. 11 of every case, knob unset and set together (1536
+comparisons; tests/test_dense_cover_gpu.py prints the column: DENSE-COVER-WORST), the dense tests' ceiling and the ceiling held here (CEILINGS
+below; the CPU test holds the two copies together):
+    family            measured    suite   here
+    fwd               1.6e-07     0.001   1e-05
+    fwd_small         4.2e-07     0.001   1e-05
+    fwd_fast          5.1e-07     0.001   1e-05
+    fwd_mfma          2.5e-07     0.001   1e-05
+    bwd_data          1.6e-07     0.001   1e-05
+    bwd_data_wide     1.4e-07     0.001   1e-05
+    bwd_data_fast     1.8e-07     0.001   1e-05
+    bwd_data_mfma     7.3e-07     0.001   0.0001
+    bwd_weight        2.9e-07     0.001   1e-05
+    bwd_weight_fast   1.5e-07     0.001   1e-05
+Beside it, worst bf16 ratio and worst err / bound (fp32 results, bf16 results) per family: fwd 3.3e-3, 0.02, 0.985; fwd_small 3.8e-3, 0.04, 0.980;
+fwd_fast 3.6e-3, 0.05, 0.990; fwd_mfma 3.6e-3, 0.02, 0.978; bwd_data 3.3e-3, 0.04, 0.993; bwd_data_wide 2.8e-3, 0.01, 0.963; bwd_data_fast 3.6e-3,
+0.02, 0.988; bwd_data_mfma 3.4e-3, 0.09, 0.993; bwd_weight (K = b <= 20) 0.32; bwd_weight_fast (K = 5) 0.40.
 """
 import ctypes
 from collections import namedtuple
 
 import torch
 
+from tests import cover_bounds as B
 from tests import igemm_cover
 
 F32, BF16 = 0, 1
@@ -28,6 +51,20 @@ ACT_NAMES = ("none", "lrelu", "tanh")
 ERR_ARG, ERR_UNSUPPORTED = -1, -3
 # the dense tests' own ceilings (tests/test_kernels_gpu.py), of max |ref|: forward and data gradient by dtype, weight gradient (fp32 out) in both
 TOLERANCE = {FWD_MAP: {F32: 1e-3, BF16: 2e-2}, BWD_DATA_MAP: {F32: 1e-3, BF16: 2e-2}, BWD_WEIGHT_MAP: {F32: 1e-3, BF16: 1e-3}}
+# kernel -> (worst fp32-result ratio measured on the MI355X, the dense tests' ceiling, the ceiling held here: cover_bounds.ceiling_rule): the
+# docstring's table.  The weight gradients of bf16 operands are fp32 results and count with their kernel.
+CEILINGS = {
+    "fwd":               (1.6e-07, 0.001, 1e-05),
+    "fwd_small":         (4.2e-07, 0.001, 1e-05),
+    "fwd_fast":          (5.1e-07, 0.001, 1e-05),
+    "fwd_mfma":          (2.5e-07, 0.001, 1e-05),
+    "bwd_data":          (1.6e-07, 0.001, 1e-05),
+    "bwd_data_wide":     (1.4e-07, 0.001, 1e-05),
+    "bwd_data_fast":     (1.8e-07, 0.001, 1e-05),
+    "bwd_data_mfma":     (7.3e-07, 0.001, 0.0001),
+    "bwd_weight":        (2.9e-07, 0.001, 1e-05),
+    "bwd_weight_fast":   (1.5e-07, 0.001, 1e-05),
+}
 ROUTE_FIELDS = ("kernel", "FB", "WPR", "step", "passes", "grid_x", "grid_y", "ksplit", "ipb", "finalize", "ws_bytes")
 DENSE_BT, DENSE_WR = 16, 16
 
@@ -246,6 +283,58 @@ def reference(c, d):
         return (d["alpha"] * a @ w.t()).reshape(_side(c))
     gw = d["alpha"] * a.reshape(c.b, -1).t() @ d["gy"].double()
     return gw + d["gw0"].double() if c.accumulate else gw
+
+
+def _map(c, a, w, gy=None):
+    """The map of the case without alpha, bias and accumulate, in the dtype of its operands."""
+    if c.map == FWD_MAP:   # (a 4-D activation: tf.layers.flatten of NCHW, column ch * hw + p)
+        return a.reshape(c.b, -1) @ w
+    if c.map == BWD_DATA_MAP:
+        return (a @ w.t()).reshape(_side(c))
+    return a.reshape(c.b, -1).t() @ gy
+
+
+def restated(c, d):
+    """An honest kernel: the map in fp32 (torch on the CPU) on the operands as stored, alpha, bias, activation and accumulate behind it in fp32,
+    one store in the result's dtype (fp32 for a weight gradient)."""
+    y = d["alpha"] * _map(c, d["a"].float(), d["w"].float(), d["gy"].float() if c.map == BWD_WEIGHT_MAP else None)
+    if c.map == BWD_WEIGHT_MAP:
+        return y + d["gw0"] if c.accumulate else y
+    if c.bias:
+        y = y + d["bias"].float()
+    y = torch.tanh(y) if c.act == TANH else (torch.where(y > 0, y, 0.2 * y) if c.act == LRELU else y)
+    return y.to(TORCH_DTYPE[c.key.dtype])
+
+
+def mag(c, d):
+    """cover_bounds' mag: |alpha| map(|a|, |w|) + |bias| + |gw0| in fp32 on the CPU."""
+    m = abs(d["alpha"]) * _map(c, d["a"].float().abs(), d["w"].float().abs(), d["gy"].float().abs() if c.map == BWD_WEIGHT_MAP else None)
+    if c.bias:
+        m = m + d["bias"].float().abs()
+    return m + d["gw0"].float().abs() if c.accumulate else m
+
+
+def products(c):
+    """K: what an element of the map sums over -- in, out or b."""
+    return (c.inp, c.out, c.b)[c.map]
+
+
+def family(c):
+    return KERNEL_NAMES[c.key.kernel]
+
+
+def roundings(c):
+    """bf16 results are rounded once (bias and activation ride in the kernel or in the finalize pass, on fp32 partials); weight gradients are fp32."""
+    return 1 if (c.key.dtype == BF16 and c.map != BWD_WEIGHT_MAP) else 0
+
+
+def bound(c, ref, m):
+    """The element-wise bound of the case's result (tests/cover_bounds.py).  dense.hip runs the f32 MFMA for bf16 as well: u = 2^-24 throughout."""
+    return B.bound(ref, m, products(c), B.E_BASE + int(c.act == LRELU), CEILINGS[family(c)][2], roundings=roundings(c), tanh_fwd=c.act == TANH)
+
+
+def macs(c):
+    return c.b * c.inp * c.out
 
 
 def run(K, c, d):

@@ -5,6 +5,25 @@ The cases are keyed by the table of compiled kernels (gs_conv_igemm_table: conv_
 (mode, dtype, configuration) `find_shapes` searches a fixed grid for the cheapest kernel-role shapes the chooser (gs_conv_igemm_config) routes to
 that kernel, `api_call` names the public entry point that reaches the dispatch with such a shape, and `conv_ref64` is the float64 reference the
 result is compared with element by element.  A retuned threshold moves the shapes; a kernel nothing reaches any more fails the reachability test.
+
+The plain rows are held element by element to the bound of tests/cover_bounds.py (`plain_bound`): K = 9 ic products (4 ic where the transposed
+walk reaches an element with at most 2 x 2 taps), e = 3, an fp32 result inside F_i, a bf16 result (rounded once) inside 2^-8 (|ref_i| + F_i) + F_i.
+The bf16 reference takes operand AND weight rounded to bf16: that is how the kernel holds them (its prepared weight is bf16, alpha stays fp32 in
+the epilogue).  The fused-norm rows and the sign-bit forms keep the assertions of tests/test_kernels_gpu.py.
+
+Worst max error over max |ref| measured on the MI355X over seeds 0 .. 11 of every plain case of at most 5e7 multiply-adds and seed 0 of the others,
+both entry points (1230 comparisons; tests/test_igemm_cover_gpu.py prints the column: IGEMM-COVER-WORST), the suite's ceiling and the ceiling held
+here (CEILINGS below; the CPU test holds the two copies together):
+    family            measured    suite   here
+    plain-f32         7.0e-07     0.001   0.0001
+(16 x 6.9e-7 = 1.1e-5 is just over 1e-5: the rule gives 1e-4, not the 1e-5 its neighbours get.)  Beside it: the bf16 rows' worst ratio 3.9e-3 (the
+store's own rounding); worst err / bound 0.10 over the fp32 rows and 0.993 over the bf16 rows (a round-to-nearest store alone reaches 1 - 2^-8).
+
+U_BF16_MFMA = 2^-24.  The guide documents the f32 MFMA as a k-ordered fmaf chain and says nothing of how v_mfma_f32_32x32x16_bf16 rounds its
+internal adds, so the bf16 rows and the bf16 weight-gradient families ran with u = 2^-24 and the worst err / bound per kernel family was read off:
+every element of every bf16-MFMA result is inside.  The bf16 rows here say little (0.993 is the store); the weight gradients of
+tests/wgrad_cover.py are fp32 results of the same instruction and sit at 0.23 (conv_wgrad_bf16_kernel), 0.06 (thin_dma), 0.22 (2x2) and 0.07 (2x2_sk)
+of their bound, against 0.40 for their fp32 sibling conv_wgrad_kernel at shapes of the same size.  Nothing is outside by any factor: no 2^-23.
 """
 import ctypes
 import json
@@ -15,6 +34,8 @@ from collections import namedtuple
 
 import torch
 import torch.nn.functional as TF
+
+from tests import cover_bounds as B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S1, S2, T2 = 0, 1, 2
@@ -29,6 +50,10 @@ MAX_MACS = 2e9   # no chosen case may cost the float64 reference more
 # max error over max |ref| a kernel's result may have against conv_ref64.  bf16: the bound of the suite's bf16 conv tests (a result rounded to 8
 # mantissa bits is within 2^-9 of its own size).  fp32: the suite's 1e-3 (BASELINE.json north star) is a ceiling.
 TOLERANCE = {F32: 1e-3, BF16: 1e-2}
+# family -> (worst fp32 ratio measured on the MI355X, the suite's ceiling, the ceiling held here: cover_bounds.ceiling_rule): the docstring's table
+CEILINGS = {
+    "plain-f32":         (7.0e-07, 0.001, 0.0001),
+}
 
 # the search grid of find_shapes (kernel-role shapes)
 GRID_N = (1, 2, 4, 8, 16, 32, 64)
@@ -185,19 +210,50 @@ def conv_ref64(call, a, w_hwio, alpha, bf16=False, drop=None):
             w[tap // 3, tap % 3, :, lo:lo + 32] = 0
         else:
             w[tap // 3, tap % 3, lo:lo + 32, :] = 0
+    return alpha * conv_map(call, a, w)
+
+
+def conv_map(call, a, w):
+    """The map of conv_ref64 without alpha, in the dtype of its operands (float64: the reference; fp32: the scale `conv_mag` and the restatement
+    of tests/test_igemm_cover_cpu.py)."""
     oihw, iohw = w.permute(3, 2, 0, 1), w.permute(2, 3, 0, 1)
     if not call.transposed and not call.data_grad:
-        y = TF.conv2d(a, oihw, padding=1) if call.stride == 1 else TF.conv2d(TF.pad(a, (0, 1, 0, 1)), oihw, stride=2)
-    elif not call.transposed:   # the conv's adjoint: a transposed conv of gy [n, co] with the same [co, ci] kernel
+        return TF.conv2d(a, oihw, padding=1) if call.stride == 1 else TF.conv2d(TF.pad(a, (0, 1, 0, 1)), oihw, stride=2)
+    if not call.transposed:   # the conv's adjoint: a transposed conv of gy [n, co] with the same [co, ci] kernel
         if call.stride == 1:
-            y = TF.conv_transpose2d(a, oihw, padding=1)
-        else:
-            y = TF.conv_transpose2d(a, oihw, stride=2)[:, :, :2 * a.shape[2], :2 * a.shape[3]]
-    elif not call.data_grad:
-        y = TF.conv_transpose2d(a, iohw, stride=2)[:, :, :2 * a.shape[2], :2 * a.shape[3]]
-    else:                       # the transposed conv's adjoint: the stride-2 conv of gy [n, co] with [ci, co] read as (out, in)
-        y = TF.conv2d(TF.pad(a, (0, 1, 0, 1)), iohw, stride=2)
-    return alpha * y
+            return TF.conv_transpose2d(a, oihw, padding=1)
+        return TF.conv_transpose2d(a, oihw, stride=2)[:, :, :2 * a.shape[2], :2 * a.shape[3]]
+    if not call.data_grad:
+        return TF.conv_transpose2d(a, iohw, stride=2)[:, :, :2 * a.shape[2], :2 * a.shape[3]]
+    return TF.conv2d(TF.pad(a, (0, 1, 0, 1)), iohw, stride=2)   # the transposed conv's adjoint: the stride-2 conv of gy [n, co] with [ci, co] read as (out, in)
+
+
+def stored(t, bf16):
+    """An operand as a plain kernel holds it, in fp32."""
+    return t.bfloat16().float() if bf16 else t.float()
+
+
+def conv_mag(call, a, w_hwio, alpha, bf16=False):
+    """cover_bounds' mag of a plain case: |alpha| times the same map on the absolute values of the operands as stored, in fp32 on the CPU."""
+    return abs(alpha) * conv_map(call, stored(a, bf16).abs(), stored(w_hwio, bf16).abs())
+
+
+def conv_restated(call, a, w_hwio, alpha, bf16=False):
+    """An honest kernel: the map in fp32 (torch's CPU conv) on the operands as stored, alpha behind it, the bf16 rows' result rounded to bf16."""
+    y = alpha * conv_map(call, stored(a, bf16), stored(w_hwio, bf16))
+    return y.bfloat16() if bf16 else y
+
+
+def plain_k(mode, s):
+    """The most products an element of a plain case sums: 9 taps of the contracted channels; the transposed walk (T2) reaches an element with at
+    most 2 x 2 of them."""
+    return (4 if mode == T2 else 9) * s.ic
+
+
+def plain_bound(kernel, s, ref, mag):
+    """The element-wise bound of a plain row's result (tests/cover_bounds.py): fp32, or bf16 rounded once; the bf16 rows run the bf16 MFMA."""
+    bf16 = kernel.dtype == BF16
+    return B.bound(ref, mag, plain_k(kernel.mode, s), B.E_BASE, CEILINGS["plain-f32"][2], roundings=1 if bf16 else 0, u=B.U_BF16_MFMA if bf16 else B.U)
 
 
 def operand_shape(call, s):

@@ -11,6 +11,7 @@ import itertools
 
 import pytest
 
+from tests import cover_bounds as B
 from tests import dense_cover as C
 
 BATCHES = (1, 5, 8, 13, 16, 17, 24, 30, 64, 65)
@@ -155,3 +156,59 @@ def test_query_refusals(lib):
     assert lib.gs_dense_route(tall, C.BWD_WEIGHT_MAP, -1, ints) == -3 and lib.gs_dense_bwd_weight(tall, P, P, P, 0, None) == -3 and b"batch <= 16" in lib.gs_last_error()
     assert lib.gs_dense_fwd(good, P, P, None, 3, P, None) == -1 and b"activation" in lib.gs_last_error()
     assert lib.gs_dense_fwd(good, P, P, None, 0, P, None) == -4 and b"workspace" in lib.gs_last_error()   # (ws_bytes 0 against 128 slices of partials)
+
+
+# ------------------------------------------------------------------------------------------------ the element-wise bound (tests/cover_bounds.py)
+def test_table_is_the_constants_and_the_bound_is_never_weaker():
+    """The docstring's table is CEILINGS (one family per kernel but the finalize pass, which rides), every ceiling is what the rule gives for its
+    measurement, and the bound at its largest stays under the max-norm tolerance each (map, dtype) was held to before."""
+    B.check_table(C.__doc__, C.CEILINGS)
+    assert set(C.CEILINGS) == set(C.KERNEL_NAMES) - {"finalize"}
+    for c in C.CASES:
+        measured, suite, here = C.CEILINGS[C.family(c)]
+        assert suite == C.TOLERANCE[c.map][C.F32]
+        assert B.never_weaker(C.TOLERANCE[c.map][c.key.dtype], here, C.roundings(c), c.act == C.TANH), C.case_id(c)
+        assert C.macs(c) <= B.SMALL_MACS, C.case_id(c)   # every case runs at all twelve seeds of the measurement
+        assert C.products(c) == {C.FWD_MAP: c.inp, C.BWD_DATA_MAP: c.out, C.BWD_WEIGHT_MAP: c.b}[c.map]
+
+
+def test_an_honest_kernel_is_inside_the_bound():
+    """The map restated in fp32 on the operands as stored (torch's CPU matmul; bias, activation and accumulate in fp32, one store in the result's
+    dtype) stays inside the bound at every case."""
+    worst = {}
+    for c in C.CASES:
+        d = C.inputs(c)
+        ref, mag = C.reference(c, d), C.mag(c, d)
+        m = B.measure(C.case_id(c), C.restated(c, d), ref, C.bound(c, ref, mag), mag)
+        assert m.over == 0 and m.compared == ref.numel() and m.worst <= 1, m.message
+        worst[(c.map, c.key.dtype)] = max(worst.get((c.map, c.key.dtype), 0.0), m.worst)
+    print(f"{len(C.CASES)} honest results, worst err / bound per (map, dtype): {worst}")
+    assert len(worst) == 6
+
+
+def test_subtly_wrong_kernels_pass_the_old_assertion_and_fail_the_bound():
+    """M1 (bf16 results): two K partials each rounded to bf16 before the last add, in front of bias and activation; M3 (bf16 results): a
+    truncating store; M5 (every case, the fp32 weight gradients among them): every element under 5 % of the largest scaled by 1 + 2^-6."""
+    import torch
+    gap = B.Gap(("M1", "M3", "M5"))
+    for c in C.CASES:
+        d = C.inputs(c)
+        ref, mag = C.reference(c, d), C.mag(c, d)
+        bnd, tag, old = C.bound(c, ref, mag), C.case_id(c), C.TOLERANCE[c.map][c.key.dtype]
+        if not C.roundings(c):
+            gap.check("M5", tag, B.stored_as(B.scale_small(ref), bf16=False), ref, bnd, old)
+            continue
+        gap.check("M5", tag, B.stored_as(B.scale_small(ref), bf16=True), ref, bnd, old)
+        gap.check("M3", tag, B.bf16_truncate(ref), ref, bnd, old)
+        axis = 0 if c.map == C.FWD_MAP else 1   # the contracted side of the [in, out] weight
+        half = d["w"].shape[axis] // 2
+        lo, hi = d["w"].clone(), d["w"].clone()
+        lo.narrow(axis, half, d["w"].shape[axis] - half).zero_()
+        hi.narrow(axis, 0, half).zero_()
+        parts = [C.reference(c._replace(bias=False, act=C.NONE), dict(d, w=w)) for w in (lo, hi)]
+        y = B.fold_through_bf16(*parts)
+        if c.bias:
+            y = y + d["bias"].double()
+        y = torch.tanh(y) if c.act == C.TANH else (torch.where(y > 0, y, 0.2 * y) if c.act == C.LRELU else y)
+        gap.check("M1", tag, B.bf16_rne(y), ref, bnd, old)
+    gap.close()

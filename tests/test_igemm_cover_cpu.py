@@ -12,6 +12,7 @@ reference by at least ten times that tolerance, at every plain case small enough
 import pytest
 import torch
 
+from tests import cover_bounds as B
 from tests import igemm_cover as C
 
 
@@ -108,3 +109,76 @@ def test_a_dropped_stage_is_ten_tolerances_away(plan):
                         checked += 1
     print(f"{checked} dropped stages, the least visible per dtype (fp32, bf16): {worst}")
     assert checked >= 100 and set(worst) == {C.F32, C.BF16}
+
+
+# ------------------------------------------------------------------------------------------------ the element-wise bound (tests/cover_bounds.py)
+def test_table_is_the_constants_and_the_bound_is_never_weaker():
+    """The docstring's table is CEILINGS, every ceiling is what the rule gives for its measurement, and the bound at its largest stays under the
+    max-norm tolerance the plain rows were held to before, for both dtypes."""
+    B.check_table(C.__doc__, C.CEILINGS)
+    for dtype, r in ((C.F32, 0), (C.BF16, 1)):
+        for family, (measured, suite, here) in C.CEILINGS.items():
+            assert suite == C.TOLERANCE[C.F32] and B.never_weaker(C.TOLERANCE[dtype], here, r), (family, dtype, r)
+    assert not B.never_weaker(C.TOLERANCE[C.BF16], 1e-2, 1)   # (the inequality can fail: it is no tautology)
+    assert B.U_BF16_MFMA in (2.0 ** -24, 2.0 ** -23)
+
+
+def _small_plain_cases(plan):
+    for knobs, found in plan:
+        for k, shapes in found.items():
+            for s in shapes:
+                if s.want == C.PLAIN and C.macs(k.mode, s) <= B.SMALL_MACS:
+                    for second in (False, True):
+                        yield k, s, C.api_call(k.mode, C.PLAIN, second)
+
+
+def test_an_honest_kernel_is_inside_the_bound(plan):
+    """The map restated in fp32 on the operands as stored (torch's CPU conv, a bf16 store for the bf16 rows) stays inside the bound at every
+    plain case of at most 5e7 multiply-adds, through both entry points."""
+    worst, n = {}, 0
+    for k, s, call in _small_plain_cases(plan):
+        a, wt, alpha = C.plain_inputs(call, s, seed=3)
+        bf16 = k.dtype == C.BF16
+        ref, mag = C.conv_ref64(call, a, wt, alpha, bf16=bf16), C.conv_mag(call, a, wt, alpha, bf16=bf16)
+        m = B.measure(f"{C.kernel_id(k)} {call.name} {tuple(s)}", C.conv_restated(call, a, wt, alpha, bf16=bf16), ref, C.plain_bound(k, s, ref, mag), mag)
+        assert m.over == 0 and m.compared == ref.numel() and m.worst <= 1, m.message
+        worst[k.dtype] = max(worst.get(k.dtype, 0.0), m.worst)
+        n += 1
+    print(f"{n} honest results, worst err / bound per dtype (fp32, bf16): {worst}")
+    assert n >= 90 and set(worst) == {C.F32, C.BF16}
+
+
+def _halves(call, wt):
+    """The weight with the second resp. the first half of its contracted channels zeroed: two K partials."""
+    axis = 3 if call.data_grad else 2
+    half = wt.shape[axis] // 2
+    lo, hi = wt.clone(), wt.clone()
+    lo.narrow(axis, half, wt.shape[axis] - half).zero_()
+    hi.narrow(axis, 0, half).zero_()
+    return lo, hi
+
+
+def test_subtly_wrong_kernels_pass_the_old_assertion_and_fail_the_bound(plan):
+    """M1 .. M5 of tests/cover_bounds.py's Gap, each built from the float64 reference the way conv_ref64(drop=...) builds the dropped stage:
+    M1 (bf16 rows) two K partials each rounded to bf16 before the last add; M2 (bf16 rows) alpha folded into the weight before its bf16
+    rounding; M3 (bf16 rows) a truncating store; M4 (fp32 rows) the centre tap's weights rounded to bf16; M5 every element under 5 % of the
+    largest scaled by 1 + 2^-6."""
+    gap = B.Gap(("M1", "M2", "M3", "M4", "M5"))
+    for k, s, call in _small_plain_cases(plan):
+        a, wt, alpha = C.plain_inputs(call, s, seed=3)
+        bf16 = k.dtype == C.BF16
+        ref, mag = C.conv_ref64(call, a, wt, alpha, bf16=bf16), C.conv_mag(call, a, wt, alpha, bf16=bf16)
+        bnd, tag, old = C.plain_bound(k, s, ref, mag), f"{C.kernel_id(k)} {call.name} {tuple(s)}", C.TOLERANCE[k.dtype]
+        if bf16:
+            lo, hi = _halves(call, wt)
+            folded = B.fold_through_bf16(C.conv_ref64(call, a, lo, alpha, bf16=True), C.conv_ref64(call, a, hi, alpha, bf16=True))
+            gap.check("M1", tag, B.bf16_rne(folded), ref, bnd, old)
+            gap.check("M2", tag, B.bf16_rne(C.conv_ref64(call, a.bfloat16(), (alpha * wt).bfloat16(), 1.0)), ref, bnd, old)
+            gap.check("M3", tag, B.bf16_truncate(ref), ref, bnd, old)
+            gap.check("M5", tag, B.stored_as(B.scale_small(ref), bf16=True), ref, bnd, old)
+        else:
+            w4 = wt.clone()
+            w4[1, 1] = wt[1, 1].bfloat16().float()
+            gap.check("M4", tag, C.conv_ref64(call, a, w4, alpha).float(), ref, bnd, old)
+            gap.check("M5", tag, B.stored_as(B.scale_small(ref), bf16=False), ref, bnd, old)
+    gap.close()

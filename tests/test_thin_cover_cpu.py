@@ -12,6 +12,7 @@ import itertools
 
 import pytest
 
+from tests import cover_bounds as B
 from tests import thin_cover as C
 
 CHANNELS = (1, 2, 3, 4, 8, 16, 32, 64, 96, 128, 256, 512)
@@ -107,7 +108,7 @@ def test_the_routes_of_the_model_and_the_passes_left_open(lib):
     r = C.query(lib, (8, 2, 16, 1, 256, 3, 1, 0), C.BF16, C.CONV_BWD_DATA, C.PLAIN, C.NONE, False, C.NONE, False)
     assert (r.kernel, r.grid, r.ppb) == (C.SINGLE3, 64, 4)
     r = C.query(lib, (8, 2, 16, 257, 256, 3, 1, 0), C.BF16, C.CONV_FWD, C.PLAIN, C.LRELU, True, C.NONE, True)
-    assert (r.kernel, r.OCV, r.VEC, r.grid) == (C.DIRECT, 4, 1, 64) and (r.epilogue_fused, r.bits_fused) == (0, 0)
+    assert (r.kernel, r.OCV, r.VEC, r.grid) == (C.DIRECT, 4, 1, 64) and (r.epilogue_fused, r.bits_fused) == (1, 0)   # (bias and leaky relu on the fp32 sum)
     # a tanh behind a 3x3 layer of the implicit GEMM's channel counts runs here
     assert C.query(lib, (2, 8, 16, 64, 64, 3, 1, 0), C.BF16, C.CONV_FWD, C.PLAIN, C.LRELU, True, C.NONE, False) is None
     assert C.query(lib, (2, 8, 16, 64, 64, 3, 1, 0), C.BF16, C.CONV_FWD, C.PLAIN, C.TANH, True, C.NONE, False).kernel == C.DIRECT
@@ -135,3 +136,76 @@ def test_query_refusals(lib):
     assert lib.gs_conv_thin_route(big, C.CONV_FWD, C.FWD_MASK, C.TANH, 0, C.LRELU, 0, None, out) == 0 and out[0] == -1
     assert lib.gs_conv_thin_route(big, C.CONV_FWD, C.PLAIN, C.TANH, 0, 0, 0, None, out) == 0 and out[0] == C.DIRECT
     assert lib.gs_conv_thin_route(_lib.GsConv(2, 8, 16, 2, 32, 5, 1, 0, C.BF16, 0, 1.0, None, 0), C.CONV_FWD, C.PLAIN, C.NONE, 0, 0, 0, None, out) == -1
+
+
+# ------------------------------------------------------------------------------------------------ the element-wise bound (tests/cover_bounds.py)
+def test_table_is_the_constants_and_the_bound_is_never_weaker():
+    """The docstring's table is CEILINGS (one family per kernel), every ceiling is what the rule gives for its measurement, and the bound at its
+    largest stays under the max-norm tolerance these cases were held to before: for every dtype, number of roundings and a forward tanh."""
+    B.check_table(C.__doc__, C.CEILINGS)
+    assert set(C.CEILINGS) == set(C.KERNEL_NAMES)
+    for family, (measured, suite, here) in C.CEILINGS.items():
+        assert suite == C.TOLERANCE[C.F32]
+        for dtype, r in ((C.F32, 0), (C.BF16, 1), (C.BF16, 2)):
+            for tanh_fwd in (False, True):
+                assert B.never_weaker(C.TOLERANCE[dtype], here, r, tanh_fwd), (family, dtype, r, tanh_fwd)
+
+
+def _routed(lib):
+    for c in C.CASES:
+        assert C.macs(c) <= B.SMALL_MACS, C.case_id(c)   # every case runs at all twelve seeds of the measurement
+        yield c, C.route(lib, c)
+
+
+def test_roundings_follow_the_route(lib):
+    """A bf16 result is rounded twice exactly where the route leaves a pass behind the kernel, and the only pass any case leaves is a mask
+    (the REDUCE kernel's masked forward, the masked data gradients of the EXPAND and direct kernels): bias and activation ride in every kernel, on the fp32 sum.
+    (As a pass of their own behind the direct and single kernels they added the bias to a sum already rounded to bf16, and where the two
+    cancel that rounding was up to 240 times this bound: the measurement of tests/thin_cover.py's docstring.)"""
+    twice = {c for c, r in _routed(lib) if C.roundings(c, r) == 2}
+    assert twice and all(c.key.dtype == C.BF16 and c.mask_act and not (c.bias or c.act) for c in twice)
+    assert {c.key.kernel for c in twice} == {C.DIRECT, C.REDUCE, C.EXPAND}
+    for c, r in _routed(lib):
+        assert r.epilogue_fused == int(bool(c.bias or c.act) or c.call == "pnbwd"), C.case_id(c)
+        assert C.roundings(c, r) == C.roundings(c, C.route(lib, c, C.CAPPED)), C.case_id(c)
+        assert C.roundings(c, r) == (0 if c.key.dtype == C.F32 else 1 + int(bool(c.mask_act) and not r.mask_fused)), C.case_id(c)
+
+
+def test_an_honest_kernel_is_inside_the_bound(lib):
+    """The map restated in fp32 on the operands as stored (torch on the CPU; bias, activation and mask in fp32, one store in the case's dtype)
+    stays inside the bound at every case."""
+    worst = {}
+    for c, r in _routed(lib):
+        d = C.inputs(c)
+        ref, mag = C.reference(c, d), C.mag(c, d)
+        m = B.measure(C.case_id(c), C.restated(c, d), ref, C.bound(c, r, ref, mag), mag)
+        assert m.over == 0 and m.compared == ref.numel() and m.worst <= 1, m.message
+        worst[c.key.dtype] = max(worst.get(c.key.dtype, 0.0), m.worst)
+    print(f"{len(C.CASES)} honest results, worst err / bound per dtype (fp32, bf16): {worst}")
+    assert set(worst) == {C.F32, C.BF16}
+
+
+def test_subtly_wrong_kernels_pass_the_old_assertion_and_fail_the_bound(lib):
+    """M1 (bf16 cases that contract more than one channel): two K partials each rounded to bf16 before the last add, in front of bias,
+    activation and mask; M3 (bf16 cases rounded once: a bound that admits two roundings admits one truncation): a truncating store; M5 (every
+    case): every element under 5 % of the largest scaled by 1 + 2^-6."""
+    gap = B.Gap(("M1", "M3", "M5"))
+    for c, r in _routed(lib):
+        d = C.inputs(c)
+        ref, mag = C.reference(c, d), C.mag(c, d)
+        bnd, tag, old = C.bound(c, r, ref, mag), C.case_id(c), C.TOLERANCE[c.key.dtype]
+        if c.key.dtype == C.F32:
+            gap.check("M5", tag, B.stored_as(B.scale_small(ref), bf16=False), ref, bnd, old)
+            continue
+        gap.check("M5", tag, B.stored_as(B.scale_small(ref), bf16=True), ref, bnd, old)
+        if C.roundings(c, r) == 1:
+            gap.check("M3", tag, B.bf16_truncate(ref), ref, bnd, old)
+        axis = 3 if c.call in ("bwd_data", "bwd_data_t", "pnbwd") else 2   # the contracted side of the HWIO weight
+        half = d["w"].shape[axis] // 2
+        if half:
+            lo, hi = d["w"].clone(), d["w"].clone()
+            lo.narrow(axis, half, d["w"].shape[axis] - half).zero_()
+            hi.narrow(axis, 0, half).zero_()
+            y = B.fold_through_bf16(d["alpha"] * C.conv64(c, d["a"], lo), d["alpha"] * C.conv64(c, d["a"], hi))
+            gap.check("M1", tag, B.bf16_rne(C.finish(c, d, y)), ref, bnd, old)
+    gap.close()

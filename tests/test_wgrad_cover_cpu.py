@@ -9,6 +9,7 @@ Cuts: over the caps of the stream-K sweep the partitions hold every kind of cut 
 import pytest
 import torch
 
+from tests import cover_bounds as B
 from tests import wgrad_cover as C
 
 
@@ -201,3 +202,70 @@ def test_stream_k_sweep_cuts_at_every_kind_of_place(lib, mode):
     assert set(hit) == C.SK_CUT_KINDS, sorted(C.SK_CUT_KINDS - set(hit))
     assert hit["run over 13 blocks or more"] == [0]
     print(f"mode {C.MODE_NAMES[mode]}: caps per kind of cut {hit}")
+
+
+# ------------------------------------------------------------------------------------------------ the element-wise bound (tests/cover_bounds.py)
+def test_table_is_the_constants_and_the_bound_is_never_weaker():
+    """The docstring's table is CEILINGS, every ceiling is what the rule gives for its measurement and none is above the 1e-4 every gradient was
+    held to before (fp32 results throughout: no bf16 term)."""
+    B.check_table(C.__doc__, C.CEILINGS)
+    assert set(C.CEILINGS) == set(C.FAMILY_NAMES) | {"bias", "scalar_fold"}
+    for family, (measured, suite, here) in C.CEILINGS.items():
+        assert suite == C.TOLERANCE and B.never_weaker(C.TOLERANCE, here, 0), family
+    assert {C.unit_roundoff(f) for f in C.BF16_MFMA_FAMILIES} == {B.U_BF16_MFMA} and C.unit_roundoff(C.MFMA_F32) == C.unit_roundoff(C.DIRECT) == B.U
+
+
+def _small_cases(shapes):
+    """(kernel, route, shape, image count) of every chosen case and sweep case of at most 5e7 reference multiply-adds."""
+    for k, found in shapes.items():
+        for s in found:
+            for route in C.routes(k):
+                for n in sorted({s.n, sum(C.deferred_counts(s))}):
+                    if C.macs(s, n) <= B.SMALL_MACS:
+                        yield k, C.route_for(route, s), s, n
+    for case, n in _sweep_cases():
+        if C.macs(case.shape, n) <= B.SMALL_MACS:
+            yield case.kernel, case.route, case.shape, n
+
+
+def _prefilled(ref, seed):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(*ref.shape, generator=g) * 0.5 * float(ref.abs().max())).float()
+
+
+def test_an_honest_kernel_is_inside_the_bound(shapes):
+    """The sums restated in fp32 (torch's CPU einsum) stay inside the bound -- fresh, adding into a pre-filled gradient, and the bias gradient --
+    at every case of at most 5e7 multiply-adds."""
+    worst, n_cases = 0.0, 0
+    for k, route, s, n in _small_cases(shapes):
+        x, gy, alpha = C.inputs(route, s, k.dtype, seed=5, n=n)
+        ref, mag = C.reference(route, s, x, gy, alpha), C.weight_mag(route, s, x, gy, alpha)
+        got, fam, K, u = C.restated(route, s, x, gy, alpha), C.FAMILY_NAMES[k.family], C.weight_products(s, n), C.unit_roundoff(k.family)
+        base = _prefilled(ref, 6)
+        tag = f"{C.kernel_id(k)} {route.name} {tuple(s)} n {n}"
+        for m in (B.measure(tag, got, ref, C.bound(fam, ref, mag, K, u), mag),
+                  B.measure(tag + " accumulate", base + got, base.double() + ref, C.bound(fam, base.double() + ref, mag + base.abs(), K, u), mag + base.abs()),
+                  B.measure(tag + " bias", gy.float().sum((0, 2, 3)), C.bias64(gy), C.bound("bias", C.bias64(gy), C.bias_mag(gy), C.bias_products([gy.shape])),
+                            C.bias_mag(gy))):
+            assert m.over == 0 and m.compared > 0 and m.worst <= 1, m.message
+            worst = max(worst, m.worst)
+        n_cases += 1
+    print(f"{n_cases} cases, three honest results each, worst err / bound {worst:.3f}")
+    assert n_cases >= 50
+
+
+def test_subtly_wrong_gradients_pass_the_old_assertion_and_fail_the_bound(shapes):
+    """Every result here is fp32, so of the covers' mutants only M5 applies (M1 and M3 are about bf16 results) -- and M5 as the other three
+    covers run it (elements under 5 % of the largest scaled by 1 + 2^-6: up to 7.8e-4 of max |ref|) is caught by the old 1e-4 at every case: it
+    is evaluated and counted here, and nothing of it is in the gap.  The same mutant at a tenth of the threshold (elements under 0.5 % of the
+    largest, up to 7.8e-5 of max |ref|) passes the old assertion and must fail the bound at every case."""
+    gap = B.Gap(("M5", "M5 under 0.5 %"))
+    for k, route, s, n in _small_cases(shapes):
+        x, gy, alpha = C.inputs(route, s, k.dtype, seed=5, n=n)
+        ref, mag = C.reference(route, s, x, gy, alpha), C.weight_mag(route, s, x, gy, alpha)
+        bnd = C.bound(C.FAMILY_NAMES[k.family], ref, mag, C.weight_products(s, n), C.unit_roundoff(k.family))
+        tag = f"{C.kernel_id(k)} {route.name} {tuple(s)} n {n}"
+        gap.check("M5", tag, B.stored_as(B.scale_small(ref), bf16=False), ref, bnd, C.TOLERANCE)
+        gap.check("M5 under 0.5 %", tag, B.stored_as(B.scale_small(ref, below=0.005), bf16=False), ref, bnd, C.TOLERANCE)
+    gap.close(need_half=("M5 under 0.5 %",))
+    assert gap.kept["M5"] == 0 and gap.evaluated["M5"] >= 50
