@@ -33,6 +33,15 @@ the device"); the figures come from the classifier's features, so `--classifier 
     python gan_synth_main.py --evaluate --prd --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
     python gan_synth_main.py --evaluate --ndb --prd --prd_k 5 --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
 
+`--f0` (not in the reference's driver) measures pitch on the AUDIO, without a classifier: a YIN f0 tracker on HIP kernels (gansynth_amd/pitch.py,
+DESIGN.md "Pitch tracking on the device") follows every real and every generated note, and the dict gains f0_pitch_accuracy (the share of notes
+within 50 cents of their label), f0_chroma_accuracy (the same up to octaves), f0_median_abs_cents, f0_jitter_cents and f0_voiced_fraction for the
+generated notes and the same five with the prefix real_ -- the calibration to read them against, since YIN is not perfect on real instruments.
+It needs no classifier either:
+
+    python gan_synth_main.py --evaluate --f0 --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
+    python gan_synth_main.py --evaluate --f0 --classifier none --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord'
+
 `--synthesize` (not in the reference) renders a score -- a Standard MIDI File or a JSON list of {"pitch", "velocity", "start", "end"}
 notes -- into one 16 kHz 16-bit WAV: every note generated at its pitch, the timbre gliding between latent anchors, the mixdown on the
 device (GANSynth.synthesize).  It needs no dataset:
@@ -132,6 +141,9 @@ parser.add_argument("--swd", action="store_true",
 parser.add_argument("--prd", action="store_true",
                     help="--evaluate: also precision, recall, density and coverage of the generated features against the real ones, from "
                          "k-nearest-neighbour radii on the device; needs the classifier")
+parser.add_argument("--f0", action="store_true",
+                    help="--evaluate: also the pitch accuracy of the audio itself, real and generated, from a YIN f0 tracker on the device: accuracy within "
+                         "50 cents, the same up to octaves, median deviation, jitter and voiced fraction; needs no classifier")
 parser.add_argument("--prd_k", type=int, default=3, help="--prd: the neighbour whose distance is a row's radius")
 parser.add_argument("--dtype", choices=["f32", "bf16"], default="bf16", help="activation storage (master weights / Adam stay fp32)")
 parser.add_argument("--save_checkpoint_steps", type=int, default=1000)
@@ -407,6 +419,8 @@ def main(args):
     check_controller_args(args)
     check_true_peak_args(args)
     check_prd_args(args)
+    if getattr(args, "f0", False) and not args.evaluate:
+        raise SystemExit("--f0 applies to --evaluate only")
     if args.pack_bank is not None:
         pack_bank(args, range(24, 85), [0])
         return
@@ -483,8 +497,8 @@ def main(args):
         if args.synthetic and args.num_generate_batches is None:
             raise SystemExit("--evaluate --synthetic needs --num_generate_batches (synthetic input never ends)")
         no_classifier = args.classifier.lower() == "none"
-        if no_classifier and not args.swd:
-            raise SystemExit("--evaluate --classifier none needs --swd (every other figure comes from the pitch classifier)")
+        if no_classifier and not (args.swd or getattr(args, "f0", False)):
+            raise SystemExit("--evaluate --classifier none needs --swd or --f0 (every other figure comes from the pitch classifier)")
         kept = model.real_input_fn   # evaluate runs over an input of its own: --generate after it still has its batches
         model.real_input_fn = real_input_fn_factory(False)
         try:
@@ -497,6 +511,7 @@ def main(args):
                 weights=args.weights,
                 **(dict(extra_metrics=True, ndb="device") if args.ndb else {}),     # (without the flags the call is the one it was)
                 **(dict(swd=True) if args.swd else {}),
+                **(dict(f0=True, pitches=pitches) if getattr(args, "f0", False) else {}),
                 **(dict(prd=True, prd_k=args.prd_k) if args.prd else {})))
         finally:
             model.real_input_fn = kept

@@ -263,6 +263,10 @@ SIGNATURES = {
     "gs_knn_slices": (I, [L, L, I]),
     "gs_knn_kth": (I, [P, L, L, P, L, L, I, I, I, P, P, Z, P]),
     "gs_knn_within": (I, [P, L, L, P, L, L, I, P, P, P, Z, P]),
+    "gs_yin_frames": (L, [L, I, I, I]),
+    "gs_yin_difference": (I, [P, L, L, L, I, I, I, P, P, P]),
+    "gs_yin_pick": (I, [P, L, L, I, I, c_double, P, P, P, P]),
+    "gs_yin_track": (I, [P, L, L, L, I, I, I, I, c_double, P, P, P, P, P]),
     # W = POINTER(GsLoudness), the meter of one rate
     "gs_loudness_design": (I, [I, W]),
     "gs_loudness_hops": (L, [W, L]),

@@ -528,6 +528,82 @@ def knn_within(q, ref, radius2):
     return get().knn_within(q, ref, radius2)
 
 
+YIN_MAX_LAGS, YIN_MAX_WINDOW = 1024, 4096   # GS_YIN_MAX_LAGS, GS_YIN_MAX_WINDOW
+
+
+def _yin_int(what, name, v):
+    if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+        raise ValueError(f"{what}: {name} must be an integer (got {v!r})")
+    return int(v)
+
+
+def yin_frames(n, window, lags, hop):
+    """gs_yin_frames restated on the host: (n - window - lags) // hop + 1 frames of a row of n samples; ValueError, by argument name, for what
+    the entries refuse."""
+    n, window, lags, hop = (_yin_int("yin", name, v) for name, v in (("n", n), ("window", window), ("lags", lags), ("hop", hop)))
+    if not 4 <= lags <= YIN_MAX_LAGS:
+        raise ValueError(f"yin: lags must be in [4, {YIN_MAX_LAGS}] (got {lags})")
+    if not lags <= window <= YIN_MAX_WINDOW:
+        raise ValueError(f"yin: window must be in [lags, {YIN_MAX_WINDOW}] (got {window}, lags {lags})")
+    if hop < 1:
+        raise ValueError(f"yin: hop must be positive (got {hop})")
+    if n < window + lags:
+        raise ValueError(f"yin: a row of {n} samples is shorter than window + lags = {window + lags}")
+    return (n - window - lags) // hop + 1
+
+
+def _yin_pick_args(what, lags, tau_min, threshold):
+    lags, tau_min = _yin_int(what, "lags", lags), _yin_int(what, "tau_min", tau_min)
+    if tau_min < 2:
+        raise ValueError(f"{what}: tau_min must be at least 2 (got {tau_min})")
+    if not tau_min + 2 <= lags <= YIN_MAX_LAGS:
+        raise ValueError(f"{what}: lags must be in [tau_min + 2, {YIN_MAX_LAGS}] (got {lags}, tau_min {tau_min})")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.floating)) or not float(threshold) == float(threshold):
+        raise ValueError(f"{what}: threshold must be a number (got {threshold!r})")
+
+
+def yin_difference_shapes(x, window, lags, hop):
+    """The host side of yin_difference: -> (rows, n, frames) of x [rows, n] (fp32).  ValueError by argument name; needs no device."""
+    rows, n = _kmeans_matrix("yin_difference", "x", x)
+    return rows, n, yin_frames(n, window, lags, hop)
+
+
+def yin_difference(x, window, lags, hop):
+    """HipKernels.yin_difference of the process-wide kernel object; the shapes are refused here, before a device is asked for."""
+    yin_difference_shapes(x, window, lags, hop)
+    return get().yin_difference(x, window, lags, hop)
+
+
+def yin_pick_shapes(d, tau_min, threshold):
+    """The host side of yin_pick: -> (rows, frames, lags) of d [rows, frames, lags] (fp32, contiguous).  ValueError by argument name; needs no
+    device."""
+    if not isinstance(d, torch.Tensor) or d.dim() != 3 or d.dtype != torch.float32 or 0 in d.shape or not d.is_contiguous():
+        got = f"{tuple(d.shape)} {d.dtype}" if isinstance(d, torch.Tensor) else type(d).__name__
+        raise ValueError(f"yin_pick: d must be a non-empty contiguous [rows, frames, lags] fp32 tensor (got {got})")
+    _yin_pick_args("yin_pick", int(d.shape[2]), tau_min, threshold)
+    return tuple(int(s) for s in d.shape)
+
+
+def yin_pick(d, tau_min, threshold):
+    """HipKernels.yin_pick of the process-wide kernel object; the shapes are refused here, before a device is asked for."""
+    yin_pick_shapes(d, tau_min, threshold)
+    return get().yin_pick(d, tau_min, threshold)
+
+
+def yin_track_shapes(x, window, lags, hop, tau_min, threshold):
+    """The host side of yin_track: -> (rows, n, frames) of x [rows, n] (fp32).  ValueError by argument name; needs no device."""
+    rows, n = _kmeans_matrix("yin_track", "x", x)
+    frames = yin_frames(n, window, lags, hop)
+    _yin_pick_args("yin_track", lags, tau_min, threshold)
+    return rows, n, frames
+
+
+def yin_track(x, window, lags, hop, tau_min, threshold):
+    """HipKernels.yin_track of the process-wide kernel object; the shapes are refused here, before a device is asked for."""
+    yin_track_shapes(x, window, lags, hop, tau_min, threshold)
+    return get().yin_track(x, window, lags, hop, tau_min, threshold)
+
+
 def swd_levels(h, w):
     """gs_swd_levels restated on the host: the number of l >= 0 with min(h, w) >> l >= 16; 0 when there is none, when a size that is halved on
     the way down is odd or when a side exceeds SWD_MAX_SIDE."""
@@ -2293,6 +2369,43 @@ class HipKernels(object):
         _lib.check(self.lib.gs_knn_within(q2.data_ptr(), ldq, n, r2.data_ptr(), ldr, m, d, radius2.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
                                           _stream()), "gs_knn_within")
         return count
+
+    def yin_difference(self, x, window, lags, hop):
+        """gs_yin_difference (include/gansynth_hip.h): -> (d [rows, frames, lags] fp32, power [rows, frames] fp32) of x [rows, n] (fp32 on the
+        device, any row stride): YIN's difference function in the direct form and the frame power."""
+        rows, n, frames = yin_difference_shapes(x, window, lags, hop)
+        x2, ldx = self._kmeans_rows("yin_difference", x)
+        d = torch.empty((rows, frames, int(lags)), dtype=torch.float32, device=x.device)
+        power = torch.empty((rows, frames), dtype=torch.float32, device=x.device)
+        _lib.check(self.lib.gs_yin_difference(x2.data_ptr(), ldx, rows, n, int(window), int(lags), int(hop), d.data_ptr(), power.data_ptr(), _stream()),
+                   "gs_yin_difference")
+        return d, power
+
+    def yin_pick(self, d, tau_min, threshold):
+        """gs_yin_pick (include/gansynth_hip.h): -> (lag [rows, frames] int32, period and aperiodicity [rows, frames] float64) from
+        d [rows, frames, lags] (fp32, contiguous, on the device): cumulative-mean normalisation, pick and parabola in float64."""
+        rows, frames, lags = yin_pick_shapes(d, tau_min, threshold)
+        if not d.is_cuda:
+            raise ValueError(f"yin_pick: d must be on the HIP device (it is on {d.device})")
+        lag = torch.empty((rows, frames), dtype=torch.int32, device=d.device)
+        period = torch.empty((rows, frames), dtype=torch.float64, device=d.device)
+        aper = torch.empty((rows, frames), dtype=torch.float64, device=d.device)
+        _lib.check(self.lib.gs_yin_pick(d.data_ptr(), rows, frames, lags, int(tau_min), float(threshold), lag.data_ptr(), period.data_ptr(), aper.data_ptr(),
+                                        _stream()), "gs_yin_pick")
+        return lag, period, aper
+
+    def yin_track(self, x, window, lags, hop, tau_min, threshold):
+        """gs_yin_track (include/gansynth_hip.h): one launch, -> (lag int32, period float64, aperiodicity float64, power fp32), each
+        [rows, frames], of x [rows, n] (fp32 on the device, any row stride); bit for bit yin_pick(yin_difference(x))."""
+        rows, n, frames = yin_track_shapes(x, window, lags, hop, tau_min, threshold)
+        x2, ldx = self._kmeans_rows("yin_track", x)
+        lag = torch.empty((rows, frames), dtype=torch.int32, device=x.device)
+        period = torch.empty((rows, frames), dtype=torch.float64, device=x.device)
+        aper = torch.empty((rows, frames), dtype=torch.float64, device=x.device)
+        power = torch.empty((rows, frames), dtype=torch.float32, device=x.device)
+        _lib.check(self.lib.gs_yin_track(x2.data_ptr(), ldx, rows, n, int(window), int(lags), int(hop), int(tau_min), float(threshold), lag.data_ptr(),
+                                         period.data_ptr(), aper.data_ptr(), power.data_ptr(), _stream()), "gs_yin_track")
+        return lag, period, aper, power
 
     @staticmethod
     def _swd_device(what, first, *others):

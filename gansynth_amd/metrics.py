@@ -2,7 +2,8 @@
 softmax, KL divergence, inception score, Frechet distance between two feature sets, the two-proportion z-test and the number of
 statistically different bins (NDB) of a k-means partition of the real features.  num_different_bins_device is NDB with the partition made on
 the device (kmeans.py: this project's own clustering rules, no scikit-learn), beside the Jensen-Shannon divergence of the bin proportions.
-precision_recall_device is precision, recall, density and coverage from k-nearest-neighbour radii on the device (manifold.py)."""
+precision_recall_device is precision, recall, density and coverage from k-nearest-neighbour radii on the device (manifold.py).
+f0_pitch_accuracy_device is pitch accuracy from the audio itself, a YIN f0 tracker on the device (pitch.py)."""
 import numpy as np
 import scipy.linalg
 import scipy.stats
@@ -142,3 +143,28 @@ def sliced_wasserstein_distance_device(real_images, fake_images, seed=0, details
     if details is not None:
         details.update(levels=out["levels"], sizes=out["sizes"], n=out["n"])
     return out["mean"]
+
+
+def f0_pitch_accuracy_device(waveforms, pitches, details=None):
+    """Pitch accuracy of notes from their AUDIO, without a classifier: waveforms [notes, n] (a tensor or array, fp32, 16 kHz) tracked by
+    pitch.track (this project's own, stated rules: a YIN tracker on HIP kernels, production parameters) and judged against `pitches` [notes]
+    (MIDI numbers) by pitch.note_statistics -> pitch.summarize's dict: f0_pitch_accuracy, f0_chroma_accuracy, f0_median_abs_cents,
+    f0_jitter_cents and f0_voiced_fraction.  `details` (a dict) receives the per-note cents and jitter (NaN: unvoiced) and voiced (frames).
+    YIN is not perfect on real instruments: read a generated set's figures against those of the real set."""
+    import torch
+    from . import kernels, pitch
+    t = waveforms if isinstance(waveforms, torch.Tensor) else torch.from_numpy(np.array(waveforms, dtype=np.float32))
+    if t.dim() != 2 or t.shape[0] == 0:
+        raise ValueError(f"f0_pitch_accuracy_device: waveforms must be a non-empty [notes, samples] set (got {tuple(t.shape)})")
+    pitches = np.asarray(pitches, dtype=np.float64).reshape(-1)
+    if pitches.shape[0] != t.shape[0]:
+        raise ValueError(f"f0_pitch_accuracy_device: {pitches.shape[0]} pitches for {t.shape[0]} notes")
+    kernels.yin_track_shapes(t.float(), pitch.WINDOW, pitch.LAGS, pitch.HOP, pitch.TAU_MIN, pitch.THRESHOLD)   # (before a device is asked for)
+    on_hip = isinstance(kernels.get(), kernels.HipKernels)   # (a host without a device fails here, with the library's message)
+    if on_hip and not t.is_cuda:
+        t = t.cuda()
+    tracked = pitch.track(t)
+    stats = pitch.note_statistics(tracked.period, tracked.aperiodicity, tracked.power, pitches)
+    if details is not None:
+        details.update(cents=stats.cents, jitter=stats.jitter, voiced=stats.voiced)
+    return pitch.summarize(stats.cents, stats.jitter)

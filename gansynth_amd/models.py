@@ -1134,7 +1134,8 @@ class GANSynth(Iterations, DataParallel, Capture):
 
     # ------------------------------------------------------------------------------------------- evaluation
     def evaluate(self, model_dir, config, classifier, input_name="images:0", output_names=("features:0", "logits:0"), batch_size=64,
-                 extra_metrics=False, classifier_dtype=torch.float32, features_out=None, weights="live", ndb="sklearn", swd=False, swd_seed=0, prd=False, prd_k=3):
+                 extra_metrics=False, classifier_dtype=torch.float32, features_out=None, weights="live", ndb="sklearn", swd=False, swd_seed=0, prd=False, prd_k=3,
+                 f0=False, pitches=range(24, 85)):
         """models.py:196-230: the Frechet distance between the pitch classifier's features of real and generated spectrograms.
 
         Restores the latest checkpoint of `model_dir` as `generate` does, then for every batch of `real_input_fn()` until it runs dry:
@@ -1154,8 +1155,17 @@ class GANSynth(Iterations, DataParallel, Capture):
         kernels, corners and directions seeded by `swd_seed`), every batch added as it arrives -- the images are not kept.  `classifier` may
         be None together with `swd`: no classifier is loaded or run and only the two SWD keys come back.  `prd`: the dict gains precision,
         recall, density and coverage of the fake features against the real ones -- the features of the FID -- from
-        metrics.precision_recall_device (manifold.py: `prd_k`-nearest-neighbour radii on HIP kernels); it needs the classifier.  One process
-        only."""
+        metrics.precision_recall_device (manifold.py: `prd_k`-nearest-neighbour radii on HIP kernels); it needs the classifier.  `f0`: pitch from
+        the AUDIO, without a classifier (pitch.py: a YIN f0 tracker on HIP kernels, DESIGN.md "Pitch tracking on the device").  Every batch's real
+        waveforms (the data itself where it is waveforms, else the images through convert_images_to_waveform) and the generated images through the
+        inverse transform `generate` uses are tracked and judged against THAT batch's labels -- a label index is a MIDI pitch through
+        sorted(`pitches`), the list `synthesize` gets -- note by note as the batches arrive; the waveforms are not kept.  The dict gains, for the
+        generated side, f0_pitch_accuracy (the share of notes whose median deviation from the label is under 50 cents), f0_chroma_accuracy (the same
+        with the cents folded to +-600: octave errors are the gap between the two), f0_median_abs_cents and f0_jitter_cents (the mean within-note
+        standard deviation), both over the notes counted accurate, and f0_voiced_fraction; and the same five with the prefix real_.  YIN is not
+        perfect on real instruments (bass notes, mallets): the real_ figures are the calibration the generated ones are read against.
+        features_out receives real_f0_cents and fake_f0_cents (one a note, NaN for an unvoiced one).  `classifier` may be None together with `swd`
+        or `f0`.  One process only."""
         import numpy as np
         from . import metrics, networks
         del config
@@ -1171,14 +1181,19 @@ class GANSynth(Iterations, DataParallel, Capture):
         if prd and (not isinstance(prd_k, int) or isinstance(prd_k, bool) or not 1 <= prd_k <= 8):   # (before the first batch, not after the last)
             raise ValueError(f"evaluate: prd_k must be an integer in [1, 8] (got {prd_k!r})")
         if classifier is None:
-            if not swd:
-                raise ValueError("evaluate: classifier=None needs swd=True (every other figure comes from the pitch classifier)")
+            if not swd and not f0:
+                raise ValueError("evaluate: classifier=None needs swd=True or f0=True (every other figure comes from the pitch classifier)")
             resnet = None
         elif isinstance(classifier, networks.ResNet):
             resnet = classifier
         else:
             resnet = networks.ResNet.pitch_classifier().load(classifier)
         sliced = None
+        tracked = None
+        if f0:
+            from . import pitch
+            table = np.asarray(sorted(pitches), dtype=np.float64)
+            tracked = {"real": pitch.NoteAccumulator(rate=self.spectral_params["sample_rate"]), "fake": pitch.NoteAccumulator(rate=self.spectral_params["sample_rate"])}
         real_f, fake_f, real_l, fake_l, labs = [], [], [], [], []
         pending = {"real": [], "fake": []}
 
@@ -1216,6 +1231,12 @@ class GANSynth(Iterations, DataParallel, Capture):
                         from . import swd as swd_module
                         sliced = swd_module.SlicedWasserstein(real.shape, seed=swd_seed)
                     sliced.add(real, fake)
+                if f0:
+                    if labels.shape[1] != len(table):
+                        raise ValueError(f"evaluate: f0=True reads a label index as a pitch: {labels.shape[1]} label columns, {len(table)} pitches")
+                    note_pitches = table[labels.argmax(dim=1).cpu().numpy()]
+                    tracked["real"].add(data if data.dim() == 2 else spectral_ops.convert_images_to_waveform(data, **self.spectral_params), note_pitches)
+                    tracked["fake"].add(spectral_ops.convert_images_to_waveform(fake, **self.spectral_params), note_pitches)
                 if resnet is None:
                     continue
                 pending["real"].append(real)
@@ -1231,6 +1252,12 @@ class GANSynth(Iterations, DataParallel, Capture):
             sliced_out = dict(sliced_wasserstein_distance=result["mean"], sliced_wasserstein_distance_levels=result["levels"])
             if features_out is not None:
                 features_out.update(swd_sizes=result["sizes"])
+        if f0:
+            for which, prefix in (("fake", ""), ("real", "real_")):
+                figures, cents, _ = tracked[which].result()
+                sliced_out.update({prefix + key: value for key, value in figures.items()})
+                if features_out is not None:
+                    features_out[which + "_f0_cents"] = cents
         if resnet is None:
             return sliced_out
         flush("real", True)

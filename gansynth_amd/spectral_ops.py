@@ -180,3 +180,21 @@ def convert_to_waveform(log_mel_magnitude_spectrograms, mel_instantaneous_freque
     """spectral_ops.py:97-149."""
     images = torch.stack([log_mel_magnitude_spectrograms, mel_instantaneous_frequencies], dim=1)
     return convert_images_to_waveform(images, waveform_length, sample_rate, spectrogram_shape, overlap)
+
+
+def estimate_f0(waveforms, sample_rate=16000, window=1024, lags=512, hop=256, tau_min=8, threshold=0.15):
+    """The fundamental frequency of waveforms [B, n] or [n] (fp32, on the device), frame by frame: a YIN tracker on HIP kernels (pitch.py,
+    one gs_yin_track call; the rules are in DESIGN.md "Pitch tracking on the device").  -> (f0 [B, frames] float64 in Hz, NaN where the frame
+    is unvoiced -- its aperiodicity is not under `threshold`, or its power not above 1e-4 of the row's largest --, aperiodicity [B, frames]
+    float64), device tensors; frame f covers the samples from f * hop.  Lags up to `lags` - 2 samples are searched: at 16 kHz the defaults
+    reach down to 31.4 Hz.  Not in the reference."""
+    from . import pitch
+    if not sample_rate > 0:
+        raise ValueError(f"estimate_f0: sample_rate must be positive (got {sample_rate})")
+    t = pitch.track(waveforms, window=window, lags=lags, hop=hop, tau_min=tau_min, threshold=threshold)
+    power = t.power.double()   # (the gate in float64, as pitch.note_statistics applies it)
+    voiced = (t.aperiodicity < threshold) & (power > pitch.POWER_GATE * power.max(dim=1, keepdim=True).values)
+    f0 = torch.where(voiced, float(sample_rate) / t.period, torch.full_like(t.period, float("nan")))
+    if waveforms.dim() == 1:
+        return f0[0], t.aperiodicity[0]
+    return f0, t.aperiodicity

@@ -1231,6 +1231,40 @@ int gs_knn_kth(const float* a, int64_t lda, int64_t n, const float* b, int64_t l
 int gs_knn_within(const float* q, int64_t ldq, int64_t n, const float* ref, int64_t ldr, int64_t m, int d, const float* radius2, int32_t* count, void* ws,
                   size_t ws_bytes, void* stream);
 
+/* ---- YIN fundamental-frequency tracker (de Cheveigne & Kawahara 2002, steps 1-5), for gansynth_amd/pitch.py, metrics.f0_pitch_accuracy_device
+ * and GANSynth.evaluate(f0=True); DESIGN.md "Pitch tracking on the device" ----
+ * x holds `rows` rows of n fp32 samples, ldx >= n floats apart, 4-byte aligned (any 4-byte alignment); inputs are finite.  A row has
+ * F = (n - W - L) / hop + 1 frames (integer division), frame f starts at t = f hop and reads x[t .. t + W + L - 2].  Deterministic: no float
+ * atomics, two calls with the same arguments write the same bits.  Capture-safe: no allocation, no synchronisation, no workspace.
+ *
+ *   1. d(tau) = sum_{j < W} (x[t + j] - x[t + j + tau])^2 for tau in [0, L), the direct form in fp32 on the vector ALU, every term a rounded
+ *      difference squared into an FMA, the terms added in a fixed order: within (W + 8) 2^-24, relative, of the exact sum, and d(0) = 0 exactly.
+ *      (Never energy plus cross-correlation: that form cancels and has no relative bound.)  power = (1 / W) sum_{j < W} x[t + j]^2, in fp32,
+ *      within the same bound.
+ *   2. In float64: S(tau) = d(1) + ... + d(tau), added sequentially in ascending order; c(0) = 1, c(tau) = d(tau) tau / S(tau), and c(tau) = 1
+ *      where S(tau) = 0.
+ *   3. Over tau in [tau_min, L - 2]: the first tau with c(tau) < threshold, then, while tau + 1 <= L - 2 and c(tau + 1) < c(tau), tau + 1.  If
+ *      no tau is under the threshold: the argmin of c over the range, the lowest index on a tie.
+ *   4. den = c(tau - 1) - 2 c(tau) + c(tau + 1); offset = 0.5 (c(tau - 1) - c(tau + 1)) / den clamped to [-1, 1] if den > 0, else 0;
+ *      period = tau + offset (float64), aperiodicity = c(tau).
+ *
+ * gs_yin_difference: rule 1.  d is [rows][F][L] fp32, power [rows][F] fp32, both dense.
+ * gs_yin_pick: rules 2-4 on a dense d [rows][F][L].  lag is [rows][F] int32, period and aperiodicity [rows][F] float64 (8-byte aligned).
+ * gs_yin_track: the production route, one launch, d never leaves the chip: the four outputs, bit for bit those of gs_yin_pick after
+ *   gs_yin_difference (the same device code).
+ * gs_yin_frames: host arithmetic; F, or 0 (and a message) for a shape the entries refuse.
+ * GS_ERR_ARG with a message that names the argument, before anything is dereferenced or launched: rows < 1, hop < 1, tau_min < 2,
+ * L outside [tau_min + 2, GS_YIN_MAX_LAGS] (gs_yin_difference: [4, GS_YIN_MAX_LAGS]), W outside [L, GS_YIN_MAX_WINDOW], n < W + L, ldx < n,
+ * more than 2^31 - 1 frames in all, a NULL or misaligned pointer. */
+#define GS_YIN_MAX_LAGS 1024
+#define GS_YIN_MAX_WINDOW 4096
+int64_t gs_yin_frames(int64_t n, int W, int L, int hop);
+int gs_yin_difference(const float* x, int64_t ldx, int64_t rows, int64_t n, int W, int L, int hop, float* d, float* power, void* stream);
+int gs_yin_pick(const float* d, int64_t rows, int64_t frames, int L, int tau_min, double threshold, int32_t* lag, double* period, double* aperiodicity,
+                void* stream);
+int gs_yin_track(const float* x, int64_t ldx, int64_t rows, int64_t n, int W, int L, int hop, int tau_min, double threshold, int32_t* lag, double* period,
+                 double* aperiodicity, float* power, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
