@@ -42,6 +42,16 @@ It needs no classifier either:
     python gan_synth_main.py --evaluate --f0 --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
     python gan_synth_main.py --evaluate --f0 --classifier none --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord'
 
+`--kid` (not in the reference's driver) adds the kernel inception distance (Binkowski et al. 2018) of the generated features against the real
+ones: kernel_inception_distance, the unbiased estimate of the squared maximum mean discrepancy under the cubic kernel over all notes -- unlike
+the Frechet distance its expectation does not depend on the number of notes, and it may be negative -- and kernel_inception_distance_subset_mean
+and kernel_inception_distance_subset_std over `--kid_subsets` seeded subsets (default 100) of `--kid_subset_size` notes a side (default 1000, or
+all there are).  All pairs on an fp64 matrix-core HIP kernel (gansynth_amd/kid.py, DESIGN.md "KID on the device"); the figures come from the
+classifier's features, so `--classifier none` is refused:
+
+    python gan_synth_main.py --evaluate --kid --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
+    python gan_synth_main.py --evaluate --prd --kid --kid_subsets 50 --kid_subset_size 500 --model_dir gan_synth_model --filenames 'nsynth_test*.tfrecord' --classifier pitch_classifier.pb
+
 `--synthesize` (not in the reference) renders a score -- a Standard MIDI File or a JSON list of {"pitch", "velocity", "start", "end"}
 notes -- into one 16 kHz 16-bit WAV: every note generated at its pitch, the timbre gliding between latent anchors, the mixdown on the
 device (GANSynth.synthesize).  It needs no dataset:
@@ -145,6 +155,11 @@ parser.add_argument("--f0", action="store_true",
                     help="--evaluate: also the pitch accuracy of the audio itself, real and generated, from a YIN f0 tracker on the device: accuracy within "
                          "50 cents, the same up to octaves, median deviation, jitter and voiced fraction; needs no classifier")
 parser.add_argument("--prd_k", type=int, default=3, help="--prd: the neighbour whose distance is a row's radius")
+parser.add_argument("--kid", action="store_true",
+                    help="--evaluate: also the kernel inception distance of the generated features against the real ones, over all notes and as mean "
+                         "and standard deviation over subsets, all pairs on the device in fp64; needs the classifier")
+parser.add_argument("--kid_subsets", type=int, default=100, help="--kid: the number of subsets behind the mean and the standard deviation (0: none)")
+parser.add_argument("--kid_subset_size", type=int, default=1000, help="--kid: notes a side of a subset (at most all there are)")
 parser.add_argument("--dtype", choices=["f32", "bf16"], default="bf16", help="activation storage (master weights / Adam stay fp32)")
 parser.add_argument("--save_checkpoint_steps", type=int, default=1000)
 parser.add_argument("--log_tensor_steps", type=int, default=100)
@@ -302,6 +317,22 @@ def check_prd_args(args):
     return wanted
 
 
+def check_kid_args(args):
+    """--kid, --kid_subsets and --kid_subset_size against --evaluate and --classifier: SystemExit with a message.  -> whether the figures are asked for."""
+    wanted, subsets, size = getattr(args, "kid", False), getattr(args, "kid_subsets", 100), getattr(args, "kid_subset_size", 1000)
+    if not wanted and (subsets != 100 or size != 1000):
+        raise SystemExit("--kid_subsets and --kid_subset_size need --kid")
+    if wanted and not getattr(args, "evaluate", False):
+        raise SystemExit("--kid applies to --evaluate only")
+    if wanted and str(getattr(args, "classifier", "")).lower() == "none":
+        raise SystemExit("--kid needs the pitch classifier (the kernel inception distance comes from its features): not --classifier none")
+    if wanted and subsets < 0:
+        raise SystemExit(f"--kid_subsets must not be negative (got {subsets})")
+    if wanted and size < 2:
+        raise SystemExit(f"--kid_subset_size must be at least 2 (got {size})")
+    return wanted
+
+
 def synthesize_to_wav(model, args, pitches, restore=True, log=print):
     """--synthesize: the score args.synthesize through GANSynth.synthesize into the 16-bit WAV args.output (the kernel's own PCM: [T], or
     the interleaved [T, 2] of --stereo, which is a two-channel WAV's layout).  With --reverb / --reverb_ir: the unnormalised clip at the
@@ -419,6 +450,7 @@ def main(args):
     check_controller_args(args)
     check_true_peak_args(args)
     check_prd_args(args)
+    check_kid_args(args)
     if getattr(args, "f0", False) and not args.evaluate:
         raise SystemExit("--f0 applies to --evaluate only")
     if args.pack_bank is not None:
@@ -512,7 +544,8 @@ def main(args):
                 **(dict(extra_metrics=True, ndb="device") if args.ndb else {}),     # (without the flags the call is the one it was)
                 **(dict(swd=True) if args.swd else {}),
                 **(dict(f0=True, pitches=pitches) if getattr(args, "f0", False) else {}),
-                **(dict(prd=True, prd_k=args.prd_k) if args.prd else {})))
+                **(dict(prd=True, prd_k=args.prd_k) if args.prd else {}),
+                **(dict(kid=True, kid_subsets=args.kid_subsets, kid_subset_size=args.kid_subset_size) if getattr(args, "kid", False) else {})))
         finally:
             model.real_input_fn = kept
 

@@ -77,6 +77,7 @@ KMEANS_MAX_K, KMEANS_TILE, KMEANS_MAX_SLICES, KMEANS_MAX_N, KMEANS_MAX_D = 256, 
 SWD_DESC, SWD_PATCHES, SWD_SORT_TILE, SWD_MAX_N, SWD_MAX_ROWS, SWD_MAX_SIDE, SWD_MAX_BATCH = 98, 128, 4096, 1 << 21, 65535, 16384, 65536   # GS_SWD_*
 SWD_STAGE_PYRAMID, SWD_STAGE_MOMENTS, SWD_STAGE_SORT, SWD_STAGE_L1 = range(4)   # GS_SWD_STAGE_*
 KNN_MAX_K, KNN_BLOCKS, KNN_MIN_SLICE_ROWS = 8, 3072, 256   # GS_KNN_MAX_K, _BLOCKS, _MIN_SLICE_ROWS
+KID_TILE, KID_MAX_ROWS, KID_MAX_SUBSETS = 128, 1 << 21, 65535   # GS_KID_TILE, _MAX_ROWS, _MAX_SUBSETS
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 192000              # GS_LOUDNESS_MIN_RATE, GS_LOUDNESS_MAX_RATE
 LOUDNESS_STEPS = 8                                                # GS_LOUDNESS_STEPS: matrix powers per scan of gs_loudness
 
@@ -267,6 +268,8 @@ SIGNATURES = {
     "gs_yin_difference": (I, [P, L, L, L, I, I, I, P, P, P]),
     "gs_yin_pick": (I, [P, L, L, I, I, c_double, P, P, P, P]),
     "gs_yin_track": (I, [P, L, L, L, I, I, I, I, c_double, P, P, P, P, P]),
+    "gs_kid_workspace_bytes": (Z, [L, L, I, I, L]),
+    "gs_kid_sums": (I, [P, L, L, P, L, L, I, P, P, I, L, P, P, Z, P]),
     # W = POINTER(GsLoudness), the meter of one rate
     "gs_loudness_design": (I, [I, W]),
     "gs_loudness_hops": (L, [W, L]),

@@ -11,7 +11,7 @@ OUT=${1:-..}
 mkdir -p obj
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result $GS_EXTRA_FLAGS"
 pids=()
-for f in conv_igemm conv_wgrad conv_thin conv_api elementwise small_ops dense spectral spectral_wave classifier classifier_bwd summary synth mix_curves warp sustain clip_finish bank resample fftconv limiter loudness true_peak kmeans swd knn yin; do
+for f in conv_igemm conv_wgrad conv_thin conv_api elementwise small_ops dense spectral spectral_wave classifier classifier_bwd summary synth mix_curves warp sustain clip_finish bank resample fftconv limiter loudness true_peak kmeans swd knn yin kid; do
   [ -f $f.hip ] || continue
   stale=0   # (-nt also holds when the object is missing)
   for s in $f.hip *.h ../../include/gansynth_hip.h; do [ $s -nt obj/$f.o ] && stale=1; done

@@ -528,6 +528,49 @@ def knn_within(q, ref, radius2):
     return get().knn_within(q, ref, radius2)
 
 
+def kid_sums_shapes(x, y, xi=None, yi=None):
+    """The host side of kid_sums: -> (n, m, d, subsets, size) of x [n, d] and y [m, d] (fp32, at least 2 rows each) and the index lists xi, yi
+    ([subsets, size] integers, numpy or torch, both or neither; (n, m, d, 0, 0) without).  ValueError by argument name; needs no device (lists
+    that live on the device are read back for their range)."""
+    n, d = _kmeans_matrix("kid_sums", "x", x)
+    m, _ = _kmeans_matrix("kid_sums", "y", y, d)
+    for name, rows in (("x", n), ("y", m)):
+        if rows < 2:
+            raise ValueError(f"kid_sums: {name} must have at least 2 rows (got {rows})")
+        if rows > _lib.KID_MAX_ROWS:
+            raise ValueError(f"kid_sums: {name} must have at most {_lib.KID_MAX_ROWS} rows (got {rows})")
+    if d > _lib.KMEANS_MAX_D:
+        raise ValueError(f"kid_sums: x must have at most {_lib.KMEANS_MAX_D} columns (got {d})")
+    if xi is None and yi is None:
+        return n, m, d, 0, 0
+    shapes = []
+    for name, t, rows in (("xi", xi, n), ("yi", yi, m)):
+        integral = (isinstance(t, torch.Tensor) and t.dtype in (torch.int32, torch.int64)) or (isinstance(t, np.ndarray) and t.dtype.kind in "iu")
+        if not integral or len(t.shape) != 2 or t.shape[0] < 1:
+            got = "None" if t is None else f"{tuple(t.shape)} {t.dtype}" if hasattr(t, "shape") else type(t).__name__
+            raise ValueError(f"kid_sums: {name} must be a [subsets, size] integer array or tensor with at least one subset (got {got})")
+        if t.shape[1] < 2:
+            raise ValueError(f"kid_sums: {name} holds subsets of size {t.shape[1]}: size must be at least 2")
+        low, high = (int(t.min()), int(t.max()))
+        if low < 0 or high >= rows:
+            raise ValueError(f"kid_sums: {name} holds an index outside its set of {rows} rows ({low if low < 0 else high})")
+        shapes.append(tuple(int(v) for v in t.shape))
+    if shapes[0] != shapes[1]:
+        raise ValueError(f"kid_sums: xi and yi differ in shape ({shapes[0]} and {shapes[1]})")
+    subsets, size = shapes[0]
+    if subsets > _lib.KID_MAX_SUBSETS:
+        raise ValueError(f"kid_sums: xi holds {subsets} subsets, at most {_lib.KID_MAX_SUBSETS} go into one call")
+    if size > min(n, m):
+        raise ValueError(f"kid_sums: xi holds subsets of size {size}, above the smaller set's {min(n, m)} rows")
+    return n, m, d, subsets, size
+
+
+def kid_sums(x, y, xi=None, yi=None):
+    """HipKernels.kid_sums of the process-wide kernel object; the shapes and the lists are refused here, before a device is asked for."""
+    kid_sums_shapes(x, y, xi, yi)
+    return get().kid_sums(x, y, xi, yi)
+
+
 YIN_MAX_LAGS, YIN_MAX_WINDOW = 1024, 4096   # GS_YIN_MAX_LAGS, GS_YIN_MAX_WINDOW
 
 
@@ -2369,6 +2412,23 @@ class HipKernels(object):
         _lib.check(self.lib.gs_knn_within(q2.data_ptr(), ldq, n, r2.data_ptr(), ldr, m, d, radius2.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
                                           _stream()), "gs_knn_within")
         return count
+
+    def kid_sums(self, x, y, xi=None, yi=None):
+        """gs_kid_sums (include/gansynth_hip.h): -> [S, 3] float64 on the device, Sxx, Syy, Sxy of the cubic kernel k(a, b) = (a.b / d + 1)^3 over
+        x [n, d] and y [m, d] (fp32 on the device, any row stride).  Without lists S = 1: the full sets.  With xi, yi ([S, size] integers, numpy or
+        torch, anywhere): row r of subset s is x[xi[s, r]] / y[yi[s, r]]; the lists go to the device as int32."""
+        n, m, d, subsets, size = kid_sums_shapes(x, y, xi, yi)
+        x2, ldx = self._kmeans_rows("kid_sums", x, ("y", y))
+        y2, ldy = (x2, ldx) if y is x else self._kmeans_rows("kid_sums", y)
+        lists = [None, None]
+        if subsets:
+            lists = [(t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t).astype(np.int32))).to(device=x.device, dtype=torch.int32).contiguous()
+                     for t in (xi, yi)]
+        out = torch.empty((max(subsets, 1), 3), dtype=torch.float64, device=x.device)
+        ws = _ws(self.lib.gs_kid_workspace_bytes(n, m, d, subsets, size), x.device)
+        _lib.check(self.lib.gs_kid_sums(x2.data_ptr(), ldx, n, y2.data_ptr(), ldy, m, d, lists[0].data_ptr() if subsets else None,
+                                        lists[1].data_ptr() if subsets else None, subsets, size, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "gs_kid_sums")
+        return out
 
     def yin_difference(self, x, window, lags, hop):
         """gs_yin_difference (include/gansynth_hip.h): -> (d [rows, frames, lags] fp32, power [rows, frames] fp32) of x [rows, n] (fp32 on the

@@ -114,6 +114,26 @@ def precision_recall_device(real_features, fake_features, k=3, details=None):
     return dict(precision=result.precision, recall=result.recall, density=result.density, coverage=result.coverage)
 
 
+def kernel_inception_distance_device(real_features, fake_features, subsets=100, subset_size=1000, seed=0, details=None):
+    """The kernel inception distance (Binkowski et al. 2018) of two feature sets [rows, columns] (numpy or torch): kid.figures (this project's
+    own, stated rules; an fp64 matrix-core HIP kernel, no Gram matrix) -> dict(kernel_inception_distance=, the unbiased estimate over all rows,
+    kernel_inception_distance_subset_mean=, kernel_inception_distance_subset_std=, its mean and population standard deviation over `subsets`
+    seeded subsets of min(subset_size, rows) rows a side; NaN with subsets = 0).  `details` (a dict) receives subset_kids (one estimate a
+    subset), sums (Sxx, Syy, Sxy of the full sets), subset_sums and size."""
+    from . import kid, kmeans
+    for name, t in (("real_features", real_features), ("fake_features", fake_features)):
+        if not hasattr(t, "shape"):
+            raise ValueError(f"kernel_inception_distance_device: {name} must be a [rows, columns] array or tensor (got {type(t).__name__})")
+    kid.check_sets(real_features, fake_features, subsets, subset_size, "kernel_inception_distance_device")   # (before a device is asked for)
+    real = kmeans.to_device(real_features, "real_features")
+    fake = kmeans.to_device(fake_features, "fake_features").to(real.device)
+    result = kid.figures(real, fake, subsets, subset_size, seed)
+    if details is not None:
+        details.update(subset_kids=result.subset_kids, sums=result.sums, subset_sums=result.subset_sums, size=result.size)
+    return dict(kernel_inception_distance=result.kid, kernel_inception_distance_subset_mean=result.subset_mean,
+                kernel_inception_distance_subset_std=result.subset_std)
+
+
 def sliced_wasserstein_distance_device(real_images, fake_images, seed=0, details=None, batch_size=None):
     """The sliced Wasserstein distance between Laplacian-pyramid patches of two image sets [n, 2, h, w] (tensors or arrays, fp32 or bf16; the
     same n): swd.SlicedWasserstein (this project's own, stated rules; HIP kernels, no classifier) -> the mean over the levels of

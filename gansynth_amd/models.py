@@ -1135,7 +1135,7 @@ class GANSynth(Iterations, DataParallel, Capture):
     # ------------------------------------------------------------------------------------------- evaluation
     def evaluate(self, model_dir, config, classifier, input_name="images:0", output_names=("features:0", "logits:0"), batch_size=64,
                  extra_metrics=False, classifier_dtype=torch.float32, features_out=None, weights="live", ndb="sklearn", swd=False, swd_seed=0, prd=False, prd_k=3,
-                 f0=False, pitches=range(24, 85)):
+                 f0=False, pitches=range(24, 85), kid=False, kid_subsets=100, kid_subset_size=1000, kid_seed=0):
         """models.py:196-230: the Frechet distance between the pitch classifier's features of real and generated spectrograms.
 
         Restores the latest checkpoint of `model_dir` as `generate` does, then for every batch of `real_input_fn()` until it runs dry:
@@ -1165,7 +1165,12 @@ class GANSynth(Iterations, DataParallel, Capture):
         standard deviation), both over the notes counted accurate, and f0_voiced_fraction; and the same five with the prefix real_.  YIN is not
         perfect on real instruments (bass notes, mallets): the real_ figures are the calibration the generated ones are read against.
         features_out receives real_f0_cents and fake_f0_cents (one a note, NaN for an unvoiced one).  `classifier` may be None together with `swd`
-        or `f0`.  One process only."""
+        or `f0`.  `kid`: the dict gains kernel_inception_distance -- the unbiased estimate of the squared maximum mean discrepancy between the
+        fake and the real features (the features of the FID) under the cubic kernel, over all rows; unlike the Frechet distance its expectation does
+        not depend on the number of notes, and it may be negative -- and kernel_inception_distance_subset_mean / _subset_std, its mean and
+        population standard deviation over `kid_subsets` subsets of min(`kid_subset_size`, rows) rows a side drawn with `kid_seed`, from
+        metrics.kernel_inception_distance_device (kid.py: an fp64 matrix-core HIP kernel, DESIGN.md "KID on the device"); it needs the classifier.
+        features_out receives kid_subset_values (one estimate a subset).  One process only."""
         import numpy as np
         from . import metrics, networks
         del config
@@ -1180,6 +1185,12 @@ class GANSynth(Iterations, DataParallel, Capture):
             raise ValueError("evaluate: prd=True needs a classifier (precision, recall, density and coverage come from its features)")
         if prd and (not isinstance(prd_k, int) or isinstance(prd_k, bool) or not 1 <= prd_k <= 8):   # (before the first batch, not after the last)
             raise ValueError(f"evaluate: prd_k must be an integer in [1, 8] (got {prd_k!r})")
+        if classifier is None and kid:
+            raise ValueError("evaluate: kid=True needs a classifier (the kernel inception distance comes from its features)")
+        if kid:   # (before the first batch, not after the last)
+            for name, v, low in (("kid_subsets", kid_subsets, 0), ("kid_subset_size", kid_subset_size, 2)):
+                if not isinstance(v, int) or isinstance(v, bool) or v < low:
+                    raise ValueError(f"evaluate: {name} must be an integer >= {low} (got {v!r})")
         if classifier is None:
             if not swd and not f0:
                 raise ValueError("evaluate: classifier=None needs swd=True or f0=True (every other figure comes from the pitch classifier)")
@@ -1281,6 +1292,11 @@ class GANSynth(Iterations, DataParallel, Capture):
                     pass
         if prd:
             out.update(metrics.precision_recall_device(real_f, fake_f, k=prd_k))
+        if kid:
+            details = {}
+            out.update(metrics.kernel_inception_distance_device(real_f, fake_f, subsets=kid_subsets, subset_size=kid_subset_size, seed=kid_seed, details=details))
+            if features_out is not None:
+                features_out.update(kid_subset_values=details["subset_kids"])
         out.update(sliced_out)
         return out
 

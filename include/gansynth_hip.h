@@ -1265,6 +1265,39 @@ int gs_yin_pick(const float* d, int64_t rows, int64_t frames, int L, int tau_min
 int gs_yin_track(const float* x, int64_t ldx, int64_t rows, int64_t n, int W, int L, int hop, int tau_min, double threshold, int32_t* lag, double* period,
                  double* aperiodicity, float* power, void* stream);
 
+/* ---- the three kernel sums of the kernel inception distance (Binkowski et al. 2018), for gansynth_amd/kid.py,
+ * metrics.kernel_inception_distance_device and GANSynth.evaluate(kid=True); DESIGN.md "KID on the device" ----
+ * x is [n][d] and y [m][d] fp32, rows ldx / ldy >= d floats apart, 4-byte aligned (any 4-byte alignment); inputs are finite.  Nothing past a
+ * row's d floats is read.  With k(a, b) = (a.b / d + 1)^3 the entry writes, as doubles,
+ *   Sxx = sum over i != j of k(x_i, x_j),   Syy = sum over i != j of k(y_i, y_j),   Sxy = sum over all i, j of k(x_i, y_j).
+ * The index alone excludes: a duplicate row elsewhere is a pair like any other.
+ *
+ * subsets == 0 (then xi == yi == NULL and size == 0): the full sets; out is [1][3] = Sxx, Syy, Sxy.
+ * subsets >= 1: xi and yi are [subsets][size] int32 on the device, row r of subset s is x[xi[s size + r]] (y[yi[s size + r]]), found by the row
+ * loader -- no gathered copy is made; out is [subsets][3].  The entry cannot see the lists: an index outside its set is the caller's to refuse
+ * (kernels.kid_sums does); the loader clamps it into the set, so that no read ever leaves the matrices.
+ *
+ * Arithmetic: the features are widened fp32 -> fp64 (exact); a.b is accumulated in fp64 by v_mfma_f64_16x16x4_f64 over the columns in ascending
+ * steps of 4 -- every product is exact, only the additions round; t = p / d + 1.0 and k = t t t in fp64; every sum in fp64 in one fixed order
+ * (no float atomics): two calls with the same arguments write the same bits, and a subset's three sums have the same bits alone and as entry s of
+ * a batch.  The longest chain of additions behind a sum: 63 (a lane's 64 values) + 8 (the block's tree over 256 lanes) +
+ * ceil(tiles / 256) - 1 (a fold thread's partials, ascending) + 8 (the fold's tree), `tiles` the job's tile count below.
+ *
+ * One launch over (tiles, subsets) and a fold of (3, subsets) blocks.  A tile is GS_KID_TILE x GS_KID_TILE pairs; with T(r) = ceil(r /
+ * GS_KID_TILE) and the rows a side r_x, r_y (n, m, or size) the symmetric jobs visit the upper triangle, T (T + 1) / 2 tiles, and Sxy
+ * T(r_x) T(r_y).  No n x m array exists at any time; ws holds one double a tile:
+ * gs_kid_workspace_bytes (host arithmetic; 0 for a shape the entry refuses) = 8 max(subsets, 1) (T_x (T_x + 1) / 2 + T_y (T_y + 1) / 2 + T_x T_y)
+ * rounded up to 16.  ws is 16-byte aligned, out 8.  Capture-safe: no allocation, no synchronisation.
+ * GS_ERR_ARG with a message that names the argument and without a launch: n or m outside [2, GS_KID_MAX_ROWS], d outside [1, GS_KMEANS_MAX_D],
+ * a row stride below d, subsets outside [0, GS_KID_MAX_SUBSETS], lists or a size with subsets == 0, a NULL or misaligned list or a size outside
+ * [2, min(n, m)] with subsets >= 1, a NULL or misaligned pointer, a workspace that is too small. */
+#define GS_KID_TILE 128
+#define GS_KID_MAX_ROWS 2097152
+#define GS_KID_MAX_SUBSETS 65535
+size_t gs_kid_workspace_bytes(int64_t n, int64_t m, int d, int subsets, int64_t size);
+int gs_kid_sums(const float* x, int64_t ldx, int64_t n, const float* y, int64_t ldy, int64_t m, int d, const int32_t* xi, const int32_t* yi, int subsets,
+                int64_t size, double* out /* [max(subsets, 1)][3]: Sxx, Syy, Sxy */, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
