@@ -179,6 +179,20 @@ __device__ inline float block_sum(float v, float* smem /* >= NT/64 floats */) {
     return r;
 }
 
+// The fixed fp64 tree over a block of NT threads: red[t] += red[t + w] for w = NT / 2 ... 1.  -> the sum, in thread 0 only.  "Two calls write
+// the same bits" rests on this order.  No barrier in front: a caller that reuses red while another call may still read it puts one there.
+template <int NT>
+__device__ inline double block_tree_f64(double v, double* red /* NT doubles */) {
+    const int t = threadIdx.x;
+    red[t] = v;
+#pragma unroll
+    for (int w = NT / 2; w >= 1; w >>= 1) {
+        __syncthreads();
+        if (t < w) red[t] += red[t + w];
+    }
+    return red[0];
+}
+
 // ------------------------------------------------------------- wave64 extremes (summary.hip, synth.hip)
 // v[lane] op v[lane ^ 16] / v[lane ^ 32]: the swaps of swap16_sum / swap32_sum above (same wait states), both halves returned
 __device__ inline void swap16_pair(float v, float& a, float& b) {
@@ -210,6 +224,15 @@ __device__ inline int quantise_s16(float x) {
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }   // a: a power of two
+
+// The bounds the entries on feature matrices share (k-means, k-NN, KID): fp32 [rows, d], rows `ld` floats apart.  `what` and `name` are
+// string literals, `d` the entry's own argument; an entry lists them in the order its refusals are documented in.
+inline bool feature_dims_ok(int64_t rows, int d) { return rows >= 1 && rows <= GS_KMEANS_MAX_N && d >= 1 && d <= GS_KMEANS_MAX_D; }
+#define GS_CHECK_FEATURE_D(what) GS_CHECK_ARG(d >= 1 && d <= GS_KMEANS_MAX_D, what ": d must be in [1, %d] (got %d)", GS_KMEANS_MAX_D, d)
+#define GS_CHECK_FEATURE_ROWS(what, name, n) \
+    GS_CHECK_ARG((n) >= 1 && (n) <= GS_KMEANS_MAX_N, what ": " name " must be in [1, 2^31 - 1] (got %lld)", (long long)(n))
+#define GS_CHECK_FEATURE_LD(what, name, ld) GS_CHECK_ARG((ld) >= d, what ": " name " %lld is below d %d", (long long)(ld), d)
 
 // dispatch on dtype id
 #define GS_DISPATCH_DTYPE(dtype, ...)                                   \

@@ -67,18 +67,6 @@ __device__ inline void kid_triangle(long idx, long T, long& row, long& col) {
     col = r + (idx - (r * T - r * (r - 1) / 2));
 }
 
-// the fixed tree over a block's 256 values: red[t] += red[t + w] for w = 128, 64 ... 1.  -> the sum, in thread 0
-__device__ inline double kid_block_tree(double v, double* red) {
-    const int t = threadIdx.x;
-    red[t] = v;
-#pragma unroll
-    for (int w = KD_NT / 2; w >= 1; w >>= 1) {
-        __syncthreads();
-        if (t < w) red[t] += red[t + w];
-    }
-    return red[0];
-}
-
 __global__ __launch_bounds__(KD_NT, 2) void kid_kernel(const float* __restrict__ x, size_t ldx, long n, const float* __restrict__ y, size_t ldy, long m, int d,
                                                        const int* __restrict__ xi, const int* __restrict__ yi, int subsets, long size, double* __restrict__ part) {
     __shared__ __attribute__((aligned(16))) float as[KD_TILE * KD_LD];
@@ -191,7 +179,7 @@ __global__ __launch_bounds__(KD_NT, 2) void kid_kernel(const float* __restrict__
                 const bool take = gi < rows_a && gj < rows_b && !(diagonal && gi == gj);
                 sum += take ? k : 0.0;
             }
-    const double total = kid_block_tree(sum, red);
+    const double total = block_tree_f64<KD_NT>(sum, red);
     if (tid == 0) part[sub * sh.per_subset + blockIdx.x] = (job != 2 && !diagonal) ? 2.0 * total : total;
 }
 
@@ -205,11 +193,10 @@ __global__ __launch_bounds__(KD_NT) void kid_fold_kernel(const double* __restric
     const double* __restrict__ p = part + (long)blockIdx.y * sh.per_subset + begin;
     double sum = 0.0;
     for (long i = threadIdx.x; i < count; i += KD_NT) sum += p[i];
-    const double total = kid_block_tree(sum, red);
+    const double total = block_tree_f64<KD_NT>(sum, red);
     if (threadIdx.x == 0) out[(long)blockIdx.y * 3 + job] = total;
 }
 
-static bool kd_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 static bool kd_shape_ok(int64_t n, int64_t m, int d, int subsets, int64_t size) {
     if (n < 2 || n > GS_KID_MAX_ROWS || m < 2 || m > GS_KID_MAX_ROWS || d < 1 || d > GS_KMEANS_MAX_D || subsets < 0 || subsets > GS_KID_MAX_SUBSETS) return false;
     return subsets == 0 ? size == 0 : (size >= 2 && size <= n && size <= m);
@@ -230,25 +217,25 @@ extern "C" size_t gs_kid_workspace_bytes(int64_t n, int64_t m, int d, int subset
 
 extern "C" int gs_kid_sums(const float* x, int64_t ldx, int64_t n, const float* y, int64_t ldy, int64_t m, int d, const int32_t* xi, const int32_t* yi, int subsets,
                            int64_t size, double* out, void* ws, size_t ws_bytes, void* stream) {
-    GS_CHECK_ARG(d >= 1 && d <= GS_KMEANS_MAX_D, "kid_sums: d must be in [1, %d] (got %d)", GS_KMEANS_MAX_D, d);
+    GS_CHECK_FEATURE_D("kid_sums");
     GS_CHECK_ARG(n >= 2 && n <= GS_KID_MAX_ROWS, "kid_sums: n must be in [2, %d] (got %lld)", GS_KID_MAX_ROWS, (long long)n);
     GS_CHECK_ARG(m >= 2 && m <= GS_KID_MAX_ROWS, "kid_sums: m must be in [2, %d] (got %lld)", GS_KID_MAX_ROWS, (long long)m);
-    GS_CHECK_ARG(ldx >= d, "kid_sums: ldx %lld is below d %d", (long long)ldx, d);
-    GS_CHECK_ARG(ldy >= d, "kid_sums: ldy %lld is below d %d", (long long)ldy, d);
+    GS_CHECK_FEATURE_LD("kid_sums", "ldx", ldx);
+    GS_CHECK_FEATURE_LD("kid_sums", "ldy", ldy);
     GS_CHECK_ARG(subsets >= 0 && subsets <= GS_KID_MAX_SUBSETS, "kid_sums: subsets must be in [0, %d] (got %d)", GS_KID_MAX_SUBSETS, subsets);
     if (subsets == 0) {
         GS_CHECK_ARG(!xi && !yi, "kid_sums: xi and yi must be NULL with subsets 0 (the full sets)");
         GS_CHECK_ARG(size == 0, "kid_sums: size must be 0 with subsets 0 (got %lld)", (long long)size);
     } else {
         GS_CHECK_ARG(xi && yi, "kid_sums: null pointer (xi and yi are required with subsets %d)", subsets);
-        GS_CHECK_ARG(kd_aligned(xi, 4) && kd_aligned(yi, 4), "kid_sums: misaligned pointer (xi and yi: 4 bytes)");
+        GS_CHECK_ARG(aligned(xi, 4) && aligned(yi, 4), "kid_sums: misaligned pointer (xi and yi: 4 bytes)");
         GS_CHECK_ARG(size >= 2 && size <= n && size <= m, "kid_sums: size must be in [2, min(n, m)] (got %lld for n %lld, m %lld)", (long long)size, (long long)n,
                      (long long)m);
     }
     GS_CHECK_ARG(x && y && out, "kid_sums: null pointer (x, y and out are required)");
-    GS_CHECK_ARG(kd_aligned(x, 4) && kd_aligned(y, 4) && kd_aligned(out, 8), "kid_sums: misaligned pointer (x and y: 4 bytes, out: 8)");
+    GS_CHECK_ARG(aligned(x, 4) && aligned(y, 4) && aligned(out, 8), "kid_sums: misaligned pointer (x and y: 4 bytes, out: 8)");
     const size_t need = kd_ws_bytes(n, m, subsets, size);
-    GS_CHECK_ARG(ws && ws_bytes >= need && kd_aligned(ws, 16), "kid_sums: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
+    GS_CHECK_ARG(ws && ws_bytes >= need && aligned(ws, 16), "kid_sums: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
     hipStream_t st = as_stream(stream);
     const KidShape sh = kid_shape((long)n, (long)m, subsets, (long)size);
     const unsigned jobs = (unsigned)(subsets > 0 ? subsets : 1);

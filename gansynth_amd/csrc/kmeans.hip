@@ -3,12 +3,9 @@
 //
 // Assign is 3 n k d flops on 4 n d bytes: the fp32 vector pipe binds.  The distance is sum (x - c)^2, a subtraction and an FMA per term -- never
 // the expansion |x|^2 - 2 x.c + |c|^2, which cancels on features with a common offset.
-//   * A block of four waves owns KM_TILE = 256 rows and walks the columns in chunks of KM_DC = 32.  A chunk of the rows is staged in LDS as
-//     xs[row][36] (global reads: a wave covers two rows' 128-byte pieces per instruction; x needs no alignment beyond 4 bytes), a chunk of the
-//     centres as cs[slot][32].  Columns past d are 0 on both sides: they add an exact 0.
-//   * A wave owns KG <= 16 consecutive centres (k = 50: 13 each), a lane KM_P = 4 rows against them: 4 KG accumulators, each ONE chain over the
-//     columns ascending.  A row's four floats are one ds_read_b128 (the stride of 36 floats puts the 16 lanes of a group on 64 distinct
-//     banks), a centre's four floats one broadcast ds_read_b128 that feeds 32 VALU instructions: the LDS pipe runs at about a third of the VALU.
+//   * The all-pairs tile is pairs_tile.h's (staging, LDS layout, the chain), in its scalar form: a block of four waves owns KM_TILE = 256 rows,
+//     a wave KG <= 16 consecutive centres (k = 50: 13 each), a lane KM_P = 4 rows against them: 4 KG accumulators, each ONE chain over the
+//     columns ascending.
 //   * k > 4 KG: rounds of 4 KG centres, the rows staged again every round (from the cache); the running (best, index) stays in registers.
 //   * The four waves' candidates meet in LDS and are folded in centre order with a strict <: ties go to the lowest index.
 //   kmeans_assign_kernel<KG>    grid (tiles): labels, dist, and the tile's moved-label count and sum of minima (double, a fixed tree)
@@ -23,30 +20,25 @@
 #include <math.h>
 
 #include "gs_common.h"
+#include "pairs_tile.h"
 
 namespace gs {
 
-constexpr int KM_NT = 256;                 // threads per block of assign
-constexpr int KM_WAVES = KM_NT / 64;
-constexpr int KM_P = 4;                    // rows a lane owns
-constexpr int KM_TILE = 64 * KM_P;         // rows a block owns
-constexpr int KM_DC = 32;                  // columns per chunk
-constexpr int KM_XS = KM_DC + 4;           // floats between two rows of xs: 16 lanes of a ds_read_b128 group on 64 distinct banks
+constexpr int KM_NT = PT_NT, KM_WAVES = PT_WAVES, KM_P = PT_P, KM_TILE = PT_TILE;   // assign's tile; the other kernels here take its block shape
 constexpr int KM_MAX_KG = 16;              // centres a wave owns, at most
 constexpr int KU_COLS = 64;                // columns a block of update owns
 constexpr int KU_ROWS = 16;                // rows in flight per wave of update
 static_assert(KM_TILE == GS_KMEANS_TILE && KM_TILE == KM_NT, "one thread per row in the epilogue");
-static_assert(KM_TILE * KM_XS >= 2 * KM_WAVES * KM_TILE + 3 * KM_TILE, "the epilogue's arrays live in xs");
+static_assert(KM_TILE * PT_XS >= 2 * KM_WAVES * KM_TILE + 3 * KM_TILE, "the epilogue's arrays live in xs");
 
 // grid (tiles of n).  labels / dist of the tile's rows; block_inertia[b] / block_changed[b] its sum of minima (in double) and count of moved labels
 template <int KG>
 __global__ __launch_bounds__(KM_NT) void kmeans_assign_kernel(const float* __restrict__ x, size_t ldx, long n, int d, const float* __restrict__ centres, int k,
                                                               int* __restrict__ labels, float* __restrict__ dist, int count_moved,
                                                               double* __restrict__ block_inertia, int* __restrict__ block_changed) {
-    __shared__ __attribute__((aligned(16))) float xs[KM_TILE * KM_XS];
-    __shared__ __attribute__((aligned(16))) float cs[KM_WAVES * KG * KM_DC];
+    __shared__ __attribute__((aligned(16))) float xs[KM_TILE * PT_XS];
+    __shared__ __attribute__((aligned(16))) float cs[KM_WAVES * KG * PT_DC];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int scol = threadIdx.x & (KM_DC - 1), srow = threadIdx.x / KM_DC;   // staging: a thread owns a column of every 8th row
     const long tile_begin = (long)blockIdx.x * KM_TILE;
     float best[KM_P];
     int best_k[KM_P];
@@ -57,65 +49,14 @@ __global__ __launch_bounds__(KM_NT) void kmeans_assign_kernel(const float* __res
     for (int r = 0; r < rounds; ++r) {
         const int round_k = r * KM_WAVES * KG;   // the round's first centre
         const int kb = round_k + wave * KG;      // the wave's first centre
-        float acc[KM_P][KG];
+        pairs_acc<KG, false> acc;
 #pragma unroll
         for (int p = 0; p < KM_P; ++p)
 #pragma unroll
             for (int j = 0; j < KG; ++j) acc[p][j] = 0.f;
-        for (int d0 = 0; d0 < d; d0 += KM_DC) {
-            __syncthreads();   // the chunk before is consumed
-            // every load is in bounds (row and column clamped) and unconditional, so that all of a thread's loads are in flight together; what
-            // lies past n, k or d is dropped for a 0 on the way into LDS
-            const bool col_ok = d0 + scol < d;
-            const size_t col = col_ok ? d0 + scol : d - 1;
-            constexpr int XL = KM_TILE / (KM_NT / KM_DC) / 2, CL = (KM_WAVES * KG + KM_NT / KM_DC - 1) / (KM_NT / KM_DC);
-            float cv[CL];
-#pragma unroll
-            for (int i = 0; i < CL; ++i) {
-                const int kk = round_k + srow + i * (KM_NT / KM_DC);
-                cv[i] = centres[(size_t)(kk < k ? kk : k - 1) * d + col];
-            }
-#pragma unroll 1
-            for (int half = 0; half < 2; ++half) {   // (two batches of 16 loads: all 32 at once cost the kernel a wave per SIMD in registers)
-                float xv[XL];
-                const int row0 = srow + half * XL * (KM_NT / KM_DC);
-#pragma unroll
-                for (int i = 0; i < XL; ++i) {
-                    const long gi = tile_begin + row0 + i * (KM_NT / KM_DC);
-                    xv[i] = x[(size_t)(gi < n ? gi : n - 1) * ldx + col];
-                }
-#pragma unroll
-                for (int i = 0; i < XL; ++i) {
-                    const int row = row0 + i * (KM_NT / KM_DC);
-                    xs[row * KM_XS + scol] = (col_ok && tile_begin + row < n) ? xv[i] : 0.f;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < CL; ++i) {
-                const int s = srow + i * (KM_NT / KM_DC);
-                if (s < KM_WAVES * KG) cs[s * KM_DC + scol] = (col_ok && round_k + s < k) ? cv[i] : 0.f;
-            }
-            __syncthreads();
-            if (kb < k) {   // (wave-uniform)
-#pragma unroll 1
-                for (int q = 0; q < KM_DC / 4; ++q) {
-                    float xr[KM_P][4];
-#pragma unroll
-                    for (int p = 0; p < KM_P; ++p) ld4(xs + (lane + 64 * p) * KM_XS + 4 * q, xr[p]);
-#pragma unroll
-                    for (int j = 0; j < KG; ++j) {
-                        float c[4];
-                        ld4(cs + (wave * KG + j) * KM_DC + 4 * q, c);   // one address a wave: a broadcast
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-#pragma unroll
-                            for (int p = 0; p < KM_P; ++p) {
-                                const float t = xr[p][e] - c[e];
-                                acc[p][j] = fmaf(t, t, acc[p][j]);
-                            }
-                    }
-                }
-            }
+        for (int d0 = 0; d0 < d; d0 += PT_DC) {
+            pairs_stage<KM_WAVES * KG>(xs, cs, x, ldx, tile_begin, n, centres, (size_t)d, round_k, k, d0, d);
+            if (kb < k) pairs_chain<KG, false>(xs, cs + wave * KG * PT_DC, lane, acc);   // (wave-uniform)
         }
 #pragma unroll
         for (int j = 0; j < KG; ++j)
@@ -315,7 +256,7 @@ __global__ __launch_bounds__(KM_NT) void kmeans_mindist_kernel(const float* __re
     }
 }
 
-static bool km_shape_ok(int64_t n, int d, int k) { return n >= 1 && n <= GS_KMEANS_MAX_N && d >= 1 && d <= GS_KMEANS_MAX_D && k >= 1 && k <= GS_KMEANS_MAX_K; }
+static bool km_shape_ok(int64_t n, int d, int k) { return feature_dims_ok(n, d) && k >= 1 && k <= GS_KMEANS_MAX_K; }
 static long km_tiles(int64_t n) { return (long)((n + KM_TILE - 1) / KM_TILE); }
 static long km_rows_per_slice(int64_t n, int d) {
     long s0 = 2048 / ((d + KU_COLS - 1) / KU_COLS);
@@ -346,13 +287,13 @@ static int km_group(int k) {
 
 using namespace gs;
 
-#define KM_CHECK_SHAPE(what)                                                                                                        \
-    GS_CHECK_ARG(k >= 1 && k <= GS_KMEANS_MAX_K, what ": k must be in [1, %d] (got %d)", GS_KMEANS_MAX_K, k);                       \
-    GS_CHECK_ARG(d >= 1 && d <= GS_KMEANS_MAX_D, what ": d must be in [1, %d] (got %d)", GS_KMEANS_MAX_D, d);                                                                \
-    GS_CHECK_ARG(n >= 1 && n <= GS_KMEANS_MAX_N, what ": n must be in [1, 2^31 - 1] (got %lld)", (long long)n);                     \
-    GS_CHECK_ARG(ldx >= d, what ": ldx %lld is below d %d", (long long)ldx, d)
-
-static bool km_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+#define KM_CHECK_ROWS(what)              \
+    GS_CHECK_FEATURE_D(what);            \
+    GS_CHECK_FEATURE_ROWS(what, "n", n); \
+    GS_CHECK_FEATURE_LD(what, "ldx", ldx)
+#define KM_CHECK_SHAPE(what)                                                                                  \
+    GS_CHECK_ARG(k >= 1 && k <= GS_KMEANS_MAX_K, what ": k must be in [1, %d] (got %d)", GS_KMEANS_MAX_K, k); \
+    KM_CHECK_ROWS(what)
 
 extern "C" size_t gs_kmeans_workspace_bytes(int64_t n, int d, int k) {
     if (!km_shape_ok(n, d, k)) return 0;
@@ -363,10 +304,10 @@ extern "C" int gs_kmeans_assign(const float* x, int64_t ldx, int64_t n, int d, c
                                 double* inertia, void* ws, size_t ws_bytes, void* stream) {
     KM_CHECK_SHAPE("kmeans_assign");
     GS_CHECK_ARG(x && centres && labels, "kmeans_assign: null pointer (x, centres and labels are required)");
-    GS_CHECK_ARG(km_aligned(x, 4) && km_aligned(centres, 4) && km_aligned(labels, 4) && km_aligned(dist, 4) && km_aligned(changed, 4) && km_aligned(inertia, 8),
+    GS_CHECK_ARG(aligned(x, 4) && aligned(centres, 4) && aligned(labels, 4) && aligned(dist, 4) && aligned(changed, 4) && aligned(inertia, 8),
                  "kmeans_assign: misaligned pointer (inertia: 8 bytes, the others: 4)");
     const size_t need = km_ws_bytes(n, d, k);
-    GS_CHECK_ARG(ws && ws_bytes >= need && km_aligned(ws, 16), "kmeans_assign: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
+    GS_CHECK_ARG(ws && ws_bytes >= need && aligned(ws, 16), "kmeans_assign: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
     hipStream_t st = as_stream(stream);
     const int tiles = (int)km_tiles(n);
     double* block_inertia = static_cast<double*>(ws);
@@ -387,10 +328,10 @@ extern "C" int gs_kmeans_inertia(const float* x, int64_t ldx, int64_t n, int d, 
                                  size_t ws_bytes, void* stream) {
     KM_CHECK_SHAPE("kmeans_inertia");
     GS_CHECK_ARG(x && centres && labels && inertia, "kmeans_inertia: null pointer (x, centres, labels and inertia are required)");
-    GS_CHECK_ARG(km_aligned(x, 4) && km_aligned(centres, 4) && km_aligned(labels, 4) && km_aligned(inertia, 8),
+    GS_CHECK_ARG(aligned(x, 4) && aligned(centres, 4) && aligned(labels, 4) && aligned(inertia, 8),
                  "kmeans_inertia: misaligned pointer (inertia: 8 bytes, the others: 4)");
     const size_t need = km_ws_bytes(n, d, k);
-    GS_CHECK_ARG(ws && ws_bytes >= need && km_aligned(ws, 16), "kmeans_inertia: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
+    GS_CHECK_ARG(ws && ws_bytes >= need && aligned(ws, 16), "kmeans_inertia: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
     hipStream_t st = as_stream(stream);
     const int tiles = (int)km_tiles(n);
     double* block_inertia = static_cast<double*>(ws);
@@ -405,9 +346,9 @@ extern "C" int gs_kmeans_update(const float* x, int64_t ldx, int64_t n, int d, c
                                 size_t ws_bytes, void* stream) {
     KM_CHECK_SHAPE("kmeans_update");
     GS_CHECK_ARG(x && labels && centres && counts, "kmeans_update: null pointer (x, labels, centres and counts are required)");
-    GS_CHECK_ARG(km_aligned(x, 4) && km_aligned(labels, 4) && km_aligned(centres, 4) && km_aligned(counts, 4), "kmeans_update: misaligned pointer (4 bytes)");
+    GS_CHECK_ARG(aligned(x, 4) && aligned(labels, 4) && aligned(centres, 4) && aligned(counts, 4), "kmeans_update: misaligned pointer (4 bytes)");
     const size_t need = km_ws_bytes(n, d, k);
-    GS_CHECK_ARG(ws && ws_bytes >= need && km_aligned(ws, 16), "kmeans_update: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
+    GS_CHECK_ARG(ws && ws_bytes >= need && aligned(ws, 16), "kmeans_update: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
     hipStream_t st = as_stream(stream);
     const long rows = km_rows_per_slice(n, d);
     const int slices = (int)km_slices(n, d);
@@ -422,11 +363,9 @@ extern "C" int gs_kmeans_update(const float* x, int64_t ldx, int64_t n, int d, c
 }
 
 extern "C" int gs_kmeans_mindist(const float* x, int64_t ldx, int64_t n, int d, const float* centre, float* dist, int first, void* stream) {
-    GS_CHECK_ARG(d >= 1 && d <= GS_KMEANS_MAX_D, "kmeans_mindist: d must be in [1, %d] (got %d)", GS_KMEANS_MAX_D, d);
-    GS_CHECK_ARG(n >= 1 && n <= GS_KMEANS_MAX_N, "kmeans_mindist: n must be in [1, 2^31 - 1] (got %lld)", (long long)n);
-    GS_CHECK_ARG(ldx >= d, "kmeans_mindist: ldx %lld is below d %d", (long long)ldx, d);
+    KM_CHECK_ROWS("kmeans_mindist");
     GS_CHECK_ARG(x && centre && dist, "kmeans_mindist: null pointer (x, centre and dist are required)");
-    GS_CHECK_ARG(km_aligned(x, 4) && km_aligned(centre, 4) && km_aligned(dist, 4), "kmeans_mindist: misaligned pointer (4 bytes)");
+    GS_CHECK_ARG(aligned(x, 4) && aligned(centre, 4) && aligned(dist, 4), "kmeans_mindist: misaligned pointer (4 bytes)");
     const long blocks = (long)((n + KM_WAVES - 1) / KM_WAVES);
     hipLaunchKernelGGL(kmeans_mindist_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(KM_NT), 0, as_stream(stream), x, (size_t)ldx, (long)n, d, centre,
                        dist, first);

@@ -3,14 +3,13 @@
 // multiset of values or an integer sum: two calls agree bit for bit, whatever the slicing.
 //
 // Both entries are all-pairs squared distances, 3 n m d flops, of which nothing is written: the fp32 vector pipe binds.  The distance is
-// kmeans.hip's, sum (x - y)^2 as ONE chain over the columns ascending -- (x - y)^2 and (y - x)^2 have the same bits, so d(i, j) is one number
+// pairs_tile.h's, sum (x - y)^2 as ONE chain over the columns ascending -- (x - y)^2 and (y - x)^2 have the same bits, so d(i, j) is one number
 // in gs_knn_kth and gs_knn_within and from either side.
-//   * The inner loop is kmeans_assign_kernel's: a block of four waves owns KN_TILE = 256 rows of the first side and walks the columns in chunks
-//     of KN_DC = 32; the rows' chunk is staged in LDS as xs[row][36], the other side's as cs[slot][32]; a wave owns KN_KG = 16 consecutive rows
-//     of the other side, a lane KN_P = 4 rows of the tile against them: 64 accumulators.  Columns past d are 0 on both sides: an exact 0.
-//   * Packed fp32 math: two rows of a lane sit in one register pair, t = x - y is a v_pk_add_f32 and the chain a v_pk_fma_f32 -- per half the
-//     same operations in the same order as the scalar chain, bit for bit (measured: the same sums over every output), and 7 to 10 % faster than
-//     v_sub_f32 / v_fmac_f32 at 50 000 rows (DESIGN.md has both numbers).
+//   * The all-pairs tile is pairs_tile.h's (staging, LDS layout, the chain), as in kmeans_assign_kernel: a block of four waves owns KN_TILE = 256
+//     rows of the first side; a wave owns KN_KG = 16 consecutive rows of the other side, a lane KN_P = 4 rows of the tile against them: 64
+//     accumulators.
+//   * Packed fp32 math, the tile's packed form: two rows of a lane sit in one register pair, t = x - y is a v_pk_add_f32 and the chain a
+//     v_pk_fma_f32 -- 7 to 10 % faster than v_sub_f32 / v_fmac_f32 at 50 000 rows (DESIGN.md has both numbers).
 //   * The grid is (row tiles) x (slices of the other side): a block walks its slice in rounds of 4 KN_KG = 64 rows.  After a round a lane holds
 //     64 finished distances.  kth: each goes through ONE compare against the lane's current K-th value for that row and, under it, a sorted
 //     insert into K registers (v_med3_f32 per place: fully unrolled, no indexed private array); within: one compare against the other row's
@@ -23,21 +22,16 @@
 #include <math.h>
 
 #include "gs_common.h"
+#include "pairs_tile.h"
 
 namespace gs {
 
-constexpr int KN_NT = 256;                 // threads per block
-constexpr int KN_WAVES = KN_NT / 64;
-constexpr int KN_P = 4;                    // rows of the tile a lane owns
-constexpr int KN_TILE = 64 * KN_P;         // rows a block owns
-constexpr int KN_DC = 32;                  // columns per chunk
-constexpr int KN_XS = KN_DC + 4;           // floats between two rows of xs: 16 lanes of a ds_read_b128 group on 64 distinct banks
+constexpr int KN_NT = PT_NT, KN_WAVES = PT_WAVES, KN_P = PT_P, KN_TILE = PT_TILE;   // the tile; the folds take its block shape
 constexpr int KN_KG = 16;                  // rows of the other side a wave owns per round
 constexpr int KN_ROUND = KN_WAVES * KN_KG; // rows of the other side a block takes per round
 constexpr int KN_OCC = 3;                  // blocks a CU is asked to hold, a wave of each per SIMD: 168 registers (at 2, kth is 14 % slower at 50 000 rows)
-typedef float f32x2 __attribute__((ext_vector_type(2)));   // two rows of a lane in one register pair
 static_assert(KN_TILE == GS_KMEANS_TILE && KN_TILE == KN_NT, "one thread per row in the epilogue");
-static_assert(KN_TILE * KN_XS >= KN_WAVES * KN_TILE * GS_KNN_MAX_K, "the epilogue's lists live in xs");
+static_assert(KN_TILE * PT_XS >= KN_WAVES * KN_TILE * GS_KNN_MAX_K, "the epilogue's lists live in xs");
 static_assert(GS_KNN_MIN_SLICE_ROWS % KN_ROUND == 0, "a slice is whole rounds");
 
 // t[0] <= ... <= t[K - 1] keeps the K smallest values it has seen: one compare for a value that does not belong, and under it a place-by-place
@@ -57,11 +51,10 @@ template <int K>
 __global__ __launch_bounds__(KN_NT, KN_OCC) void knn_kernel(const float* __restrict__ a, size_t lda, long n, const float* __restrict__ b, size_t ldb, long m, int d,
                                                     long rows_per_slice, int k, int exclude, const float* __restrict__ radius2, float* __restrict__ part,
                                                     int* __restrict__ cnt_part) {
-    __shared__ __attribute__((aligned(16))) float xs[KN_TILE * KN_XS];
-    __shared__ __attribute__((aligned(16))) float cs[KN_ROUND * KN_DC];
+    __shared__ __attribute__((aligned(16))) float xs[KN_TILE * PT_XS];
+    __shared__ __attribute__((aligned(16))) float cs[KN_ROUND * PT_DC];
     constexpr int KK = K > 0 ? K : 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int scol = threadIdx.x & (KN_DC - 1), srow = threadIdx.x / KN_DC;   // staging: a thread owns a column of every 8th row
     const long tile_begin = (long)blockIdx.x * KN_TILE;
     const long m0 = (long)blockIdx.y * rows_per_slice;
     const long m1 = m0 + rows_per_slice < m ? m0 + rows_per_slice : m;
@@ -76,68 +69,15 @@ __global__ __launch_bounds__(KN_NT, KN_OCC) void knn_kernel(const float* __restr
 
     for (long round_b = m0; round_b < m1; round_b += KN_ROUND) {
         const long kb = round_b + wave * KN_KG;   // the wave's first row of b
-        f32x2 acc[KN_P / 2][KN_KG];   // rows (2 pp, 2 pp + 1) of the lane side by side: v_pk_add_f32 / v_pk_fma_f32, each half its own chain
+        pairs_acc<KN_KG, true> acc;   // rows (2 pp, 2 pp + 1) of the lane side by side, each half its own chain
 #define KN_ACC(p, j) acc[(p) / 2][j][(p) & 1]
 #pragma unroll
         for (int p = 0; p < KN_P; ++p)
 #pragma unroll
             for (int j = 0; j < KN_KG; ++j) KN_ACC(p, j) = 0.f;
-        for (int d0 = 0; d0 < d; d0 += KN_DC) {
-            __syncthreads();   // the chunk before is consumed
-            // every load is in bounds (row and column clamped) and unconditional, so that all of a thread's loads are in flight together; what
-            // lies past n, the slice or d is dropped for a 0 on the way into LDS
-            const bool col_ok = d0 + scol < d;
-            const size_t col = col_ok ? d0 + scol : d - 1;
-            constexpr int XL = KN_TILE / (KN_NT / KN_DC) / 2, CL = KN_ROUND / (KN_NT / KN_DC);
-            float cv[CL];
-#pragma unroll
-            for (int i = 0; i < CL; ++i) {
-                const long bj = round_b + srow + i * (KN_NT / KN_DC);
-                cv[i] = b[(size_t)(bj < m1 ? bj : m1 - 1) * ldb + col];
-            }
-#pragma unroll 1
-            for (int half = 0; half < 2; ++half) {   // (two batches of 16 loads, as in kmeans_assign_kernel)
-                float xv[XL];
-                const int row0 = srow + half * XL * (KN_NT / KN_DC);
-#pragma unroll
-                for (int i = 0; i < XL; ++i) {
-                    const long gi = tile_begin + row0 + i * (KN_NT / KN_DC);
-                    xv[i] = a[(size_t)(gi < n ? gi : n - 1) * lda + col];
-                }
-#pragma unroll
-                for (int i = 0; i < XL; ++i) {
-                    const int row = row0 + i * (KN_NT / KN_DC);
-                    xs[row * KN_XS + scol] = (col_ok && tile_begin + row < n) ? xv[i] : 0.f;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < CL; ++i) {
-                const int s = srow + i * (KN_NT / KN_DC);
-                cs[s * KN_DC + scol] = (col_ok && round_b + s < m1) ? cv[i] : 0.f;
-            }
-            __syncthreads();
-            if (kb < m1) {   // (wave-uniform)
-#pragma unroll 1
-                for (int q = 0; q < KN_DC / 4; ++q) {
-                    float xr[KN_P][4];
-#pragma unroll
-                    for (int p = 0; p < KN_P; ++p) ld4(xs + (lane + 64 * p) * KN_XS + 4 * q, xr[p]);
-#pragma unroll
-                    for (int j = 0; j < KN_KG; ++j) {
-                        float c[4];
-                        ld4(cs + (wave * KN_KG + j) * KN_DC + 4 * q, c);   // one address a wave: a broadcast
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                            for (int pp = 0; pp < KN_P / 2; ++pp) {
-                                const f32x2 x2 = {xr[2 * pp][e], xr[2 * pp + 1][e]};
-                                const f32x2 t = x2 - c[e];
-                                acc[pp][j] = __builtin_elementwise_fma(t, t, acc[pp][j]);
-                            }
-                        }
-                    }
-                }
-            }
+        for (int d0 = 0; d0 < d; d0 += PT_DC) {
+            pairs_stage<KN_ROUND>(xs, cs, a, lda, tile_begin, n, b, ldb, round_b, m1, d0, d);
+            if (kb < m1) pairs_chain<KN_KG, true>(xs, cs + wave * KN_KG * PT_DC, lane, acc);   // (wave-uniform)
         }
 #pragma unroll
         for (int j = 0; j < KN_KG; ++j)
@@ -220,7 +160,7 @@ __global__ __launch_bounds__(KN_NT) void knn_within_fold_kernel(const int* __res
 }
 
 static bool kn_shape_ok(int64_t n, int64_t m, int d, int k) {
-    return n >= 1 && n <= GS_KMEANS_MAX_N && m >= 1 && m <= GS_KMEANS_MAX_N && d >= 1 && d <= GS_KMEANS_MAX_D && k >= 1 && k <= GS_KNN_MAX_K;
+    return feature_dims_ok(n, d) && feature_dims_ok(m, d) && k >= 1 && k <= GS_KNN_MAX_K;
 }
 static long kn_tiles(int64_t n) { return (long)((n + KN_TILE - 1) / KN_TILE); }
 // the rows of the other side a block walks: whole rounds, at least GS_KNN_MIN_SLICE_ROWS, and few enough for GS_KNN_BLOCKS blocks where m allows
@@ -240,18 +180,17 @@ static size_t kn_ws_bytes(int64_t n, int64_t m, int k) {
     if (slices == 1) return 16;
     return ((size_t)slices * (size_t)n * k * sizeof(float) + 15) & ~(size_t)15;
 }
-static bool kn_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace gs
 
 using namespace gs;
 
-#define KN_CHECK_SHAPE(what, lda, ldb, sa, sb)                                                                                      \
-    GS_CHECK_ARG(d >= 1 && d <= GS_KMEANS_MAX_D, what ": d must be in [1, %d] (got %d)", GS_KMEANS_MAX_D, d);                        \
-    GS_CHECK_ARG(n >= 1 && n <= GS_KMEANS_MAX_N, what ": n must be in [1, 2^31 - 1] (got %lld)", (long long)n);                      \
-    GS_CHECK_ARG(m >= 1 && m <= GS_KMEANS_MAX_N, what ": m must be in [1, 2^31 - 1] (got %lld)", (long long)m);                      \
-    GS_CHECK_ARG(lda >= d, what ": " sa " %lld is below d %d", (long long)lda, d);                                                  \
-    GS_CHECK_ARG(ldb >= d, what ": " sb " %lld is below d %d", (long long)ldb, d)
+#define KN_CHECK_SHAPE(what, lda, ldb, sa, sb) \
+    GS_CHECK_FEATURE_D(what);                  \
+    GS_CHECK_FEATURE_ROWS(what, "n", n);       \
+    GS_CHECK_FEATURE_ROWS(what, "m", m);       \
+    GS_CHECK_FEATURE_LD(what, sa, lda);        \
+    GS_CHECK_FEATURE_LD(what, sb, ldb)
 
 extern "C" int gs_knn_slices(int64_t n, int64_t m, int d) {
     if (!kn_shape_ok(n, m, d, 1)) return 0;
@@ -268,9 +207,9 @@ extern "C" int gs_knn_kth(const float* a, int64_t lda, int64_t n, const float* b
     GS_CHECK_ARG(k >= 1 && k <= GS_KNN_MAX_K, "knn_kth: k must be in [1, %d] (got %d)", GS_KNN_MAX_K, k);
     KN_CHECK_SHAPE("knn_kth", lda, ldb, "lda", "ldb");
     GS_CHECK_ARG(a && b && out, "knn_kth: null pointer (a, b and out are required)");
-    GS_CHECK_ARG(kn_aligned(a, 4) && kn_aligned(b, 4) && kn_aligned(out, 4), "knn_kth: misaligned pointer (a, b and out: 4 bytes)");
+    GS_CHECK_ARG(aligned(a, 4) && aligned(b, 4) && aligned(out, 4), "knn_kth: misaligned pointer (a, b and out: 4 bytes)");
     const size_t need = kn_ws_bytes(n, m, k);
-    GS_CHECK_ARG(ws && ws_bytes >= need && kn_aligned(ws, 16), "knn_kth: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
+    GS_CHECK_ARG(ws && ws_bytes >= need && aligned(ws, 16), "knn_kth: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
     hipStream_t st = as_stream(stream);
     const unsigned tiles = (unsigned)kn_tiles(n);
     const long rows = kn_rows_per_slice(n, m);
@@ -292,10 +231,10 @@ extern "C" int gs_knn_within(const float* q, int64_t ldq, int64_t n, const float
                              void* ws, size_t ws_bytes, void* stream) {
     KN_CHECK_SHAPE("knn_within", ldq, ldr, "ldq", "ldr");
     GS_CHECK_ARG(q && ref && radius2 && count, "knn_within: null pointer (q, ref, radius2 and count are required)");
-    GS_CHECK_ARG(kn_aligned(q, 4) && kn_aligned(ref, 4) && kn_aligned(radius2, 4) && kn_aligned(count, 4),
+    GS_CHECK_ARG(aligned(q, 4) && aligned(ref, 4) && aligned(radius2, 4) && aligned(count, 4),
                  "knn_within: misaligned pointer (q, ref, radius2 and count: 4 bytes)");
     const size_t need = kn_ws_bytes(n, m, 1);
-    GS_CHECK_ARG(ws && ws_bytes >= need && kn_aligned(ws, 16), "knn_within: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
+    GS_CHECK_ARG(ws && ws_bytes >= need && aligned(ws, 16), "knn_within: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, need);
     hipStream_t st = as_stream(stream);
     const unsigned tiles = (unsigned)kn_tiles(n);
     const long rows = kn_rows_per_slice(n, m);

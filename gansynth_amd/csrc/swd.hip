@@ -134,16 +134,10 @@ __global__ __launch_bounds__(SW_NT) void swd_patches_kernel(const float* __restr
     }
 }
 
-// the sum over the block in thread 0 (a fixed tree); sm: SW_NT doubles
+// the sum over the block in thread 0 (block_tree_f64's fixed tree); sm: SW_NT doubles, shared by a kernel's calls
 __device__ inline double block_tree_sum(double v, double* sm) {
-    const int t = threadIdx.x;
     __syncthreads();   // (the array may still be read from the call before)
-    sm[t] = v;
-    for (int s = SW_NT / 2; s > 0; s >>= 1) {
-        __syncthreads();
-        if (t < s) sm[t] += sm[t + s];
-    }
-    return sm[0];
+    return block_tree_f64<SW_NT>(v, sm);
 }
 
 // part[block][4] = sum c0, sum of squares c0, sum c1, sum of squares c1 over the block's share [block * share, ...) of the count values
@@ -368,7 +362,6 @@ static size_t sw_ws_bytes(int stage, int64_t a, int64_t b, int64_t c) {
         default: return 0;
     }
 }
-static bool sw_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 static unsigned sw_grid(int64_t threads) {
     const int64_t blocks = (threads + SW_NT - 1) / SW_NT;
     return (unsigned)(blocks < 65536 ? blocks : 65536);
@@ -379,7 +372,7 @@ static unsigned sw_grid(int64_t threads) {
 using namespace gs;
 
 #define SW_CHECK_WS(what, need) \
-    GS_CHECK_ARG(ws && ws_bytes >= (need) && sw_aligned(ws, 16), what ": workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, (size_t)(need))
+    GS_CHECK_ARG(ws && ws_bytes >= (need) && aligned(ws, 16), what ": workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes, (size_t)(need))
 
 extern "C" int gs_swd_levels(int h, int w) { return sw_levels(h, w); }
 
@@ -391,7 +384,7 @@ extern "C" int gs_swd_pyramid(const void* x, int dtype, int64_t b, int h, int w,
     const int levels = sw_levels(h, w);
     GS_CHECK_ARG(levels > 0, "swd_pyramid: %d x %d has no level (both sides at least 16 and at most %d, every halved size even)", h, w, GS_SWD_MAX_SIDE);
     GS_CHECK_ARG(x && lap, "swd_pyramid: null pointer (x and lap are required)");
-    GS_CHECK_ARG(sw_aligned(x, 4) && sw_aligned(lap, 4), "swd_pyramid: misaligned pointer (4 bytes)");
+    GS_CHECK_ARG(aligned(x, 4) && aligned(lap, 4), "swd_pyramid: misaligned pointer (4 bytes)");
     SW_CHECK_WS("swd_pyramid", sw_ws_bytes(GS_SWD_STAGE_PYRAMID, b, h, w));
     hipStream_t st = as_stream(stream);
     GS_DISPATCH_DTYPE(dtype, {
@@ -431,7 +424,7 @@ extern "C" int gs_swd_patches(const float* level, int64_t b, int h, int w, const
     GS_CHECK_ARG(row_offset >= 0 && row_offset + b * SW_PP <= desc_rows, "swd_patches: rows [%lld, %lld) do not lie inside desc_rows %lld", (long long)row_offset,
                  (long long)(row_offset + b * SW_PP), (long long)desc_rows);
     GS_CHECK_ARG(level && ys && xs && desc, "swd_patches: null pointer (level, ys, xs and desc are required)");
-    GS_CHECK_ARG(sw_aligned(level, 4) && sw_aligned(ys, 4) && sw_aligned(xs, 4) && sw_aligned(desc, 4), "swd_patches: misaligned pointer (4 bytes)");
+    GS_CHECK_ARG(aligned(level, 4) && aligned(ys, 4) && aligned(xs, 4) && aligned(desc, 4), "swd_patches: misaligned pointer (4 bytes)");
     hipLaunchKernelGGL(swd_patches_kernel, dim3(sw_grid(b * SW_PP * SW_D)), dim3(SW_NT), 0, as_stream(stream), level, (long)b, h, w, ys, xs, desc, (long)row_offset);
     GS_CHECK_LAUNCH();
     return 0;
@@ -440,7 +433,7 @@ extern "C" int gs_swd_patches(const float* level, int64_t b, int h, int w, const
 extern "C" int gs_swd_moments(const float* desc, int64_t rows, double* out, void* ws, size_t ws_bytes, void* stream) {
     GS_CHECK_ARG(rows >= 1 && rows <= GS_SWD_MAX_N, "swd_moments: rows must be in [1, %d] (got %lld)", GS_SWD_MAX_N, (long long)rows);
     GS_CHECK_ARG(desc && out, "swd_moments: null pointer (desc and out are required)");
-    GS_CHECK_ARG(sw_aligned(desc, 4) && sw_aligned(out, 8), "swd_moments: misaligned pointer (out: 8 bytes, desc: 4)");
+    GS_CHECK_ARG(aligned(desc, 4) && aligned(out, 8), "swd_moments: misaligned pointer (out: 8 bytes, desc: 4)");
     SW_CHECK_WS("swd_moments", sw_ws_bytes(GS_SWD_STAGE_MOMENTS, rows, 0, 0));
     hipStream_t st = as_stream(stream);
     const long count = (long)rows * SW_D;
@@ -457,7 +450,7 @@ extern "C" int gs_swd_project(const float* desc, int64_t n, const double* moment
     GS_CHECK_ARG(n >= 1 && n <= GS_SWD_MAX_N, "swd_project: n must be in [1, %d] (got %lld)", GS_SWD_MAX_N, (long long)n);
     GS_CHECK_ARG(ndir >= 1 && ndir <= GS_SWD_MAX_ROWS, "swd_project: ndir must be in [1, %d] (got %d)", GS_SWD_MAX_ROWS, ndir);
     GS_CHECK_ARG(desc && moments && dirs && out, "swd_project: null pointer (desc, moments, dirs and out are required)");
-    GS_CHECK_ARG(sw_aligned(desc, 4) && sw_aligned(moments, 8) && sw_aligned(dirs, 4) && sw_aligned(out, 4), "swd_project: misaligned pointer (moments: 8 bytes, the others: 4)");
+    GS_CHECK_ARG(aligned(desc, 4) && aligned(moments, 8) && aligned(dirs, 4) && aligned(out, 4), "swd_project: misaligned pointer (moments: 8 bytes, the others: 4)");
     hipLaunchKernelGGL(swd_project_kernel, dim3((unsigned)((n + PJ_ROWS - 1) / PJ_ROWS)), dim3(SW_NT), 0, as_stream(stream), desc, (long)n, moments, dirs, ndir, out);
     GS_CHECK_LAUNCH();
     return 0;
@@ -467,7 +460,7 @@ extern "C" int gs_swd_sort(float* data, int64_t rows, int64_t n, void* ws, size_
     GS_CHECK_ARG(rows >= 1 && rows <= GS_SWD_MAX_ROWS, "swd_sort: rows must be in [1, %d] (got %lld)", GS_SWD_MAX_ROWS, (long long)rows);
     GS_CHECK_ARG(n >= 1 && n <= GS_SWD_MAX_N, "swd_sort: n must be in [1, %d] (got %lld)", GS_SWD_MAX_N, (long long)n);
     GS_CHECK_ARG(data, "swd_sort: null pointer (data is required)");
-    GS_CHECK_ARG(sw_aligned(data, 4), "swd_sort: misaligned pointer (4 bytes)");
+    GS_CHECK_ARG(aligned(data, 4), "swd_sort: misaligned pointer (4 bytes)");
     SW_CHECK_WS("swd_sort", sw_ws_bytes(GS_SWD_STAGE_SORT, rows, n, 0));
     hipStream_t st = as_stream(stream);
     int passes = 0;
@@ -489,7 +482,7 @@ extern "C" int gs_swd_l1(const float* a, const float* b, int64_t rows, int64_t n
     GS_CHECK_ARG(rows >= 1 && rows <= GS_SWD_MAX_ROWS, "swd_l1: rows must be in [1, %d] (got %lld)", GS_SWD_MAX_ROWS, (long long)rows);
     GS_CHECK_ARG(n >= 1 && n <= GS_SWD_MAX_N, "swd_l1: n must be in [1, %d] (got %lld)", GS_SWD_MAX_N, (long long)n);
     GS_CHECK_ARG(a && b && out, "swd_l1: null pointer (a, b and out are required)");
-    GS_CHECK_ARG(sw_aligned(a, 4) && sw_aligned(b, 4) && sw_aligned(out, 8), "swd_l1: misaligned pointer (out: 8 bytes, the others: 4)");
+    GS_CHECK_ARG(aligned(a, 4) && aligned(b, 4) && aligned(out, 8), "swd_l1: misaligned pointer (out: 8 bytes, the others: 4)");
     SW_CHECK_WS("swd_l1", sw_ws_bytes(GS_SWD_STAGE_L1, rows, n, 0));
     hipStream_t st = as_stream(stream);
     const long count = (long)rows * n;

@@ -261,7 +261,6 @@ __global__ __launch_bounds__(YN_NT) void yin_track_kernel(const float* __restric
     }
 }
 
-static bool yn_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace gs
 
@@ -298,7 +297,7 @@ extern "C" int gs_yin_difference(const float* x, int64_t ldx, int64_t rows, int6
     GS_CHECK_ARG(frames <= INT_MAX, "yin_difference: n %lld gives more than 2^31 - 1 frames", (long long)n);
     YN_CHECK_ROWS("yin_difference", frames);
     GS_CHECK_ARG(x && d && power, "yin_difference: null pointer (x, d and power are required)");
-    GS_CHECK_ARG(yn_aligned(x, 4) && yn_aligned(d, 4) && yn_aligned(power, 4), "yin_difference: misaligned pointer (x, d and power: 4 bytes)");
+    GS_CHECK_ARG(aligned(x, 4) && aligned(d, 4) && aligned(power, 4), "yin_difference: misaligned pointer (x, d and power: 4 bytes)");
     const YinLds s = yin_lds(W, L, true);
     hipLaunchKernelGGL(yin_difference_kernel, dim3((unsigned)(rows * frames)), dim3(YN_NT), (size_t)s.bytes, as_stream(stream), x, (size_t)ldx, (int)frames, W, L, hop,
                        d, power);
@@ -312,7 +311,7 @@ extern "C" int gs_yin_pick(const float* d, int64_t rows, int64_t frames, int L, 
     GS_CHECK_ARG(frames >= 1 && frames <= INT_MAX, "yin_pick: F must be in [1, 2^31 - 1] (got %lld)", (long long)frames);
     YN_CHECK_ROWS("yin_pick", frames);
     GS_CHECK_ARG(d && lag && period && aperiodicity, "yin_pick: null pointer (d, lag, period and aperiodicity are required)");
-    GS_CHECK_ARG(yn_aligned(d, 4) && yn_aligned(lag, 4) && yn_aligned(period, 8) && yn_aligned(aperiodicity, 8),
+    GS_CHECK_ARG(aligned(d, 4) && aligned(lag, 4) && aligned(period, 8) && aligned(aperiodicity, 8),
                  "yin_pick: misaligned pointer (d and lag: 4 bytes; period and aperiodicity: 8)");
     const YinLds s = yin_lds(L, L, false);
     hipLaunchKernelGGL(yin_pick_kernel, dim3((unsigned)(rows * frames)), dim3(YN_NT), (size_t)s.bytes, as_stream(stream), d, L, tau_min, threshold, lag, period,
@@ -330,7 +329,7 @@ extern "C" int gs_yin_track(const float* x, int64_t ldx, int64_t rows, int64_t n
     GS_CHECK_ARG(frames <= INT_MAX, "yin_track: n %lld gives more than 2^31 - 1 frames", (long long)n);
     YN_CHECK_ROWS("yin_track", frames);
     GS_CHECK_ARG(x && lag && period && aperiodicity && power, "yin_track: null pointer (x, lag, period, aperiodicity and power are required)");
-    GS_CHECK_ARG(yn_aligned(x, 4) && yn_aligned(lag, 4) && yn_aligned(power, 4) && yn_aligned(period, 8) && yn_aligned(aperiodicity, 8),
+    GS_CHECK_ARG(aligned(x, 4) && aligned(lag, 4) && aligned(power, 4) && aligned(period, 8) && aligned(aperiodicity, 8),
                  "yin_track: misaligned pointer (x, lag and power: 4 bytes; period and aperiodicity: 8)");
     const YinLds s = yin_lds(W, L, true);
     hipLaunchKernelGGL(yin_track_kernel, dim3((unsigned)(rows * frames)), dim3(YN_NT), (size_t)s.bytes, as_stream(stream), x, (size_t)ldx, (int)frames, W, L, hop,

@@ -272,6 +272,43 @@ def test_within_admits_exactly_the_pairs_kth_returned():
             assert lists[i, place] == lists[j, list(order[j]).index(i)]
 
 
+@pytest.mark.parametrize("aligned", [True, False], ids=["aligned", "one float off"])
+@pytest.mark.parametrize("d", [1, 33, 64])
+def test_assign_and_knn_share_one_distance(d, aligned):
+    """gs_kmeans_assign, gs_knn_kth and gs_knn_within add d(i, j) through the one chain of csrc/pairs_tile.h (assign in its scalar form, k-NN in
+    its packed form), so on inputs without NaN every figure below is an equality of bits: no tolerance.  n = T + 1 rows (one past a tile);
+    d below a chunk of 32 columns, one past it and two whole chunks; k = 1, 16, 32, 50, 65, 256 centres: assign's KG = 4, 4, 8, 13, 13 in two
+    rounds and 16 in four, and one to four k-NN rounds of 64 (five, the last with one row, where x is the other side).
+      * assign's dist is knn_kth(x, c, 1), the minimum over the same centres.
+      * The counts of knn_within(x, c, R), R[j] = knn_kth(c, x, 1)[j] centre j's own radius (the distance to its nearest row, x now the
+        broadcast side), are recomputed on the host.  The minima alone do not hold the k - 1 other distances of a row, so the host takes all of
+        d(., j) from the device as assign's dist against centre j alone, which is that chain again: the row minimum of that matrix must be
+        dist, its first arg-minimum the label, its column minimum R."""
+    from gansynth_amd import kernels
+    n = T + 1
+    rng = np.random.default_rng(5000 + d)
+    x, centres = NR.clustered(n, d, rng)
+    _, xv, _ = _place(x, aligned)
+    for k in (1, 16, 32, 50, 65, 256):
+        c = NR.clustered(k, d, rng, centres)[0]
+        _, cflat = _out(k * d, F_SENT, torch.float32, aligned)                               # (assign takes contiguous centres: no row slack)
+        cv = cflat.view(k, d)
+        cv.copy_(torch.from_numpy(c))
+        assert (cv.data_ptr() % 16 == 0) == aligned
+        labels, dist, _, _ = kernels.kmeans_assign(xv, cv)
+        nearest = kernels.knn_kth(xv, cv, 1)[:, 0]
+        assert torch.equal(dist, nearest)
+        full = torch.stack([kernels.kmeans_assign(xv, cv[j:j + 1])[1] for j in range(k)], dim=1).cpu().numpy()   # [n, k]
+        radius2 = kernels.knn_kth(cv, xv, 1)[:, 0].contiguous()
+        count = kernels.knn_within(xv, cv, radius2).cpu().numpy()
+        want = (full <= radius2.cpu().numpy()[None, :]).sum(axis=1)
+        print(f"d {d} k {k}: dist from {float(dist.min()):.6g} to {float(dist.max()):.6g}; rows inside a centre's radius {int((count > 0).sum())}, "
+              f"pairs {int(count.sum())} (host {int(want.sum())})")
+        assert np.array_equal(full.min(axis=1), dist.cpu().numpy()) and np.array_equal(full.argmin(axis=1), labels.cpu().numpy())
+        assert np.array_equal(full.min(axis=0), radius2.cpu().numpy())
+        assert np.array_equal(count, want) and count.sum() >= k                              # (every centre's nearest row lies AT its radius)
+
+
 @functools.lru_cache(maxsize=None)
 def _clean_set(d, n, k):
     """The first seed whose n rows have, in float64, no pair other than the n k defining ones within the bound of a radius."""
